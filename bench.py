@@ -2,13 +2,17 @@
 """Headline benchmark: windows/s of the WindGNN training step (forward + MSE + backward + Adam, with a
 gradient all-reduce when N > 1) on synthetic 34-station hourly windows.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  Inputs are resident in HBM before the
 timed region; every arithmetic op of the step is a libwindgnn_hip.so kernel.
 
-Order of a default N = 1 run: (1) two short child runs of this script under `rocprofv3 --pmc` (FETCH_SIZE, then
+A plain run does what the headline needs and nothing else: set-up, untimed steps (a first pass as long as --full's
+first pass + per-kernel pass, the spin-up, `warmup`), exactly `steps` timed steps, the outputs of the last timed step
+written to DIR (--dump-outputs), the JSON line.
+
+Order of a --full N = 1 run: (1) two short child runs of this script under `rocprofv3 --pmc` (FETCH_SIZE, then
 WRITE_SIZE: the counters cannot share a pass) measure the HBM traffic of every kernel of THIS build, before this
 process touches the GPU; (2) a per-kernel pass with hipEvents inside the library and the forward-only timing (so the
 GPU does not enter the timed region cold); (3) `warmup` untimed steps + exactly `steps` timed steps; (4) the exact-fp32
@@ -43,6 +47,10 @@ BOUND_HBM_PREFIXES = ("mse_", "adam_", "finish_", "amax_", "splitk_reduce", "tn_
 
 
 SPINUP_STEPS = int(os.environ.get("WGNN_BENCH_SPINUP", "60"))   # untimed steps in front of the W warm-up steps (the GPU's clock ramp after an idle gap: see main())
+# --dump-outputs: arrays with more elements than these are written as a fixed, seeded sample; at most
+# 11 M + 8 x 0.5 M + 1 float32 values = 60 MB in all (the c3 workload's Y, 4096 x 24 x 102 = 10.0 M, is written whole)
+DUMP_Y_MAX = 11_000_000
+DUMP_PARAM_MAX = 500_000
 
 
 def committed_traffic():
@@ -292,6 +300,34 @@ def c5_in_child(math, timeout_s=420):
         return {"error": "c5 child (%s): unreadable output: %r" % (math, e)}
 
 
+def _dump_sample(t, cap, seed):
+    """`t` as a float32 copy on its device: whole if it has at most `cap` elements, otherwise flattened and cut to `cap`
+    elements, one at a seeded offset inside each of `cap` near-equal strides (the same positions in every run)."""
+    t = t.detach()
+    n = t.numel()
+    if n <= cap:
+        return t.to(torch.float32, copy=True)
+    edges = torch.arange(cap + 1, dtype=torch.int64) * n // cap
+    g = torch.Generator().manual_seed(seed)
+    idx = edges[:-1] + (torch.rand(cap, generator=g, dtype=torch.float64) * (edges[1:] - edges[:-1])).long()
+    return t.reshape(-1).index_select(0, idx.to(t.device)).to(torch.float32)
+
+
+def snapshot_outputs(loss, Y, model):
+    """What the caller of the timed step receives from its last call: the loss, Y and the updated parameters.  Copied on the
+    GPU right after the timed region (no host synchronisation; the loss is a view the next step would overwrite)."""
+    out = {"loss": _dump_sample(loss, 1, 0), "Y": _dump_sample(Y, DUMP_Y_MAX, 1)}
+    for i, (name, p) in enumerate(model.named_parameters()):
+        out["param_" + name] = _dump_sample(p, DUMP_PARAM_MAX, 2 + i)
+    return out
+
+
+def write_outputs(snap, out_dir):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in snap.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -306,10 +342,18 @@ def main():
                     help="c3: 34 stations, the headline config; c5: 4096-station k-NN CSR stress config")
     ap.add_argument("--io", default="fp32", choices=["fp32", "fp16", "bf16"],
                     help="element type of X, Y and the labels on the wire (16-bit: BASELINE configs[2]; needs --math f16x3|f16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the live rocprofv3 PMC passes (N = 1 only)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the exact-fp32 secondary measurement")
-    ap.add_argument("--no-c5", action="store_true", help="skip the 4096-station secondary (c5_csr_b128: ~40 GB of GPU memory, ~20 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: live HBM traffic, the per-kernel pass and "
+                         "roofline, the checked forward-only timing, the secondary configurations, the CPU baselines and, "
+                         "with N > 1, rccl_ranks_seen (off: set-up, warm-up, the timed steps, the JSON line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (loss, Y, the updated parameters) to DIR/<name>.npy as "
+                         "float32; arrays beyond %d (Y) / %d (each parameter) elements as a fixed, seeded sample"
+                         % (DUMP_Y_MAX, DUMP_PARAM_MAX))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: skip the live rocprofv3 PMC passes (N = 1 only)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary configurations")
+    ap.add_argument("--no-c5", action="store_true", help="--full: skip the 4096-station secondary (c5_csr_b128: ~40 GB of GPU memory, ~20 s)")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--c5-child", default=None, choices=["f16x3", "f16x3g"], help=argparse.SUPPRESS)
     ap.add_argument("--direct-rccl", action="store_true",
@@ -319,6 +363,9 @@ def main():
                     help="initialise the RCCL process group and run the collective step even with one rank (rehearses the "
                          "N > 1 code path on a one-GPU box; launch with torch.distributed.run --nproc-per-node 1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    full = args.full and not args.traffic_child
 
     # RCCL on this pool needs dmabuf IPC (HSA_ENABLE_IPC_MODE_LEGACY=0): exported here, before anything initialises the
     # GPU, so the line does not depend on the launcher's environment (windgnn_amd/distributed.py)
@@ -344,7 +391,7 @@ def main():
                          "--nproc-per-node <= %d" % (local_rank, ndev, ndev))
 
     traffic, traffic_src = {}, None
-    if world == 1 and not args.traffic_child:
+    if world == 1 and full:
         if not args.no_traffic:
             traffic, traffic_src = measure_traffic_live(args)
         if not traffic:
@@ -374,7 +421,7 @@ def main():
     trainer = TrainStep(model, process_group=dist.group.WORLD if use_dist else None,
                         direct_rccl=True if args.direct_rccl else None)
     # an all-reduce of ones through the path the step's bucket takes: the ranks that really exchange data
-    ranks_seen = trainer.exchange.ranks_seen() if use_dist else None
+    ranks_seen = trainer.exchange.ranks_seen() if use_dist and full else None
     A = (adjacency_34() if args.workload == "c3" else adjacency_knn(S)).to(dev)
     X, L = make_inputs(B, rank, dev, S, H, args.io)
     esz = 4.0 if args.io == "fp32" else 2.0
@@ -388,12 +435,17 @@ def main():
     # the per-kernel pass (hipEvents inside the library) and the forward-only timing.  A 20 + 20 step run is 33 ms of GPU
     # time; entered cold it times the clock ramp (round 1: 4.59 M windows/s in the driver's 20-step run vs 4.85 M over 200
     # steps of the same code).  The timed region below is still exactly `warmup` untimed + `steps` timed steps.
+    # A plain run takes `steps` more untimed steps in place of the per-kernel pass: the GPU enters the spin-up below with the
+    # same history as with --full (15 ms less of it read 0.7 % slower in 20-step runs), and the timed steps continue the same
+    # training trajectory (the same loss and outputs in either mode).
     recs, fwd_s = None, None
     if not args.traffic_child:
-        from windgnn_amd.functional import gcn_gru_forward_raw
-        for _ in range(max(args.warmup, 20) if args.workload == "c3" else args.warmup):   # untimed: first launches, clock ramp
+        nfirst = max(args.warmup, 20) if args.workload == "c3" else args.warmup
+        for _ in range(nfirst + (0 if full else args.steps)):   # untimed: first launches, clock ramp
             trainer.step(A, X, L, world * B)
         torch.cuda.synchronize()
+    if full:
+        from windgnn_amd.functional import gcn_gru_forward_raw
         _lib.profile_enable(True)
         for _ in range(args.steps):
             trainer.step(A, X, L, world * B)        # the kernels of the timed step, optimiser tail included
@@ -412,8 +464,9 @@ def main():
     gc.collect()                                        # (tens of ms of host time: BEFORE the spin-up, or the GPU idles again)
     gc.disable()                                        # no collector pause inside a 15 ms timed region (as timeit does)
     if not args.traffic_child:
-        # Untimed spin-up on every rank, before the contract's own W warm-up steps: the checks above synchronise with the host,
-        # the GPU idles for a few ms and drops its clocks, and it takes ~25 training steps (20 ms) of load to get them back
+        # Untimed spin-up on every rank, before the contract's own W warm-up steps: the passes above (with --full, the checks
+        # too) end in a host synchronisation, the GPU idles for a few ms and drops its clocks, and it takes ~25 training
+        # steps (20 ms) of load to get them back
         # (per-step times after a 5 ms idle gap: 773 794 822 848 860 852 830 808 ... 753 us against 745 steady:
         # profiles/r5_b_clock_ramp.txt).  With --steps 20 --warmup 5 the timed region would otherwise sit inside that ramp.
         nspin = SPINUP_STEPS if args.workload == "c3" else 2              # (a configs[4] step is 140 ms: two are a ramp's worth)
@@ -431,13 +484,14 @@ def main():
     t0 = time.perf_counter()
     g0.record()
     for _ in range(args.steps):
-        loss, _ = trainer.step(A, X, L, n_global)
+        loss, Y = trainer.step(A, X, L, n_global)
     g1.record()
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
     if args.traffic_child:
         return
+    snap = snapshot_outputs(loss, Y, model) if args.dump_outputs and rank == 0 else None
     gpu_dt = g0.elapsed_time(g1) * 1e-3                # the same K steps on the GPU's clock: a host stall shows as dt >> gpu_dt
     h = max(nspin // 2, 1)
     spin_ms = [round(spin_ev[0].elapsed_time(spin_ev[1]) / h, 4), round(spin_ev[1].elapsed_time(spin_ev[2]) / max(nspin - h, 1), 4)] if nspin >= 2 else None
@@ -460,7 +514,7 @@ def main():
 
     # ---- per-kernel pass (same workload, hipEvents inside the library) for the roofline object
     roofline, forward, kernels, mfma, path, secondary, extra = None, None, None, None, None, None, {}
-    if rank == 0:
+    if rank == 0 and full:
         recs.sort(key=lambda r: -r["ms"])
         kernels = []
         for r in recs:
@@ -566,6 +620,7 @@ def main():
             "value": round(world * B * args.steps / dt, 1),
             "unit": "windows/s",
             "n_gpus": world,
+            "full": full,
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(1e3 * dt / args.steps, 4),
@@ -590,24 +645,34 @@ def main():
                                                                   % trainer.exchange.direct_declined
                                                                   if trainer.exchange.direct_declined else "")))
                                       if use_dist else "none (one rank)")},
-            "rccl_ranks_seen": ranks_seen,
-            "loss": round(float(loss), 6),
-            "roofline": roofline,
-            "path": path,
-            "mfma": mfma,
-            "forward": forward,
-            "f16x3g_mixed": extra.get("f16x3g_mixed"),
-            "exact_f32": secondary,
-            "c1_f32_b256": extra.get("c1_f32_b256"),
-            "c2_f16_bf16io_b4096": extra.get("c2_f16_bf16io_b4096"),
-            "c5_csr_b128": extra.get("c5_csr_b128"),
-            "measurement_order": "traffic children (N=1), untimed per-kernel pass + forward output check, %d untimed spin-up steps (clock ramp after the host-synchronising checks), then `warmup` untimed and `steps` timed steps, forward-only timing, secondaries (f16x3g_mixed, exact_f32, c1, c2), cpu baseline" % SPINUP_STEPS,
-            "kernels": kernels,
-            "kernels_note": "hipEvent-bracketed inside the library: every launch carries 1-2 us of event latency, so the sum "
-                            "runs 3-4 % above ms_per_step; the rocprofv3 durations (profiles/*_kernel_stats.csv) sum to it",
         }
-        if world == 1 and not args.no_cpu_baseline and args.workload == "c3":
-            out["cpu_baseline"] = cpu_baseline()
+        if full:
+            out["rccl_ranks_seen"] = ranks_seen
+        out["loss"] = round(float(loss), 6)
+        if full:
+            out.update({
+                "roofline": roofline,
+                "path": path,
+                "mfma": mfma,
+                "forward": forward,
+                "f16x3g_mixed": extra.get("f16x3g_mixed"),
+                "exact_f32": secondary,
+                "c1_f32_b256": extra.get("c1_f32_b256"),
+                "c2_f16_bf16io_b4096": extra.get("c2_f16_bf16io_b4096"),
+                "c5_csr_b128": extra.get("c5_csr_b128"),
+                "measurement_order": "traffic children (N=1), untimed per-kernel pass + forward output check, %d untimed spin-up steps (clock ramp after the host-synchronising checks), then `warmup` untimed and `steps` timed steps, forward-only timing, secondaries (f16x3g_mixed, exact_f32, c1, c2), cpu baseline" % SPINUP_STEPS,
+                "kernels": kernels,
+                "kernels_note": "hipEvent-bracketed inside the library: every launch carries 1-2 us of event latency, so the sum "
+                                "runs 3-4 % above ms_per_step; the rocprofv3 durations (profiles/*_kernel_stats.csv) sum to it",
+            })
+            if world == 1 and not args.no_cpu_baseline and args.workload == "c3":
+                out["cpu_baseline"] = cpu_baseline()
+        else:
+            out["measurement_order"] = ("untimed first pass (first launches; as many steps as with --full), %d untimed spin-up "
+                                        "steps, then `warmup` untimed and `steps` timed steps (--full adds traffic, per-kernel, "
+                                        "forward, secondary and CPU figures)" % nspin)
+        if snap is not None:
+            write_outputs(snap, args.dump_outputs)
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.barrier()

@@ -282,7 +282,7 @@ def test_bench_multi_gpu_code_path_runs_under_torchrun_with_rccl():
     from conftest import ROOT
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5",
-           "--warmup", "2", "--force-dist", "--no-cpu-baseline", "--no-traffic", "--no-secondary", "--batch", "512"]
+           "--warmup", "2", "--force-dist", "--full", "--no-cpu-baseline", "--no-traffic", "--no-secondary", "--batch", "512"]
     env = {k: v for k, v in os.environ.items() if k != "HSA_ENABLE_IPC_MODE_LEGACY"}   # bench.py must set it itself
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -6,9 +6,9 @@ tag=${1:-rX}
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-python bench.py --steps 20 --warmup 5 > $out/${tag}_bench_driver_shape.json 2> $out/bench.err      # the driver's own command line
-python bench.py --no-cpu-baseline --no-c5 > $out/${tag}_bench.json 2>> $out/bench.err              # 200 steps
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --no-cpu-baseline --no-traffic --no-secondary > $out/bench_under_rocprof.json 2> $out/stats.err
+python bench.py --full --steps 20 --warmup 5 > $out/${tag}_bench_driver_shape.json 2> $out/bench.err      # the driver's step counts, every figure
+python bench.py --full --no-cpu-baseline --no-c5 > $out/${tag}_bench.json 2>> $out/bench.err              # 200 steps
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --no-cpu-baseline --no-traffic --no-secondary > $out/bench_under_rocprof.json 2> $out/stats.err
 cp $(ls $out/stats/*/*kernel_stats.csv | head -1) $out/${tag}_kernel_stats.csv
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmcF -- python3 bench.py --traffic-child --steps 5 --warmup 1 > /dev/null 2> $out/pmcF.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/pmcW -- python3 bench.py --traffic-child --steps 5 --warmup 1 > /dev/null 2> $out/pmcW.err
@@ -27,7 +27,7 @@ done
 unset WGNN_FUSED_FWD
 # BASELINE configs[4] (4096 stations, CSR, H = 12288, B = 128): kernel stats of 3 steps, strict and mixed
 for m in f16x3 f16x3g; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/c5$m -- python3 bench.py --workload c5 --math $m --steps 3 --warmup 2 --no-traffic --no-cpu-baseline > $out/${tag}_bench_c5_$m.json 2> $out/c5$m.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/c5$m -- python3 bench.py --full --workload c5 --math $m --steps 3 --warmup 2 --no-traffic --no-cpu-baseline > $out/${tag}_bench_c5_$m.json 2> $out/c5$m.err
   cp $(ls $out/c5$m/*/*kernel_stats.csv | head -1) $out/${tag}_c5_${m}_kernel_stats.csv
   rm -rf $out/c5$m
 done
