@@ -6,6 +6,7 @@
  * reference lines it stands in for (paths relative to the reference repo):
  *
  *   wgnn_fwd            GCN_GRU.forward            src/step6_gcn_gru_combined_model.py:13-27
+ *   wgnn_fwd_state      the same with nn.GRU's hx / h_n (inference, carried state)
  *                       (GraphConvLayer.forward x2  src/step5_gcn_layer_model.py:13-23, nn.GRU :23)
  *   wgnn_bwd            loss.backward() through it  src/main.py:79
  *   wgnn_gcn_layer_fwd  GraphConvLayer.forward      src/step5_gcn_layer_model.py:13-23
@@ -212,6 +213,24 @@ int wgnn_fwd_loss(const wgnn_dims* d, const float* A, const void* X, const wgnn_
  * and read the last row out.  fp32 I/O only. */
 int wgnn_fwd_last(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, float wind_min,
                   float wind_max, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Carried state (inference): nn.GRU's forward(input, hx) -> (output, h_n) (src/step6_gcn_gru_combined_model.py:23 calls it
+ * without hx, i.e. with zeros).  wgnn_fwd without a stash, from a caller-given initial state:
+ *   h0  [B,H] fp32 device memory, or NULL (= zeros: exactly wgnn_fwd's kernels and bits)
+ *   Y   [B,T,H] d->io, or NULL (not written)
+ *   h_n [B,H] fp32, or NULL (not written); the UNROUNDED fp32 h_{T-1}, also with 16-bit I/O.
+ * Y and h_n may not both be NULL (WGNN_ERR_NULL).  h0, Y and h_n may not overlap (WGNN_ERR_UNSUPPORTED).  Same dims,
+ * workspace (wgnn_workspace_bytes), math modes, io types and adjacency formats as wgnn_fwd; with h0 the first step computes
+ * the full W_hh h0 + b_hh in the mode's arithmetic.  Chunks compose: the h_n of X[:, :T1] fed as h0 of X[:, T1:] gives the
+ * Y and h_n of the whole X (within each mode's tolerance; summation orders differ only where a kernel's schedule does).
+ * The one-hour step: T == 1, a dense A (S <= 64), fp32 I/O, H <= 128 and B <= 256 run the whole hour -- both graph
+ * convolutions, the input projection, W_hh h0 and the GRU cell -- as ONE kernel (csrc/gru_step.hip) in exact fp32 VALU
+ * arithmetic in every math mode: within each mode's tolerance of the windowed forward, not bitwise equal to it.  Other
+ * T == 1 calls take the general path with h0.  wgnn_params.prepared is not needed by the step (and ignored by it).
+ * Training with a carried state (truncated BPTT: h0 in the backward's dW_hh rows, dh0) is not provided: wgnn_bwd* assume
+ * h0 = 0 and take no stash from this call. */
+int wgnn_fwd_state(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const float* h0, void* Y,
+                   float* h_n, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Gradients of sum(Y * dY) w.r.t. the 8 parameters (overwritten, not accumulated).
  * No dX and no dA: neither requires grad in the reference (src/main.py:26,

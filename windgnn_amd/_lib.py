@@ -18,6 +18,7 @@ MATH_F16X3G = 3       # f16x3 whose backward gate gradients travel as one fp16 p
 ADJ_DENSE = 0
 ADJ_CSR = 1
 IO_F32, IO_F16, IO_BF16 = 0, 1, 2   # wgnn_io: element type of X, Y and the labels
+STEP_MAX_B = 256            # wgnn_fwd_state: T == 1 calls up to this batch (dense A, fp32 I/O, H <= 128) run ONE kernel
 STATUS_BYTES = 256          # WGNN_STATUS_BYTES: status block at the start of every workspace
 OPT_FUSED_FWD = 0           # WGNN_OPT_FUSED_FWD (wgnn_set_option): 0 never / 1 stash-less forwards / 2 every supported forward
 OPT_GG_ROLE_SPLIT, OPT_GG_GEMM_PRIO, OPT_BWD2_CHUNKS, OPT_BIG_GEMM, OPT_GEMM32_FORM = 1, 2, 3, 4, 5   # measurement aids (include/windgnn.h): same results, another schedule
@@ -64,6 +65,8 @@ EXPORTS = {
                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "wgnn_fwd_last": (C.c_int, [C.POINTER(Dims), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_float, C.c_float,
                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wgnn_fwd_state": (C.c_int, [C.POINTER(Dims), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "wgnn_bwd": (C.c_int, [C.POINTER(Dims), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,
                            C.c_void_p, C.POINTER(Grads), C.c_void_p, C.c_size_t, C.c_void_p]),
     "wgnn_bwd_part": (C.c_int, [C.POINTER(Dims), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,

@@ -380,14 +380,17 @@ size_t wgnn_stash_bytes(const wgnn_dims* d) {
 // last != nullptr (wgnn_fwd_last): no stash; last[B][H] = Y[:, T-1, :] * y_mul + y_add and Y itself is only written
 // where the kernels cannot skip it (into the workspace, for the exact-fp32 and general-shape recurrences).
 // g_in != nullptr (wgnn_gru_fwd): the recurrent half alone on a caller-supplied g [B*T][S*F]; A, X and the conv slots of p unused.
+// state (wgnn_fwd_state): no stash; the recurrence starts from h0 (nullable = zeros: then exactly wgnn_fwd's kernels) and
+// leaves the unrounded h_{T-1} in hn (nullable); Y may be NULL (then only hn is written).
 static int fwd_impl(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* labels,
                     void* Y, void* stash, void* workspace, size_t workspace_bytes, void* stream, float* last = nullptr,
-                    float wind_min = 0.f, float wind_max = 1.f, const float* g_in = nullptr) {
+                    float wind_min = 0.f, float wind_max = 1.f, const float* g_in = nullptr, bool state = false,
+                    const float* h0 = nullptr, float* hn = nullptr) {
   // every read-out path forms its multiplier the same way, (wind_max - wind_min) in fp32, from the caller's two values
   const float y_mul = wind_max - wind_min, y_add = wind_min;
   int rc = check_dims(d);
   if (rc != WGNN_OK) return rc;
-  if ((!g_in && (!A || !X)) || !p || (!Y && !last) || !workspace) return WGNN_ERR_NULL;
+  if ((!g_in && (!A || !X)) || !p || (!Y && !last && !(state && hn)) || !workspace) return WGNN_ERR_NULL;
   if ((!g_in && (!p->conv1_weight || !p->conv1_bias || !p->conv2_weight || !p->conv2_bias)) || !p->w_ih || !p->w_hh ||
       !p->b_ih || !p->b_hh)
     return WGNN_ERR_NULL;
@@ -397,6 +400,16 @@ static int fwd_impl(const wgnn_dims* d, const float* A, const void* X, const wgn
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
   if (last && !(L.x3 && !L.gen_gru) && !L.rec32) Y = ws + L.ws_Ylast;   // these recurrences write every row: then read the last one out
+  // wgnn_fwd_state without Y: the register-resident recurrences write h_n alone (last_only into hn, or no Y rows with 16-bit
+  // I/O); the others write Y into the workspace, like wgnn_fwd_last, and h_n is a copy of its last row
+  const bool y_ws = state && !Y && !(L.x3 && !L.gen_gru) && !L.rec32;
+  if (y_ws) Y = ws + L.ws_Ylast;
+  const bool hn_only = state && !Y;                  // ... the last_only form (fp32 I/O) or the no-Y form (16-bit I/O)
+  auto copy_hn = [&](const float* Yf) -> int {       // h_n = Y[:, T-1, :] (fp32 Y), for the recurrences without an hn output
+    if (!hn) return WGNN_OK;
+    return hipMemcpy2DAsync(hn, (size_t)d->H * 4, Yf + (size_t)(d->T - 1) * d->H, (size_t)d->T * d->H * 4, (size_t)d->H * 4,
+                            d->B, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess ? WGNN_OK : WGNN_ERR_HIP;
+  };
   unsigned* status = (unsigned*)workspace;           // word 0 of the status block (include/windgnn.h)
   float* sf = (float*)stash;
   float* GI = (sf && L.gi_stash) ? sf + L.st_GI : ws + L.ws_GI;
@@ -426,6 +439,11 @@ static int fwd_impl(const wgnn_dims* d, const float* A, const void* X, const wgn
       if (last)
         return launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, last, nullptr, nullptr, full, status,
                                nullptr, nullptr, 0, 1, y_mul, y_add, st);
+      if (state) {
+        const int lo = hn_only && d->io == WGNN_IO_F32;
+        return launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, lo ? (void*)hn : Y, nullptr, nullptr, full,
+                               status, nullptr, nullptr, d->io, lo, 1.f, 0.f, st, h0, lo ? nullptr : hn);
+      }
       return launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, Y, gates, sf ? sf + L.st_yp : nullptr,
                              full, status, sf ? labels : nullptr, sf ? sf + L.st_stats : nullptr, d->io, 0, 1.f, 0.f, st);
     }
@@ -448,13 +466,19 @@ static int fwd_impl(const wgnn_dims* d, const float* A, const void* X, const wgn
       if (rc != WGNN_OK) return rc;
       rc = launch_gru_gen_fwd_x3(d->B, d->T, d->H, GI, (int)L.Gp, ws + L.ws_hhp_f, L.np_g3, p->b_hh, (float*)Y, gates,
                                  sf ? sf + L.st_yp : ws + L.ws_yp, ws + L.ws_gh, ws + L.ws_kp_f, ws + L.ws_hc, full,
-                                 st);
+                                 st, h0);
+      if (rc == WGNN_OK && state) return copy_hn((const float*)Y);
       if (rc != WGNN_OK || !last) return rc;
       return wgnn_predict_last((const float*)Y, d->B, d->T, d->H, wind_min, wind_max, last, stream);
     }
     if (last)   // the register-resident recurrence writes the read-out itself
       return launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, last, nullptr, nullptr, full, status,
                              nullptr, nullptr, 0, 1, y_mul, y_add, st);
+    if (state) {
+      const int lo = hn_only && d->io == WGNN_IO_F32;
+      return launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, lo ? (void*)hn : Y, nullptr, nullptr, full,
+                             status, nullptr, nullptr, d->io, lo, 1.f, 0.f, st, h0, lo ? nullptr : hn);
+    }
     // labels (wgnn_fwd_loss): the recurrence also leaves the MSE partial sums / maxima of (Y - labels) in the stash
     // (a stash without labels gets its tag word cleared: bit 8 of a later backward cannot trust stale statistics)
     return launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, Y, gates, sf ? sf + L.st_yp : nullptr,
@@ -489,11 +513,15 @@ static int fwd_impl(const wgnn_dims* d, const float* A, const void* X, const wgn
   }
   if (rc != WGNN_OK) return rc;
   float* hprev = (sf && L.g32tn) ? sf + L.st_hprev : nullptr;      // [Hprev | 1 | 0..] rows for the backward's dW_hh GEMM
-  if (L.gen_gru)
-    rc = launch_gru_gen_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, (float*)Y, gates, ws + L.ws_gh, st);
-  else if (L.small)   // few windows: one per workgroup instead of sixteen
+  if (L.gen_gru) {
+    rc = launch_gru_gen_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, (float*)Y, gates, ws + L.ws_gh, st, h0);
+    if (rc == WGNN_OK && state) return copy_hn((const float*)Y);
+  } else if (L.small) {   // few windows: one per workgroup instead of sixteen
     rc = launch_gru_small_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, (float*)Y, gates, hprev, L.hq,
-                              sf ? (const float*)labels : nullptr, sf ? sf + L.st_stats : nullptr, st);
+                              sf ? (const float*)labels : nullptr, sf ? sf + L.st_stats : nullptr, st, h0, hn);
+  } else if (state)   // the register-resident recurrence: h_n from its registers (and with Y = NULL the last_only form alone)
+    return launch_gru_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, hn_only ? hn : (float*)Y, nullptr, nullptr, nullptr,
+                          nullptr, 0, hn_only ? 1 : 0, 1.f, 0.f, st, h0, hn_only ? nullptr : hn);
   else if (last)      // the register-resident recurrence writes the read-out itself
     return launch_gru_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, last, nullptr, nullptr, nullptr, nullptr, 0, 1,
                           y_mul, y_add, st);
@@ -520,6 +548,31 @@ int wgnn_fwd_last(const wgnn_dims* d, const float* A, const void* X, const wgnn_
   if (!out) return WGNN_ERR_NULL;
   if (d && d->io != WGNN_IO_F32) return WGNN_ERR_UNSUPPORTED;
   return fwd_impl(d, A, X, p, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream, out, wind_min, wind_max);
+}
+
+int wgnn_fwd_state(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const float* h0, void* Y,
+                   float* h_n, void* workspace, size_t workspace_bytes, void* stream) {
+  int rc = check_dims(d);
+  if (rc != WGNN_OK) return rc;
+  if (!Y && !h_n) return WGNN_ERR_NULL;
+  if (!A || !X || !p || !workspace) return WGNN_ERR_NULL;
+  if (!p->conv1_weight || !p->conv1_bias || !p->conv2_weight || !p->conv2_bias || !p->w_ih || !p->w_hh || !p->b_ih ||
+      !p->b_hh)
+    return WGNN_ERR_NULL;
+  // h0 is read by every workgroup while others already write h_n / Y: the buffers must not overlap
+  const size_t hb = (size_t)d->B * d->H * sizeof(float);
+  const size_t yb = (size_t)d->B * d->T * d->H * (d->io == WGNN_IO_F32 ? 4 : 2);
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    return a && b && (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
+  };
+  if (overlap(h0, hb, h_n, hb) || overlap(h0, hb, Y, yb) || overlap(Y, yb, h_n, hb)) return WGNN_ERR_UNSUPPORTED;
+  if (workspace_bytes < sizeof(float) * make_layout(d).fwd_floats) return WGNN_ERR_WORKSPACE;
+  // one hour, small batch, the reference's dense graph: the whole step as one launch (csrc/gru_step.hip)
+  if (d->T == 1 && d->adj_format == WGNN_ADJ_DENSE && d->io == WGNN_IO_F32 && gru_step_supported(d->B, d->S, d->H))
+    return launch_gru_step(d->B, d->S, d->H, A, (const float*)X, p->conv1_weight, p->conv1_bias, p->conv2_weight,
+                           p->conv2_bias, p->w_ih, p->b_ih, p->w_hh, p->b_hh, h0, (float*)Y, h_n, (hipStream_t)stream);
+  return fwd_impl(d, A, X, p, nullptr, Y, nullptr, workspace, workspace_bytes, stream, nullptr, 0.f, 1.f, nullptr, true, h0,
+                  h_n);
 }
 
 size_t wgnn_prepared_bytes(const wgnn_dims* d) {

@@ -120,7 +120,9 @@ int grux_hp(int H);   // row width (halfs) of the Y planes: 32*ceil((H+1)/32)
 size_t grux_gates_floats(int B, int T, int H, int io);   // gate stash of the register-resident recurrences (their own layout)
 int launch_grux_fwd(int B, int T, int H, const void* GI /*fp32 rows if x3, else fp16 rows*/, int ldgi, const float* Whh, const float* bhh, void* Y,
                     float* gates, void* y_planes, bool x3, unsigned* status, const void* labels, float* stat_part,
-                    int io /*wgnn_io of Y and labels*/, int last_only, float y_mul, float y_add, hipStream_t st);
+                    int io /*wgnn_io of Y and labels*/, int last_only, float y_mul, float y_add, hipStream_t st,
+                    const float* h0 = nullptr /*[B][H] initial state (wgnn_fwd_state)*/,
+                    float* hn = nullptr /*[B][H] fp32 h_{T-1}; Y may then be NULL with 16-bit I/O*/);
 int grux_blocks(int B);   // workgroups of launch_grux_fwd = MSE partial pairs it writes when given labels
 int mse_stats_blocks();
 // exactly one of dY / labels is non-null (labels: dY = (Y - labels) * scales[2], see launch_mse_stats)
@@ -219,12 +221,12 @@ int launch_gcn2_csr_bwd(int ntiles, int S, int nnz, const void* csr, const float
                         hipStream_t st);
 int launch_gru_gen_fwd_x3(int B, int T, int H, const float* GI, int ldgi, const void* whh_planes, int np_g3,
                           const float* bhh, float* Y, float* gates, void* y_planes, float* gh, float* kpart, void* hc,
-                          bool x3, hipStream_t st);
+                          bool x3, hipStream_t st, const float* h0 = nullptr);
 int launch_gru_gen_bwd_x3(int B, int T, int H, const void* whhT_planes, int np_h, const float* Y, const float* dY,
                           const float* gates, const float* scales, void* dgi_planes, void* dgh_planes, int ldd,
                           float* dhz, float* dhw, float* kpart, void* dc, bool x3, hipStream_t st);
 int launch_gru_gen_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
-                       float* gates, float* gh, hipStream_t st);
+                       float* gates, float* gh, hipStream_t st, const float* h0 = nullptr);
 int launch_gru_gen_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* gates,
                        float* dGI, float* dGH, int ldd, float* dhz, float* dhw, hipStream_t st);
 size_t gcn1_csr_bwd_ws_floats(int ntiles, int S);
@@ -245,7 +247,7 @@ int launch_gcn1_bwd(int ntiles, int S, const float* A, const float* X, const flo
 //   last_only: Y is [B][H] and receives only h_{T-1} * y_mul + y_add
 int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
                    float* gates, const float* labels, float* stat_part, float* hprev, int hq, int last_only, float y_mul,
-                   float y_add, hipStream_t st);
+                   float y_add, hipStream_t st, const float* h0 = nullptr, float* hn = nullptr);
 //   backward: exactly one of dY / labels; dGI [B*T][ldd] and EITHER dGHn [B*T][gru_hn(H)] (dGH's r and z thirds equal
 //   dGI's) OR the full dGH [B*T][ldd]; stat_part (nullable, with labels): loss[0] is finalised from the forward's partials
 int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
@@ -261,12 +263,20 @@ bool gru_small_supported(int B, int H);
 int launch_gru_small_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
                          float* gates, float* hprev /*nullable: [B*T][hq] rows [h_{t-1} | 1 | 0..]*/, int hq,
                          const float* labels /*nullable*/, float* stat_part /*2 * gru_small_blocks(B) + 1 floats*/,
-                         hipStream_t st);
+                         hipStream_t st, const float* h0 = nullptr, float* hn = nullptr);
 int gru_small_blocks(int B);
 // exactly one of dY / labels (labels: dY formed in the kernel, loss finalised from stat_part as launch_gru_bwd)
 int launch_gru_small_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
                          const float* gates, float* dGI, float* dGH, int ldd, const float* stat_part, int64_t n_loss,
                          float grad_scale, float* loss, unsigned* status, hipStream_t st);
+
+// one hour of carried-state inference as ONE launch (gru_step.hip): T = 1, dense A with S <= 64, F = 13, H <= 128, B <= WGNN_STEP_MAX_B;
+// exact fp32 VALU arithmetic in every math mode.  Y [B][H] and hn [B][H] nullable (not both).
+#define WGNN_STEP_MAX_B 256
+bool gru_step_supported(int B, int S, int H);
+int launch_gru_step(int B, int S, int H, const float* A, const float* X, const float* W1, const float* b1, const float* W2,
+                    const float* b2, const float* Wih, const float* bih, const float* Whh, const float* bhh, const float* h0,
+                    float* Y, float* hn, hipStream_t st);
 
 int launch_mse(const float* Y, const float* L, int64_t n, float scale, float* dY, float* loss,
                float* ws, hipStream_t st);

@@ -387,19 +387,19 @@ __global__ void __launch_bounds__(CT) csr_layer_bwd_kernel(int ntiles, int S, Cs
 // ---- GRU cell, forward: one thread per (window, hidden unit) -----------------------------------
 __global__ void gru_cell_fwd_kernel(int B, int T, int t, int H, const float* __restrict__ GI, int ldgi,
                                     const float* __restrict__ GH, int ldgh, const float* __restrict__ bhh,
-                                    float* __restrict__ Y, float* __restrict__ gates) {
+                                    float* __restrict__ Y, float* __restrict__ gates, const float* __restrict__ h0) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)B * H) return;
   const int b = (int)(i / H), j = (int)(i % H);
   const size_t bt = (size_t)b * T + t;
   const float* gi = GI + bt * ldgi;
   float ghr, ghz, ghn, hprev = 0.f;
-  if (t == 0) {   // h0 = 0: gh = b_hh
+  if (t == 0 && !h0) {   // h0 = 0: gh = b_hh
     ghr = bhh[j]; ghz = bhh[H + j]; ghn = bhh[2 * H + j];
-  } else {
+  } else {               // (t = 0 with a caller's h0: the GEMM ran on it)
     const float* gh = GH + (size_t)b * ldgh;
     ghr = gh[j]; ghz = gh[H + j]; ghn = gh[2 * H + j];
-    hprev = Y[(bt - 1) * H + j];
+    hprev = t > 0 ? Y[(bt - 1) * H + j] : h0[i];
   }
   const float r = sigmoidf_(gi[j] + ghr);
   const float z = sigmoidf_(gi[H + j] + ghz);
@@ -444,7 +444,7 @@ __global__ void gru_cell_fwd_x3_kernel(int B, int T, int t, int H, int Hp, const
                                        const float* __restrict__ GH, int ldgh, const float* __restrict__ bhh,
                                        float* __restrict__ Y, float* __restrict__ gates, _Float16* __restrict__ yhi,
                                        _Float16* __restrict__ ylo, _Float16* __restrict__ chi,
-                                       _Float16* __restrict__ clo) {
+                                       _Float16* __restrict__ clo, const float* __restrict__ h0) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)B * Hp) return;
   const int b = (int)(i / Hp), j = (int)(i % Hp);
@@ -460,12 +460,12 @@ __global__ void gru_cell_fwd_x3_kernel(int B, int T, int t, int H, int Hp, const
   }
   const float* gi = GI + bt * ldgi;
   float ghr, ghz, ghn, hprev = 0.f;
-  if (t == 0) {
+  if (t == 0 && !h0) {
     ghr = bhh[j]; ghz = bhh[H + j]; ghn = bhh[2 * H + j];
   } else {
     const float* gh = GH + (size_t)b * ldgh;
     ghr = gh[j]; ghz = gh[H + j]; ghn = gh[2 * H + j];
-    hprev = Y[(bt - 1) * H + j];
+    hprev = t > 0 ? Y[(bt - 1) * H + j] : h0[(size_t)b * H + j];
   }
   const float r = sigmoid_fast(gi[j] + ghr);
   const float z = sigmoid_fast(gi[H + j] + ghz);
@@ -479,6 +479,18 @@ __global__ void gru_cell_fwd_x3_kernel(int B, int T, int t, int H, int Hp, const
     float* gp = gates + bt * 4 * H;
     gp[j] = r; gp[H + j] = z; gp[2 * H + j] = n; gp[3 * H + j] = ghn;
   }
+}
+
+// wgnn_fwd_state: the caller's h0 [B][H] as the compact [B][Hp] planes the step-0 GEMM reads ([h0 | 1 | 0..])
+__global__ void h0_planes_kernel(int B, int H, int Hp, const float* __restrict__ h0, _Float16* __restrict__ chi,
+                                 _Float16* __restrict__ clo) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)B * Hp) return;
+  const int b = (int)(i / Hp), j = (int)(i % Hp);
+  const float v = j < H ? h0[(size_t)b * H + j] : (j == H ? 1.f : 0.f);
+  const _Float16 hh = (_Float16)v;
+  chi[i] = hh;
+  if (clo) clo[i] = (_Float16)(v - (float)hh);
 }
 
 __device__ __forceinline__ void put_planes(_Float16* hi, _Float16* lo, size_t idx, float v) {
@@ -625,13 +637,16 @@ int launch_gcn2_csr_bwd(int ntiles, int S, int nnz, const void* csr, const float
 int gcn_csr_bwd_rows() { return CSR_BLOCKS; }
 
 // Y, gates from GI: per step gh = Hprev W_hh^T + b_hh (GEMM, skipped at t = 0 where h = 0) and the cell.
+// h0 (nullable, wgnn_fwd_state): [B][H] initial state; then step 0 runs the GEMM on it too.
 int launch_gru_gen_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
-                       float* gates, float* gh /*[B][3H]*/, hipStream_t st) {
+                       float* gates, float* gh /*[B][3H]*/, hipStream_t st, const float* h0) {
   const int nb = (int)(((long long)B * H + 255) / 256);
   for (int t = 0; t < T; ++t) {
-    if (t > 0) {
+    if (t > 0 || h0) {
       GemmArgs a = {};
-      a.A = Y + (size_t)(t - 1) * H; a.lda = T * H; a.a_kcontig = 1;     // row b = h_{t-1} of window b
+      if (t > 0) { a.A = Y + (size_t)(t - 1) * H; a.lda = T * H; }     // row b = h_{t-1} of window b
+      else { a.A = h0; a.lda = H; }
+      a.a_kcontig = 1;
       a.B = Whh; a.ldb = H; a.b_kcontig = 1;
       a.C = gh; a.ldc = 3 * H; a.M = B; a.N = 3 * H; a.K = H;
       a.bias = bhh; a.splitk = 1;
@@ -640,7 +655,7 @@ int launch_gru_gen_fwd(int B, int T, int H, const float* GI, int ldgi, const flo
     }
     PROF_LAUNCH("gru_cell_fwd_kernel", 0.0, (double)B * H * 4.0 * 9, st,
                 hipLaunchKernelGGL(gru_cell_fwd_kernel, dim3(nb), dim3(256), 0, st, B, T, t, H, GI, ldgi, gh, 3 * H, bhh,
-                                   Y, gates));
+                                   Y, gates, h0));
     WGNN_CHECK_LAUNCH();
   }
   return WGNN_OK;
@@ -672,7 +687,7 @@ int launch_gru_gen_bwd(int B, int T, int H, const float* Whh, const float* Y, co
 // y_planes: 2 x [B*T+1][Hp] halfs (hi, lo); gh: [B][ldgi] floats.
 int launch_gru_gen_fwd_x3(int B, int T, int H, const float* GI, int ldgi, const void* whh_planes, int np_g3,
                           const float* bhh, float* Y, float* gates, void* y_planes, float* gh, float* kpart,
-                          void* hc /*B*Hp floats*/, bool x3, hipStream_t st) {
+                          void* hc /*B*Hp floats*/, bool x3, hipStream_t st, const float* h0) {
   const int Hp = grux_hp(H);
   _Float16* yhi = (_Float16*)y_planes;
   _Float16* ylo = yhi + ((size_t)B * T + 1) * Hp;
@@ -681,14 +696,20 @@ int launch_gru_gen_fwd_x3(int B, int T, int H, const float* GI, int ldgi, const 
   _Float16* chi = (_Float16*)hc;
   _Float16* clo = chi + (size_t)B * Hp;
   const int nb = (int)(((long long)B * Hp + 255) / 256);
+  if (h0) {        // wgnn_fwd_state: step 0 multiplies the caller's state too
+    PROF_LAUNCH("h0_planes_kernel", 0.0, (double)B * (4.0 * H + 4.0 * Hp), st,
+                hipLaunchKernelGGL(h0_planes_kernel, dim3(nb), dim3(256), 0, st, B, H, Hp, h0, chi,
+                                   x3 ? clo : (_Float16*)nullptr));
+    WGNN_CHECK_LAUNCH();
+  }
   for (int t = 0; t < T; ++t) {
-    if (t > 0) {   // gh = [h_{t-1} | 1] (W_hh | b_hh)^T
+    if (t > 0 || h0) {   // gh = [h_{t-1} | 1] (W_hh | b_hh)^T
       int rc = launch_pgemm_nt(chi, clo, Hp, B, Hp, whh_planes, np_g3, gh, ldgi, 3 * H, nullptr, x3, kpart, st);
       if (rc != WGNN_OK) return rc;
     }
     PROF_LAUNCH("gru_cell_fwd_x3_kernel", 0.0, (double)B * H * 4.0 * 10, st,
                 hipLaunchKernelGGL(gru_cell_fwd_x3_kernel, dim3(nb), dim3(256), 0, st, B, T, t, H, Hp, GI, ldgi, gh, ldgi,
-                                   bhh, Y, gates, yhi, x3 ? ylo : (_Float16*)nullptr, chi, clo));
+                                   bhh, Y, gates, yhi, x3 ? ylo : (_Float16*)nullptr, chi, clo, h0));
     WGNN_CHECK_LAUNCH();
   }
   return WGNN_OK;

@@ -54,16 +54,22 @@ __host__ __device__ inline size_t gate_floats(int B, int T, int H) {
   return (size_t)((B + MB - 1) / MB) * T * ((H + 15) / 16) * 4 * 64 * 4;
 }
 
-template <int KS>   // k steps of 4 over the hidden index, 4 KS >= H, KS even
+template <int KS, bool ST = false>   // k steps of 4 over the hidden index, 4 KS >= H, KS even; ST: the wgnn_fwd_state instance
 __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, const float* __restrict__ GI, int ldgi,
                                                            const float* __restrict__ Whh,
                                                            const float* __restrict__ bhh, float* __restrict__ Y,
                                                            float* __restrict__ gates, const float* __restrict__ Lab,
                                                            float* __restrict__ stat_part, float* __restrict__ hprev,
-                                                           int hq, int last_only, float y_mul, float y_add) {
+                                                           int hq, int last_only, float y_mul, float y_add,
+                                                           const float* __restrict__ h0, float* __restrict__ hn) {
+  // h0 (nullable, wgnn_fwd_state): [B][H] initial state instead of zeros; hn (nullable): h_{T-1} [B][H], unrounded
+  if (!ST) { h0 = nullptr; hn = nullptr; }       // (the plain forward's instance compiles exactly as before)
   constexpr int KP = 4 * KS, HS = KP + 4;          // row stride: 16-byte aligned rows
   __shared__ __attribute__((aligned(16))) float hbuf[2 * MB * HS];
-  for (int i = threadIdx.x; i < 2 * MB * HS; i += NTHREADS) hbuf[i] = 0.f;
+  for (int i = threadIdx.x; i < 2 * MB * HS; i += NTHREADS) {
+    const int m = i / HS, k = i % HS;              // buffer 0 (m < MB) holds h_{-1}
+    hbuf[i] = (h0 && m < MB && k < H && blockIdx.x * MB + m < B) ? h0[(size_t)(blockIdx.x * MB + m) * H + k] : 0.f;
+  }
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lm = lane & 15, lk = lane >> 4;
@@ -128,6 +134,10 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
   };
   load_gi(0, gi, lab);
   float hold[4] = {0.f, 0.f, 0.f, 0.f};
+  if (h0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) hold[r] = rowok[r] ? h0[(size_t)(b0 + 4 * lk + r) * H + j] : 0.f;
+  }
   float ssum = 0.f, smax = 0.f;
   __syncthreads();
 
@@ -164,6 +174,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
         if (rowok[r]) {
           if (!last_only) Yw[(rowt[r] + t) * H + j] = hnew[r];
           else if (t == T - 1) Y[(size_t)(b0 + 4 * lk + r) * H + j] = hnew[r] * y_mul + y_add;
+          if (hn && t == T - 1) hn[(size_t)(b0 + 4 * lk + r) * H + j] = hnew[r];
           if (Hpw && t + 1 < T) Hpw[(rowt[r] + t + 1) * hq + j] = hnew[r];
           if (Lab) {
             const float dl = hnew[r] - lab[r];
@@ -415,7 +426,7 @@ int gru_msplit(int H) { return 4 * cdiv_i(2 * H, 4); }   // first GEMM row of th
 
 int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
                    float* gates, const float* labels, float* stat_part, float* hprev, int hq, int last_only, float y_mul,
-                   float y_add, hipStream_t st) {
+                   float y_add, hipStream_t st, const float* h0, float* hn) {
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
   if (last_only && (gates || labels || hprev)) return WGNN_ERR_UNSUPPORTED;
   if (hprev && (hq < H + 1 || hq % 4 != 0)) return WGNN_ERR_SHAPE;
@@ -427,8 +438,12 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
 #define FCASE(K)                                                                                                  \
   case K:                                                                                                         \
     PROF_LAUNCH("gru_fwd_kernel<" #K ">", fl, by, st,                                                             \
-                hipLaunchKernelGGL(gru_fwd_kernel<K>, dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, GI, ldgi, Whh, \
-                                   bhh, Y, gates, labels, stat_part, hprev, hq, last_only, y_mul, y_add));        \
+                if (h0 || hn) hipLaunchKernelGGL((gru_fwd_kernel<K, true>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, \
+                                                 GI, ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq, last_only, y_mul,  \
+                                                 y_add, h0, hn);                                                                \
+                else hipLaunchKernelGGL((gru_fwd_kernel<K, false>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, GI,    \
+                                        ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq, last_only, y_mul, y_add,         \
+                                        nullptr, nullptr));                                                                     \
     break
   switch (ks) {
     FCASE(4); FCASE(8); FCASE(12); FCASE(16); FCASE(20); FCASE(24); FCASE(26); FCASE(28); FCASE(32);

@@ -27,7 +27,7 @@ constexpr int small_threads(int HMAX) {
 static int small_hmax(int H) { return H <= 32 ? 32 : H <= 64 ? 64 : H <= 96 ? 96 : H <= 106 ? 108 : H <= 112 ? 112 : 128; }
 
 // ------------------------------------------------------------------------------------------------
-template <int HMAX, int WPB, int KSP>
+template <int HMAX, int WPB, int KSP, bool ST = false>   // ST: the wgnn_fwd_state instance (h0 / hn); without it both are ignored
 __global__ void __launch_bounds__(small_threads(HMAX)) gru_small_fwd_kernel(int B, int T, int H,
                                                                       const float* __restrict__ GI, int ldgi,
                                                                       const float* __restrict__ Whh,
@@ -35,7 +35,11 @@ __global__ void __launch_bounds__(small_threads(HMAX)) gru_small_fwd_kernel(int 
                                                                       float* __restrict__ Y, float* __restrict__ gates,
                                                                       int stage_w, float* __restrict__ hprev, int hq,
                                                                       const float* __restrict__ Lab,
-                                                                      float* __restrict__ stat_part) {
+                                                                      float* __restrict__ stat_part,
+                                                                      const float* __restrict__ h0,
+                                                                      float* __restrict__ hn) {
+  // h0 (nullable, wgnn_fwd_state): [B][H] initial state instead of zeros; hn (nullable): h_{T-1} [B][H], unrounded fp32
+  if (!ST) { h0 = nullptr; hn = nullptr; }       // (the plain forward's instance compiles exactly as before)
   // Lab + stat_part (wgnn_fwd_loss): this workgroup's sum of (h - label)^2 (and max |h - label|) goes to
   // stat_part[blockIdx.x] / stat_part[gridDim.x + blockIdx.x], the tag behind them says so; a forward without labels
   // clears the tag (as gru.hip / grux.hip)
@@ -87,7 +91,10 @@ __global__ void __launch_bounds__(small_threads(HMAX)) gru_small_fwd_kernel(int 
   }
   const float bh = part_id == 0 ? bhh[ic] : 0.f;
   const int b0 = blockIdx.x * WPB;
-  for (int k = threadIdx.x; k < WPB * HMAX; k += blockDim.x) (&hs[0][0])[k] = 0.f;
+  for (int k = threadIdx.x; k < WPB * HMAX; k += blockDim.x) {
+    const int b = b0 + k / HMAX, kk = k % HMAX;
+    (&hs[0][0])[k] = (h0 && kk < H && b < B) ? h0[(size_t)b * H + kk] : 0.f;
+  }
   // gate phase: thread j < H owns hidden unit j of every window of the workgroup
   const int j = threadIdx.x;
   const bool jv = j < H;
@@ -166,6 +173,11 @@ __global__ void __launch_bounds__(small_threads(HMAX)) gru_small_fwd_kernel(int 
     for (int wdw = 0; wdw < WPB; ++wdw)
 #pragma unroll
       for (int c = 0; c < 4; ++c) gi[wdw][c] = gin[wdw][c];
+  }
+  if (hn && jv) {   // h_{T-1}, from LDS after the last step's barrier (off the step loop: no extra registers in it)
+#pragma unroll
+    for (int wdw = 0; wdw < WPB; ++wdw)
+      if (b0 + wdw < B) hn[(size_t)(b0 + wdw) * H + j] = hs[wdw][j];
   }
   if (Lab) {   // fixed order: lanes (xor tree), then the waves
     __shared__ float red[2][SMALL_THREADS / 64];
@@ -375,33 +387,43 @@ bool gru_small_supported(int B, int H) { return H >= 1 && H <= 128 && B <= 768; 
     }                                                                                                            \
   } while (0)
 
-template <int HMAX>
+template <int HMAX, bool ST>
 static int launch_small_fwd_t(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
-                              float* gates, float* hprev, int hq, const float* labels, float* stat_part, hipStream_t st) {
+                              float* gates, float* hprev, int hq, const float* labels, float* stat_part, const float* h0,
+                              float* hn, hipStream_t st) {
   const size_t wbytes = (size_t)3 * H * H * sizeof(float);
   const int stage_w = wbytes <= 140 * 1024;
   const size_t smem = stage_w ? wbytes : 0;
   static std::atomic<unsigned long long> done{0};
   constexpr int KSP = small_ksp(HMAX);
-  if (ensure_dyn_smem((const void*)gru_small_fwd_kernel<HMAX, 1, KSP>, 140 * 1024, done) != WGNN_OK) return WGNN_ERR_HIP;
-  hipLaunchKernelGGL((gru_small_fwd_kernel<HMAX, 1, KSP>), dim3(B), dim3(KSP * cdiv_i(3 * H, 64) * 64), smem, st, B, T, H, GI,
-                     ldgi, Whh, bhh, Y, gates, stage_w, hprev, hq, labels, stat_part);
+  if (ensure_dyn_smem((const void*)gru_small_fwd_kernel<HMAX, 1, KSP, ST>, 140 * 1024, done) != WGNN_OK) return WGNN_ERR_HIP;
+  hipLaunchKernelGGL((gru_small_fwd_kernel<HMAX, 1, KSP, ST>), dim3(B), dim3(KSP * cdiv_i(3 * H, 64) * 64), smem, st, B, T, H, GI,
+                     ldgi, Whh, bhh, Y, gates, stage_w, hprev, hq, labels, stat_part, h0, hn);
   return WGNN_OK;
 }
 
+template <bool ST>
+static int launch_small_fwd_s(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
+                              float* gates, float* hprev, int hq, const float* labels, float* stat_part, const float* h0,
+                              float* hn, hipStream_t st) {
+  return small_hmax(H) == 32   ? launch_small_fwd_t<32, ST>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st)
+         : small_hmax(H) == 64  ? launch_small_fwd_t<64, ST>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st)
+         : small_hmax(H) == 96  ? launch_small_fwd_t<96, ST>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st)
+         : small_hmax(H) == 108 ? launch_small_fwd_t<108, ST>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st)
+         : small_hmax(H) == 112 ? launch_small_fwd_t<112, ST>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st)
+         : launch_small_fwd_t<128, ST>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st);
+}
+
 int launch_gru_small_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
-                         float* gates, float* hprev, int hq, const float* labels, float* stat_part, hipStream_t st) {
+                         float* gates, float* hprev, int hq, const float* labels, float* stat_part, hipStream_t st,
+                         const float* h0, float* hn) {
   if (!gru_small_supported(B, H)) return WGNN_ERR_UNSUPPORTED;
   if (hprev && (hq < H + 1 || hq % 4 != 0)) return WGNN_ERR_SHAPE;
   const double bt = (double)B * T;
   int rc = WGNN_OK;
   PROF_LAUNCH("gru_small_fwd_kernel", bt * 2.0 * 3 * H * H, bt * 4.0 * (3 * H + H + (gates ? 4 * H : 0) + (hprev ? hq : 0)), st,
-              rc = small_hmax(H) == 32   ? launch_small_fwd_t<32>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, st)
-                   : small_hmax(H) == 64  ? launch_small_fwd_t<64>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, st)
-                   : small_hmax(H) == 96  ? launch_small_fwd_t<96>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, st)
-                   : small_hmax(H) == 108 ? launch_small_fwd_t<108>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, st)
-                   : small_hmax(H) == 112 ? launch_small_fwd_t<112>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, st)
-                                          : launch_small_fwd_t<128>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, st));
+              rc = (h0 || hn) ? launch_small_fwd_s<true>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st)
+                              : launch_small_fwd_s<false>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st));
   if (rc != WGNN_OK) return rc;
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;

@@ -93,7 +93,7 @@ __device__ __forceinline__ void put_split(_Float16* hi, _Float16* lo, int idx, f
 // instance keeps the direct per-lane accesses (the row path was 30 % slower there: measured 116 vs 84 us).
 // GI: the input projection [B*T][ldgi] in the 3H layout -- fp32 for the split (X3) instances, ONE fp16 plane for the one-pass
 // fp16 instances (WGNN_MATH_F16: pgemm_nt's OUT16 epilogue; half the bytes of the largest intermediate of that mode)
-template <int KS, bool X3, bool IO>   // K steps of 32 over the hidden index (+ the ones column): KS = ceil((H+1)/32)
+template <int KS, bool X3, bool IO, bool ST = false>   // K steps of 32 over the hidden index (+ the ones column): KS = ceil((H+1)/32)
 __global__ void __launch_bounds__(NTHREADS) grux_fwd_kernel(int B, int T, int H, const void* __restrict__ GI, int ldgi,
                                                             const float* __restrict__ Whh,
                                                             const float* __restrict__ bhh, void* __restrict__ Y,
@@ -101,7 +101,12 @@ __global__ void __launch_bounds__(NTHREADS) grux_fwd_kernel(int B, int T, int H,
                                                             _Float16* __restrict__ yp_lo, unsigned* status,
                                                             const void* __restrict__ Lab,
                                                             float* __restrict__ stat_part, int io, int last_only,
-                                                            float y_mul, float y_add) {
+                                                            float y_mul, float y_add, const float* __restrict__ h0,
+                                                            float* __restrict__ hn) {
+  // h0 (nullable, wgnn_fwd_state): [B][H] fp32 initial state instead of zeros, split into the planes like every h_t (a value
+  // beyond fp16's range is reported as WGNN_STATUS_ACT_RANGE); hn (nullable): h_{T-1} [B][H] as fp32, never rounded to `io`.
+  // ST: the wgnn_fwd_state instance; the plain forward's (ST = false) ignores h0 / hn and compiles exactly as before
+  if (!ST) { h0 = nullptr; hn = nullptr; }
   // last_only (wgnn_fwd_last, inference): Y is [B][H] fp32 and receives only h_{T-1} * y_mul + y_add -- the evaluation
   // read-out of src/main.py:103,116 without writing (and re-reading) the other T-1 rows
   constexpr int HP = 32 * KS;                      // plane row width (halfs): h, then 1.0 at column H, then 0
@@ -109,7 +114,18 @@ __global__ void __launch_bounds__(NTHREADS) grux_fwd_kernel(int B, int T, int H,
   // h state is double-buffered: step t reads buffer t&1 and writes h_t into the other one, so a single
   // barrier per step suffices (the recurrence is latency-bound: every barrier is on the critical path)
   __shared__ __attribute__((aligned(16))) _Float16 hbuf[2 * 2 * MB * HS];
-  for (int i = threadIdx.x; i < 2 * 2 * MB * HS; i += NTHREADS) hbuf[i] = (_Float16)0.f;
+  bool h0bad = false;
+  for (int i = threadIdx.x; i < 2 * 2 * MB * HS; i += NTHREADS) {
+    const int m = (i % (MB * HS)) / HS, k = i % HS, b = blockIdx.x * MB + m;
+    float v = 0.f;                                 // buffer 0 (i < 2 MB HS) holds h_{-1}: hi plane, then lo plane
+    if (h0 && i < 2 * MB * HS && k < H && b < B) {
+      const float x = h0[(size_t)b * H + k];
+      h0bad |= out_of_fp16_range(x);
+      v = i < MB * HS ? x : (X3 ? x - (float)(_Float16)x : 0.f);
+    }
+    hbuf[i] = (_Float16)v;
+  }
+  report_status(status, h0bad, WGNN_STATUS_ACT_RANGE);
   __syncthreads();
   if (threadIdx.x < 2 * MB)   // ones column of both buffers' hi planes (W_hh fragments are 0 there)
     hbuf[(threadIdx.x / MB) * 2 * MB * HS + (threadIdx.x % MB) * HS + H] = (_Float16)1.f;
@@ -250,6 +266,10 @@ __global__ void __launch_bounds__(NTHREADS) grux_fwd_kernel(int B, int T, int H,
   stage_lab(0);
   load_gi(0, gi, lab);
   float hold[4] = {0.f, 0.f, 0.f, 0.f};
+  if (h0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) hold[r] = rowok[r] ? h0[(size_t)(b0 + 4 * g + r) * H + j] : 0.f;
+  }
   __syncthreads();
 
   for (int t = 0; t < T; ++t) {
@@ -298,6 +318,7 @@ __global__ void __launch_bounds__(NTHREADS) grux_fwd_kernel(int B, int T, int H,
           if (!last_only) ((float*)Yw)[(rowt[r] + t) * H + j] = hnew[r];
           else if (t == T - 1) ((float*)Y)[(size_t)(b0 + 4 * g + r) * H + j] = hnew[r] * y_mul + y_add;
         }
+        if (hn && rowok[r] && t == T - 1) hn[(size_t)(b0 + 4 * g + r) * H + j] = hnew[r];
         if (rowok[r] && Lab) {                          // the statistics use the unrounded h
           const float dl = hnew[r] - (IO ? lt[(4 * g + r) * HY + j] : lab[r]);
           ssum = fmaf(dl, dl, ssum);
@@ -336,6 +357,7 @@ __global__ void __launch_bounds__(NTHREADS) grux_fwd_kernel(int B, int T, int H,
     __syncthreads();                               // h_t complete; everyone is done reading h_{t-1}
 #pragma unroll
     for (int i = 0; i < (IO ? NU : 0); ++i) {      // row (b, t) of Y, 2 elements per thread, rounded once to the I/O type
+      if (ST && !Y) break;                         // (wgnn_fwd_state with Y = NULL: h_n only)
       if (u_n[i] == 0) continue;
       const float v0 = yt[u_lds[i]], v1 = yt[u_lds[i] + 1];
       const int o = u_glb[i] + t * H;
@@ -751,8 +773,9 @@ int launch_grux_fwd(int B, int T, int H, const void* GI /*fp32 rows (x3) or fp16
                     float* gates, void* y_planes /*nullable: 2 x [B*T+1][grux_hp(H)] halfs*/, bool x3, unsigned* status,
                     const void* labels /*nullable*/, float* stat_part /*2 * grux_blocks(B) floats if labels*/, int io,
                     int last_only /*Y is [B][H]: only h_{T-1} * y_mul + y_add is written (fp32 I/O, no stash)*/,
-                    float y_mul, float y_add, hipStream_t st) {
+                    float y_mul, float y_add, hipStream_t st, const float* h0, float* hn) {
   if (last_only && (io != 0 || gates || y_planes || labels)) return WGNN_ERR_UNSUPPORTED;
+  if (!Y && (!io || !hn || last_only)) return WGNN_ERR_NULL;   // Y = NULL: 16-bit I/O with h_n only (fp32: last_only into h_n)
   _Float16* yh = (_Float16*)y_planes;
   _Float16* yl = yh ? yh + ((size_t)B * T + 1) * grux_hp(H) : nullptr;   // each plane has B*T + 1 rows
   const double bt = (double)B * T;
@@ -762,8 +785,12 @@ int launch_grux_fwd(int B, int T, int H, const void* GI /*fp32 rows (x3) or fp16
   const dim3 grid(cdiv_i(B, MB));
 #define FLAUNCH(K, X3V, IOV, NAME)                                                                                 \
   PROF_LAUNCH(NAME, fl, by, st,                                                                                    \
-              hipLaunchKernelGGL((grux_fwd_kernel<K, X3V, IOV>), grid, dim3(NTHREADS), 0, st, B, T, H, GI, ldgi, Whh, bhh, Y, \
-                                 gates, yh, yl, status, labels, stat_part, io, last_only, y_mul, y_add))
+              if (h0 || hn) hipLaunchKernelGGL((grux_fwd_kernel<K, X3V, IOV, true>), grid, dim3(NTHREADS), 0, st, B, T, H, GI,  \
+                                               ldgi, Whh, bhh, Y, gates, yh, yl, status, labels, stat_part, io, last_only,     \
+                                               y_mul, y_add, h0, hn);                                                          \
+              else hipLaunchKernelGGL((grux_fwd_kernel<K, X3V, IOV, false>), grid, dim3(NTHREADS), 0, st, B, T, H, GI, ldgi,   \
+                                      Whh, bhh, Y, gates, yh, yl, status, labels, stat_part, io, last_only, y_mul, y_add,      \
+                                      nullptr, nullptr))
 #define FCASE(K)                                                                                                   \
   if (x3 && !io) FLAUNCH(K, true, false, "grux_fwd_kernel<" #K ">");                                               \
   else if (x3) FLAUNCH(K, true, true, "grux_fwd_kernel<" #K ">");                                                  \

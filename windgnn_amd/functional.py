@@ -162,6 +162,44 @@ def gcn_gru_forward_raw(A, X, params: Sequence[torch.Tensor], math=_lib.MATH_F32
     return Y, stash, d
 
 
+def gcn_gru_state(A, X, params: Sequence[torch.Tensor], math=_lib.MATH_F32, h0=None, want_y=True, h_n=None):
+    """(Y or None, h_n) = wgnn_fwd_state(...): the forward from the initial state h0 [B,H] (None = zeros, exactly wgnn_fwd's
+    recurrence), returning the unrounded fp32 last state h_n [B,H] as nn.GRU does.  No autograd (inference only).  X is
+    [B,T,S,F]; Y comes back in X's dtype.  h_n: optional caller buffer [B,H] fp32 (it must not share memory with h0).
+    T == 1 with a dense A (S <= 64), fp32 X, H <= 128 and B <= _lib.STEP_MAX_B is ONE kernel launch."""
+    lib = _lib.load()
+    _require_gpu(X, io_ok=True)
+    _require_gpu(*params)
+    _require_contiguous(X=X, **{"params[%d]" % i: q for i, q in enumerate(params)})
+    if X.dim() != 4:
+        raise RuntimeError("windgnn_amd: X must be [B, T, S, 13], got %s" % (tuple(X.shape),))
+    B, T, S, F = X.shape
+    A, fmt, nnz = _adj(A, S)
+    H = params[5].shape[1]
+    for name, t in (("h0", h0), ("h_n", h_n)):
+        if t is None:
+            continue
+        _require_gpu(t)
+        _require_contiguous(**{name: t})
+        if tuple(t.shape) != (B, H) or t.device != X.device:
+            raise RuntimeError("windgnn_amd: %s must be [B, H] = [%d, %d] float32 on %s, got %s on %s"
+                               % (name, B, H, X.device, tuple(t.shape), t.device))
+    d = _lib.Dims(B, T, S, F, H, math, fmt, nnz, _IO_OF[X.dtype])
+    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
+    if ws_bytes == 0:
+        _lib.check(-5 if F == 13 else -2, "wgnn_workspace_bytes(B=%d,T=%d,S=%d,F=%d,H=%d,math=%d,io=%s)"
+                   % (B, T, S, F, H, math, X.dtype))
+    ws = _Workspace.get(X.device, ws_bytes)
+    Y = torch.empty(B, T, H, dtype=X.dtype, device=X.device) if want_y else None
+    if h_n is None:
+        h_n = torch.empty(B, H, dtype=torch.float32, device=X.device)
+    ps = _params_struct(_lib.Params, params)
+    rc = lib.wgnn_fwd_state(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(h0), _ptr(Y), _ptr(h_n), _ptr(ws), ws_bytes,
+                            _stream())
+    _lib.check(rc, "wgnn_fwd_state")
+    return Y, h_n
+
+
 def gcn_gru_backward_raw(d, A, X, params, Y, dY, stash, grads: Sequence[torch.Tensor], part: int = 7, stream=None):
     """part bit mask (wgnn_bwd_part): 1 = BPTT recurrence, 4 = GRU weight-gradient GEMMs, 2 = dg + GCN backward."""
     lib = _lib.load()
