@@ -8,6 +8,7 @@
  *   wgnn_fwd            GCN_GRU.forward            src/step6_gcn_gru_combined_model.py:13-27
  *   wgnn_fwd_state      the same with nn.GRU's hx / h_n (inference, carried state)
  *                       (GraphConvLayer.forward x2  src/step5_gcn_layer_model.py:13-23, nn.GRU :23)
+ *   wgnn_fwd_state_stash / wgnn_bwd_state_part   the same for training: autograd through hx and h_n (truncated BPTT)
  *   wgnn_bwd            loss.backward() through it  src/main.py:79
  *   wgnn_gcn_layer_fwd  GraphConvLayer.forward      src/step5_gcn_layer_model.py:13-23
  *   wgnn_gcn_layer_bwd  its autograd backward       src/main.py:79
@@ -40,7 +41,8 @@
 extern "C" {
 #endif
 
-#define WGNN_VERSION 122 /* 0.1.2: wgnn_params.prepared, wgnn_finish, WGNN_BWD_DEFER; 121: WGNN_FINISH_ADAM_GRU / _CONV; 122: wgnn_set_option */
+#define WGNN_VERSION 122 /* 0.1.2: wgnn_params.prepared, wgnn_finish, WGNN_BWD_DEFER; 121: WGNN_FINISH_ADAM_GRU / _CONV; 122: wgnn_set_option
+                            (+ wgnn_fwd_state, wgnn_state_stash_bytes / wgnn_fwd_state_stash / wgnn_bwd_state_part: additions only) */
 
 /* Status block: the first 256 bytes of every `workspace` passed to wgnn_fwd / wgnn_bwd* belong to the library as a
  * sticky status area that kernels only ever OR into; word 0 (uint32) holds the bits below.  The caller zeroes the
@@ -227,10 +229,33 @@ int wgnn_fwd_last(const wgnn_dims* d, const float* A, const void* X, const wgnn_
  * convolutions, the input projection, W_hh h0 and the GRU cell -- as ONE kernel (csrc/gru_step.hip) in exact fp32 VALU
  * arithmetic in every math mode: within each mode's tolerance of the windowed forward, not bitwise equal to it.  Other
  * T == 1 calls take the general path with h0.  wgnn_params.prepared is not needed by the step (and ignored by it).
- * Training with a carried state (truncated BPTT: h0 in the backward's dW_hh rows, dh0) is not provided: wgnn_bwd* assume
- * h0 = 0 and take no stash from this call. */
+ * This call keeps no stash; training with a carried state takes the pair below. */
 int wgnn_fwd_state(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const float* h0, void* Y,
                    float* h_n, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Carried state for training (truncated BPTT): nn.GRU's forward(input, hx) -> (output, h_n) and its autograd backward
+ * through hx and h_n.
+ *   wgnn_state_stash_bytes  the stash of this pair (>= wgnn_stash_bytes(d)): the stash of wgnn_fwd, plus a copy of h0 and
+ *                           the window-start rows [h0[b] | 1] of the dW_hh product's operand.  Dims only.
+ *   wgnn_fwd_state_stash    wgnn_fwd with a stash (Y and stash required), started from h0 [B,H] fp32 (NULL = zeros); the
+ *                           unrounded h_{T-1} goes to h_n [B,H] (NULL = not written).  Same dims, workspace, math modes, io types
+ *                           and adjacency formats as wgnn_fwd; h0, Y and h_n may not overlap (WGNN_ERR_UNSUPPORTED).  The
+ *                           stash records h0, so the backward takes no h0 argument (and cannot be handed a different one).
+ *                           The one-kernel hourly step of wgnn_fwd_state is not used: T = 1 runs the windowed kernels.
+ *   wgnn_bwd_state_part     gradients of sum(Y * dY) + sum(h_n * dh_n) w.r.t. the 8 parameters (overwritten) and, if dh0 is
+ *                           not NULL, dh0 [B,H] fp32 w.r.t. h0; dh_n [B,H] fp32 or NULL (= zeros).  `stash` must come from
+ *                           wgnn_fwd_state_stash with the same dims.  The part bits, WGNN_BWD_DEFER, the ordering rules and the
+ *                           workspace (wgnn_workspace_bytes) are wgnn_bwd_part's, and wgnn_finish follows it unchanged; dh0 is
+ *                           final after the call that has part bit 1.  dh0 may not overlap dY, dh_n or the stash.
+ * With h0 = dh_n = dh0 = NULL the pair computes exactly wgnn_fwd + wgnn_bwd_part, bit for bit.  Chunks compose: forward
+ * X[:, :T1] and X[:, T1:] with h_n handed over as h0, then the backward of the second chunk and that of the first with the
+ * second's dh0 as its dh_n give the gradients of the whole window (within each mode's tolerance). */
+size_t wgnn_state_stash_bytes(const wgnn_dims* d);
+int wgnn_fwd_state_stash(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const float* h0, void* Y,
+                         float* h_n, void* stash, void* workspace, size_t workspace_bytes, void* stream);
+int wgnn_bwd_state_part(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* Y,
+                        const float* dY, const float* dh_n, const void* stash, const wgnn_grads* g, float* dh0,
+                        void* workspace, size_t workspace_bytes, void* stream, int part /* as wgnn_bwd_part */);
 
 /* Gradients of sum(Y * dY) w.r.t. the 8 parameters (overwritten, not accumulated).
  * No dX and no dA: neither requires grad in the reference (src/main.py:26,

@@ -67,6 +67,12 @@ EXPORTS = {
                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "wgnn_fwd_state": (C.c_int, [C.POINTER(Dims), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wgnn_state_stash_bytes": (C.c_size_t, [C.POINTER(Dims)]),
+    "wgnn_fwd_state_stash": (C.c_int, [C.POINTER(Dims), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wgnn_bwd_state_part": (C.c_int, [C.POINTER(Dims), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.POINTER(Grads), C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.c_void_p, C.c_int]),
     "wgnn_bwd": (C.c_int, [C.POINTER(Dims), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,
                            C.c_void_p, C.POINTER(Grads), C.c_void_p, C.c_size_t, C.c_void_p]),
     "wgnn_bwd_part": (C.c_int, [C.POINTER(Dims), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,

@@ -46,6 +46,12 @@ struct Layout {
   size_t ws_gh, ws_h1, ws_yp, ws_hhp_f, ws_kp_f, ws_hc, ws_du, ws_dhz, ws_dhw, ws_hhp_b, ws_kp_b, ws_dc;   // general GRU / GCN scratch
   size_t ws_ntk_f, ws_ntk_b;                     // exact fp32, few rows: split-K partial sums of the GI / dg products
   size_t ws_aimg_f, ws_aimg_b;                   // large-shape NT plane GEMMs (configs[4]): the A operand (g / dGI) rewritten as an image
+  // the state stash (wgnn_state_stash_bytes): the stash plus a copy of h0, and the dW_hh product's B operand holds h0 at every
+  // window start -- fp16-plane modes: B more plane rows [h0[b] | 1 | 0..] behind the B*T rows of h_t (plane_rows = B*T + B);
+  // exact fp32: the [Hprev | 1 | 0..] rows on every path, with row (b, 0) = h0[b]
+  bool state;
+  size_t plane_rows;                             // rows per Y plane: B*T + 1, or B*T + B in the state stash
+  size_t st_h0;                                  // [B][H] fp32: h0 (zeros when the caller passed none)
 };
 
 // (min_rows = 64 measured against 128 / 192 / 256 at B*T = 6144 in round 3: fewer, longer K chunks cost the split-K GEMMs more
@@ -58,8 +64,9 @@ int pick_splitk(size_t BT, int tiles, int target_wgs, int min_rows) {
   return sk < 1 ? 1 : sk;
 }
 
-Layout make_layout(const wgnn_dims* d) {
+Layout make_layout(const wgnn_dims* d, bool state = false) {
   Layout L;
+  L.state = state;
   L.x3 = d->math != WGNN_MATH_F32;                                      // the fp16-plane kernel family
   L.gen_gcn = d->adj_format == WGNN_ADJ_CSR;
   L.gen_gru = L.x3 ? !grux_shape_supported(d->H) : !gru_shape_supported(d->H);
@@ -120,7 +127,8 @@ Layout make_layout(const wgnn_dims* d) {
                                                                    : (L.rec32 ? gru_gates_floats(d->B, d->T, d->H) : 0);
     L.st_gates = o; o += al(plain > rec ? plain : rec);
   }
-  L.st_yp = o; o += al((L.BT + 1) * L.Hp);   // two planes of B*T + 1 rows
+  L.plane_rows = L.BT + (state ? (size_t)d->B : 1);
+  L.st_yp = o; o += al(L.plane_rows * L.Hp);   // two planes of B*T + 1 rows (state stash: B*T + B)
   L.st_h1 = o; o += al(L.gen_gcn ? L.BT * L.I : 0);
   {  // partial pairs (sum | max) + the tag word: one pair per workgroup of the forward recurrence (B / 16, or B for gru_small)
     const size_t nb = L.small ? (size_t)gru_small_blocks(d->B) : (size_t)grux_blocks(d->B);
@@ -131,7 +139,9 @@ Layout make_layout(const wgnn_dims* d) {
   L.gi_stash = (x3 && !L.gen_gru && (d->math == WGNN_MATH_F16X3 || d->math == WGNN_MATH_F16X3G)) || L.rec32;   // (and gru.hip's)
   L.st_GI = o; o += al(L.gi_stash ? L.BT * L.Gp : 0);
   L.hq = (int)rup(L.H + 1, 16);
-  L.st_hprev = o; o += al(L.g32tn ? L.BT * (size_t)L.hq : 0);     // [Hprev|1] with 16-byte aligned rows (exact fp32, large B*T)
+  const bool hprev_rows = L.g32tn || (state && !x3);                // (the state stash: every exact-fp32 path)
+  L.st_hprev = o; o += al(hprev_rows ? L.BT * (size_t)L.hq : 0);   // [Hprev|1] with 16-byte aligned rows (exact fp32, large B*T)
+  L.st_h0 = o; o += al(state ? (size_t)d->B * L.H : 0);
   L.stash_floats = o;
   L.dghn = (x3 && !L.gen_gru) || (L.rec32 && L.g32tn);
   // WGNN_MATH_F16X3G, from B*T = 4096 rows: dGI / dGHn travel as ONE fp16 plane (relative rounding 2^-12, independent per
@@ -382,10 +392,12 @@ size_t wgnn_stash_bytes(const wgnn_dims* d) {
 // g_in != nullptr (wgnn_gru_fwd): the recurrent half alone on a caller-supplied g [B*T][S*F]; A, X and the conv slots of p unused.
 // state (wgnn_fwd_state): no stash; the recurrence starts from h0 (nullable = zeros: then exactly wgnn_fwd's kernels) and
 // leaves the unrounded h_{T-1} in hn (nullable); Y may be NULL (then only hn is written).
+// sst (wgnn_fwd_state_stash): the training forward from h0 (nullable) into the state stash (make_layout(d, true)), which also
+// receives h0 itself and the window-start rows of the dW_hh product's B operand; hn nullable.
 static int fwd_impl(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* labels,
                     void* Y, void* stash, void* workspace, size_t workspace_bytes, void* stream, float* last = nullptr,
                     float wind_min = 0.f, float wind_max = 1.f, const float* g_in = nullptr, bool state = false,
-                    const float* h0 = nullptr, float* hn = nullptr) {
+                    const float* h0 = nullptr, float* hn = nullptr, bool sst = false) {
   // every read-out path forms its multiplier the same way, (wind_max - wind_min) in fp32, from the caller's two values
   const float y_mul = wind_max - wind_min, y_add = wind_min;
   int rc = check_dims(d);
@@ -395,7 +407,7 @@ static int fwd_impl(const wgnn_dims* d, const float* A, const void* X, const wgn
       !p->b_ih || !p->b_hh)
     return WGNN_ERR_NULL;
   if (g_in && (d->math != WGNN_MATH_F32 || d->io != WGNN_IO_F32 || d->adj_format != WGNN_ADJ_DENSE)) return WGNN_ERR_UNSUPPORTED;
-  const Layout L = make_layout(d);
+  const Layout L = make_layout(d, sst);
   if (workspace_bytes < sizeof(float) * L.fwd_floats) return WGNN_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
@@ -420,6 +432,36 @@ static int fwd_impl(const wgnn_dims* d, const float* A, const void* X, const wgn
   // the staged image of [W_ih | b_ih]: the caller's (wgnn_prepare_weights / wgnn_finish keep it current) or rebuilt here
   const bool kept = p->prepared != nullptr && L.prep_kind != 0;
   float* img_f = kept ? (float*)p->prepared + L.prep_f : ws + L.ws_planes_f;
+  // the state stash: h0 (or zeros) is kept for the backward, and once the recurrence has run, the window-start rows of the
+  // dW_hh product's B operand are set to it (they are written as zeros / [0 | 1] by the recurrence kernels)
+  float* h0c = sst ? sf + L.st_h0 : nullptr;
+  if (sst) {
+    const size_t hb = (size_t)d->B * d->H * sizeof(float);
+    if ((h0 ? hipMemcpyAsync(h0c, h0, hb, hipMemcpyDeviceToDevice, (hipStream_t)stream)
+            : hipMemsetAsync(h0c, 0, hb, (hipStream_t)stream)) != hipSuccess)
+      return WGNN_ERR_HIP;
+  }
+  auto state_rows = [&]() -> int {
+    if (L.x3) {     // B planes rows [h0[b] | 1 | 0..] behind the B*T rows of h_t (pgemm_tn's per-window extra rows)
+      _Float16* yh = (_Float16*)(sf + L.st_yp);
+      return launch_h0_planes(d->B, d->H, (int)L.Hp, h0c, yh + L.BT * L.Hp, yh + (L.plane_rows + L.BT) * L.Hp,
+                              (hipStream_t)stream);
+    }
+    float* hp = sf + L.st_hprev;
+    const size_t hq4 = (size_t)L.hq * 4, h4 = (size_t)d->H * 4;
+    if (L.gen_gru && L.BT > 1 &&       // the general recurrence writes no [Hprev | 1] rows: row k = Y row k - 1 (the ones
+        hipMemcpy2DAsync(hp + L.hq, hq4, Y, h4, h4, L.BT - 1, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+      return WGNN_ERR_HIP;             // column is gemm_f32's virtual one)
+    return hipMemcpy2DAsync(hp, (size_t)d->T * hq4, h0c, h4, h4, d->B, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess
+               ? WGNN_OK : WGNN_ERR_HIP;
+  };
+  // the register-resident split-fp16 recurrence of a training forward (with labels: wgnn_fwd_loss)
+  auto grux_train = [&]() -> int {
+    const int r = launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, Y, gates, sf ? sf + L.st_yp : nullptr,
+                                  full, status, sf ? labels : nullptr, sf ? sf + L.st_stats : nullptr, d->io, 0, 1.f, 0.f, st,
+                                  h0, hn, sst ? L.plane_rows : 0);
+    return (r != WGNN_OK || !sst) ? r : state_rows();
+  };
 
   if (x3) {
     // W_ih as stage-major fp16 planes [np_g3][Ip] with b_ih folded into column I (g's ones column)
@@ -444,8 +486,7 @@ static int fwd_impl(const wgnn_dims* d, const float* A, const void* X, const wgn
         return launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, lo ? (void*)hn : Y, nullptr, nullptr, full,
                                status, nullptr, nullptr, d->io, lo, 1.f, 0.f, st, h0, lo ? nullptr : hn);
       }
-      return launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, Y, gates, sf ? sf + L.st_yp : nullptr,
-                             full, status, sf ? labels : nullptr, sf ? sf + L.st_stats : nullptr, d->io, 0, 1.f, 0.f, st);
+      return grux_train();
     }
     if (L.gen_gcn)    // CSR adjacency: fp32 SpMM layers, layer 2 writes the g planes
       rc = launch_gcn2_csr_fwd((int)L.BT, d->S, d->nnz, A, (const float*)X, p->conv1_weight, p->conv1_bias,
@@ -466,8 +507,10 @@ static int fwd_impl(const wgnn_dims* d, const float* A, const void* X, const wgn
       if (rc != WGNN_OK) return rc;
       rc = launch_gru_gen_fwd_x3(d->B, d->T, d->H, GI, (int)L.Gp, ws + L.ws_hhp_f, L.np_g3, p->b_hh, (float*)Y, gates,
                                  sf ? sf + L.st_yp : ws + L.ws_yp, ws + L.ws_gh, ws + L.ws_kp_f, ws + L.ws_hc, full,
-                                 st, h0);
+                                 st, h0, sst ? L.plane_rows : 0);
       if (rc == WGNN_OK && state) return copy_hn((const float*)Y);
+      if (rc == WGNN_OK && sst) rc = copy_hn((const float*)Y);
+      if (rc == WGNN_OK && sst) return state_rows();
       if (rc != WGNN_OK || !last) return rc;
       return wgnn_predict_last((const float*)Y, d->B, d->T, d->H, wind_min, wind_max, last, stream);
     }
@@ -481,8 +524,7 @@ static int fwd_impl(const wgnn_dims* d, const float* A, const void* X, const wgn
     }
     // labels (wgnn_fwd_loss): the recurrence also leaves the MSE partial sums / maxima of (Y - labels) in the stash
     // (a stash without labels gets its tag word cleared: bit 8 of a later backward cannot trust stale statistics)
-    return launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, Y, gates, sf ? sf + L.st_yp : nullptr,
-                           full, status, sf ? labels : nullptr, sf ? sf + L.st_stats : nullptr, d->io, 0, 1.f, 0.f, st);
+    return grux_train();
   }
   if (L.gen_gcn) {
     float* h1 = sf ? sf + L.st_h1 : ws + L.ws_h1;    // layer-1 activations: kept for the backward if there is a stash
@@ -512,22 +554,27 @@ static int fwd_impl(const wgnn_dims* d, const float* A, const void* X, const wgn
     rc = launch_gemm_f32_nt(ga, gemm_f32_nt_splitk(ga.M, ga.N, ga.K) > 1 && L.BT < 65536 ? ws + L.ws_ntk_f : nullptr, st);
   }
   if (rc != WGNN_OK) return rc;
-  float* hprev = (sf && L.g32tn) ? sf + L.st_hprev : nullptr;      // [Hprev | 1 | 0..] rows for the backward's dW_hh GEMM
+  float* hprev = (sf && (L.g32tn || sst)) ? sf + L.st_hprev : nullptr;      // [Hprev | 1 | 0..] rows for the backward's dW_hh GEMM
   if (L.gen_gru) {
     rc = launch_gru_gen_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, (float*)Y, gates, ws + L.ws_gh, st, h0);
     if (rc == WGNN_OK && state) return copy_hn((const float*)Y);
+    if (rc == WGNN_OK && sst) rc = copy_hn((const float*)Y);
+    if (rc == WGNN_OK && sst) return state_rows();
   } else if (L.small) {   // few windows: one per workgroup instead of sixteen
     rc = launch_gru_small_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, (float*)Y, gates, hprev, L.hq,
                               sf ? (const float*)labels : nullptr, sf ? sf + L.st_stats : nullptr, st, h0, hn);
+    if (rc == WGNN_OK && sst) return state_rows();
   } else if (state)   // the register-resident recurrence: h_n from its registers (and with Y = NULL the last_only form alone)
     return launch_gru_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, hn_only ? hn : (float*)Y, nullptr, nullptr, nullptr,
                           nullptr, 0, hn_only ? 1 : 0, 1.f, 0.f, st, h0, hn_only ? nullptr : hn);
   else if (last)      // the register-resident recurrence writes the read-out itself
     return launch_gru_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, last, nullptr, nullptr, nullptr, nullptr, 0, 1,
                           y_mul, y_add, st);
-  else                // labels (wgnn_fwd_loss): the recurrence also leaves the MSE partial sums of (Y - labels) in the stash
-    return launch_gru_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, (float*)Y, gates,
-                          sf ? (const float*)labels : nullptr, sf ? sf + L.st_stats : nullptr, hprev, L.hq, 0, 1.f, 0.f, st);
+  else {              // labels (wgnn_fwd_loss): the recurrence also leaves the MSE partial sums of (Y - labels) in the stash
+    rc = launch_gru_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, (float*)Y, gates,
+                        sf ? (const float*)labels : nullptr, sf ? sf + L.st_stats : nullptr, hprev, L.hq, 0, 1.f, 0.f, st, h0, hn);
+    return (rc != WGNN_OK || !sst) ? rc : state_rows();
+  }
   if (rc != WGNN_OK || !last) return rc;
   return wgnn_predict_last((const float*)Y, d->B, d->T, d->H, wind_min, wind_max, last, stream);
 }
@@ -573,6 +620,31 @@ int wgnn_fwd_state(const wgnn_dims* d, const float* A, const void* X, const wgnn
                            p->conv2_bias, p->w_ih, p->b_ih, p->w_hh, p->b_hh, h0, (float*)Y, h_n, (hipStream_t)stream);
   return fwd_impl(d, A, X, p, nullptr, Y, nullptr, workspace, workspace_bytes, stream, nullptr, 0.f, 1.f, nullptr, true, h0,
                   h_n);
+}
+
+size_t wgnn_state_stash_bytes(const wgnn_dims* d) {
+  if (check_dims(d) != WGNN_OK) return 0;
+  return sizeof(float) * make_layout(d, true).stash_floats;
+}
+
+int wgnn_fwd_state_stash(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const float* h0, void* Y,
+                         float* h_n, void* stash, void* workspace, size_t workspace_bytes, void* stream) {
+  int rc = check_dims(d);
+  if (rc != WGNN_OK) return rc;
+  if (!A || !X || !p || !Y || !stash || !workspace) return WGNN_ERR_NULL;
+  if (!p->conv1_weight || !p->conv1_bias || !p->conv2_weight || !p->conv2_bias || !p->w_ih || !p->w_hh || !p->b_ih ||
+      !p->b_hh)
+    return WGNN_ERR_NULL;
+  // as wgnn_fwd_state: h0 is read while h_n / Y are written
+  const size_t hb = (size_t)d->B * d->H * sizeof(float);
+  const size_t yb = (size_t)d->B * d->T * d->H * (d->io == WGNN_IO_F32 ? 4 : 2);
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    return a && b && (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
+  };
+  if (overlap(h0, hb, h_n, hb) || overlap(h0, hb, Y, yb) || overlap(Y, yb, h_n, hb)) return WGNN_ERR_UNSUPPORTED;
+  if (workspace_bytes < sizeof(float) * make_layout(d, true).fwd_floats) return WGNN_ERR_WORKSPACE;
+  return fwd_impl(d, A, X, p, nullptr, Y, stash, workspace, workspace_bytes, stream, nullptr, 0.f, 1.f, nullptr, false, h0,
+                  h_n, /*sst=*/true);
 }
 
 size_t wgnn_prepared_bytes(const wgnn_dims* d) {
@@ -675,7 +747,10 @@ namespace {
 // of p and of g unused.
 int bwd_impl(const wgnn_dims* d, const float* A, const void* Xv, const wgnn_params* p, const void* Yv,
              const float* dY, const void* labelsv, float grad_scale, float* loss, const void* stash,
-             const wgnn_grads* g, void* workspace, size_t workspace_bytes, void* stream, int which, float* dg_out = nullptr) {
+             const wgnn_grads* g, void* workspace, size_t workspace_bytes, void* stream, int which, float* dg_out = nullptr,
+             bool sst = false, const float* dhn = nullptr, float* dh0 = nullptr) {
+  // sst (wgnn_bwd_state_part): the stash is a state stash; the BPTT kernels start from dh_n (nullable) and h0 (the stash's
+  // copy) and leave dh_{-1} in dh0 (nullable); the dW_hh products read h0 at every window start
   if (which < 1 || which > 31 || (which & 7) == 0) return WGNN_ERR_SHAPE;
   const bool do_rec = which & 1, do_gcn = which & 2, do_wg = which & 4;
   const bool defer = which & WGNN_BWD_DEFER;          // partial sums stay in the workspace for wgnn_finish
@@ -692,12 +767,14 @@ int bwd_impl(const wgnn_dims* d, const float* A, const void* Xv, const wgnn_para
     return WGNN_ERR_NULL;
   if (dg_out && (d->math != WGNN_MATH_F32 || d->io != WGNN_IO_F32 || d->adj_format != WGNN_ADJ_DENSE || which != 7))
     return WGNN_ERR_UNSUPPORTED;
-  const Layout L = make_layout(d);
+  const Layout L = make_layout(d, sst);
   if (workspace_bytes < sizeof(float) * L.bwd_floats) return WGNN_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
   unsigned* status = (unsigned*)workspace;
   const float* sf = (const float*)stash;
+  const BwdState sbs = {sst ? sf + L.st_h0 : nullptr, dhn, dh0};
+  const BwdState* sb = sst ? &sbs : nullptr;
   const float* gact = sf + L.st_g;
   const float* gates = sf + L.st_gates;
   float* dGI = ws + L.ws_dGI;
@@ -733,6 +810,7 @@ int bwd_impl(const wgnn_dims* d, const float* A, const void* Xv, const wgnn_para
     _Float16* dGHh = (_Float16*)dGH;
     const _Float16* gh = (const _Float16*)gact;
     const _Float16* yph = (const _Float16*)(sf + L.st_yp);
+    const _Float16* ypl = yph + L.plane_rows * L.Hp;
     const size_t PG = L.BT * L.Gp;
     const _Float16* dGIlo = L.dgi1 ? nullptr : dGIh + PG;                    // nullptr: single-plane A operand, two passes
     const _Float16* dGHnlo = L.dgi1 ? nullptr : dGHh + L.BT * (size_t)L.hn;
@@ -742,32 +820,35 @@ int bwd_impl(const wgnn_dims* d, const float* A, const void* Xv, const wgnn_para
       else if (fused_loss)   // loss, the range scale and the dY coefficient in one pass over Y and the labels
         rc = launch_mse_stats(Y, labels, (int64_t)L.BT * L.H, grad_scale, loss, scales, scales + 64, st);
       else
-        rc = launch_amax_scale(dY, (int64_t)L.BT * L.H, scales, scales + 64, st);   // 448 partials after the scales
+        rc = launch_amax_scale(dY, (int64_t)L.BT * L.H, scales, scales + 64, st,    // 448 partials after the scales (896
+                               dhn, dhn ? (int64_t)d->B * d->H : 0);                 // with dh_n: the carry is scaled too)
       if (rc != WGNN_OK) return rc;
       if (L.gen_gru) {
         rc = launch_split_weight2(p->w_hh, (int)L.G3, (int)L.H, 1, nullptr, 0, ws + L.ws_hhp_b, L.np_h, (int)L.Gp, status,
                                   st);
         if (rc != WGNN_OK) return rc;
         rc = launch_gru_gen_bwd_x3(d->B, d->T, d->H, ws + L.ws_hhp_b, L.np_h, Y, dY, gates, scales, dGIh, dGHh,
-                                   (int)L.Gp, ws + L.ws_dhz, ws + L.ws_dhw, ws + L.ws_kp_b, ws + L.ws_dc, full, st);
+                                   (int)L.Gp, ws + L.ws_dhz, ws + L.ws_dhw, ws + L.ws_kp_b, ws + L.ws_dc, full, st, sb);
       } else {
         rc = launch_grux_bwd(d->B, d->T, d->H, p->w_hh, Yv, fused_loss ? nullptr : dY, fused_loss ? labelsv : nullptr,
                              d->io, gates, L.gi_stash ? sf + L.st_GI : nullptr, (int)L.Gp, scales, dGIh, dGHh, (int)L.Gp, full,
                              fused_loss && stats_ready ? sf + L.st_stats : nullptr, (int64_t)L.BT * L.H, grad_scale, loss,
-                             scales, status, L.dgi1 ? 0 : 1, st);
+                             scales, status, L.dgi1 ? 0 : 1, st, sb);
       }
       if (rc != WGNN_OK) return rc;
     }
     if (do_wg) {
-      // dW_hh | db_hh = dGH^T [Hprev | 1]   (Hprev row (b,t) = Y-plane row (b,t-1); row B*T stands in at t = 0).
+      // dW_hh | db_hh = dGH^T [Hprev | 1]   (Hprev row (b,t) = Y-plane row (b,t-1); row B*T stands in at t = 0, or in the
+      // state stash row B*T + b, window b's own [h0 | 1]).
       // Register-resident recurrence: dGH = [dGI_r | dGI_z | dGHn], the A operand takes GEMM rows < msplit from the dGI
       // planes and rows >= msplit from the dGHn planes; the reduce kernel maps the GEMM rows back to W_hh's rows.
       if (L.dghn) {
-        rc = launch_pgemm_tn(dGIh, dGIlo, (int)L.Gp, yph, yph + (L.BT + 1) * L.Hp, (int)L.Hp, d->T, (int)L.BT,
-                             L.sk_hh, part_hh, L.m_hh, (int)L.H + 1, full, dGHh, dGHnlo, L.hn, L.msplit, st, /*b_stream=*/true);
+        rc = launch_pgemm_tn(dGIh, dGIlo, (int)L.Gp, yph, ypl, (int)L.Hp, d->T, (int)L.BT, L.sk_hh, part_hh, L.m_hh,
+                             (int)L.H + 1, full, dGHh, dGHnlo, L.hn, L.msplit, st, /*b_stream=*/true, /*per_window=*/sst);
       } else {
-        rc = launch_pgemm_tn(dGHh, L.gen2p ? nullptr : dGHh + PG, (int)L.Gp, yph, yph + (L.BT + 1) * L.Hp, (int)L.Hp, d->T,
-                             (int)L.BT, L.sk_hh, part_hh, (int)L.G3, (int)L.H + 1, full, nullptr, nullptr, 0, 0, st);
+        rc = launch_pgemm_tn(dGHh, L.gen2p ? nullptr : dGHh + PG, (int)L.Gp, yph, ypl, (int)L.Hp, d->T, (int)L.BT, L.sk_hh,
+                             part_hh, (int)L.G3, (int)L.H + 1, full, nullptr, nullptr, 0, 0, st, /*b_stream=*/false,
+                             /*per_window=*/sst);
       }
       if (rc != WGNN_OK) return rc;
       // dW_ih | db_ih = dGI^T [g | 1]
@@ -827,15 +908,15 @@ int bwd_impl(const wgnn_dims* d, const float* A, const void* Xv, const wgnn_para
   if (do_rec) {
     if (L.gen_gru)
       rc = launch_gru_gen_bwd(d->B, d->T, d->H, p->w_hh, Y, dY, gates, dGI, dGH, (int)L.Gp, ws + L.ws_dhz,
-                              ws + L.ws_dhw, st);
+                              ws + L.ws_dhw, st, sb);
     else if (L.small)
       rc = launch_gru_small_bwd(d->B, d->T, d->H, p->w_hh, Y, fused_loss ? nullptr : dY, fused_loss ? labels : nullptr, gates,
                                 dGI, dGH, (int)L.Gp, fused_loss ? sf + L.st_stats : nullptr, (int64_t)L.BT * L.H, grad_scale,
-                                loss, status, st);
+                                loss, status, st, sb);
     else   // register-resident recurrence: dGHn alone when the dW_hh GEMM has the two-source A operand; fused loss
       rc = launch_gru_bwd(d->B, d->T, d->H, p->w_hh, Y, fused_loss ? nullptr : dY, fused_loss ? labels : nullptr, gates,
                           sf + L.st_GI, (int)L.Gp, dGI, (int)L.Gp, L.dghn ? dGH : nullptr, L.dghn ? nullptr : dGH,
-                          fused_loss ? sf + L.st_stats : nullptr, (int64_t)L.BT * L.H, grad_scale, loss, status, st);
+                          fused_loss ? sf + L.st_stats : nullptr, (int64_t)L.BT * L.H, grad_scale, loss, status, st, sb);
     if (rc != WGNN_OK) return rc;
   }
   if (do_wg) {
@@ -852,6 +933,7 @@ int bwd_impl(const wgnn_dims* d, const float* A, const void* Xv, const wgnn_para
       GemmArgs a = {};
       a.A = dGH; a.lda = (int)L.Gp; a.a_kcontig = 0;
       a.B = Y; a.ldb = (int)L.H; a.b_kcontig = 0; a.ones_col = 1; a.shift_T = d->T;
+      if (sst) { a.B = sf + L.st_hprev; a.ldb = L.hq; a.shift_T = 0; }   // the state stash's rows, h0 at window starts
       a.M = (int)L.G3; a.N = (int)L.H + 1; a.K = (int)L.BT;
       a.splitk = L.sk_hh; a.partial = part_hh;
       rc = launch_gemm_f32(a, st);
@@ -919,6 +1001,23 @@ int wgnn_bwd_mse_part(const wgnn_dims* d, const float* A, const void* X, const w
   if (!labels) return WGNN_ERR_NULL;
   return bwd_impl(d, A, X, p, Y, nullptr, labels, grad_scale, loss, stash, g, workspace, workspace_bytes, stream,
                   which);
+}
+
+int wgnn_bwd_state_part(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* Y,
+                        const float* dY, const float* dh_n, const void* stash, const wgnn_grads* g, float* dh0,
+                        void* workspace, size_t workspace_bytes, void* stream, int part) {
+  int rc = check_dims(d);
+  if (rc != WGNN_OK) return rc;
+  if (!dY) return WGNN_ERR_NULL;
+  // dh0 is written while dY, dh_n and the stash are read
+  const size_t hb = (size_t)d->B * d->H * sizeof(float), yb = (size_t)d->B * d->T * d->H * sizeof(float);
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    return a && b && (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
+  };
+  if (overlap(dh0, hb, dh_n, hb) || overlap(dh0, hb, dY, yb) || overlap(dh0, hb, stash, wgnn_state_stash_bytes(d)))
+    return WGNN_ERR_UNSUPPORTED;
+  return bwd_impl(d, A, X, p, Y, dY, nullptr, 1.f, nullptr, stash, g, workspace, workspace_bytes, stream, part, nullptr,
+                  /*sst=*/true, dh_n, dh0);
 }
 
 int wgnn_gru_fwd(const wgnn_dims* d, const float* g, const wgnn_params* p, void* Y, void* stash, void* workspace,

@@ -81,6 +81,17 @@ __device__ __forceinline__ void report_status(unsigned* status, bool bad, unsign
   if (status && bad) atomicOr(status, bit);   // call once per thread, after the loop (error path only)
 }
 
+// Carried-state boundaries of a BPTT recurrence (wgnn_bwd_state_part): h0 [B][H] fp32 (the state stash's copy) is h_{-1};
+// dhn [B][H] (nullable = zeros) seeds the carry at t = T-1 (scaled by scales[0] in the split-fp16 kernels); dh0 [B][H]
+// (nullable) receives dh_{-1} (times scales[1] there).  The BPTT kernels take it as an optional trailing argument pack, so the
+// instances without it -- the plain backward's -- keep their argument list and their code.
+struct BwdState { const float* h0; const float* dhn; float* dh0; };
+template <typename... S>
+__device__ __forceinline__ BwdState bwd_state(S... s) {
+  if constexpr (sizeof...(S) == 0) return BwdState{nullptr, nullptr, nullptr};
+  else return BwdState{s...};
+}
+
 // ---- internal launchers (defined in the .hip files, used by api.hip) -------------------------
 struct GemmArgs {
   const float* A; int lda; int a_kcontig;   // A(m,k) = a_kcontig ? A[m*lda+k] : A[k*lda+m]
@@ -113,7 +124,8 @@ int launch_gemm32_tn(const float* A, int lda, const float* B, int ldb, int K, in
 
 int launch_mse_stats(const float* Y, const float* L, int64_t n, float grad_scale, float* loss, float* scales,
                      float* part /*>= 2048 floats*/, hipStream_t st);
-int launch_amax_scale(const float* x, int64_t n, float* scales, float* part /*>= 448 floats*/, hipStream_t st);
+int launch_amax_scale(const float* x, int64_t n, float* scales, float* part /*>= 448 floats, 896 with x2*/, hipStream_t st,
+                      const float* x2 = nullptr, int64_t n2 = 0 /*a second tensor the scale must cover (dh_n)*/);
 // split-fp16 GRU recurrences with register-resident weights (grux.hip)
 bool grux_shape_supported(int H);
 int grux_hp(int H);   // row width (halfs) of the Y planes: 32*ceil((H+1)/32)
@@ -122,7 +134,8 @@ int launch_grux_fwd(int B, int T, int H, const void* GI /*fp32 rows if x3, else 
                     float* gates, void* y_planes, bool x3, unsigned* status, const void* labels, float* stat_part,
                     int io /*wgnn_io of Y and labels*/, int last_only, float y_mul, float y_add, hipStream_t st,
                     const float* h0 = nullptr /*[B][H] initial state (wgnn_fwd_state)*/,
-                    float* hn = nullptr /*[B][H] fp32 h_{T-1}; Y may then be NULL with 16-bit I/O*/);
+                    float* hn = nullptr /*[B][H] fp32 h_{T-1}; Y may then be NULL with 16-bit I/O*/,
+                    size_t plane_rows = 0 /*rows per y plane: 0 = B*T + 1 (wgnn_stash_bytes' layout)*/);
 int grux_blocks(int B);   // workgroups of launch_grux_fwd = MSE partial pairs it writes when given labels
 int mse_stats_blocks();
 // exactly one of dY / labels is non-null (labels: dY = (Y - labels) * scales[2], see launch_mse_stats)
@@ -135,8 +148,10 @@ int launch_grux_bwd(int B, int T, int H, const float* Whh, const void* Y, const 
                     const float* gates, const float* GI /*split modes: the forward's GI rows (stash), n recomputed*/, int ldgi,
                     const float* scales, void* dGI_planes, void* dGHn_planes, int ldd, bool x3, const float* stat_part,
                     int64_t n_loss, float grad_scale, float* loss, float* scales_out, unsigned* status,
-                    int write_lo /*0: dGI / dGHn as one fp16 plane (x3 only)*/, hipStream_t st);
+                    int write_lo /*0: dGI / dGHn as one fp16 plane (x3 only)*/, hipStream_t st,
+                    const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given, no labels*/);
 #define WGNN_STATS_TAG 20261004.0f   // float word behind the MSE partial pairs: "wgnn_fwd_loss wrote these"
+
 
 int launch_gcn_partial_reduce(const float* partial, int nblk, float* dW1, float* db1, float* dW2, float* db2,
                               unsigned* status, hipStream_t st);
@@ -209,7 +224,8 @@ int launch_pgemm_nt(const void* Ahi, const void* Alo, int lda, int M, int Kp, co
 // A2hi != null: columns m >= msplit of the A operand are column m - msplit of the planes A2hi / A2lo (row stride lda2)
 int launch_pgemm_tn(const void* Ahi, const void* Alo, int lda, const void* Bhi, const void* Blo, int ldb, int shift_T,
                     int K, int splitk, float* partial, int Mout, int Nout, bool x3, const void* A2hi, const void* A2lo,
-                    int lda2, int msplit, hipStream_t st, bool b_stream = false /*B: old read-once data, non-temporal*/);
+                    int lda2, int msplit, hipStream_t st, bool b_stream = false /*B: old read-once data, non-temporal*/,
+                    bool per_window = false /*shift_T: window b starts at the extra row K + b, not K*/);
 // general shapes (general.hip): CSR adjacency (blob layout: see include/windgnn.h) and any hidden width
 size_t gcn_csr_bwd_partial_floats();
 int launch_gcn2_csr_fwd(int ntiles, int S, int nnz, const void* csr, const float* X, const float* W1, const float* b1,
@@ -221,14 +237,18 @@ int launch_gcn2_csr_bwd(int ntiles, int S, int nnz, const void* csr, const float
                         hipStream_t st);
 int launch_gru_gen_fwd_x3(int B, int T, int H, const float* GI, int ldgi, const void* whh_planes, int np_g3,
                           const float* bhh, float* Y, float* gates, void* y_planes, float* gh, float* kpart, void* hc,
-                          bool x3, hipStream_t st, const float* h0 = nullptr);
+                          bool x3, hipStream_t st, const float* h0 = nullptr,
+                          size_t plane_rows = 0 /*rows per y plane: 0 = B*T + 1 (wgnn_stash_bytes' layout)*/);
+int launch_h0_planes(int B, int H, int Hp, const float* h0, void* hi, void* lo, hipStream_t st);
 int launch_gru_gen_bwd_x3(int B, int T, int H, const void* whhT_planes, int np_h, const float* Y, const float* dY,
                           const float* gates, const float* scales, void* dgi_planes, void* dgh_planes, int ldd,
-                          float* dhz, float* dhw, float* kpart, void* dc, bool x3, hipStream_t st);
+                          float* dhz, float* dhw, float* kpart, void* dc, bool x3, hipStream_t st,
+                          const BwdState* state = nullptr);
 int launch_gru_gen_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
                        float* gates, float* gh, hipStream_t st, const float* h0 = nullptr);
 int launch_gru_gen_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* gates,
-                       float* dGI, float* dGH, int ldd, float* dhz, float* dhw, hipStream_t st);
+                       float* dGI, float* dGH, int ldd, float* dhz, float* dhw, hipStream_t st,
+                       const BwdState* state = nullptr);
 size_t gcn1_csr_bwd_ws_floats(int ntiles, int S);
 int launch_gcn1_csr_fwd(int ntiles, int S, int nnz, const void* csr, const float* X, const float* W, const float* b,
                         float* out, hipStream_t st);
@@ -252,7 +272,8 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
 //   dGI's) OR the full dGH [B*T][ldd]; stat_part (nullable, with labels): loss[0] is finalised from the forward's partials
 int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
                    const float* gates, const float* GI /*forward's GI rows (stash): n is recomputed*/, int ldgi, float* dGI, int ldd, float* dGHn, float* dGH, const float* stat_part,
-                   int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st);
+                   int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st,
+                   const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given*/);
 bool gru_shape_supported(int H);
 size_t gru_gates_floats(int B, int T, int H);
 int gru_blocks(int B);
@@ -268,7 +289,8 @@ int gru_small_blocks(int B);
 // exactly one of dY / labels (labels: dY formed in the kernel, loss finalised from stat_part as launch_gru_bwd)
 int launch_gru_small_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
                          const float* gates, float* dGI, float* dGH, int ldd, const float* stat_part, int64_t n_loss,
-                         float grad_scale, float* loss, unsigned* status, hipStream_t st);
+                         float grad_scale, float* loss, unsigned* status, hipStream_t st,
+                         const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given*/);
 
 // one hour of carried-state inference as ONE launch (gru_step.hip): T = 1, dense A with S <= 64, F = 13, H <= 128, B <= WGNN_STEP_MAX_B;
 // exact fp32 VALU arithmetic in every math mode.  Y [B][H] and hn [B][H] nullable (not both).

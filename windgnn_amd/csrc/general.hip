@@ -412,19 +412,25 @@ __global__ void gru_cell_fwd_kernel(int B, int T, int t, int H, const float* __r
 }
 
 // backward cell: dh = dY_t + dhz + dhw (the two carries of step t+1)
+// St (empty, or one BwdState: wgnn_bwd_state_part): at t = T-1 the carry is dh_n, at t = 0 h_{-1} = h0 (dh_{-1} is
+// dhz + dhw after the step-0 GEMM: state_dh0_kernel)
+template <typename... St>
 __global__ void gru_cell_bwd_kernel(int B, int T, int t, int H, const float* __restrict__ Y,
                                     const float* __restrict__ dY, const float* __restrict__ gates,
                                     float* __restrict__ dhz, const float* __restrict__ dhw, float* __restrict__ dGI,
-                                    float* __restrict__ dGH, int ldd) {
+                                    float* __restrict__ dGH, int ldd, St... state) {
+  constexpr bool ST = sizeof...(St) > 0;
+  const BwdState sb = bwd_state(state...);
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)B * H) return;
   const int b = (int)(i / H), j = (int)(i % H);
   const size_t bt = (size_t)b * T + t;
   float dh = dY[bt * H + j];
   if (t < T - 1) dh += dhz[i] + (dhw ? dhw[i] : 0.f);
+  else if (ST && sb.dhn) dh += sb.dhn[i];
   const float* gp = gates + bt * 4 * H;
   const float r = gp[j], z = gp[H + j], n = gp[2 * H + j], ghn = gp[3 * H + j];
-  const float hprev = t > 0 ? Y[(bt - 1) * H + j] : 0.f;
+  const float hprev = t > 0 ? Y[(bt - 1) * H + j] : (ST ? sb.h0[i] : 0.f);
   const float dn = dh * (1.f - z);
   const float dzg = dh * (hprev - n);
   const float dnt = dn * (1.f - n * n);
@@ -493,29 +499,41 @@ __global__ void h0_planes_kernel(int B, int H, int Hp, const float* __restrict__
   if (clo) clo[i] = (_Float16)(v - (float)hh);
 }
 
+// wgnn_bwd_state_part: dh_{-1} = dhz + dhw of step 0 (times s = scales[1] in the split modes, else s = NULL: 1)
+__global__ void state_dh0_kernel(int n, const float* __restrict__ dhz, const float* __restrict__ dhw,
+                                 const float* __restrict__ s, float* __restrict__ dh0) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dh0[i] = (dhz[i] + dhw[i]) * (s ? s[1] : 1.f);
+}
+
 __device__ __forceinline__ void put_planes(_Float16* hi, _Float16* lo, size_t idx, float v) {
   const _Float16 h = (_Float16)v;
   hi[idx] = h;
   if (lo) lo[idx] = (_Float16)(v - (float)h);
 }
 
-// dY is scaled by scales[0] on the way in; everything downstream stays in those units
+// dY is scaled by scales[0] on the way in; everything downstream stays in those units.  St: as gru_cell_bwd_kernel (dh_n is
+// scaled like dY)
+template <typename... St>
 __global__ void gru_cell_bwd_x3_kernel(int B, int T, int t, int H, const float* __restrict__ Y,
                                        const float* __restrict__ dY, const float* __restrict__ gates,
                                        const float* __restrict__ scales, float* __restrict__ dhz,
                                        const float* __restrict__ dhw, _Float16* __restrict__ gihi,
                                        _Float16* __restrict__ gilo, _Float16* __restrict__ ghhi,
                                        _Float16* __restrict__ ghlo, int ldd, _Float16* __restrict__ chi,
-                                       _Float16* __restrict__ clo) {
+                                       _Float16* __restrict__ clo, St... state) {
+  constexpr bool ST = sizeof...(St) > 0;
+  const BwdState sb = bwd_state(state...);
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)B * H) return;
   const int b = (int)(i / H), j = (int)(i % H);
   const size_t bt = (size_t)b * T + t;
   float dh = dY[bt * H + j] * scales[0];
   if (t < T - 1) dh += dhz[i] + dhw[i];
+  else if (ST && sb.dhn) dh += sb.dhn[i] * scales[0];
   const float* gp = gates + bt * 4 * H;
   const float r = gp[j], z = gp[H + j], n = gp[2 * H + j], ghn = gp[3 * H + j];
-  const float hprev = t > 0 ? Y[(bt - 1) * H + j] : 0.f;
+  const float hprev = t > 0 ? Y[(bt - 1) * H + j] : (ST ? sb.h0[i] : 0.f);
   const float dn = dh * (1.f - z);
   const float dzg = dh * (hprev - n);
   const float dnt = dn * (1.f - n * n);
@@ -662,15 +680,21 @@ int launch_gru_gen_fwd(int B, int T, int H, const float* GI, int ldgi, const flo
 }
 
 // dGI, dGH rows for all (b, t); dhz / dhw: scratch [B][H] each
+// state (wgnn_bwd_state_part): h0 / dh_n at the two boundaries, and the step-0 GEMM runs too, for dh_{-1} -> state->dh0
 int launch_gru_gen_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* gates,
-                       float* dGI, float* dGH, int ldd, float* dhz, float* dhw, hipStream_t st) {
+                       float* dGI, float* dGH, int ldd, float* dhz, float* dhw, hipStream_t st, const BwdState* state) {
   const int nb = (int)(((long long)B * H + 255) / 256);
   for (int t = T - 1; t >= 0; --t) {
-    PROF_LAUNCH("gru_cell_bwd_kernel", 0.0, (double)B * H * 4.0 * 14, st,
-                hipLaunchKernelGGL(gru_cell_bwd_kernel, dim3(nb), dim3(256), 0, st, B, T, t, H, Y, dY, gates, dhz, dhw,
-                                   dGI, dGH, ldd));
+    if (state)
+      PROF_LAUNCH("gru_cell_bwd_kernel", 0.0, (double)B * H * 4.0 * 14, st,
+                  hipLaunchKernelGGL(gru_cell_bwd_kernel<BwdState>, dim3(nb), dim3(256), 0, st, B, T, t, H, Y, dY, gates, dhz,
+                                     dhw, dGI, dGH, ldd, *state));
+    else
+      PROF_LAUNCH("gru_cell_bwd_kernel", 0.0, (double)B * H * 4.0 * 14, st,
+                  hipLaunchKernelGGL(gru_cell_bwd_kernel<>, dim3(nb), dim3(256), 0, st, B, T, t, H, Y, dY, gates, dhz, dhw,
+                                     dGI, dGH, ldd));
     WGNN_CHECK_LAUNCH();
-    if (t > 0) {   // dhw = dGH_t W_hh: the recurrent part of dh_{t-1}
+    if (t > 0 || (state && state->dh0)) {   // dhw = dGH_t W_hh: the recurrent part of dh_{t-1}
       GemmArgs a = {};
       a.A = dGH + (size_t)t * ldd; a.lda = T * ldd; a.a_kcontig = 1;
       a.B = Whh; a.ldb = H; a.b_kcontig = 0;
@@ -678,6 +702,10 @@ int launch_gru_gen_bwd(int B, int T, int H, const float* Whh, const float* Y, co
       int rc = launch_gemm_f32(a, st);
       if (rc != WGNN_OK) return rc;
     }
+  }
+  if (state && state->dh0) {
+    hipLaunchKernelGGL(state_dh0_kernel, dim3(nb), dim3(256), 0, st, B * H, dhz, dhw, nullptr, state->dh0);
+    WGNN_CHECK_LAUNCH();
   }
   return WGNN_OK;
 }
@@ -687,10 +715,10 @@ int launch_gru_gen_bwd(int B, int T, int H, const float* Whh, const float* Y, co
 // y_planes: 2 x [B*T+1][Hp] halfs (hi, lo); gh: [B][ldgi] floats.
 int launch_gru_gen_fwd_x3(int B, int T, int H, const float* GI, int ldgi, const void* whh_planes, int np_g3,
                           const float* bhh, float* Y, float* gates, void* y_planes, float* gh, float* kpart,
-                          void* hc /*B*Hp floats*/, bool x3, hipStream_t st, const float* h0) {
+                          void* hc /*B*Hp floats*/, bool x3, hipStream_t st, const float* h0, size_t plane_rows) {
   const int Hp = grux_hp(H);
   _Float16* yhi = (_Float16*)y_planes;
-  _Float16* ylo = yhi + ((size_t)B * T + 1) * Hp;
+  _Float16* ylo = yhi + (plane_rows ? plane_rows : (size_t)B * T + 1) * Hp;
   // The GEMM reads h_{t-1} from a compact [B][Hp] copy: rows of the [B*T][Hp] planes are T*Hp apart, and 64-byte
   // row segments that far apart (0.6 MB at H = 12288) cost 5x in the staging loads.
   _Float16* chi = (_Float16*)hc;
@@ -715,11 +743,21 @@ int launch_gru_gen_fwd_x3(int B, int T, int H, const float* GI, int ldgi, const 
   return WGNN_OK;
 }
 
+// wgnn_fwd_state_stash: the rows [h0[b] | 1 | 0..] of the dW_hh product's B operand, as [B][Hp] fp16 planes (hi, lo)
+int launch_h0_planes(int B, int H, int Hp, const float* h0, void* hi, void* lo, hipStream_t st) {
+  const int nb = (int)(((long long)B * Hp + 255) / 256);
+  PROF_LAUNCH("h0_planes_kernel", 0.0, (double)B * (4.0 * H + 4.0 * Hp), st,
+              hipLaunchKernelGGL(h0_planes_kernel, dim3(nb), dim3(256), 0, st, B, H, Hp, h0, (_Float16*)hi, (_Float16*)lo));
+  WGNN_CHECK_LAUNCH();
+  return WGNN_OK;
+}
+
 // whhT_planes: split(W_hh^T) as launch_split_weight2(w_hh, 3H, H, 1, nullptr, 0, ., pgemm_nt_np(H), ldd) makes it;
 // dgi / dgh planes: hi [B*T][ldd] followed by lo [B*T][ldd]
 int launch_gru_gen_bwd_x3(int B, int T, int H, const void* whhT_planes, int np_h, const float* Y, const float* dY,
                           const float* gates, const float* scales, void* dgi_planes, void* dgh_planes, int ldd,
-                          float* dhz, float* dhw, float* kpart, void* dc /*B*ldd floats*/, bool x3, hipStream_t st) {
+                          float* dhz, float* dhw, float* kpart, void* dc /*B*ldd floats*/, bool x3, hipStream_t st,
+                          const BwdState* state) {
   const size_t PG = (size_t)B * T * ldd;
   _Float16* chi = (_Float16*)dc;               // compact [B][ldd] planes of the current step's dgh
   _Float16* clo = chi + (size_t)B * ldd;
@@ -729,14 +767,23 @@ int launch_gru_gen_bwd_x3(int B, int T, int H, const void* whhT_planes, int np_h
   _Float16* ghlo = x3 ? ghhi + PG : nullptr;
   const int nb = (int)(((long long)B * H + 255) / 256);
   for (int t = T - 1; t >= 0; --t) {
-    PROF_LAUNCH("gru_cell_bwd_x3_kernel", 0.0, (double)B * H * 4.0 * 14, st,
-                hipLaunchKernelGGL(gru_cell_bwd_x3_kernel, dim3(nb), dim3(256), 0, st, B, T, t, H, Y, dY, gates, scales,
-                                   dhz, dhw, gihi, gilo, ghhi, ghlo, ldd, chi, x3 ? clo : (_Float16*)nullptr));
+    if (state)
+      PROF_LAUNCH("gru_cell_bwd_x3_kernel", 0.0, (double)B * H * 4.0 * 14, st,
+                  hipLaunchKernelGGL(gru_cell_bwd_x3_kernel<BwdState>, dim3(nb), dim3(256), 0, st, B, T, t, H, Y, dY, gates,
+                                     scales, dhz, dhw, gihi, gilo, ghhi, ghlo, ldd, chi, x3 ? clo : (_Float16*)nullptr, *state));
+    else
+      PROF_LAUNCH("gru_cell_bwd_x3_kernel", 0.0, (double)B * H * 4.0 * 14, st,
+                  hipLaunchKernelGGL(gru_cell_bwd_x3_kernel<>, dim3(nb), dim3(256), 0, st, B, T, t, H, Y, dY, gates, scales,
+                                     dhz, dhw, gihi, gilo, ghhi, ghlo, ldd, chi, x3 ? clo : (_Float16*)nullptr));
     WGNN_CHECK_LAUNCH();
-    if (t > 0) {   // dhw = dGH_t W_hh, stays in scaled units
+    if (t > 0 || (state && state->dh0)) {   // dhw = dGH_t W_hh, stays in scaled units
       int rc = launch_pgemm_nt(chi, clo, ldd, B, ldd, whhT_planes, np_h, dhw, H, H, nullptr, x3, kpart, st);
       if (rc != WGNN_OK) return rc;
     }
+  }
+  if (state && state->dh0) {
+    hipLaunchKernelGGL(state_dh0_kernel, dim3(nb), dim3(256), 0, st, B * H, dhz, dhw, scales, state->dh0);
+    WGNN_CHECK_LAUNCH();
   }
   return WGNN_OK;
 }

@@ -233,7 +233,9 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
 //   dar = dr r (1-r), daz = dz z (1-z);  dgi = [dar, daz, dnt], dgh = [dar, daz, dnt r]
 //   dh_next = dh z + dgh W_hh
 // Outputs for the GEMMs that follow: dGI rows [B*T][ldd] (3H layout, zero K padding) and dGHn = dnt r rows [B*T][hn].
-template <int KS3>   // k steps of 4 over the gate-row index, 4 KS3 >= 3H, KS3 even
+// St (empty, or one BwdState: wgnn_bwd_state_part): h_{-1} = h0, the carry starts at dh_n, and the step at t = 0 also forms
+// dh_{-1} = dh z + dgh W_hh into dh0.
+template <int KS3, typename... St>   // k steps of 4 over the gate-row index, 4 KS3 >= 3H, KS3 even
 __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, const float* __restrict__ Whh,
                                                            const float* __restrict__ Y, const float* __restrict__ dY,
                                                            const float* __restrict__ Lab,
@@ -244,7 +246,9 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
                                                            float* __restrict__ dGH /*nullable: full rows [B*T][ldd]*/,
                                                            const float* __restrict__ stat_part, int nstat, float inv_n,
                                                            float coef_lab, float* __restrict__ loss_out,
-                                                           unsigned* status) {
+                                                           unsigned* status, St... state) {
+  constexpr bool ST = sizeof...(St) > 0;
+  const BwdState sb = bwd_state(state...);
   constexpr int KP = 4 * KS3, DS = KP + 4;
   __shared__ __attribute__((aligned(16))) float dbuf[2 * MB * DS];   // dgh rows [dar | daz | dnr | 0..], by step parity
   for (int i = threadIdx.x; i < 2 * MB * DS; i += NTHREADS) dbuf[i] = 0.f;
@@ -310,6 +314,13 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
     rowok[r] = jv && b0 + m < B;
     rowt[r] = (b0 + m < B ? m : B - 1 - b0) * T;
   }
+  // h0 in registers before the loop: a load under `tc == 0` inside load_step would make the compiler wait for all of
+  // the step's prefetches at the join
+  float h0r[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (ST) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) h0r[r] = sb.h0[(size_t)(b0 + rowt[r] / T) * H + jc];
+  }
   struct StepIn { float dy[4], r[4], z[4], n[4], ghn[4], hp[4]; };
   auto load_step = [&](int t, StepIn& s) {
     const int tc = t > 0 ? t : 0;
@@ -325,6 +336,9 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
       s.ghn[r] = g4[r];
       const float hp = Yw[(bt - (tc > 0 ? 1 : 0)) * H + jc];
       s.hp[r] = tc > 0 ? hp : 0.f;
+      if constexpr (ST) {   // (a discarded branch: the plain instance's lambda does not even capture sb)
+        if (tc == 0) s.hp[r] = h0r[r];
+      }
     }
   };
   StepIn cur, nxt;
@@ -335,6 +349,10 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
     for (int r = 0; r < 4; ++r) ycur[r] = Yw[(rowt[r] + T - 1) * H + jc];
   }
   f32x4 dhn = {0.f, 0.f, 0.f, 0.f};
+  if (ST && sb.dhn) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dhn[r] = rowok[r] ? sb.dhn[(size_t)(b0 + 4 * lk + r) * H + j] : 0.f;
+  }
   __syncthreads();
 
   for (int t = T - 1; t >= 0; --t) {
@@ -378,7 +396,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
       }
     }
     __syncthreads();
-    if (active && t > 0) {
+    if (active && (ST || t > 0)) {
       // dgh W_hh over the 3H gate rows: four independent accumulator chains (one KS3-long dependent chain of 16x16x4
       // MFMAs is pure latency)
       f32x4 a1 = {0.f, 0.f, 0.f, 0.f}, a2 = a1, a3 = a1;
@@ -399,6 +417,11 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
         }
       }
       acc = (acc + a1) + (a2 + a3);
+      if (ST && t == 0 && sb.dh0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (rowok[r]) sb.dh0[(size_t)(b0 + 4 * lk + r) * H + j] = acc[r];
+      }
     }
     dhn = acc;
 #pragma unroll
@@ -458,8 +481,9 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
 // with stat_part (the forward's partial sums + tag) workgroup 0 also writes loss[0] = mean((Y - labels)^2).
 int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
                    const float* gates, const float* GI /*the forward's GI rows [B*T][ldgi] (stash)*/, int ldgi, float* dGI, int ldd, float* dGHn, float* dGH, const float* stat_part,
-                   int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st) {
+                   int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st, const BwdState* state) {
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
+  if (state && (!state->h0 || labels)) return WGNN_ERR_UNSUPPORTED;
   if ((dY == nullptr) == (labels == nullptr) || ldd < 3 * H || (dGHn == nullptr) == (dGH == nullptr)) return WGNN_ERR_SHAPE;
   if (stat_part && (!labels || !loss)) return WGNN_ERR_NULL;
   if (!GI || ldgi < 3 * H) return WGNN_ERR_NULL;
@@ -472,7 +496,10 @@ int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const 
 #define BCASE(K)                                                                                                  \
   case K:                                                                                                         \
     PROF_LAUNCH("gru_bwd_kernel<" #K ">", fl, by, st,                                                             \
-                hipLaunchKernelGGL(gru_bwd_kernel<K>, dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY,  \
+                if (state) hipLaunchKernelGGL((gru_bwd_kernel<K, BwdState>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, \
+                                              Whh, Y, dY, labels, gates, GI, ldgi, dGI, ldd, dGHn, hn, dGH, stat_part,            \
+                                              gru_blocks(B), inv_n, coef, loss, status, *state);                                   \
+                else hipLaunchKernelGGL(gru_bwd_kernel<K>, dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY,  \
                                    labels, gates, GI, ldgi, dGI, ldd, dGHn, hn, dGH, stat_part, gru_blocks(B), inv_n, coef,  \
                                    loss, status));                                                                      \
     break

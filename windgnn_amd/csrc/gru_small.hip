@@ -208,7 +208,9 @@ __global__ void __launch_bounds__(small_threads(HMAX)) gru_small_fwd_kernel(int 
 //   dn = dh (1-z), dz = dh (hprev - n), dnt = dn (1-n^2), dr = dnt gh_n,
 //   dar = dr r (1-r), daz = dz z (1-z);  dgi = [dar, daz, dnt], dgh = [dar, daz, dnt r]
 //   dh_next = dh z + dgh W_hh                       (thread (q, j): sum over gate block q of dgh[q][k] W_hh[qH+k][j])
-template <int HMAX, int WPB, int KSP>
+// St (empty, or one BwdState: wgnn_bwd_state_part): h_{-1} = h0, the carry starts at dh_n, and the step at t = 0 also forms
+// dh_{-1} = dh z + dgh W_hh into dh0.
+template <int HMAX, int WPB, int KSP, typename... St>
 __global__ void __launch_bounds__(small_threads(HMAX)) gru_small_bwd_kernel(int B, int T, int H,
                                                                       const float* __restrict__ Whh,
                                                                       const float* __restrict__ Y,
@@ -218,7 +220,9 @@ __global__ void __launch_bounds__(small_threads(HMAX)) gru_small_bwd_kernel(int 
                                                                       int ldd, const float* __restrict__ Lab,
                                                                       float coef_lab, const float* __restrict__ stat_part,
                                                                       int nstat, float inv_n, float* __restrict__ loss_out,
-                                                                      unsigned* status) {
+                                                                      unsigned* status, St... state) {
+  constexpr bool ST = sizeof...(St) > 0;
+  const BwdState sb = bwd_state(state...);
   // Lab: dY = (Y - Lab) * coef_lab is formed here (Y[b, t] is the h_prev this kernel loads for step t + 1 anyway);
   // stat_part: workgroup 0 finalises loss = (sum of the forward's nstat partial sums) / n in a fixed order
   if (stat_part && blockIdx.x == 0) {
@@ -264,6 +268,16 @@ __global__ void __launch_bounds__(small_threads(HMAX)) gru_small_bwd_kernel(int 
     }
   }
   const bool own = i < H;                                             // gate-phase owner of unit i (then q == 0, j == i)
+  // h0 in registers before the loop: a load under `tc == 0` inside load_step would make the compiler wait for all of
+  // the step's prefetches at the join
+  float h0r[WPB];
+#pragma unroll
+  for (int wdw = 0; wdw < WPB; ++wdw) h0r[wdw] = 0.f;
+  if constexpr (ST) {
+#pragma unroll
+    for (int wdw = 0; wdw < WPB; ++wdw)
+      if (own) h0r[wdw] = sb.h0[(size_t)(b0 + wdw < B ? b0 + wdw : B - 1) * H + i];
+  }
   struct StepIn { float dy, r, z, n, ghn, hp; };
   StepIn cur[WPB], nxt[WPB];
   auto load_step = [&](int t, StepIn (&s)[WPB]) {
@@ -282,14 +296,17 @@ __global__ void __launch_bounds__(small_threads(HMAX)) gru_small_bwd_kernel(int 
       s[wdw].ghn = gq[3];
       const float hp = Y[(bt - (tc > 0 ? 1 : 0)) * H + jj];
       s[wdw].hp = tc > 0 ? hp : 0.f;
+      if constexpr (ST) {   // (a discarded branch: the plain instance's lambda does not even capture sb)
+        if (tc == 0) s[wdw].hp = h0r[wdw];
+      }
     }
   };
   load_step(T - 1, cur);
   float dhn[WPB], dhz[WPB], ycur[WPB];                                // ycur = Y[b, t]
 #pragma unroll
   for (int wdw = 0; wdw < WPB; ++wdw) {
-    dhn[wdw] = 0.f;
     const int b = b0 + wdw < B ? b0 + wdw : B - 1;
+    dhn[wdw] = (ST && sb.dhn && own) ? sb.dhn[(size_t)b * H + i] : 0.f;
     ycur[wdw] = (Lab && own) ? Y[((size_t)b * T + T - 1) * H + i] : 0.f;
   }
   __syncthreads();
@@ -324,7 +341,7 @@ __global__ void __launch_bounds__(small_threads(HMAX)) gru_small_bwd_kernel(int 
       }
     }
     __syncthreads();
-    if (t > 0) {
+    if (ST || t > 0) {
       float p[WPB];
 #pragma unroll
       for (int wdw = 0; wdw < WPB; ++wdw) {
@@ -346,7 +363,7 @@ __global__ void __launch_bounds__(small_threads(HMAX)) gru_small_bwd_kernel(int 
       }
     }
     __syncthreads();
-    if (own && t > 0) {
+    if (own && (ST || t > 0)) {
 #pragma unroll
       for (int wdw = 0; wdw < WPB; ++wdw)
       {
@@ -354,6 +371,7 @@ __global__ void __launch_bounds__(small_threads(HMAX)) gru_small_bwd_kernel(int 
 #pragma unroll
         for (int pp = 0; pp < KSP; ++pp) acc += (part[pp][wdw][0][i] + part[pp][wdw][1][i]) + part[pp][wdw][2][i];   // fixed order
         dhn[wdw] = dhz[wdw] + acc;
+        if (ST && t == 0 && sb.dh0 && b0 + wdw < B) sb.dh0[(size_t)(b0 + wdw) * H + i] = dhn[wdw];
       }
     }
 #pragma unroll
@@ -363,6 +381,10 @@ __global__ void __launch_bounds__(small_threads(HMAX)) gru_small_bwd_kernel(int 
     }
   }
 }
+
+// the carried-state instances under a name SMALL_DISPATCH can take
+template <int HMAX, int WPB, int KSP>
+constexpr auto gru_small_bwd_state_kernel = gru_small_bwd_kernel<HMAX, WPB, KSP, BwdState>;
 
 int pick_wpb(int B) { return 1; }   // 2 and 4 windows per workgroup spill at H > 96 (604-848 B of scratch): 409 us at B = 1024
 
@@ -433,15 +455,21 @@ int gru_small_blocks(int B) { return B; }        // workgroups of the forward = 
 
 int launch_gru_small_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
                          const float* gates, float* dGI, float* dGH, int ldd, const float* stat_part, int64_t n_loss,
-                         float grad_scale, float* loss, unsigned* status, hipStream_t st) {
+                         float grad_scale, float* loss, unsigned* status, hipStream_t st, const BwdState* state) {
   if (!gru_small_supported(B, H)) return WGNN_ERR_UNSUPPORTED;
   if ((dY == nullptr) == (labels == nullptr)) return WGNN_ERR_SHAPE;
+  if (state && (!state->h0 || labels)) return WGNN_ERR_UNSUPPORTED;
   if (stat_part && (!labels || !loss)) return WGNN_ERR_NULL;
   const double bt = (double)B * T;
   const float inv_n = 1.0f / (float)n_loss, coef = 2.0f * grad_scale / (float)n_loss;
-  PROF_LAUNCH("gru_small_bwd_kernel", bt * 2.0 * 3 * H * H, bt * 4.0 * (4 * H + 2 * H + 6 * H), st,
-              SMALL_DISPATCH(gru_small_bwd_kernel, B, T, H, Whh, Y, dY, gates, dGI, dGH, ldd, labels, coef, stat_part,
-                             gru_small_blocks(B), inv_n, loss, status));
+  if (state)
+    PROF_LAUNCH("gru_small_bwd_kernel", bt * 2.0 * 3 * H * H, bt * 4.0 * (4 * H + 2 * H + 6 * H), st,
+                SMALL_DISPATCH(gru_small_bwd_state_kernel, B, T, H, Whh, Y, dY, gates, dGI, dGH, ldd, labels, coef, stat_part,
+                               gru_small_blocks(B), inv_n, loss, status, *state));
+  else
+    PROF_LAUNCH("gru_small_bwd_kernel", bt * 2.0 * 3 * H * H, bt * 4.0 * (4 * H + 2 * H + 6 * H), st,
+                SMALL_DISPATCH(gru_small_bwd_kernel, B, T, H, Whh, Y, dY, gates, dGI, dGH, ldd, labels, coef, stat_part,
+                               gru_small_blocks(B), inv_n, loss, status));
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;
 }

@@ -432,7 +432,9 @@ __global__ void __launch_bounds__(NTHREADS) grux_fwd_kernel(int B, int T, int H,
 // dGHn = dnt*r, planes [B*T][HN] (dGH's r and z thirds equal dGI's: the dW_hh GEMM takes them from the dGI planes).
 // In LDS the dgh row is laid out [dar | daz | pad to MS = 8*ceil(2H/8) | dnr] so that the dnr block is 16-byte aligned
 // for the copy-out; the W_hh^T fragments' k index follows the same layout.
-template <int KSB, bool X3, bool IO>   // K steps of 32 over the padded dgh row: KSB = ceil((MS + H) / 32); IO: as grux_fwd_kernel
+// St (empty, or one BwdState: wgnn_bwd_state_part): h_{-1} = h0, the carry starts at s dh_n, and the step at t = 0 also
+// forms dh_{-1} = dh z + dgh W_hh, written (times scales[1]) to dh0.
+template <int KSB, bool X3, bool IO, typename... St>   // K steps of 32 over the padded dgh row: KSB = ceil((MS + H) / 32); IO: as grux_fwd_kernel
 __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H, const float* __restrict__ Whh,
                                                             const void* __restrict__ Y, const float* __restrict__ dY,
                                                             const void* __restrict__ Lab, int io,
@@ -445,7 +447,9 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
                                                             const float* __restrict__ stat_part, int nstat, float inv_n,
                                                             float coef_in, float* __restrict__ loss_out,
                                                             float* __restrict__ scales_out, unsigned* status,
-                                                            int write_lo) {
+                                                            int write_lo, St... state) {
+  constexpr bool ST = sizeof...(St) > 0;
+  const BwdState sb = bwd_state(state...);
   // write_lo == 0 (X3, large B*T): dGI / dGHn leave the chip as ONE fp16 plane (the lo halves stay in LDS, where the
   // recurrence's own product dgh W_hh uses them): the three GEMMs that consume them run two passes
   constexpr int DS = 32 * KSB + 24;   // row stride in halfs: odd in 16-byte units (conflict-free b128 rows); 8 zero pad halfs, then 8 dump halfs
@@ -620,6 +624,15 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
       if (u_n[i] == 2) lt[u_lds[i] + 1] = v[1];
     }
   };
+  // the state's boundary values in registers before the loop: a load under `tc == 0` inside load_step would make the
+  // compiler wait for all of the step's prefetches at the join
+  float h0r[4] = {0.f, 0.f, 0.f, 0.f};
+  float s_out = 1.f;
+  if constexpr (ST) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) h0r[r] = sb.h0[(size_t)(b0 + rowt[r] / T) * H + jc];
+    s_out = scales ? scales[1] : 1.f;
+  }
   struct StepIn { float dy[4], r[4], z[4], n[4], ghn[4], hp[4]; };
   auto load_step = [&](int t, StepIn& s) {
     const int tc = t > 0 ? t : 0;
@@ -650,6 +663,9 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
       s.ghn[r] = g4[r];
       const float hp = IO ? 0.f : Yw[(bt - (tc > 0 ? 1 : 0)) * H + jc];
       s.hp[r] = tc > 0 ? hp : 0.f;
+      if constexpr (ST) {   // (a discarded branch: the plain instance's lambda does not even capture sb)
+        if (tc == 0) s.hp[r] = h0r[r];
+      }
     }
     if (IO && tc > 0) {                                  // h_{t-1} = 5th component of step t-1's record
       const f32x4 h4 = (gatesw + (size_t)(tc - 1) * NW * GREC * 64)[(GREC - 1) * 64];
@@ -675,6 +691,10 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
     }
   }
   f32x4 dhn = {0.f, 0.f, 0.f, 0.f};
+  if (ST && sb.dhn) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dhn[r] = rowok[r] ? sb.dhn[(size_t)(b0 + 4 * g + r) * H + j] * s_in : 0.f;
+  }
   // columns of this lane's unit in the dgh row (r | z | pad | n r) and the dgi row (r | z | n); lanes past H: the dump halfs
   const int o_pad = 32 * KSB + 8 + (c & 7);
   const int o_r = jv ? j : o_pad, o_z = jv ? H + j : o_pad, o_n = jv ? MS + j : o_pad, o_t = jv ? 2 * H + j : o_pad;
@@ -736,7 +756,7 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
         *(h8*)(c_dst[i] + (size_t)t * c_step[i]) = v;
       }
     }
-    if (active && t > 0) {
+    if (active && (ST || t > 0)) {
 #pragma unroll
       for (int ks = 0; ks < KSB; ++ks) {
         Frag a;
@@ -744,6 +764,11 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
         if (X3) a.lo = *(const h8*)(dlo + c * DS + 32 * ks + 8 * g);
         else a.lo = a.hi;
         acc = mfma3<X3>(a, WT[ks], acc);
+      }
+      if (ST && t == 0 && sb.dh0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (rowok[r]) sb.dh0[(size_t)(b0 + 4 * g + r) * H + j] = acc[r] * s_out;
       }
     }
     dhn = acc;
@@ -773,11 +798,12 @@ int launch_grux_fwd(int B, int T, int H, const void* GI /*fp32 rows (x3) or fp16
                     float* gates, void* y_planes /*nullable: 2 x [B*T+1][grux_hp(H)] halfs*/, bool x3, unsigned* status,
                     const void* labels /*nullable*/, float* stat_part /*2 * grux_blocks(B) floats if labels*/, int io,
                     int last_only /*Y is [B][H]: only h_{T-1} * y_mul + y_add is written (fp32 I/O, no stash)*/,
-                    float y_mul, float y_add, hipStream_t st, const float* h0, float* hn) {
+                    float y_mul, float y_add, hipStream_t st, const float* h0, float* hn, size_t plane_rows) {
   if (last_only && (io != 0 || gates || y_planes || labels)) return WGNN_ERR_UNSUPPORTED;
   if (!Y && (!io || !hn || last_only)) return WGNN_ERR_NULL;   // Y = NULL: 16-bit I/O with h_n only (fp32: last_only into h_n)
   _Float16* yh = (_Float16*)y_planes;
-  _Float16* yl = yh ? yh + ((size_t)B * T + 1) * grux_hp(H) : nullptr;   // each plane has B*T + 1 rows
+  _Float16* yl = yh ? yh + (plane_rows ? plane_rows : (size_t)B * T + 1) * grux_hp(H) : nullptr;   // each plane has B*T + 1 rows
+                                                                                                    // (the state stash: B*T + B)
   const double bt = (double)B * T;
   const double fl = bt * 2.0 * 3 * H * H,
                by = bt * ((x3 ? 4.0 : 2.0) * 3 * H + (io ? 2.0 : 4.0) * ((last_only ? 0 : H) + (labels ? H : 0))) +
@@ -816,7 +842,8 @@ int launch_grux_bwd(int B, int T, int H, const float* Whh, const void* Y, const 
                     const float* gates, const float* GI /*x3: the forward's GI rows [B*T][ldgi] fp32 (stash)*/, int ldgi,
                     const float* scales, void* dGI_planes, void* dGHn_planes, int ldd, bool x3, const float* stat_part,
                     int64_t n_loss, float grad_scale, float* loss, float* scales_out, unsigned* status, int write_lo,
-                    hipStream_t st) {
+                    hipStream_t st, const BwdState* state) {
+  if (state && (!state->h0 || labels || stat_part)) return WGNN_ERR_UNSUPPORTED;   // (the state backward takes dY)
   // stat_part != null: loss and scales are finalised inside the kernel (once a separate one-block launch)
   const int nstat = grux_blocks(B);
   const float inv_n = stat_part ? 1.0f / (float)n_loss : 0.f, coef_in = stat_part ? 2.0f * grad_scale / (float)n_loss : 0.f;
@@ -834,7 +861,10 @@ int launch_grux_bwd(int B, int T, int H, const float* Whh, const void* Y, const 
   const dim3 grid(cdiv_i(B, MB));
 #define BLAUNCH(K, X3V, IOV, NAME, BYTES)                                                                         \
   PROF_LAUNCH(NAME, fl, BYTES, st,                                                                                \
-              hipLaunchKernelGGL((grux_bwd_kernel<K, X3V, IOV>), grid, dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY, labels, io, \
+              if (state) hipLaunchKernelGGL((grux_bwd_kernel<K, X3V, IOV, BwdState>), grid, dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY, \
+                                            labels, io, gates, GI, ldgi, scales, ih, il, ldd, nh, nl, stat_part, nstat, inv_n, coef_in, \
+                                            loss, scales_out, status, write_lo, *state);                                            \
+              else hipLaunchKernelGGL((grux_bwd_kernel<K, X3V, IOV>), grid, dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY, labels, io, \
                                  gates, GI, ldgi, scales, ih, il, ldd, nh, nl, stat_part, nstat, inv_n, coef_in, loss, scales_out, status, write_lo))
 #define BCASE(K)                                                                                                  \
   if (x3 && !io) BLAUNCH(K, true, false, "grux_bwd_kernel<" #K ">", by);                                          \

@@ -347,7 +347,9 @@ __device__ __forceinline__ int tn_g(int stride32, int r) {   // stride32 = row b
 // A2hi / A2lo (row stride lda2); msplit is a multiple of 8 so no 16-byte chunk straddles the two sources.  Used for
 // dW_hh = [dGI_r | dGI_z | dGH_n]^T Hprev: the BPTT kernel stores the n third of dGH only (its r and z thirds equal dGI's).
 // ALO (with X3): as in pgemm_nt_kernel -- false: the A operand (dGI [+ dGHn]) is a single fp16 plane, two passes.
-template <int T, bool X3, bool A2, bool ALO>
+// PW (the state stash, wgnn_bwd_state_part): with shift_T, the row read at a window start k = b shift_T is the extra row
+// K + b (the window's own h0 row) instead of the one shared row K.
+template <int T, bool X3, bool A2, bool ALO, bool PW = false>
 __global__ void __launch_bounds__(64 * TN_WAVES) pgemm_tn_kernel(const _Float16* __restrict__ Ahi,
                                                                 const _Float16* __restrict__ Alo, int lda,
                                                                 const _Float16* __restrict__ Bhi,
@@ -425,7 +427,7 @@ __global__ void __launch_bounds__(64 * TN_WAVES) pgemm_tn_kernel(const _Float16*
     for (int it = 0; it < NIT; ++it)
       if (on[it]) {
         int k = min(k0 + prow[it], kend - 1);                      // rows past the chunk: zeroed in LDS below
-        if (isb[it] && shift_T > 0) k = (k % shift_T) != 0 ? k - 1 : K;   // row K = the stored t = 0 row
+        if (isb[it] && shift_T > 0) k = (k % shift_T) != 0 ? k - 1 : (PW ? K + k / shift_T : K);   // row K = the stored t = 0 row
         // b_stream: the B operand is an old, read-once tensor (the g plane, the Hprev planes): non-temporal, so that it does
         // not push the A operand's planes (dGI: read again by the other GEMMs) out of the Infinity Cache
         if (isb[it] && b_stream)
@@ -729,7 +731,7 @@ int pgemm_tn_tiles(int Mout, int Nout) {
 template <int T>
 static int launch_tn_t(const void* Ahi, const void* Alo, int lda, const void* Bhi, const void* Blo, int ldb, int shift_T,
                        int K, int splitk, float* partial, int Mout, int Nout, bool x3, int nNb, const void* A2hi,
-                       const void* A2lo, int lda2, int msplit, hipStream_t st, bool b_stream) {
+                       const void* A2lo, int lda2, int msplit, hipStream_t st, bool b_stream, bool pw) {
   const int nMb = cdiv_i(Mout, TN_BM);
   const int kchunk = cdiv_i(cdiv_i(K, splitk), 32) * 32;
   const size_t smem = 2 * (size_t)(2 * 32 * 2 * (TN_BM + 32 * T));
@@ -744,12 +746,17 @@ static int launch_tn_t(const void* Ahi, const void* Alo, int lda, const void* Bh
   if (!alo) { Alo = Ahi; A2lo = A2hi; }            // never read
 #define TN_ARGS (const _Float16*)Ahi, (const _Float16*)Alo, lda, (const _Float16*)Bhi, (const _Float16*)Blo, ldb, shift_T, K, \
                 kchunk, partial, Mout, Nout, nNb, (const _Float16*)A2hi, (const _Float16*)A2lo, lda2, msplit, (int)b_stream
-#define TN_GO(NAME, X3V, A2V, ALOV)                                                                                  \
+#define TN_GO1(NAME, X3V, A2V, ALOV, PWV)                                                                            \
   do {                                                                                                               \
     static std::atomic<unsigned long long> done_{0};                                                                 \
-    if (ensure_dyn_smem((const void*)pgemm_tn_kernel<T, X3V, A2V, ALOV>, smem, done_) != WGNN_OK) return WGNN_ERR_HIP; \
+    if (ensure_dyn_smem((const void*)pgemm_tn_kernel<T, X3V, A2V, ALOV, PWV>, smem, done_) != WGNN_OK) return WGNN_ERR_HIP; \
     PROF_LAUNCH(NAME.c_str(), fl, by, st,                                                                            \
-                hipLaunchKernelGGL((pgemm_tn_kernel<T, X3V, A2V, ALOV>), grid, block, smem, st, TN_ARGS));           \
+                hipLaunchKernelGGL((pgemm_tn_kernel<T, X3V, A2V, ALOV, PWV>), grid, block, smem, st, TN_ARGS));      \
+  } while (0)
+#define TN_GO(NAME, X3V, A2V, ALOV)                 \
+  do {                                              \
+    if (pw) TN_GO1(NAME, X3V, A2V, ALOV, true);     \
+    else TN_GO1(NAME, X3V, A2V, ALOV, false);       \
   } while (0)
   if (A2hi) {
     if constexpr (T <= 4) {     // only the narrow dW_hh product has a two-source A operand
@@ -767,6 +774,7 @@ static int launch_tn_t(const void* Ahi, const void* Alo, int lda, const void* Bh
     TN_GO(name16, false, false, true);
   }
 #undef TN_GO
+#undef TN_GO1
 #undef TN_ARGS
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;
@@ -786,18 +794,20 @@ size_t pgemm_tn_partial_floats(int Mout, int Nout, int splitk) {
 // partial (pgemm_tn_kernel's own layout, read by finish.hip; pgemm_tn_partial_floats floats) = per-K-chunk sums of A[k][m] B[k][n].
 // A planes [K][lda], B planes [K][ldb].
 // shift_T > 0: B row k is taken from row k-1, and from the extra row K (which the producer fills with what the
-// operand looks like at a window start) where k % shift_T == 0.
+// operand looks like at a window start) where k % shift_T == 0; per_window: from the extra row K + k / shift_T instead
+// (one per window: the state stash's [h0 | 1] rows).
 int launch_pgemm_tn(const void* Ahi, const void* Alo, int lda, const void* Bhi, const void* Blo, int ldb, int shift_T,
                     int K, int splitk, float* partial, int Mout, int Nout, bool x3, const void* A2hi, const void* A2lo,
-                    int lda2, int msplit, hipStream_t st, bool b_stream) {
+                    int lda2, int msplit, hipStream_t st, bool b_stream, bool per_window) {
   if (lda % 8 != 0 || ldb % 8 != 0 || K < 1) return WGNN_ERR_SHAPE;
+  if (per_window && shift_T < 1) return WGNN_ERR_SHAPE;
   if (A2hi && (lda2 % 8 != 0 || msplit % 8 != 0 || msplit > lda)) return WGNN_ERR_SHAPE;
   int nNb, T;
   tn_shape(Nout, nNb, T);
   switch (T) {
 #define TN_CASE(t) \
   case t: return launch_tn_t<t>(Ahi, Alo, lda, Bhi, Blo, ldb, shift_T, K, splitk, partial, Mout, Nout, x3, nNb, A2hi, A2lo, \
-                                lda2, msplit, st, b_stream);
+                                lda2, msplit, st, b_stream, per_window);
     TN_CASE(1) TN_CASE(2) TN_CASE(3) TN_CASE(4) TN_CASE(5) TN_CASE(6) TN_CASE(7)
 #undef TN_CASE
   }

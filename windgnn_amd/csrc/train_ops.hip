@@ -188,11 +188,17 @@ int launch_mse_stats(const float* Y, const float* L, int64_t n, float grad_scale
 
 int mse_stats_blocks() { return MSE_BLOCKS; }
 
-int launch_amax_scale(const float* x, int64_t n, float* scales, float* part /*>=448 floats*/, hipStream_t st) {
+int launch_amax_scale(const float* x, int64_t n, float* scales, float* part /*>=448 floats*/, hipStream_t st, const float* x2,
+                      int64_t n2) {
   PROF_LAUNCH("amax_partial_kernel", (double)n, 4.0 * n, st,
               hipLaunchKernelGGL(amax_partial_kernel, dim3(448), dim3(256), 0, st, x, n, part));
   WGNN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(amax_finalize_kernel, dim3(1), dim3(64), 0, st, part, 448, scales);
+  if (x2 && n2 > 0) {   // max(|x|, |x2|): the second tensor's 448 partials behind the first's
+    PROF_LAUNCH("amax_partial_kernel", (double)n2, 4.0 * n2, st,
+                hipLaunchKernelGGL(amax_partial_kernel, dim3(448), dim3(256), 0, st, x2, n2, part + 448));
+    WGNN_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(amax_finalize_kernel, dim3(1), dim3(64), 0, st, part, (x2 && n2 > 0) ? 896 : 448, scales);
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;
 }

@@ -317,6 +317,107 @@ def gcn_gru(A, X, params, math=_lib.MATH_F32):
     return GCNGRUFunction.apply(A, X, math, *params)
 
 
+def gcn_gru_state_forward_raw(A, X, params: Sequence[torch.Tensor], math=_lib.MATH_F32, h0=None, h_n=None, prepared=None):
+    """Y, h_n, stash, d = wgnn_fwd_state_stash(...): the training forward from h0 [B,H] fp32 (None = zeros), with the state
+    stash the backward (gcn_gru_state_backward_raw) needs; h_n [B,H] fp32 is the unrounded last state (a new tensor unless
+    a caller buffer is given; it must not share memory with h0)."""
+    lib = _lib.load()
+    _require_gpu(X, io_ok=True)
+    _require_gpu(*params)
+    _require_contiguous(X=X, **{"params[%d]" % i: q for i, q in enumerate(params)})
+    if X.dim() != 4:
+        raise RuntimeError("windgnn_amd: X must be [B, T, S, 13], got %s" % (tuple(X.shape),))
+    B, T, S, F = X.shape
+    A, fmt, nnz = _adj(A, S)
+    H = params[5].shape[1]
+    for name, t in (("h0", h0), ("h_n", h_n)):
+        if t is None:
+            continue
+        _require_gpu(t)
+        _require_contiguous(**{name: t})
+        if tuple(t.shape) != (B, H) or t.device != X.device:
+            raise RuntimeError("windgnn_amd: %s must be [B, H] = [%d, %d] float32 on %s, got %s on %s"
+                               % (name, B, H, X.device, tuple(t.shape), t.device))
+    d = _lib.Dims(B, T, S, F, H, math, fmt, nnz, _IO_OF[X.dtype])
+    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
+    if ws_bytes == 0:
+        _lib.check(-5 if F == 13 else -2, "wgnn_workspace_bytes(B=%d,T=%d,S=%d,F=%d,H=%d,math=%d,io=%s)"
+                   % (B, T, S, F, H, math, X.dtype))
+    ws = _Workspace.get(X.device, ws_bytes)
+    stash = torch.empty(lib.wgnn_state_stash_bytes(C.byref(d)), dtype=torch.uint8, device=X.device)
+    Y = torch.empty(B, T, H, dtype=X.dtype, device=X.device)
+    if h_n is None:
+        h_n = torch.empty(B, H, dtype=torch.float32, device=X.device)
+    ps = _params_struct(_lib.Params, params, prepared)
+    rc = lib.wgnn_fwd_state_stash(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(h0), _ptr(Y), _ptr(h_n), _ptr(stash),
+                                  _ptr(ws), ws_bytes, _stream())
+    _lib.check(rc, "wgnn_fwd_state_stash")
+    return Y, h_n, stash, d
+
+
+def gcn_gru_state_backward_raw(d, A, X, params, Y, dY, dh_n, stash, grads: Sequence[torch.Tensor], dh0=None,
+                               part: int = 7, stream=None, prepared=None):
+    """wgnn_bwd_state_part: the gradients of sum(Y dY) + sum(h_n dh_n) (dh_n None = zeros) into `grads`, and dh0 [B,H]
+    (None = not computed) w.r.t. the h0 recorded in the state stash.  Parts as gcn_gru_backward_raw."""
+    lib = _lib.load()
+    _require_contiguous(X=X, Y=Y, dY=dY, dh_n=dh_n, dh0=dh0, **{"grads[%d]" % i: q for i, q in enumerate(grads)},
+                        **{"params[%d]" % i: q for i, q in enumerate(params)})
+    for name, t in (("dh_n", dh_n), ("dh0", dh0)):
+        if t is not None and (tuple(t.shape) != (d.B, d.H) or t.dtype != torch.float32 or t.device != X.device):
+            raise RuntimeError("windgnn_amd: %s must be [B, H] = [%d, %d] float32 on %s, got %s %s on %s"
+                               % (name, d.B, d.H, X.device, tuple(t.shape), t.dtype, t.device))
+    A = getattr(A, "blob", A)
+    _require_contiguous(adj_matrix=A)
+    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
+    ws = _Workspace.get(X.device, ws_bytes)
+    ps = _params_struct(_lib.Params, params, prepared)
+    gs = _params_struct(_lib.Grads, grads)
+    rc = lib.wgnn_bwd_state_part(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(Y), _ptr(dY), _ptr(dh_n), _ptr(stash),
+                                 C.byref(gs), _ptr(dh0), _ptr(ws), ws_bytes,
+                                 _stream() if stream is None else C.c_void_p(stream.cuda_stream), part)
+    _lib.check(rc, "wgnn_bwd_state_part(%d)" % part)
+
+
+class GCNGRUStateFunction(torch.autograd.Function):
+    """(Y, h_n) = GCN_GRU(A, X, h0; 8 params), nn.GRU's forward(input, hx) -> (output, h_n).  Differentiable in the 8
+    parameters and in h0; a loss may depend on Y, on h_n or on both (truncated BPTT over chunks of a long series).
+    h0 None: zeros.  Like GCNGRUFunction, no gradient for X or A."""
+
+    @staticmethod
+    def forward(ctx, A, X, math, h0, *params):
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[0]:
+            raise RuntimeError("windgnn_amd: GCN_GRU gives gradients for its 8 parameters and the initial state only; "
+                               "attr_matrix / adj_matrix with requires_grad=True are not supported (detach them)")
+        ctx.set_materialize_grads(False)
+        X = X.contiguous()
+        params = tuple(p.contiguous() for p in params)
+        h0c = h0.detach().contiguous() if h0 is not None else None
+        Y, h_n, stash, d = gcn_gru_state_forward_raw(A, X, params, math, h0c)
+        ctx.d = d
+        ctx.has_h0 = h0 is not None
+        ctx.save_for_backward(_adj(A)[0], X, Y, stash, *params)
+        return Y, h_n
+
+    @staticmethod
+    def backward(ctx, dY, dh_n):
+        A, X, Y, stash, *params = ctx.saved_tensors
+        if dY is None:                     # a loss on h_n alone
+            dY = torch.zeros(Y.shape, dtype=torch.float32, device=Y.device)
+        sizes = [p.numel() for p in params]
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=X.device)
+        grads = [g.view_as(p) for g, p in zip(flat.split(sizes), params)]
+        want_dh0 = ctx.has_h0 and ctx.needs_input_grad[3]
+        dh0 = torch.empty(ctx.d.B, ctx.d.H, dtype=torch.float32, device=X.device) if want_dh0 else None
+        gcn_gru_state_backward_raw(ctx.d, A, X, params, Y, dY.float().contiguous(),
+                                   dh_n.float().contiguous() if dh_n is not None else None, stash, grads, dh0)
+        return (None, None, None, dh0, *grads)
+
+
+def gcn_gru_with_state(A, X, params, math=_lib.MATH_F32, h0=None):
+    """(Y [B,T,H], h_n [B,H]) from the initial state h0 [B,H] fp32 (None = zeros), differentiable in the 8 parameters and h0."""
+    return GCNGRUStateFunction.apply(A, X, math, h0, *params)
+
+
 class GraphConvFunction(torch.autograd.Function):
     """out = relu(A X W + b) for X [..., S, F_in], W [F_in, F_out] (src/step5_gcn_layer_model.py:13-23).  Dense adjacency: any
     widths up to 64 (13 -> 13, the reference model's own, on the MFMA kernels); CSR adjacency: 13 -> 13 only."""
@@ -416,15 +517,17 @@ class GRUFunction(torch.autograd.Function):
         return (dg, None, *grads)
 
 
-def mse_loss_grad(Y, L, grad_scale: float = 1.0, want_grad=True):
-    """loss (0-dim tensor on device) and dY for nn.MSELoss()(Y, L) (src/main.py:49,72)."""
+def mse_loss_grad(Y, L, grad_scale: float = 1.0, want_grad=True, loss=None):
+    """loss (0-dim tensor on device) and dY for nn.MSELoss()(Y, L) (src/main.py:49,72).  loss: optional 0-dim fp32 device
+    tensor (a view is fine) that receives it instead of a new one."""
     lib = _lib.load()
     _require_gpu(Y, L)
     Y, L = Y.contiguous(), L.contiguous()
     if Y.numel() != L.numel():
         raise RuntimeError("windgnn_amd: MSE operands differ in size: %s vs %s" % (tuple(Y.shape), tuple(L.shape)))
     dY = torch.empty_like(Y) if want_grad else None
-    loss = torch.empty((), dtype=torch.float32, device=Y.device)
+    if loss is None:
+        loss = torch.empty((), dtype=torch.float32, device=Y.device)
     wsp, wsn = _scratch(Y.device, 4096)
     rc = lib.wgnn_mse_loss_grad(_ptr(Y), _ptr(L), Y.numel(), grad_scale, _ptr(dY), _ptr(loss), wsp, wsn, _stream())
     _lib.check(rc, "wgnn_mse_loss_grad")

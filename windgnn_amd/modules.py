@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .functional import GraphConvFunction, GRUFunction, check_range_status, gcn_gru, gcn_gru_state
+from .functional import GraphConvFunction, GRUFunction, check_range_status, gcn_gru, gcn_gru_state, gcn_gru_with_state
 
 NUM_FEATURES = 13   # hard-coded in the reference: src/step6_gcn_gru_combined_model.py:16
 
@@ -108,32 +108,51 @@ class GCN_GRU(nn.Module):
         if torch.is_grad_enabled() and (any(p.requires_grad for p in self.hot_path_parameters()) or
                                         (hx is not None and hx.requires_grad)):
             raise RuntimeError("GCN_GRU.forward_state is inference only (no gradients flow through the carried state): "
-                               "call it under torch.no_grad() (or torch.inference_mode())")
+                               "call it under torch.no_grad() (or torch.inference_mode()), or train through "
+                               "GCN_GRU.forward_with_state")
+        hx = self._check_state("forward_state", attr_matrix, hx)
+        h0 = hx.detach().contiguous() if hx is not None else None
+        params = [p.detach().contiguous() for p in self.hot_path_parameters()]
+        out, h_n = gcn_gru_state(adj_matrix, attr_matrix.contiguous(), params, self.math, h0=h0)
+        if self.validate and self.math != _lib.MATH_F32:
+            check_range_status(out.device)
+        return out.squeeze(0), h_n.unsqueeze(0)
+
+    def _check_state(self, who, attr_matrix, hx):
+        """hx as [B, H] (or None) after the checks both carried-state methods make."""
         if not self.fused:
-            raise RuntimeError("GCN_GRU.forward_state: carried state is built for the reference model's 13 / 13 widths only "
-                               "(got input_dim / hidden_dim = %d / %d)" % (self.conv1.weight.shape[0],
+            raise RuntimeError("GCN_GRU.%s: carried state is built for the reference model's 13 / 13 widths only "
+                               "(got input_dim / hidden_dim = %d / %d)" % (who, self.conv1.weight.shape[0],
                                                                            self.conv1.weight.shape[1]))
         if attr_matrix.dim() != 4:
-            raise RuntimeError("GCN_GRU.forward_state: attr_matrix must be [B, T, S, 13], got %s"
-                               % (tuple(attr_matrix.shape),))
+            raise RuntimeError("GCN_GRU.%s: attr_matrix must be [B, T, S, 13], got %s" % (who, tuple(attr_matrix.shape)))
         B, T, S, F = attr_matrix.shape
         if F != NUM_FEATURES or S * NUM_FEATURES != self.gru.input_size:
             raise RuntimeError("shape '[%d, %d, %d]' is invalid for input of size %d"
                                % (B, T, self.gru.input_size, attr_matrix.numel()))
         H = self.gru.hidden_size
-        h0 = None
-        if hx is not None:
-            if tuple(hx.shape) == (1, B, H):
-                hx = hx[0]
-            if tuple(hx.shape) != (B, H):
-                raise RuntimeError("GCN_GRU.forward_state: hx must be [1, B, H] or [B, H] = [1, %d, %d], got %s"
-                                   % (B, H, tuple(hx.shape)))
-            if hx.dtype != torch.float32 or hx.device != attr_matrix.device:
-                raise RuntimeError("GCN_GRU.forward_state: hx must be float32 on %s, got %s on %s"
-                                   % (attr_matrix.device, hx.dtype, hx.device))
-            h0 = hx.detach().contiguous()
-        params = [p.detach().contiguous() for p in self.hot_path_parameters()]
-        out, h_n = gcn_gru_state(adj_matrix, attr_matrix.contiguous(), params, self.math, h0=h0)
+        if hx is None:
+            return None
+        if tuple(hx.shape) == (1, B, H):
+            hx = hx[0]
+        if tuple(hx.shape) != (B, H):
+            raise RuntimeError("GCN_GRU.%s: hx must be [1, B, H] or [B, H] = [1, %d, %d], got %s"
+                               % (who, B, H, tuple(hx.shape)))
+        if hx.dtype != torch.float32 or hx.device != attr_matrix.device:
+            raise RuntimeError("GCN_GRU.%s: hx must be float32 on %s, got %s on %s"
+                               % (who, attr_matrix.device, hx.dtype, hx.device))
+        return hx
+
+    def forward_with_state(self, adj_matrix, attr_matrix, hx=None):
+        """(out, h_n) with nn.GRU(batch_first=True)'s full state semantics, training included: hx / h_n are [1, B, H] (hx may
+        also be [B, H]; None = zeros).  Gradients flow to the parameters and to hx, and a loss may use out, h_n or both
+        (truncated BPTT: feed h_n.detach() as the next chunk's hx).  With no gradient to record it is forward_state (the same
+        kernels, the one-launch hourly step included).  h_n is the unrounded fp32 state also with a 16-bit attr_matrix."""
+        if not (torch.is_grad_enabled() and (any(p.requires_grad for p in self.hot_path_parameters()) or
+                                             (hx is not None and hx.requires_grad))):
+            return self.forward_state(adj_matrix, attr_matrix, hx)
+        h0 = self._check_state("forward_with_state", attr_matrix, hx)
+        out, h_n = gcn_gru_with_state(adj_matrix, attr_matrix, self.hot_path_parameters(), self.math, h0)
         if self.validate and self.math != _lib.MATH_F32:
             check_range_status(out.device)
         return out.squeeze(0), h_n.unsqueeze(0)

@@ -29,14 +29,19 @@ import torch
 from . import _lib
 from .distributed import HEADER, LOSS_SLOT, BucketExchange
 from .functional import (check_range_status, finish_step, gcn_gru_backward_mse_raw, gcn_gru_forward_raw,
-                         prepared_weights, refresh_prepared)
+                         gcn_gru_state_backward_raw, gcn_gru_state_forward_raw, mse_loss_grad, prepared_weights,
+                         refresh_prepared)
 from .modules import GCN_GRU
 
 
 class TrainStep:
     def __init__(self, model: GCN_GRU, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  process_group=None, check_every: int = 100, overlap_collectives: bool = False, direct_rccl=None,
-                 rccl_loader=None):
+                 rccl_loader=None, carry_state: bool = False):
+        """carry_state: truncated BPTT over consecutive chunks -- each step starts the recurrence from the h_n of the previous
+        step (detached; zeros on the first step and after reset_state()), so a model trained on chunks of a long series
+        learns the carried-state regime StreamingForecaster(window=None) serves.  The batch size must stay the same
+        between resets; fp32 I/O only."""
         if not getattr(model, "fused", True):
             raise RuntimeError("windgnn_amd: TrainStep drives the fused hot path, i.e. the reference model's own widths "
                                "(input_dim = hidden_dim = 13, src/main.py:41); a GCN_GRU of other widths trains through "
@@ -83,6 +88,9 @@ class TrainStep:
                                            rccl_loader)
         self.check_every = check_every          # f16x3 / f16: read the library's range-status word every N steps
         self.device = dev
+        # carried state: two [B, H] buffers (h0 of this step, h_n into the other: they may not alias), swapped per step
+        self.carry_state = carry_state
+        self._hbuf, self._hcur, self._has_state = None, 0, False
 
     def _param_version(self):
         """torch's in-place version counters of the parameters: load_state_dict / optimiser-free edits through the
@@ -154,6 +162,75 @@ class TrainStep:
             self._images(_lib.Dims(B, T, S, F, self.p_views[5].shape[1], self.model.math, fmt, nnz, _IO_OF[X.dtype]))
         return gcn_gru_forward_raw(A, X, self.p_views, self.model.math, want_stash=True, labels=L, prepared=self._prepared)
 
+    @property
+    def state(self):
+        """A copy of the state the next carry_state step starts from ([B, H] fp32), or None (zeros: no step since the
+        last reset)."""
+        return self._hbuf[self._hcur].clone() if self._has_state else None
+
+    def reset_state(self):
+        """The next carry_state step starts from zeros (e.g. at the start of a new series / epoch)."""
+        self._has_state = False
+
+    def _state_forward(self, A, X, L):
+        """Forward from the carried state (carry_state=True): returns Y, stash, d and leaves h_n in the other buffer."""
+        if X.dtype != torch.float32:
+            raise RuntimeError("windgnn_amd: TrainStep(carry_state=True) takes fp32 attr_matrix / labels (the loss pass, "
+                               "wgnn_mse_loss_grad, reads fp32), got %s" % X.dtype)
+        B, H = X.shape[0], self.p_views[5].shape[1]
+        if self._hbuf is None or self._hbuf.shape[1] != B:
+            if self._has_state:
+                raise RuntimeError("windgnn_amd: TrainStep(carry_state=True): the batch changed from %d to %d windows while "
+                                   "a state is carried; call reset_state() first" % (self._hbuf.shape[1], B))
+            self._hbuf = torch.zeros(2, B, H, dtype=torch.float32, device=self.device)
+        if self._prepared_version != self._param_version():
+            from .functional import _IO_OF, _adj
+            _, T, S, F = X.shape
+            _, fmt, nnz = _adj(A, S)
+            self._images(_lib.Dims(B, T, S, F, H, self.model.math, fmt, nnz, _IO_OF[X.dtype]))
+        h0 = self._hbuf[self._hcur] if self._has_state else None
+        Y, _, stash, d = gcn_gru_state_forward_raw(A, X, self.p_views, self.model.math, h0, self._hbuf[1 - self._hcur],
+                                                   prepared=self._prepared)
+        return Y, stash, d
+
+    def _state_step(self, A, X, L, n_global):
+        """step() with carry_state=True: the same schedule, with the loss and dY from wgnn_mse_loss_grad (into the bucket's
+        loss slot) and the backward through wgnn_bwd_state_part (dh_n = 0, no dh0: the carried state is detached)."""
+        DEFER = _lib.BWD_DEFER
+        loss = self._loss
+        gs = self.exchange.shard_weight(X.shape[0], n_global) if self.collective else 1.0
+        Y, stash, d = self._state_forward(A, X, L)
+        pre = self._prepared
+        _, dY = mse_loss_grad(Y, L, gs, loss=loss)    # the unweighted shard mean: the exchange weights it, as in step()
+
+        def bwd(part):
+            gcn_gru_state_backward_raw(d, A, X, self.p_views, Y, dY, None, stash, self.g_views, part=part | DEFER,
+                                       prepared=pre)
+        if self.collective and not self.overlap_collectives:
+            for part in (1, 2, 4):
+                bwd(part)
+            finish_step(d, self.p_views, self.g_views, 6, device=self.device)
+            self.exchange.all_reduce_all(gs)
+            finish_step(d, self.p_views, self.g_views, 0, self._adam(), pre, self.device)
+        elif self.collective:
+            bwd(1 | 4)
+            finish_step(d, self.p_views, self.g_views, 4, device=self.device)
+            work = self.exchange.start_gru()
+            bwd(2)
+            finish_step(d, self.p_views, self.g_views, 2, device=self.device)
+            wconv = self.exchange.start_conv(gs)
+            work.wait()
+            adam = self._adam()
+            finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_GRU, adam, pre, self.device)
+            wconv.wait()
+            finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_CONV, adam, pre, self.device)
+        else:
+            for part in (1, 2, 4):
+                bwd(part)
+            finish_step(d, self.p_views, self.g_views, 6, self._adam(), pre, self.device)
+        self._hcur, self._has_state = 1 - self._hcur, True     # h_n of this step is the next step's h0
+        return loss, Y
+
     def step(self, A, X, L, n_global=None):
         """One optimiser step on this rank's windows (src/main.py:66-80).  `n_global`: windows of ALL ranks in this step,
         when the caller knows it (a fixed global batch); None = the exchange all-reduces the count on every step (a host
@@ -165,7 +242,9 @@ class TrainStep:
         if X.shape[0] == 0:
             return self._empty_shard_step(A, X, n_global)
         loss = self._loss
-        if self.collective and not self.overlap_collectives:
+        if self.carry_state:
+            loss, Y = self._state_step(A, X, L, n_global)
+        elif self.collective and not self.overlap_collectives:
             # the single-rank schedule, with ONE all-reduce of [loss | conv | GRU gradients] between the reduce-only finish and
             # the optimiser's: one collective, one stream dependency each way per step
             gs = self.exchange.shard_weight(X.shape[0], n_global)
