@@ -310,6 +310,40 @@ int wgnn_bwd_mse_part(const wgnn_dims* d, const float* A, const void* X, const w
 int wgnn_finish(const wgnn_dims* d, const wgnn_params* p, const wgnn_grads* g, int which, const wgnn_adam* adam,
                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* Part 4 and the optimiser step over ROW RANGES of one GRU tensor pair, so that a data-parallel caller can all-reduce a large
+ * bucket in row blocks while the rest of the backward still computes (no reference counterpart).  `which`:
+ *   WGNN_ROWS_IH   gate rows [row0, row0 + rows) of w_ih and b_ih;
+ *   WGNN_ROWS_HH   the same rows of w_hh and b_hh;
+ *   + WGNN_ROWS_STATE  the stash came from wgnn_fwd_state_stash: refused (WGNN_ERR_UNSUPPORTED; its dW_hh operand reads
+ *                  per-window rows, and its buckets are small).
+ * Supported: the wide-GRU path (the per-step GEMM recurrence: H > 127 in f16x3 / f16x3g, H > 128 in f32), dense or CSR
+ * adjacency, math F32, F16X3, F16X3G.  Anything else is WGNN_ERR_UNSUPPORTED, and wgnn_bwd_rows_align() returns 0 for it.
+ *
+ * wgnn_bwd_rows_align   the alignment (in rows) of every range: row0 must be a multiple of it, and row0 + rows a multiple
+ *                       of it or 3H.  It is the M tile of the weight-gradient GEMM, so two ranges never share a tile and
+ *                       the product of a range is the whole product's rows, bit for bit.  0 = not supported.
+ * wgnn_bwd_rows         after part 1 of wgnn_bwd_part / wgnn_bwd_mse_part (on the SAME workspace, nothing else in between
+ *                       that uses it): dW | db = dGI^T [g | 1] (WGNN_ROWS_IH) or dGH^T [Hprev | 1] (WGNN_ROWS_HH) for those
+ *                       rows, with the split-K count of the whole product, reduced into those rows of g (the rest of g is
+ *                       not touched).  Calls for ranges that cover all 3H rows give exactly what part 4 gives.  Y and
+ *                       stash are the forward's; the ranges use the part-4 scratch, so they run one after another on one
+ *                       stream.
+ * wgnn_finish_rows      torch.optim.Adam on those rows of the pair (p, adam->exp_avg / exp_avg_sq updated in place) with
+ *                       the gradients as they stand in g; with WGNN_ROWS_IH and p->prepared set, the parts of the staged
+ *                       W_ih images those rows own are rewritten.  After ranges that cover every row of both pairs the
+ *                       parameters, moments and images equal what wgnn_finish(.., adam) gives, bit for bit.  Nothing reads
+ *                       w_ih or its images in between: a range may run only after every call that still reads the old
+ *                       weights (part 2's dg GEMM reads W_ih^T's image) has been enqueued.
+ * Misaligned or out-of-range rows: WGNN_ERR_SHAPE. */
+#define WGNN_ROWS_IH 1
+#define WGNN_ROWS_HH 2
+#define WGNN_ROWS_STATE 4
+int wgnn_bwd_rows_align(const wgnn_dims* d);
+int wgnn_bwd_rows(const wgnn_dims* d, const void* Y, const void* stash, const wgnn_grads* g, int which, int row0, int rows,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int wgnn_finish_rows(const wgnn_dims* d, const wgnn_params* p, const wgnn_grads* g, int which, int row0, int rows,
+                     const wgnn_adam* adam, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Bytes of the caller-kept W_ih images (wgnn_params.prepared); depends on S, H and math only; 0 = this configuration
  * stages W_ih as it is (then wgnn_prepare_weights returns WGNN_ERR_UNSUPPORTED and `prepared` is ignored). */
 size_t wgnn_prepared_bytes(const wgnn_dims* d);

@@ -50,6 +50,7 @@ class Adam(C.Structure):
 BWD_DEFER = 16              # WGNN_BWD_DEFER
 FINISH_ADAM_GRU = 16        # WGNN_FINISH_ADAM_GRU / _CONV: wgnn_finish's optimiser step of one tensor family only
 FINISH_ADAM_CONV = 32
+ROWS_IH, ROWS_HH, ROWS_STATE = 1, 2, 4   # WGNN_ROWS_*: wgnn_bwd_rows / wgnn_finish_rows (row ranges of one GRU pair)
 
 
 EXPORTS = {
@@ -82,6 +83,11 @@ EXPORTS = {
                                     C.c_void_p, C.c_int]),
     "wgnn_finish": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Grads), C.c_int, C.POINTER(Adam), C.c_void_p,
                               C.c_size_t, C.c_void_p]),
+    "wgnn_bwd_rows_align": (C.c_int, [C.POINTER(Dims)]),
+    "wgnn_bwd_rows": (C.c_int, [C.POINTER(Dims), C.c_void_p, C.c_void_p, C.POINTER(Grads), C.c_int, C.c_int, C.c_int,
+                                C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wgnn_finish_rows": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Grads), C.c_int, C.c_int, C.c_int,
+                                   C.POINTER(Adam), C.c_void_p, C.c_size_t, C.c_void_p]),
     "wgnn_prepared_bytes": (C.c_size_t, [C.POINTER(Dims)]),
     "wgnn_prepare_weights": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.c_void_p, C.c_size_t, C.c_void_p]),
     "wgnn_gcn_layer_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

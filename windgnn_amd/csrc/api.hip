@@ -732,6 +732,144 @@ int wgnn_finish(const wgnn_dims* d, const wgnn_params* p, const wgnn_grads* g, i
   return launch_finish(a, (hipStream_t)stream);
 }
 
+}  // extern "C"
+
+namespace {
+// Row ranges of the weight-gradient products (wgnn_bwd_rows / wgnn_finish_rows): the wide-GRU path only, where each product
+// is ONE TN GEMM with a plain A operand -- the register-resident recurrences remap dW_hh's GEMM rows (msplit), and the one-pass
+// fp16 mode is not offered.  The alignment is the GEMM's M tile: a range is an offset on the A operand plus a smaller Mout,
+// and with whole tiles and the whole product's split-K count every element sums the same terms in the same order.
+int rows_align(const wgnn_dims* d, const Layout& L) {
+  if (!L.gen_gru || d->math == WGNN_MATH_F16) return 0;
+  return L.x3 ? TN_BM : 128;
+}
+
+int check_rows(const wgnn_dims* d, const Layout& L, int which, int row0, int rows) {
+  if ((which & ~(WGNN_ROWS_IH | WGNN_ROWS_HH | WGNN_ROWS_STATE)) != 0 ||
+      ((which & 3) != WGNN_ROWS_IH && (which & 3) != WGNN_ROWS_HH))
+    return WGNN_ERR_SHAPE;
+  if (which & WGNN_ROWS_STATE) return WGNN_ERR_UNSUPPORTED;          // per-window dW_hh rows (the state stash)
+  const int al = rows_align(d, L);
+  if (al == 0) return WGNN_ERR_UNSUPPORTED;
+  const int64_t end = (int64_t)row0 + rows;
+  if (row0 < 0 || rows < 1 || end > (int64_t)L.G3 || row0 % al != 0 || (end % al != 0 && end != (int64_t)L.G3))
+    return WGNN_ERR_SHAPE;
+  return WGNN_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int wgnn_bwd_rows_align(const wgnn_dims* d) {
+  if (check_dims(d) != WGNN_OK) return 0;
+  return rows_align(d, make_layout(d));
+}
+
+int wgnn_bwd_rows(const wgnn_dims* d, const void* Yv, const void* stash, const wgnn_grads* g, int which, int row0, int rows,
+                  void* workspace, size_t workspace_bytes, void* stream) {
+  int rc = check_dims(d);
+  if (rc != WGNN_OK) return rc;
+  if (!Yv || !stash || !g || !workspace) return WGNN_ERR_NULL;
+  const bool ih = (which & 3) == WGNN_ROWS_IH;
+  if (ih ? (!g->w_ih || !g->b_ih) : (!g->w_hh || !g->b_hh)) return WGNN_ERR_NULL;
+  const Layout L = make_layout(d);
+  rc = check_rows(d, L, which, row0, rows);
+  if (rc != WGNN_OK) return rc;
+  if (workspace_bytes < sizeof(float) * L.bwd_floats) return WGNN_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = (float*)workspace;
+  const float* sf = (const float*)stash;
+  // the reduce half of part 4, narrowed to the range: the other product's segment is off, the output pointers start at row0
+  FinishArgs a = {};
+  fill_reduce(L, d, g, ws, 4, a);
+  FinSeg& s = ih ? a.ih : a.hh;
+  (ih ? a.hh : a.ih) = FinSeg{};
+  s.Mout = s.Mgemm = rows;
+  if (L.x3) pgemm_tn_geom(rows, s.Nout, &s.T, &s.nNb, &s.ntiles);
+  a.g[ih ? 4 : 5] += (size_t)row0 * s.ncols;                         // w_ih / w_hh
+  a.g[ih ? 6 : 7] += row0;                                           // b_ih / b_hh
+  // (the A operand is read from column row0 on; the last range's final tile reads columns past 3H exactly as the whole
+  // product's does -- any finite data, inside the workspace -- and its rows are never stored)
+  if (L.x3) {
+    const bool full = d->math == WGNN_MATH_F16X3 || d->math == WGNN_MATH_F16X3G;
+    const size_t PG = L.BT * L.Gp;
+    const _Float16* dGIh = (const _Float16*)(ws + L.ws_dGI) + row0;
+    const _Float16* dGHh = (const _Float16*)(ws + L.ws_dGH) + row0;
+    if (ih) {
+      const _Float16* gh = (const _Float16*)(sf + L.st_g);
+      rc = launch_pgemm_tn(dGIh, L.gen2p ? dGIh : dGIh + PG, (int)L.Gp, gh, gh + L.BT * L.Ip, (int)L.Ip, 0, (int)L.BT,
+                           L.sk_ih, ws + L.ws_part_ih, rows, (int)L.I + 1, full && !L.gen2p, nullptr, nullptr, 0, 0, st,
+                           /*b_stream=*/true);
+    } else {
+      const _Float16* yph = (const _Float16*)(sf + L.st_yp);
+      const _Float16* ypl = yph + L.plane_rows * L.Hp;
+      rc = launch_pgemm_tn(dGHh, L.gen2p ? nullptr : dGHh + PG, (int)L.Gp, yph, ypl, (int)L.Hp, d->T, (int)L.BT, L.sk_hh,
+                           ws + L.ws_part_hh, rows, (int)L.H + 1, full, nullptr, nullptr, 0, 0, st, /*b_stream=*/false,
+                           /*per_window=*/false);
+    }
+  } else {
+    GemmArgs b = {};
+    b.a_kcontig = 0; b.b_kcontig = 0; b.ones_col = 1; b.lda = (int)L.Gp; b.M = rows; b.K = (int)L.BT;
+    if (ih) {
+      b.A = ws + L.ws_dGI + row0;
+      b.B = sf + L.st_g; b.ldb = (int)L.Ip; b.N = (int)L.I + 1;
+      b.splitk = L.sk_ih; b.partial = ws + L.ws_part_ih;
+    } else {
+      b.A = ws + L.ws_dGH + row0;
+      b.B = (const float*)Yv; b.ldb = (int)L.H; b.shift_T = d->T; b.N = (int)L.H + 1;
+      b.splitk = L.sk_hh; b.partial = ws + L.ws_part_hh;
+    }
+    rc = launch_gemm_f32(b, st);
+  }
+  if (rc != WGNN_OK) return rc;
+  return launch_finish(a, st);
+}
+
+int wgnn_finish_rows(const wgnn_dims* d, const wgnn_params* p, const wgnn_grads* g, int which, int row0, int rows,
+                     const wgnn_adam* adam, void* workspace, size_t workspace_bytes, void* stream) {
+  int rc = check_dims(d);
+  if (rc != WGNN_OK) return rc;
+  if (!p || !g || !adam || !workspace) return WGNN_ERR_NULL;
+  const Layout L = make_layout(d);
+  rc = check_rows(d, L, which, row0, rows);
+  if (rc != WGNN_OK) return rc;
+  if (adam->step < 1) return WGNN_ERR_SHAPE;
+  if (workspace_bytes < WGNN_STATUS_BYTES) return WGNN_ERR_WORKSPACE;
+  const bool ih = (which & 3) == WGNN_ROWS_IH;
+  const wgnn_grads& m = adam->exp_avg;
+  const wgnn_grads& v = adam->exp_avg_sq;
+  RowsAdamArgs r = {};
+  r.ncols = ih ? (int)L.I : (int)L.H;
+  const size_t off = (size_t)row0 * r.ncols;
+  r.p_w = const_cast<float*>(ih ? p->w_ih : p->w_hh);               // the optimiser updates the parameters in place
+  r.m_w = ih ? m.w_ih : m.w_hh;
+  r.v_w = ih ? v.w_ih : v.w_hh;
+  r.g_w = ih ? g->w_ih : g->w_hh;
+  r.p_b = const_cast<float*>(ih ? p->b_ih : p->b_hh);
+  r.m_b = ih ? m.b_ih : m.b_hh;
+  r.v_b = ih ? v.b_ih : v.b_hh;
+  r.g_b = ih ? g->b_ih : g->b_hh;
+  if (!r.p_w || !r.m_w || !r.v_w || !r.g_w || !r.p_b || !r.m_b || !r.v_b || !r.g_b) return WGNN_ERR_NULL;
+  r.p_w += off; r.m_w += off; r.v_w += off; r.g_w += off;
+  r.p_b += row0; r.m_b += row0; r.v_b += row0; r.g_b += row0;
+  r.row0 = row0;
+  r.rows = rows;
+  const double bc1 = 1.0 - pow((double)adam->beta1, (double)adam->step);     // as wgnn_finish
+  const double bc2 = 1.0 - pow((double)adam->beta2, (double)adam->step);
+  r.lr_over_bc1 = (float)(adam->lr / bc1);
+  r.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  r.b1 = adam->beta1; r.b2 = adam->beta2; r.eps = adam->eps;
+  r.status = (unsigned*)workspace;
+  if (ih && p->prepared && L.prep_kind == 1) {
+    r.pf_hi = (_Float16*)((float*)p->prepared + L.prep_f);
+    r.pf_lo = r.pf_hi + (size_t)L.np_g3 * L.Ip;
+    r.pb_hi = (_Float16*)((float*)p->prepared + L.prep_b);
+    r.pb_lo = r.pb_hi + (size_t)L.np_i * L.Gp;
+    r.np_g3 = L.np_g3; r.np_i = L.np_i;
+  }
+  return launch_adam_rows(r, (hipStream_t)stream);
+}
+
 int wgnn_bwd(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* Y,
              const float* dY, const void* stash, const wgnn_grads* g, void* workspace, size_t workspace_bytes,
              void* stream) {

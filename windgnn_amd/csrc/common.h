@@ -341,5 +341,20 @@ struct FinishArgs {
   int Ip, Gp, I;
 };
 int launch_finish(FinishArgs a, hipStream_t st);
+// wgnn_finish_rows: Adam on rows [row0, row0 + rows) of one GRU pair (W [.][ncols] and its bias), the pointers already offset
+// to row row0; pf_hi != null (W_ih with fp16-plane images): the parts of both images those rows own (row0 a multiple of 8)
+struct RowsAdamArgs {
+  float *p_w, *m_w, *v_w;
+  const float* g_w;
+  float *p_b, *m_b, *v_b;
+  const float* g_b;
+  int row0, rows, ncols;
+  float lr_over_bc1, inv_sqrt_bc2, b1, b2, eps;
+  _Float16 *pf_hi, *pf_lo, *pb_hi, *pb_lo;
+  int np_g3, np_i;
+  unsigned* status;
+  int vec;                     // set by launch_adam_rows: 16-byte loads and stores of whole row octets
+};
+int launch_adam_rows(const RowsAdamArgs& a, hipStream_t st);
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr,
                 float b1, float b2, float eps, hipStream_t st);

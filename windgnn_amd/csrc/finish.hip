@@ -272,7 +272,133 @@ __global__ void __launch_bounds__(256) finish_kernel(const FinishArgs a) {
   report_status(a.status, bad_w, WGNN_STATUS_WEIGHT_RANGE);
 }
 
+// ---- wgnn_finish_rows: Adam on a row range of one GRU pair, and the parts of the W_ih images those rows own.
+// Thread = 8 rows x one octet of 8 columns (the bias is column ncols, as in the forward image).  Each weight is stepped once,
+// with emit's formulas, and its fp16 split goes to both images: one 16-byte piece per row of the forward image (8 consecutive
+// k of one B row) and one per column of the W_ih^T image (its k = the 8 rows).  Padding inside a piece -- columns past the
+// bias, rows past 3H -- is written as the zeros wgnn_prepare_weights left there.  Per row, all loads come before any store
+// (16-byte loads where the rows allow them): the in-place updates would otherwise order every load after the last store.
+__device__ __forceinline__ float adam_rows_step(const RowsAdamArgs& a, float p, float& m, float& v, float gval, bool& bad_g) {
+  bad_g |= !(__builtin_fabsf(gval) <= 3.0e38f);
+  const float mi = __fmaf_rn(a.b1, m, __fmul_rn(1.f - a.b1, gval));
+  const float vi = __fmaf_rn(a.b2, v, __fmul_rn(__fmul_rn(1.f - a.b2, gval), gval));
+  m = mi;
+  v = vi;
+  const float denom = __fadd_rn(__fmul_rn(__fsqrt_rn(vi), a.inv_sqrt_bc2), a.eps);
+  return __fsub_rn(p, __fmul_rn(a.lr_over_bc1, __fdiv_rn(mi, denom)));
+}
+
+template <bool IMG>
+__global__ void __launch_bounds__(256) adam_rows_kernel(const RowsAdamArgs a) {
+  typedef _Float16 h8v __attribute__((ext_vector_type(8)));
+  const int c8n = (a.ncols + 8) / 8;                                  // column octets, the bias column included
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int r8 = (int)(t / c8n), c0 = 8 * (int)(t % c8n);
+  if (8 * r8 >= a.rows) return;
+  bool bad_g = false, bad_w = false;
+  h8v th[8], tl[8];                                                   // W_ih^T pieces: [column j][row i]
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int r = 8 * r8 + i;
+    const bool live = r < a.rows;
+    const bool wide = live && a.vec && c0 + 8 <= a.ncols;
+    const size_t e = (size_t)r * a.ncols + c0;
+    float gv[8], pv[8], mv[8], vv[8], w[8];
+    if (wide) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const f32x4 g4 = *(const f32x4*)(a.g_w + e + 4 * h), p4 = *(const f32x4*)(a.p_w + e + 4 * h);
+        const f32x4 m4 = *(const f32x4*)(a.m_w + e + 4 * h), v4 = *(const f32x4*)(a.v_w + e + 4 * h);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { gv[4 * h + q] = g4[q]; pv[4 * h + q] = p4[q]; mv[4 * h + q] = m4[q]; vv[4 * h + q] = v4[q]; }
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int c = c0 + j;
+        gv[j] = pv[j] = mv[j] = vv[j] = 0.f;
+        if (live && c < a.ncols) {
+          gv[j] = a.g_w[e + j]; pv[j] = a.p_w[e + j]; mv[j] = a.m_w[e + j]; vv[j] = a.v_w[e + j];
+        } else if (live && c == a.ncols) {
+          gv[j] = a.g_b[r]; pv[j] = a.p_b[r]; mv[j] = a.m_b[r]; vv[j] = a.v_b[r];
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool on = live && c0 + j <= a.ncols;
+      w[j] = on ? adam_rows_step(a, pv[j], mv[j], vv[j], gv[j], bad_g) : 0.f;
+    }
+    if (wide) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        *(f32x4*)(a.p_w + e + 4 * h) = f32x4{w[4 * h], w[4 * h + 1], w[4 * h + 2], w[4 * h + 3]};
+        *(f32x4*)(a.m_w + e + 4 * h) = f32x4{mv[4 * h], mv[4 * h + 1], mv[4 * h + 2], mv[4 * h + 3]};
+        *(f32x4*)(a.v_w + e + 4 * h) = f32x4{vv[4 * h], vv[4 * h + 1], vv[4 * h + 2], vv[4 * h + 3]};
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int c = c0 + j;
+        if (live && c < a.ncols) {
+          a.p_w[e + j] = w[j]; a.m_w[e + j] = mv[j]; a.v_w[e + j] = vv[j];
+        } else if (live && c == a.ncols) {
+          a.p_b[r] = w[j]; a.m_b[r] = mv[j]; a.v_b[r] = vv[j];
+        }
+      }
+    }
+    if (IMG) {
+      h8v fh, fl;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float x = w[j];
+        bad_w |= out_of_fp16_range(x);
+        asm volatile("" : "+v"(x));       // split the stored fp32 value (no fp16-output fma contraction: see seg_tn)
+        const _Float16 h = (_Float16)x, l = (_Float16)(x - (float)h);
+        fh[j] = h; fl[j] = l;
+        th[j][i] = h; tl[j][i] = l;
+      }
+      if (live) {
+        const size_t f = bimg_off(a.row0 + r, c0, a.np_g3);
+        *(h8v*)(a.pf_hi + f) = fh;
+        *(h8v*)(a.pf_lo + f) = fl;
+      }
+    }
+  }
+  if (IMG) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (c0 + j >= a.ncols) break;
+      const size_t b = bimg_off(c0 + j, a.row0 + 8 * r8, a.np_i);
+      *(h8v*)(a.pb_hi + b) = th[j];
+      *(h8v*)(a.pb_lo + b) = tl[j];
+    }
+  }
+  report_status(a.status, bad_g, WGNN_STATUS_GRAD_NONFINITE);
+  report_status(a.status, bad_w, WGNN_STATUS_WEIGHT_RANGE);
+}
+
 }  // namespace
+
+int launch_adam_rows(const RowsAdamArgs& a, hipStream_t st) {
+  if (a.rows < 1 || a.ncols < 1) return WGNN_ERR_SHAPE;
+  if (a.pf_hi && (a.row0 & 7)) return WGNN_ERR_SHAPE;                 // W_ih^T pieces hold 8 rows
+  const int64_t threads = (int64_t)cdiv_i(a.rows, 8) * ((a.ncols + 8) / 8);
+  const int64_t grid = (threads + 255) / 256;
+  if (grid > 0x7fffffffll) return WGNN_ERR_SHAPE;
+  const double np = (double)a.rows * (a.ncols + 1);
+  RowsAdamArgs k = a;                 // 16-byte row pieces: every row of all four arrays starts 16-byte aligned
+  k.vec = (a.ncols % 4 == 0) && ((((uintptr_t)a.p_w) | ((uintptr_t)a.m_w) | ((uintptr_t)a.v_w) | ((uintptr_t)a.g_w)) & 15) == 0;
+  if (a.pf_hi) {
+    PROF_LAUNCH("adam_rows_kernel<img>", 12.0 * np, 36.0 * np, st,
+                hipLaunchKernelGGL(adam_rows_kernel<true>, dim3((unsigned)grid), dim3(256), 0, st, k));
+  } else {
+    PROF_LAUNCH("adam_rows_kernel", 12.0 * np, 28.0 * np, st,
+                hipLaunchKernelGGL(adam_rows_kernel<false>, dim3((unsigned)grid), dim3(256), 0, st, k));
+  }
+  WGNN_CHECK_LAUNCH();
+  return WGNN_OK;
+}
 
 int finish_seg_blocks(const FinSeg& s) {
   if (s.kind == 2) {                                                           // slab4 / 64, or slab4 / 256 (seg_tn, few K chunks)

@@ -14,7 +14,7 @@ process initialises the GPU (bench.py calls it first thing).
 from __future__ import annotations
 
 import os
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
@@ -50,6 +50,66 @@ def grad_scale_for_shard(n_local: int, n_global: int) -> float:
 
 def flatten(tensors: Sequence[torch.Tensor]) -> torch.Tensor:
     return torch.cat([t.reshape(-1) for t in tensors])
+
+
+class GradBlock(NamedTuple):
+    """One row block of the blocked exchange: gate rows [row0, row0 + rows) of w_ih (tensor "ih") or w_hh ("hh"), whose
+    gradient is the bucket slice [offset, offset + numel)."""
+    tensor: str
+    row0: int
+    rows: int
+    offset: int
+    numel: int
+
+
+class GradBlockPlan(NamedTuple):
+    """The bucket of the blocked exchange, [4-float header | conv | b_ih | b_hh | w_ih | w_hh] (floats):
+    `slots` = (offset, numel) of the 8 gradients in state_dict order, `tail` = (offset, numel) of [loss | conv | b_ih | b_hh]
+    (one slice: the biases are final only after every block), `blocks` = the row blocks of w_ih, then those of w_hh, each one
+    contiguous slice, together exactly the rest of the bucket."""
+    blocks: Tuple[GradBlock, ...]
+    tail: Tuple[int, int]
+    slots: Tuple[Tuple[int, int], ...]
+    numel: int
+
+
+def _row_blocks(G3: int, k: int, align: int):
+    """[row0, row1) of up to k blocks of G3 rows: whole units of `align` rows (the last block ends at G3), as equal as
+    the units allow."""
+    units = -(-G3 // align)
+    n = min(k, units)
+    cuts = [min(G3, (i * units // n) * align) for i in range(n + 1)]
+    return [(cuts[i], cuts[i + 1]) for i in range(n)]
+
+
+def grad_block_plan(S: int, H: int, k: int, align: int, F: int = 13) -> GradBlockPlan:
+    """The blocked exchange of a GCN_GRU with S stations and hidden width H: w_ih and w_hh (3H rows each) cut into row blocks
+    whose boundaries are multiples of `align` (wgnn_bwd_rows_align) -- up to `k` of the wider one, proportionally fewer (at
+    least one) of the other.  A pure function of its arguments, so
+    every rank computes the same plan."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError("windgnn_amd: grad_blocks must be an int >= 1 (or None / 'auto'), got %r" % (k,))
+    if align < 1:
+        raise ValueError("windgnn_amd: row alignment must be >= 1, got %r" % (align,))
+    G3, I = 3 * H, S * F
+    n_conv = 2 * (F * F + F)
+    sizes = [F * F, F, F * F, F, G3 * I, G3 * H, G3, G3]
+    order = (0, 1, 2, 3, 6, 7, 4, 5)                 # bucket order: conv, b_ih, b_hh, w_ih, w_hh
+    slots = [None] * 8
+    o = HEADER
+    for t in order:
+        slots[t] = (o, sizes[t])
+        o += sizes[t]
+    blocks = []
+    # the wider weight gets k blocks, the other as many as keep the blocks about equally large (at least one): equal messages,
+    # and no small GEMM whose last wave of tiles leaves most CUs idle
+    big = max(I, H)
+    for name, t, ncols in (("ih", 4, I), ("hh", 5, H)):
+        base = slots[t][0]
+        for r0, r1 in _row_blocks(G3, max(1, round(k * ncols / big)), align):
+            blocks.append(GradBlock(name, r0, r1 - r0, base + r0 * ncols, (r1 - r0) * ncols))
+    tail = (LOSS_SLOT, HEADER - LOSS_SLOT + n_conv + 2 * G3)
+    return GradBlockPlan(tuple(blocks), tail, tuple(slots), o)
 
 
 class RcclApi:
@@ -341,3 +401,23 @@ class BucketExchange:
             self.bucket[LOSS_SLOT].mul_(weight)
         dist.all_reduce(self.bucket[LOSS_SLOT:HEADER + self.n_conv], group=self.group)
         work.wait()
+
+    # ---- the blocked exchange (TrainStep(grad_blocks=...)): the bucket is laid out by grad_block_plan; every rank issues
+    # start_block for every block of the plan, in plan order, then start_tail -- an empty shard included
+    record = None        # a list: every blocked collective appends (offset, numel) of its slice (tests compare the ranks)
+
+    def _start_slice(self, offset: int, numel: int):
+        if self.record is not None:
+            self.record.append((offset, numel))
+        return dist.all_reduce(self.bucket[offset:offset + numel], group=self.group, async_op=True)
+
+    def start_block(self, block: GradBlock):
+        """Start summing one row block's slice (its rows are final after wgnn_bwd_rows); returns the async work handle."""
+        return self._start_slice(block.offset, block.numel)
+
+    def start_tail(self, plan: GradBlockPlan, weight: float):
+        """Weight this shard's mean loss and start summing [loss | conv | b_ih | b_hh] (final after part 2 and every block);
+        returns the async work handle."""
+        if weight != 1.0:
+            self.bucket[LOSS_SLOT].mul_(weight)
+        return self._start_slice(*plan.tail)

@@ -280,6 +280,43 @@ def finish_step(d, params, grads, which: int, adam=None, prepared=None, device=N
     _lib.check(rc, "wgnn_finish(%d%s)" % (which, ", adam" if adam is not None else ""))
 
 
+def _adam_struct(adam):
+    ad = _lib.Adam()
+    ad.exp_avg = _params_struct(_lib.Grads, adam["exp_avg"])
+    ad.exp_avg_sq = _params_struct(_lib.Grads, adam["exp_avg_sq"])
+    ad.step, ad.lr, ad.beta1, ad.beta2, ad.eps = adam["step"], adam["lr"], adam["beta1"], adam["beta2"], adam["eps"]
+    return ad
+
+
+def rows_align(d) -> int:
+    """wgnn_bwd_rows_align: the row alignment of a range of wgnn_bwd_rows / wgnn_finish_rows; 0 = not offered for this shape."""
+    return int(_lib.load().wgnn_bwd_rows_align(C.byref(d)))
+
+
+def bwd_rows(d, Y, stash, grads, which: int, row0: int, rows: int, device=None) -> None:
+    """wgnn_bwd_rows: part 4 of the backward (weight-gradient GEMMs + their reduction) for gate rows [row0, row0 + rows) of
+    the pair `which` (_lib.ROWS_IH: w_ih / b_ih, _lib.ROWS_HH: w_hh / b_hh), after part 1 on the same workspace."""
+    lib = _lib.load()
+    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
+    ws = _Workspace.get(device if device is not None else grads[0].device, ws_bytes)
+    gs = _params_struct(_lib.Grads, grads)
+    rc = lib.wgnn_bwd_rows(C.byref(d), _ptr(Y), _ptr(stash), C.byref(gs), which, row0, rows, _ptr(ws), ws_bytes, _stream())
+    _lib.check(rc, "wgnn_bwd_rows(%d, %d, %d)" % (which, row0, rows))
+
+
+def finish_rows(d, params, grads, which: int, row0: int, rows: int, adam, prepared=None, device=None) -> None:
+    """wgnn_finish_rows: Adam (adam: as finish_step) on rows [row0, row0 + rows) of the pair `which`, and the parts of
+    `prepared` those rows own."""
+    lib = _lib.load()
+    ws = _Workspace.get(device if device is not None else grads[0].device, _lib.STATUS_BYTES)
+    ps = _params_struct(_lib.Params, params, prepared)
+    gs = _params_struct(_lib.Grads, grads)
+    ad = _adam_struct(adam)
+    rc = lib.wgnn_finish_rows(C.byref(d), C.byref(ps), C.byref(gs), which, row0, rows, C.byref(ad), _ptr(ws), ws.numel(),
+                              _stream())
+    _lib.check(rc, "wgnn_finish_rows(%d, %d, %d)" % (which, row0, rows))
+
+
 class GCNGRUFunction(torch.autograd.Function):
     """Y = GCN_GRU(A, X; 8 params).  Gradients flow to the parameters only: the reference's
     adjacency and inputs do not require grad (src/main.py:26, src/step4_sequence_preparer.py:58)."""

@@ -18,6 +18,15 @@ The loss a step returns is a 0-dim VIEW of the bucket's header (no clone launch 
 A rank whose shard is EMPTY (fewer windows than ranks) still issues every collective of the step: it contributes a zero
 bucket and runs the optimiser's launch on the summed gradient, so no rank is left waiting in an all-reduce.
 
+Blocked exchange (`grad_blocks`, opt-in, for buckets of GB: BASELINE configs[4] has 9.66 GB): the weight-gradient GEMMs run
+per row block of w_ih, then of w_hh (wgnn_bwd_rows), and each block's all-reduce starts as soon as its rows are final, so the
+exchange runs under the remaining blocks' GEMMs and under part 2; the tail [loss | conv | b_ih | b_hh] follows part 2, and
+Adam runs per block (wgnn_finish_rows) once the tail -- which holds the biases every block's Adam reads -- and the block have
+arrived.  HAZARD: part 2 (dg = dGI W_ih, through the staged W_ih^T image) reads the OLD weights, and wgnn_finish_rows
+rewrites W_ih and its images in place: every block's Adam must be enqueued after part 2.  One enqueued earlier gives a wrong
+dg -- and wrong conv gradients -- without any error (tests/test_gpu_grad_blocks.py shows the difference).  With one rank the
+blocked step is the one-bucket step bit for bit.
+
 A step that RAISES (a refused launch, a failed collective) leaves the optimiser state undefined: `steps` counts completed
 steps only, but in the two-collective form the GRU tensors and their moments may already have been stepped when a later
 launch of the same step fails, and a retry would then apply the same bias-correction step number to them twice.  Do not
@@ -27,21 +36,31 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .distributed import HEADER, LOSS_SLOT, BucketExchange
-from .functional import (check_range_status, finish_step, gcn_gru_backward_mse_raw, gcn_gru_forward_raw,
-                         gcn_gru_state_backward_raw, gcn_gru_state_forward_raw, mse_loss_grad, prepared_weights,
-                         refresh_prepared)
+from .distributed import HEADER, LOSS_SLOT, BucketExchange, grad_block_plan
+from .functional import (bwd_rows, check_range_status, finish_rows, finish_step, gcn_gru_backward_mse_raw,
+                         gcn_gru_forward_raw, gcn_gru_state_backward_raw, gcn_gru_state_forward_raw, mse_loss_grad,
+                         prepared_weights, refresh_prepared, rows_align)
 from .modules import GCN_GRU
+
+AUTO_GRAD_BLOCKS = 8                # grad_blocks="auto": row blocks per GRU weight ...
+AUTO_BLOCK_BYTES = 64 << 20         # ... from a gradient bucket of this size (smaller ones are latency-bound: one bucket)
 
 
 class TrainStep:
     def __init__(self, model: GCN_GRU, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  process_group=None, check_every: int = 100, overlap_collectives: bool = False, direct_rccl=None,
-                 rccl_loader=None, carry_state: bool = False):
+                 rccl_loader=None, carry_state: bool = False, grad_blocks=None):
         """carry_state: truncated BPTT over consecutive chunks -- each step starts the recurrence from the h_n of the previous
         step (detached; zeros on the first step and after reset_state()), so a model trained on chunks of a long series
         learns the carried-state regime StreamingForecaster(window=None) serves.  The batch size must stay the same
-        between resets; fp32 I/O only."""
+        between resets; fp32 I/O only.
+
+        grad_blocks (with a process group): None = the schedules above; an int k = the blocked exchange, the wider of w_ih
+        and w_hh cut into up to k row blocks (multiples of wgnn_bwd_rows_align), the other into about as large ones
+        (distributed.grad_block_plan), each block's all-reduce started as soon as its weight-gradient GEMM is done (module
+        docstring); "auto" = k = AUTO_GRAD_BLOCKS when the bucket reaches
+        AUTO_BLOCK_BYTES and the shape has the row-range entry points, else None.  Not with carry_state,
+        overlap_collectives or direct_rccl."""
         if not getattr(model, "fused", True):
             raise RuntimeError("windgnn_amd: TrainStep drives the fused hot path, i.e. the reference model's own widths "
                                "(input_dim = hidden_dim = 13, src/main.py:41); a GCN_GRU of other widths trains through "
@@ -51,15 +70,28 @@ class TrainStep:
         sizes = [p.numel() for p in self.params]
         dev = self.params[0].device
         self.flat_p = torch.cat([p.detach().reshape(-1) for p in self.params]).contiguous()
+        self.group = process_group
+        self.world = 1
+        if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
+            self.world = torch.distributed.get_world_size(process_group)
+        # an explicitly passed group runs the collective path even with one rank (the all-reduces execute)
+        self.collective = self.world > 1 or process_group is not None
+        self.plan = self._grad_block_plan(grad_blocks, sizes, carry_state, overlap_collectives, direct_rccl)
         # gradient bucket with a 4-float header (16-byte aligned bucket): header[3] = the step's loss, so that the loss
-        # rides in the conv-gradient all-reduce (the conv gradients are the first 364 floats of the bucket)
-        self._gbuf = torch.zeros(self.flat_p.numel() + HEADER, dtype=torch.float32, device=dev)
+        # rides in the conv-gradient all-reduce (the conv gradients are the first 364 floats of the bucket).  The blocked
+        # exchange lays it out as its plan says: [header | conv | b_ih | b_hh | w_ih | w_hh]
+        if self.plan is None:
+            self._gbuf = torch.zeros(self.flat_p.numel() + HEADER, dtype=torch.float32, device=dev)
+            g_split = self._gbuf[HEADER:].split(sizes)
+        else:
+            self._gbuf = torch.zeros(self.plan.numel, dtype=torch.float32, device=dev)
+            g_split = [self._gbuf[o:o + n] for o, n in self.plan.slots]
         self.flat_g = self._gbuf[HEADER:]
         self._loss = self._gbuf[LOSS_SLOT]
         self.exp_avg = torch.zeros_like(self.flat_p)
         self.exp_avg_sq = torch.zeros_like(self.flat_p)
         self.p_views, self.g_views = [], []
-        for p, pv, gv in zip(self.params, self.flat_p.split(sizes), self.flat_g.split(sizes)):
+        for p, pv, gv in zip(self.params, self.flat_p.split(sizes), g_split):
             p.data = pv.view_as(p)              # parameters become views of the flat bucket
             p.grad = gv.view_as(p)
             self.p_views.append(p.data)
@@ -72,25 +104,49 @@ class TrainStep:
         self.n_conv = sum(sizes[:4])
         self.lr, self.betas, self.eps = lr, betas, eps
         self.steps = 0
-        self.group = process_group
-        self.world = 1
-        if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
-            self.world = torch.distributed.get_world_size(process_group)
-        # an explicitly passed group runs the collective path even with one rank (the all-reduces execute)
-        self.collective = self.world > 1 or process_group is not None
         self.overlap_collectives = overlap_collectives
         # direct_rccl: None = only if WGNN_RCCL_DIRECT=1 (opt-in: distributed.DirectRccl); the two-collective form overlaps
         # through torch.distributed's own stream by design and never takes it
         self.exchange = None
         if self.collective:
             self.exchange = BucketExchange(self._gbuf, self.n_conv, process_group,
-                                           False if (overlap_collectives and direct_rccl is None) else direct_rccl,
-                                           rccl_loader)
+                                           False if ((overlap_collectives or self.plan is not None) and direct_rccl is None)
+                                           else direct_rccl, rccl_loader)
         self.check_every = check_every          # f16x3 / f16: read the library's range-status word every N steps
         self.device = dev
         # carried state: two [B, H] buffers (h0 of this step, h_n into the other: they may not alias), swapped per step
         self.carry_state = carry_state
         self._hbuf, self._hcur, self._has_state = None, 0, False
+
+    def _grad_block_plan(self, grad_blocks, sizes, carry_state, overlap_collectives, direct_rccl):
+        """The blocked exchange's plan (distributed.grad_block_plan), or None for the one-bucket schedules."""
+        if grad_blocks is None:
+            return None
+        if isinstance(grad_blocks, str) and grad_blocks != "auto":
+            raise ValueError("windgnn_amd: grad_blocks must be None, an int >= 1 or 'auto', got %r" % (grad_blocks,))
+        why = None
+        if not self.collective:
+            why = "it needs a process group (it blocks the gradient all-reduce)"
+        elif carry_state:
+            why = "the carried-state step (carry_state=True) keeps the one-bucket schedule"
+        elif overlap_collectives:
+            why = "overlap_collectives=True is another schedule of the same collectives"
+        elif direct_rccl:
+            why = "direct_rccl enqueues the all-reduce on the compute stream, so nothing could overlap it"
+        if why is not None:
+            raise RuntimeError("windgnn_amd: TrainStep(grad_blocks=%r): %s" % (grad_blocks, why))
+        S, H = self.params[4].shape[1] // 13, self.params[5].shape[1]
+        math = self.model.math
+        align = rows_align(_lib.Dims(1, 1, S, 13, H, math, _lib.ADJ_CSR, 1, _lib.IO_F32))
+        if grad_blocks == "auto":
+            if align == 0 or 4 * sum(sizes) < AUTO_BLOCK_BYTES:
+                return None
+            grad_blocks = AUTO_GRAD_BLOCKS
+        elif align == 0:
+            raise RuntimeError("windgnn_amd: TrainStep(grad_blocks=%r): the row-range weight gradients (wgnn_bwd_rows) "
+                               "need the wide-GRU path (H > 127 in f16x3 / f16x3g, H > 128 in f32; not the f16 mode), got "
+                               "H = %d, math = %d" % (grad_blocks, H, math))
+        return grad_block_plan(S, H, grad_blocks, align)
 
     def _param_version(self):
         """torch's in-place version counters of the parameters: load_state_dict / optimiser-free edits through the
@@ -129,7 +185,10 @@ class TrainStep:
         pre = self._prepared
         gs = self.exchange.shard_weight(0, n_global)                   # 0.0; the count collective, if any, is issued
         self._gbuf.zero_()
-        if not self.overlap_collectives:
+        if self.plan is not None:
+            works = [self.exchange.start_block(b) for b in self.plan.blocks]
+            self._blocked_adam(d, works, self.exchange.start_tail(self.plan, gs), pre)
+        elif not self.overlap_collectives:
             self.exchange.all_reduce_all(gs)
             finish_step(d, self.p_views, self.g_views, 0, self._adam(), pre, self.device)
         else:
@@ -142,6 +201,40 @@ class TrainStep:
             finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_CONV, adam, pre, self.device)
         self.steps += 1
         return self._loss, torch.empty(0, T, H, dtype=X.dtype, device=X.device)
+
+    def _blocked_adam(self, d, works, wtail, pre):
+        """The optimiser half of the blocked step: Adam per row block once its all-reduce (and the tail's) has arrived, then
+        the conv tensors."""
+        wtail.wait()                    # b_ih / b_hh ride in the tail, and every block's Adam steps its rows' biases
+        adam = self._adam()
+        for b, work in zip(self.plan.blocks, works):
+            work.wait()
+            finish_rows(d, self.p_views, self.g_views, _lib.ROWS_IH if b.tensor == "ih" else _lib.ROWS_HH, b.row0, b.rows,
+                        adam, pre, self.device)
+        finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_CONV, adam, pre, self.device)
+
+    def _blocked_step(self, A, X, L, n_global):
+        """step() with grad_blocks: part 1, then per row block its weight-gradient GEMM + reduction and the start of its
+        all-reduce, then part 2 under the last blocks' collectives, the tail's all-reduce and the blocked Adam."""
+        DEFER = _lib.BWD_DEFER
+        loss = self._loss
+        gs = self.exchange.shard_weight(X.shape[0], n_global)
+        Y, stash, d = self._forward(A, X, L)
+        pre = self._prepared
+        gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, loss, gs, part=1 | 8 | DEFER,
+                                 prepared=pre)
+        works = []
+        for b in self.plan.blocks:
+            bwd_rows(d, Y, stash, self.g_views, _lib.ROWS_IH if b.tensor == "ih" else _lib.ROWS_HH, b.row0, b.rows,
+                     self.device)
+            works.append(self.exchange.start_block(b))
+        # HAZARD: part 2 reads W_ih through its W_ih^T image, and the blocks' Adam rewrites both in place.  Part 2 is enqueued
+        # here, after every block's GEMM and before ANY block's Adam; moving a wgnn_finish_rows above this line gives a wrong
+        # dg (and wrong conv gradients) with no error.
+        gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, loss, gs, part=2 | DEFER, prepared=pre)
+        finish_step(d, self.p_views, self.g_views, 2, device=self.device)
+        self._blocked_adam(d, works, self.exchange.start_tail(self.plan, gs), pre)   # loss: the big-batch mean
+        return loss, Y
 
     def forward_backward(self, A, X, L):
         """src/main.py:66,72,79: returns (loss, Y); gradients land in the flat bucket (no optimiser step).  `loss` is a
@@ -244,6 +337,8 @@ class TrainStep:
         loss = self._loss
         if self.carry_state:
             loss, Y = self._state_step(A, X, L, n_global)
+        elif self.plan is not None:
+            loss, Y = self._blocked_step(A, X, L, n_global)
         elif self.collective and not self.overlap_collectives:
             # the single-rank schedule, with ONE all-reduce of [loss | conv | GRU gradients] between the reduce-only finish and
             # the optimiser's: one collective, one stream dependency each way per step
