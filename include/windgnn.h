@@ -158,22 +158,19 @@ typedef struct wgnn_adam {
 int wgnn_version(void);
 const char* wgnn_strerror(int status);
 
-/* Process-wide options: which of two bit-identical kernel schedules runs.  Options 0-3 do not change a result bit, option 4 only the summation order of some products; there is no
- * reference counterpart (the reference has no kernels to choose between).  wgnn_set_option returns the PREVIOUS value (>= 0)
- * or WGNN_ERR_SHAPE for an unknown key / value; it takes effect for calls issued after it returns and is atomic, but callers
- * that flip an option while other threads launch get either schedule for those launches.
+/* Process-wide options: which of two kernel schedules runs.  Keys 0, 1, 2 and 5 do not change a result bit; key 4 changes the
+ * summation order of some products.  Key 3 (a chunked backward part 2, measured slower) is retired: it is an unknown key now.
+ * There is no reference counterpart (the reference has no kernels to choose between).  wgnn_set_option returns the PREVIOUS
+ * value (>= 0) or WGNN_ERR_SHAPE for an unknown key / value; it takes effect for calls issued after it returns and is atomic,
+ * but callers that flip an option while other threads launch get either schedule for those launches.
  *   WGNN_OPT_FUSED_FWD  0 never / 1 stash-less forwards (default) / 2 every supported forward run the fused GCN + input
  *                       projection kernel (csrc/gcngi.hip).  Initial value: environment variable WGNN_FUSED_FWD, read once at
  *                       the first call that needs it (never again). */
 #define WGNN_OPT_FUSED_FWD 0
-/* Measurement aids (same results, another schedule; defaults 0 / 0 / 1): roles of the fused kernel's waves assigned per SIMD
- * instead of per wave index (0 / 1); s_setprio level of its projection waves (0..3); backward part 2 (dg GEMM -> GCN backward)
- * as 1 / 2 / 4 / 8 producer -> consumer pairs over row chunks (taken only where every chunk still fills the chip; must not
- * change between a WGNN_BWD_DEFER part 2 and its wgnn_finish). */
+/* Measurement aids (same results, another schedule; defaults 0 / 0): roles of the fused kernel's waves assigned per SIMD
+ * instead of per wave index (0 / 1); s_setprio level of its projection waves (0..3). */
 #define WGNN_OPT_GG_ROLE_SPLIT 1
 #define WGNN_OPT_GG_GEMM_PRIO 2
-#define WGNN_OPT_BWD2_CHUNKS 3
-#define WGNN_BWD2_MAX_CHUNKS 8
 /* 1 (default): NT plane products with >= 1024 rows, >= 2048 columns and a contraction >= 1024 long (BASELINE configs[4]) run
  * the 256 x 256-tile kernel of csrc/pgemm_big.hip (their activation operand rewritten as an image first); 0: the 192 x 448-tile
  * kernel shaped for the 34-station widths.  The two sum each dot product in a different order (results differ by fp32
@@ -368,7 +365,8 @@ int wgnn_gcn_layer_bwd(int32_t ntiles, int32_t S, int32_t F, int32_t F_out, cons
  * not 13 runs behind two wgnn_gcn_layer_* calls (the fused path's kernels hard-code 13 features, like the reference's
  * :16).  d: the same dims as for wgnn_fwd with math WGNN_MATH_F32, io WGNN_IO_F32, a dense adjacency format (else
  * WGNN_ERR_UNSUPPORTED); only p->w_ih, w_hh, b_ih, b_hh are read.  Workspace / stash sizes: wgnn_workspace_bytes /
- * wgnn_stash_bytes of d.  wgnn_gru_bwd writes the four GRU slots of `grads` (the conv slots may be NULL) and dg [B,T,S*13]. */
+ * wgnn_stash_bytes of d.  wgnn_gru_bwd writes the four GRU slots of `grads` (the conv slots may be NULL) and dg [B,T,S*13];
+ * its `g` is only checked for NULL: what it reads is the copy of g that wgnn_gru_fwd left in the stash. */
 int wgnn_gru_fwd(const wgnn_dims* d, const float* g, const wgnn_params* p, void* Y, void* stash, void* workspace,
                  size_t workspace_bytes, void* stream);
 int wgnn_gru_bwd(const wgnn_dims* d, const float* g, const wgnn_params* p, const void* Y, const float* dY, const void* stash,

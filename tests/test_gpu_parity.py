@@ -1595,45 +1595,6 @@ def test_4096_station_config_full_size_properties_B128_T24(math):
     torch.cuda.empty_cache()
 
 
-@pytest.mark.parametrize("math", ["f16x3", "f16x3g", "f16"])
-def test_backward_part2_in_row_chunks_equals_one_launch(math):
-    """WGNN_OPT_BWD2_CHUNKS (a schedule option): dg GEMM -> GCN backward as 2 / 4 / 8 producer -> consumer
-    pairs over row chunks.  The GRU gradients do not depend on it at all; the conv gradients are the same per-tile products
-    summed over per-workgroup partial rows in another grouping: 2e-6 of max against the single launch pair, and still inside
-    the mode's tolerance against the fp64 oracle.  Chunks that would not fill the chip are refused silently (1536 windows x 24
-    = 36 864 rows: 8 chunks of 4608 rows = 24 GEMM tiles are taken; 1537 windows: no chunk count divides, one launch)."""
-    from oracle import windgnn_oracle as orc
-    from windgnn_amd import _lib
-    dev = _dev()
-    S, T, H = 34, 24, 102
-    p = orc.init_params(S, 13, H, seed=9)
-    g = torch.Generator().manual_seed(55)
-    A = torch.rand(S, S, generator=g) / S + 0.01
-    for B in (1536, 1537):
-        X = torch.rand(B, T, S, 13, generator=g)
-        L = torch.rand(B, T, H, generator=g)
-        res = {}
-        try:
-            for ch in (1, 2, 4, 8):
-                _lib.set_option(_lib.OPT_BWD2_CHUNKS, ch)
-                res[ch] = _run_step(_model_from(p, S, H, math), A.to(dev), X.to(dev), L.to(dev))
-        finally:
-            _lib.set_option(_lib.OPT_BWD2_CHUNKS, 1)
-        for ch in (2, 4, 8):
-            assert torch.equal(res[1][0], res[ch][0]) and res[1][1] == res[ch][1]
-            for k in PARAM_KEYS:
-                if k.startswith("gru") or B == 1537:
-                    assert torch.equal(res[1][2][k], res[ch][2][k]), (B, ch, k)
-                else:
-                    assert rel_to_max(res[ch][2][k], res[1][2][k]) <= 2e-6, (B, ch, k)
-        if B == 1536:
-            assert any(not torch.equal(res[1][2][k], res[8][2][k]) for k in PARAM_KEYS[:4])      # the chunked schedule really ran
-            Yo, loss_o, go = orc.train_step(A.double(), X.double(), L.double(), {k: v.double() for k, v in p.items()})
-            tol = F16_G_TOL if math == "f16" else G_TOL
-            for k in PARAM_KEYS:
-                assert rel_to_max(res[8][2][k], go[k]) <= tol, k
-
-
 def test_exact_fp32_projection_as_two_workgroups_per_cu_is_bitwise_the_one_workgroup_form():
     """WGNN_OPT_GEMM32_FORM (a schedule option, round 5): the exact-fp32 NT products (GI, dg) from 24 448 rows on as two 4-wave
     workgroups per CU (128 x 160 tiles; dg's 14 column tiles as slices of 5, 5 and 4) with and without the late start, against

@@ -66,6 +66,7 @@ assert lib.wgnn_gru_bwd(C.byref(dg), None, C.byref(L.Params()), None, None, None
 for k in range(-1, 7):
     lib.wgnn_get_option(k); lib.wgnn_set_option(k, 9)
 assert lib.wgnn_set_option(0, 2) in (0, 1, 2) and lib.wgnn_get_option(0) == 2 and lib.wgnn_set_option(0, 1) == 2
+assert lib.wgnn_set_option(3, 1) == -2 and lib.wgnn_get_option(3) == -2      # key 3 (chunked backward part 2) is retired
 assert lib.wgnn_gcn_layer_csr_fwd(4, 34, 13, 0, None, None, None, None, None, None) == -2
 assert lib.wgnn_mse_loss_grad(None, None, 5, 1.0, None, None, None, 0, None) == -1
 assert lib.wgnn_adam_step(None, None, None, None, 5, 1, 1e-3, 0.9, 0.999, 1e-8, None) == -1

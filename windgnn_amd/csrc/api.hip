@@ -64,6 +64,9 @@ int pick_splitk(size_t BT, int tiles, int target_wgs, int min_rows) {
   return sk < 1 ? 1 : sk;
 }
 
+// the split-fp16 modes whose products take three passes (hi x hi + hi x lo + lo x hi); f16 takes one, f32 none
+bool three_pass(const wgnn_dims* d) { return d->math == WGNN_MATH_F16X3 || d->math == WGNN_MATH_F16X3G; }
+
 Layout make_layout(const wgnn_dims* d, bool state = false) {
   Layout L;
   L.state = state;
@@ -136,7 +139,7 @@ Layout make_layout(const wgnn_dims* d, bool state = false) {
   }
   // split fp16 modes with the register-resident recurrence: the gate records hold r | z | gh_n only and the BPTT kernel forms
   // n = tanh(gi_n + r gh_n) from GI, so GI (which the projection GEMM writes anyway) goes into the stash, not the workspace
-  L.gi_stash = (x3 && !L.gen_gru && (d->math == WGNN_MATH_F16X3 || d->math == WGNN_MATH_F16X3G)) || L.rec32;   // (and gru.hip's)
+  L.gi_stash = (x3 && !L.gen_gru && three_pass(d)) || L.rec32;   // (and gru.hip's)
   L.st_GI = o; o += al(L.gi_stash ? L.BT * L.Gp : 0);
   L.hq = (int)rup(L.H + 1, 16);
   const bool hprev_rows = L.g32tn || (state && !x3);                // (the state stash: every exact-fp32 path)
@@ -187,7 +190,6 @@ Layout make_layout(const wgnn_dims* d, bool state = false) {
   {
     size_t a = gcn32_bwd_partial_floats((int)L.BT), b = gcnx2_bwd_partial_floats((int)L.BT);
     if (L.gen_gcn) a = gcn_csr_bwd_partial_floats();
-    b *= WGNN_BWD2_MAX_CHUNKS;                                         // (chunked part 2: one set of partial rows per chunk)
     L.ws_gcnpart = o; o += al(a > b ? a : b);
   }
   L.ws_du = o; o += al(L.gen_gcn ? L.BT * L.I : 0);
@@ -209,21 +211,56 @@ Layout make_layout(const wgnn_dims* d, bool state = false) {
   return L;
 }
 
-int bwd2_chunks(const Layout& L);
+// The eight slots of wgnn_params / wgnn_grads in state_dict order: conv1.w, conv1.b, conv2.w, conv2.b, w_ih, w_hh, b_ih, b_hh
+template <class P>
+void slots(const P& s, float* out[8]) {
+  const float* v[8] = {s.conv1_weight, s.conv1_bias, s.conv2_weight, s.conv2_bias, s.w_ih, s.w_hh, s.b_ih, s.b_hh};
+  for (int t = 0; t < 8; ++t) out[t] = const_cast<float*>(v[t]);
+}
+
+// every slot is set; conv = false: the four GRU slots only (wgnn_gru_fwd / wgnn_gru_bwd)
+template <class P>
+bool complete(const P& s, bool conv = true) {
+  float* v[8];
+  slots(s, v);
+  for (int t = conv ? 0 : 4; t < 8; ++t)
+    if (!v[t]) return false;
+  return true;
+}
+
+// two buffers share a byte (a NULL one shares none)
+bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+  return a && b && (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
+}
+
+// torch.optim.Adam's bias corrections and hyper-parameters, into FinishArgs or RowsAdamArgs
+template <class Args>
+void set_adam(Args& a, const wgnn_adam* adam) {
+  const double bc1 = 1.0 - pow((double)adam->beta1, (double)adam->step);
+  const double bc2 = 1.0 - pow((double)adam->beta2, (double)adam->step);
+  a.lr_over_bc1 = (float)(adam->lr / bc1);
+  a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  a.b1 = adam->beta1; a.b2 = adam->beta2; a.eps = adam->eps;
+}
+
+// the caller-kept fp16-plane images of [W_ih | b_ih] and W_ih^T (prep_kind 1), into FinishArgs or RowsAdamArgs
+template <class Args>
+void set_planes(Args& a, const Layout& L, void* prepared) {
+  a.pf_hi = (_Float16*)((float*)prepared + L.prep_f); a.pf_lo = a.pf_hi + (size_t)L.np_g3 * L.Ip;
+  a.pb_hi = (_Float16*)((float*)prepared + L.prep_b); a.pb_lo = a.pb_hi + (size_t)L.np_i * L.Gp;
+  a.np_g3 = L.np_g3; a.np_i = L.np_i;
+}
 
 // The reduction half of a finish launch: which & 4 -> the split-K partials of the two GRU weight-gradient products,
 // which & 2 -> the per-workgroup partial rows of the GCN backward; gradients go to `g`.
 void fill_reduce(const Layout& L, const wgnn_dims* d, const wgnn_grads* g, float* ws, int which, FinishArgs& a) {
   a.scales = ws + L.ws_scales;
   a.status = (unsigned*)ws;
-  float* gs[8] = {g->conv1_weight, g->conv1_bias, g->conv2_weight, g->conv2_bias, g->w_ih, g->w_hh, g->b_ih, g->b_hh};
+  slots(*g, a.g);
   const int F = d->F;
   const int64_t n[8] = {(int64_t)F * F, F, (int64_t)F * F, F, (int64_t)L.G3 * (int64_t)L.I, (int64_t)L.G3 * (int64_t)L.H,
                         (int64_t)L.G3, (int64_t)L.G3};
-  for (int t = 0; t < 8; ++t) {
-    a.g[t] = gs[t];
-    a.n[t] = (int)n[t];
-  }
+  for (int t = 0; t < 8; ++t) a.n[t] = (int)n[t];
   a.I = (int)L.I;
   if (which & 4) {
     FinSeg& ih = a.ih;
@@ -248,14 +285,13 @@ void fill_reduce(const Layout& L, const wgnn_dims* d, const wgnn_grads* g, float
   }
   if (which & 2) {
     a.conv_partial = ws + L.ws_gcnpart;
-    const int ch = bwd2_chunks(L);      // (the option must not change between a deferred part 2 and its wgnn_finish)
     a.conv_rows = L.gen_gcn ? gcn_csr_bwd_rows()
-                            : (L.x3 ? ch * gcnx_bwd_grid((int)(L.BT / ch), d->S, d->math == WGNN_MATH_F16X3 || d->math == WGNN_MATH_F16X3G)
-                                    : gcn32_bwd_grid((int)L.BT, d->S));
+                            : (L.x3 ? gcnx_bwd_grid((int)L.BT, d->S, three_pass(d)) : gcn32_bwd_grid((int)L.BT, d->S));
   }
 }
 
-// Process-wide options (wgnn_set_option / wgnn_get_option).  None of them changes a result bit.
+// Process-wide options (wgnn_set_option / wgnn_get_option).  Keys 0, 1, 2 and 5 choose between schedules with bit-identical
+// results; key 4 (WGNN_OPT_BIG_GEMM) changes the summation order of the large NT plane products.  Key 3 is retired.
 //
 // WGNN_OPT_FUSED_FWD: which forwards run the fused GCN + projection kernel (gcngi.hip).
 //   1 (default)  forwards WITHOUT a stash (inference: wgnn_fwd(stash = NULL), wgnn_fwd_last) -- where it measured faster
@@ -280,7 +316,6 @@ void init_options() {
   std::call_once(g_opt_once, [] {
     for (int k = 0; k < WGNN_OPT_COUNT; ++k) g_opt[k].store(0, std::memory_order_relaxed);
     g_opt[WGNN_OPT_FUSED_FWD].store(env_int("WGNN_FUSED_FWD", 1, 0, 2), std::memory_order_relaxed);
-    g_opt[WGNN_OPT_BWD2_CHUNKS].store(1, std::memory_order_relaxed);
     g_opt[WGNN_OPT_BIG_GEMM].store(1, std::memory_order_relaxed);
   });
 }
@@ -290,20 +325,8 @@ int opt(int key) {
   return g_opt[key].load(std::memory_order_relaxed);
 }
 
-// WGNN_OPT_BWD2_CHUNKS: backward part 2 (dg GEMM -> GCN backward) as C producer -> consumer pairs over C row chunks, so that a
-// chunk of dg is read back while it is still cache-resident.  Only the dense fp16-plane path, only when
-// every chunk still fills the chip: whole 192-row GEMM tiles, >= 12 GCN tiles per workgroup.  Else 1.
-int bwd2_chunks(const Layout& L) {
-  const int c = opt(WGNN_OPT_BWD2_CHUNKS);
-  if (c <= 1 || !L.x3 || L.gen_gcn || L.gen_gru) return 1;
-  if (L.BT % (size_t)c != 0 || (L.BT / c) % 192 != 0 || L.BT / c < 3072) return 1;
-  return c;
-}
-
-int fused_fwd_mode() {
-  init_options();
-  return g_opt[WGNN_OPT_FUSED_FWD].load(std::memory_order_relaxed);
-}
+// option keys wgnn_set_option / wgnn_get_option accept (key 3, the chunked backward part 2, was removed)
+bool known_option(int key) { return key >= 0 && key < WGNN_OPT_COUNT && key != 3; }
 
 int check_dims(const wgnn_dims* d) {
   if (!d) return WGNN_ERR_NULL;
@@ -331,6 +354,514 @@ int check_dims(const wgnn_dims* d) {
   return WGNN_OK;
 }
 
+// ---- the forward ----------------------------------------------------------------------------------------------------------
+// One forward request; every forward entry point fills one and calls fwd().
+//   wgnn_fwd, wgnn_fwd_loss  Y, and with a stash what the backward needs (with labels also the MSE partials of Y - labels)
+//   wgnn_gru_fwd             the same from g_in [B*T][S*F] instead of A and X: the recurrent half alone, conv slots unused
+//   wgnn_fwd_last            last [B][H] = Y[:, T-1, :] * (wind_max - wind_min) + wind_min, no stash; Y is only written where
+//                            the recurrence cannot skip it (into the workspace)
+//   wgnn_fwd_state           state: no stash; the recurrence starts from h0 (NULL = zeros: exactly wgnn_fwd's kernels) and
+//                            leaves the unrounded h_{T-1} in hn (nullable); Y may be NULL (then only hn is written)
+//   wgnn_fwd_state_stash     sst: the training forward from h0 (nullable) into the state stash (make_layout(d, true)), which
+//                            also receives h0 itself and the window-start rows of the dW_hh product's B operand; hn nullable
+struct FwdCall {
+  const float* A = nullptr;
+  const void* X = nullptr;
+  const float* g_in = nullptr;
+  const wgnn_params* p = nullptr;
+  const void* labels = nullptr;
+  const float* h0 = nullptr;
+  void* Y = nullptr;
+  float* hn = nullptr;
+  float* last = nullptr;
+  float wind_min = 0.f, wind_max = 1.f;
+  void* stash = nullptr;
+  bool state = false, sst = false;
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+  FwdCall(void* ws, size_t ws_bytes, void* st) : workspace(ws), workspace_bytes(ws_bytes), stream(st) {}
+};
+
+// A validated forward: its layout and the buffers it resolves to
+struct Fwd {
+  const wgnn_dims* d;
+  const FwdCall& c;
+  const Layout& L;
+  hipStream_t st = (hipStream_t)c.stream;
+  float* ws = (float*)c.workspace;
+  unsigned* status = (unsigned*)c.workspace;       // word 0 of the status block (include/windgnn.h)
+  float* sf = (float*)c.stash;
+  float* GI = (sf && L.gi_stash) ? sf + L.st_GI : ws + L.ws_GI;
+  float* g = sf ? sf + L.st_g : ws + L.ws_g;
+  float* gates = sf ? sf + L.st_gates : nullptr;
+  bool full = three_pass(d);                       // three-pass split products (false: one fp16 pass, or exact fp32)
+  // the staged image of [W_ih | b_ih]: the caller's (wgnn_prepare_weights / wgnn_finish keep it current) or rebuilt here
+  bool kept = c.p->prepared != nullptr && L.prep_kind != 0;
+  float* img_f = kept ? (float*)c.p->prepared + L.prep_f : ws + L.ws_planes_f;
+  // the register-resident recurrences write last / h_n themselves; the others write every row of Y -- into the workspace
+  // when the caller has no Y (wgnn_fwd_last, wgnn_fwd_state without Y) -- and last / h_n are read out of it
+  bool reg = (L.x3 && !L.gen_gru) || L.rec32;
+  void* Y = (!reg && (c.last || (c.state && !c.Y))) ? ws + L.ws_Ylast : c.Y;
+};
+
+// Front end: A and X (or g_in) -> GI = [g | 1] [W_ih | b_ih]^T, with g kept in the stash if there is one
+int fwd_front(const Fwd& f) {
+  const wgnn_dims* d = f.d;
+  const FwdCall& c = f.c;
+  const Layout& L = f.L;
+  const wgnn_params* p = c.p;
+  const int fmode = opt(WGNN_OPT_FUSED_FWD);
+  int rc;
+  if (c.g_in) {   // wgnn_gru_fwd: the caller's g (exact fp32, dense: checked in fwd), given its ones column
+    rc = launch_pack_g(c.g_in, L.BT, (int)L.I, f.g, (int)L.Ip, f.st);
+  } else if (L.x3 && !L.gen_gcn && !L.gen_gru && (fmode == 2 || (fmode == 1 && !f.sf)) && gcngi_supported(d->S, d->H, f.full)) {
+    // Fused (gcngi.hip): GCN layers + input projection in one persistent kernel, g through LDS.  The results are bit-identical
+    // to the separate launches below (same products, same summation order); WGNN_OPT_FUSED_FWD selects (above).
+    const int planes = f.sf ? ((f.full && !L.dgi1) ? 2 : 1) : 0;   // what the backward reads of g: hi (mask, one-pass dW_ih), + lo (strict)
+    return launch_gcngi_fwd((int)L.BT, d->S, c.A, c.X, d->io, p->conv1_weight, p->conv1_bias, p->conv2_weight, p->conv2_bias,
+                            f.sf ? (void*)f.g : nullptr, (int)L.Ip, planes, f.img_f, L.np_g3, f.GI, (int)L.Gp, (int)L.G3, f.full,
+                            f.status, f.ws + L.ws_xtail_f, f.st, opt(WGNN_OPT_GG_ROLE_SPLIT), opt(WGNN_OPT_GG_GEMM_PRIO));
+  } else if (L.gen_gcn) {   // CSR adjacency: exact fp32 SpMM layers; layer 2 writes g as fp32 rows, or as the split modes' planes
+    rc = launch_gcn2_csr_fwd((int)L.BT, d->S, d->nnz, c.A, (const float*)c.X, p->conv1_weight, p->conv1_bias, p->conv2_weight,
+                             p->conv2_bias, f.sf ? f.sf + L.st_h1 : f.ws + L.ws_h1, L.x3 ? nullptr : f.g, L.x3 ? f.g : nullptr,
+                             L.Ip, f.full, L.x3 ? f.status : nullptr, f.st);
+  } else if (L.x3) {
+    rc = launch_gcnx2_fwd((int)L.BT, d->S, c.A, c.X, d->io, p->conv1_weight, p->conv1_bias, p->conv2_weight, p->conv2_bias, f.g,
+                          (int)L.Ip, f.full, f.status, f.ws + L.ws_xtail_f, f.st);
+  } else {
+    rc = launch_gcn32_fwd((int)L.BT, d->S, c.A, (const float*)c.X, p->conv1_weight, p->conv1_bias, p->conv2_weight,
+                          p->conv2_bias, f.g, (int)L.Ip, f.ws + L.ws_xtail_f, f.st);
+  }
+  if (rc != WGNN_OK) return rc;
+  if (L.x3) {      // against the stage-major planes of [W_ih | b_ih]
+    const _Float16* ghi = (const _Float16*)f.g;
+    const size_t aimg_f = pgemm_nt256_aimg_bytes((int)L.BT, (int)L.G3, (int)L.Ip, 2);
+    return launch_pgemm_nt(ghi, ghi + L.BT * L.Ip, (int)L.Ip, (int)L.BT, (int)L.Ip, f.img_f, L.np_g3, f.GI, (int)L.Gp,
+                           (int)L.G3, nullptr, f.full, nullptr, f.st, L.gi16, aimg_f ? f.ws + L.ws_aimg_f : nullptr);
+  }
+  if (L.g32) {     // against a zero-padded copy of [W_ih | b_ih]
+    if (!f.kept) {
+      rc = launch_pad_weight(p->w_ih, (int)L.G3, (int)L.I, 0, p->b_ih, f.img_f, gemm32_nt_rows((int)L.G3), (int)L.Ip, f.st);
+      if (rc != WGNN_OK) return rc;
+    }
+    return launch_gemm32_nt(f.g, (int)L.Ip, (int)L.BT, (int)L.Ip, f.img_f, f.GI, (int)L.Gp, (int)L.G3, f.st);
+  }
+  GemmArgs ga = {};
+  ga.A = f.g; ga.lda = (int)L.Ip; ga.a_kcontig = 1;
+  ga.B = p->w_ih; ga.ldb = (int)L.I; ga.b_kcontig = 1;
+  ga.C = f.GI; ga.ldc = (int)L.Gp; ga.M = (int)L.BT; ga.N = (int)L.G3; ga.K = (int)L.I;
+  ga.bias = p->b_ih; ga.splitk = 1;
+  // few rows (the reference's own call shape: 168): split-K + a fixed-order sum, so that more than 15 workgroups work
+  return launch_gemm_f32_nt(ga, gemm_f32_nt_splitk(ga.M, ga.N, ga.K) > 1 && L.BT < 65536 ? f.ws + L.ws_ntk_f : nullptr, f.st);
+}
+
+// Recurrence: GI -> Y, last or h_n (and, with a stash, the gate records, the Y planes / [Hprev | 1] rows and the loss statistics)
+int fwd_recurrence(const Fwd& f) {
+  const wgnn_dims* d = f.d;
+  const FwdCall& c = f.c;
+  const Layout& L = f.L;
+  const wgnn_params* p = c.p;
+  const float y_mul = c.wind_max - c.wind_min, y_add = c.wind_min;   // every read-out forms its multiplier this way, in fp32
+  const bool hn_only = c.state && !f.Y;   // a register-resident recurrence without Y: last_only into hn (fp32 I/O) / no Y rows
+  float* Y = (float*)f.Y;
+  // labels (wgnn_fwd_loss): the training recurrences also leave the MSE partial sums / maxima of (Y - labels) in the stash
+  // (a stash without labels gets its tag word cleared: bit 8 of a later backward cannot trust stale statistics)
+  const void* labels = f.sf ? c.labels : nullptr;
+  float* stats = f.sf ? f.sf + L.st_stats : nullptr;
+  float* hprev = (f.sf && (L.g32tn || c.sst)) ? f.sf + L.st_hprev : nullptr;   // [Hprev | 1 | 0..] rows for the dW_hh GEMM
+  int rc;
+  if (L.x3 && !L.gen_gru) {   // split fp16, W_hh in registers
+    if (c.last)
+      return launch_grux_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, c.last, nullptr, nullptr, f.full, f.status,
+                             nullptr, nullptr, 0, 1, y_mul, y_add, f.st);
+    if (c.state) {
+      const int lo = hn_only && d->io == WGNN_IO_F32;
+      return launch_grux_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, lo ? (void*)c.hn : f.Y, nullptr, nullptr,
+                             f.full, f.status, nullptr, nullptr, d->io, lo, 1.f, 0.f, f.st, c.h0, lo ? nullptr : c.hn);
+    }
+    rc = launch_grux_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, f.Y, f.gates, f.sf ? f.sf + L.st_yp : nullptr,
+                         f.full, f.status, labels, stats, d->io, 0, 1.f, 0.f, f.st, c.h0, c.hn, c.sst ? L.plane_rows : 0);
+  } else if (L.rec32) {       // exact fp32, W_hh in registers
+    if (c.last)
+      return launch_gru_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, c.last, nullptr, nullptr, nullptr, nullptr, 0,
+                            1, y_mul, y_add, f.st);
+    if (c.state)
+      return launch_gru_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, hn_only ? c.hn : Y, nullptr, nullptr, nullptr,
+                            nullptr, 0, hn_only ? 1 : 0, 1.f, 0.f, f.st, c.h0, hn_only ? nullptr : c.hn);
+    rc = launch_gru_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, Y, f.gates, (const float*)labels, stats, hprev,
+                        L.hq, 0, 1.f, 0.f, f.st, c.h0, c.hn);
+  } else if (L.small) {       // few windows: one per workgroup instead of sixteen
+    rc = launch_gru_small_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, Y, f.gates, hprev, L.hq,
+                              (const float*)labels, stats, f.st, c.h0, c.hn);
+  } else if (L.x3) {          // any hidden width: one plane GEMM per step against split(W_hh | b_hh)
+    rc = launch_split_weight2(p->w_hh, (int)L.G3, (int)L.H, 0, p->b_hh, (int)L.H, f.ws + L.ws_hhp_f, L.np_g3, (int)L.Hp,
+                              f.status, f.st);
+    if (rc == WGNN_OK)
+      rc = launch_gru_gen_fwd_x3(d->B, d->T, d->H, f.GI, (int)L.Gp, f.ws + L.ws_hhp_f, L.np_g3, p->b_hh, Y, f.gates,
+                                 f.sf ? f.sf + L.st_yp : f.ws + L.ws_yp, f.ws + L.ws_gh, f.ws + L.ws_kp_f, f.ws + L.ws_hc,
+                                 f.full, f.st, c.h0, c.sst ? L.plane_rows : 0);
+  } else {
+    rc = launch_gru_gen_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, Y, f.gates, f.ws + L.ws_gh, f.st, c.h0);
+  }
+  if (rc != WGNN_OK) return rc;
+  const size_t h4 = (size_t)d->H * 4;
+  if (L.gen_gru && c.hn &&    // the general recurrences have no h_n output: h_n = Y[:, T-1, :]
+      hipMemcpy2DAsync(c.hn, h4, Y + (size_t)(d->T - 1) * d->H, d->T * h4, h4, d->B, hipMemcpyDeviceToDevice, f.st) != hipSuccess)
+    return WGNN_ERR_HIP;
+  if (c.sst) {   // the dW_hh product's B operand at every window start: h0 (the recurrences wrote zeros / [0 | 1] there)
+    const float* h0c = f.sf + L.st_h0;
+    if (L.x3) {  // B plane rows [h0[b] | 1 | 0..] behind the B*T rows of h_t (pgemm_tn's per-window extra rows)
+      _Float16* yh = (_Float16*)(f.sf + L.st_yp);
+      return launch_h0_planes(d->B, d->H, (int)L.Hp, h0c, yh + L.BT * L.Hp, yh + (L.plane_rows + L.BT) * L.Hp, f.st);
+    }
+    float* hp = f.sf + L.st_hprev;
+    const size_t hq4 = (size_t)L.hq * 4;
+    if (L.gen_gru && L.BT > 1 &&       // the general recurrence writes no [Hprev | 1] rows: row k = Y row k - 1 (the ones
+        hipMemcpy2DAsync(hp + L.hq, hq4, Y, h4, h4, L.BT - 1, hipMemcpyDeviceToDevice, f.st) != hipSuccess)
+      return WGNN_ERR_HIP;             // column is gemm_f32's virtual one)
+    return hipMemcpy2DAsync(hp, (size_t)d->T * hq4, h0c, h4, h4, d->B, hipMemcpyDeviceToDevice, f.st) == hipSuccess ? WGNN_OK
+                                                                                                              : WGNN_ERR_HIP;
+  }
+  if (c.last)    // the recurrences that cannot skip Y: read the last row out of the workspace
+    return wgnn_predict_last(Y, d->B, d->T, d->H, c.wind_min, c.wind_max, c.last, c.stream);
+  return WGNN_OK;
+}
+
+int fwd(const wgnn_dims* d, const FwdCall& c) {
+  int rc = check_dims(d);
+  if (rc != WGNN_OK) return rc;
+  if ((!c.g_in && (!c.A || !c.X)) || !c.p || (!c.Y && !c.last && !(c.state && c.hn)) || (c.sst && !c.stash) || !c.workspace)
+    return WGNN_ERR_NULL;
+  if (!complete(*c.p, !c.g_in)) return WGNN_ERR_NULL;
+  if (c.g_in && (d->math != WGNN_MATH_F32 || d->io != WGNN_IO_F32 || d->adj_format != WGNN_ADJ_DENSE)) return WGNN_ERR_UNSUPPORTED;
+  // h0 is read by every workgroup while others already write h_n / Y: the buffers must not overlap
+  const size_t hb = (size_t)d->B * d->H * sizeof(float), yb = (size_t)d->B * d->T * d->H * (d->io == WGNN_IO_F32 ? 4 : 2);
+  if (overlap(c.h0, hb, c.hn, hb) || overlap(c.h0, hb, c.Y, yb) || overlap(c.Y, yb, c.hn, hb)) return WGNN_ERR_UNSUPPORTED;
+  const Layout L = make_layout(d, c.sst);
+  if (c.workspace_bytes < sizeof(float) * L.fwd_floats) return WGNN_ERR_WORKSPACE;
+  const wgnn_params* p = c.p;
+  hipStream_t st = (hipStream_t)c.stream;
+  // wgnn_fwd_state, one hour, small batch, the reference's dense graph: the whole step as one launch (csrc/gru_step.hip)
+  if (c.state && d->T == 1 && d->adj_format == WGNN_ADJ_DENSE && d->io == WGNN_IO_F32 && gru_step_supported(d->B, d->S, d->H))
+    return launch_gru_step(d->B, d->S, d->H, c.A, (const float*)c.X, p->conv1_weight, p->conv1_bias, p->conv2_weight,
+                           p->conv2_bias, p->w_ih, p->b_ih, p->w_hh, p->b_hh, c.h0, (float*)c.Y, c.hn, st);
+  const Fwd f{d, c, L};
+  if (c.sst &&   // the state stash keeps h0 (or zeros) for the backward
+      (c.h0 ? hipMemcpyAsync(f.sf + L.st_h0, c.h0, hb, hipMemcpyDeviceToDevice, st)
+            : hipMemsetAsync(f.sf + L.st_h0, 0, hb, st)) != hipSuccess)
+    return WGNN_ERR_HIP;
+  if (L.x3 && !f.kept) {   // W_ih as stage-major fp16 planes [np_g3][Ip] with b_ih folded into column I (g's ones column)
+    rc = launch_split_weight2(p->w_ih, (int)L.G3, (int)L.I, 0, p->b_ih, (int)L.I, f.img_f, L.np_g3, (int)L.Ip, f.status, st);
+    if (rc != WGNN_OK) return rc;
+  }
+  rc = fwd_front(f);
+  if (rc != WGNN_OK) return rc;
+  return fwd_recurrence(f);
+}
+
+// ---- the backward ---------------------------------------------------------------------------------------------------------
+// One backward request; every backward entry point fills one and calls bwd().  part: the bit mask of wgnn_bwd_part.
+//   wgnn_bwd_part        dY
+//   wgnn_bwd_mse_part    labels, grad_scale, loss: dY = 2 (Y - labels) grad_scale / n is never written where the recurrence
+//                        kernel forms it itself; loss[0] = mean((Y - labels)^2); part bit 8: the forward was wgnn_fwd_loss
+//   wgnn_bwd_state_part  sst: a state stash; the BPTT kernels start from dh_n (nullable) and h0 (the stash's copy) and leave
+//                        dh_{-1} in dh0 (nullable); the dW_hh products read h0 at every window start
+//   wgnn_gru_bwd         dg_out: the recurrent half alone -- the four GRU gradients and dg [B*T][S*F]; A, X and the conv slots
+//                        of p and of g unused
+//   wgnn_bwd_rows        part 4 alone over a row range (bwd_weights): Y, stash, g only
+struct BwdCall {
+  const float* A = nullptr;
+  const void* X = nullptr;
+  const wgnn_params* p = nullptr;
+  const void* Y = nullptr;
+  const float* dY = nullptr;
+  const void* labels = nullptr;
+  float grad_scale = 1.f;
+  float* loss = nullptr;
+  const void* stash = nullptr;
+  const wgnn_grads* g = nullptr;
+  int part = 0;
+  float* dg_out = nullptr;
+  bool sst = false;
+  const float* dhn = nullptr;
+  float* dh0 = nullptr;
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+  BwdCall(void* ws, size_t ws_bytes, void* st) : workspace(ws), workspace_bytes(ws_bytes), stream(st) {}
+};
+
+// A validated backward: its layout and the buffers it resolves to
+struct Bwd {
+  const wgnn_dims* d;
+  const BwdCall& c;
+  const Layout& L;
+  hipStream_t st = (hipStream_t)c.stream;
+  float* ws = (float*)c.workspace;
+  unsigned* status = (unsigned*)c.workspace;
+  const float* sf = (const float*)c.stash;
+  const float* Y = (const float*)c.Y;          // io-typed (d->io): only the kernels that take `io` see 16-bit data
+  const float* gact = sf + L.st_g;
+  float* dGI = ws + L.ws_dGI;
+  float* dGH = ws + L.ws_dGH;
+  float* dg = ws + L.ws_dg;
+  float* scales = ws + L.ws_scales;   // [0] = 2^k, [1] = 2^-k (split-fp16 range scaling), [2] = dY coefficient; partials from 64
+  bool full = three_pass(d);
+  bool defer = c.part & WGNN_BWD_DEFER;          // partial sums stay in the workspace for wgnn_finish
+  bool stats_ready = (c.part & 8) && c.labels;   // wgnn_fwd_loss left the MSE partials in the stash
+  // the recurrence kernel forms dY from the labels itself: the fast f16x3 recurrence always (its statistics pass is
+  // cheap), the exact-fp32 register-resident one when the forward left the loss statistics in the stash
+  bool fused_loss = c.labels && ((L.x3 && !L.gen_gru) || ((L.rec32 || L.small) && stats_ready));
+};
+
+// Part 1: the BPTT recurrence, dY (or the loss and dY from the labels) -> the dGI / dGH buffers of the workspace
+int bwd_rec(const Bwd& b) {
+  const wgnn_dims* d = b.d;
+  const BwdCall& c = b.c;
+  const Layout& L = b.L;
+  const wgnn_params* p = c.p;
+  const float* labels = (const float*)c.labels;
+  const float* gates = b.sf + L.st_gates;
+  const float* stats = b.fused_loss && b.stats_ready ? b.sf + L.st_stats : nullptr;
+  const BwdState sbs = {c.sst ? b.sf + L.st_h0 : nullptr, c.dhn, c.dh0};
+  const BwdState* sb = c.sst ? &sbs : nullptr;
+  const float* dY = c.dY;
+  int rc;
+  if (labels && !b.fused_loss) {   // other kernels: materialise dY in the workspace
+    rc = launch_mse(b.Y, labels, (int64_t)L.BT * L.H, c.grad_scale, b.ws + L.ws_dY, c.loss, b.scales + 64, b.st);
+    if (rc != WGNN_OK) return rc;
+    dY = b.ws + L.ws_dY;
+  }
+  if (L.x3) {
+    // Everything downstream of dY is linear in it: run it in units scaled by scales[0] = 2^k (so that
+    // fp16 never sees ~1e-9 values) and multiply only the final gradients by scales[1] = 2^-k.
+    if (b.fused_loss && b.stats_ready)   // the forward recurrence already reduced (Y - labels): the BPTT kernel finalises
+      rc = WGNN_OK;
+    else if (b.fused_loss)   // loss, the range scale and the dY coefficient in one pass over Y and the labels
+      rc = launch_mse_stats(b.Y, labels, (int64_t)L.BT * L.H, c.grad_scale, c.loss, b.scales, b.scales + 64, b.st);
+    else
+      rc = launch_amax_scale(dY, (int64_t)L.BT * L.H, b.scales, b.scales + 64, b.st,   // 448 partials after the scales (896
+                             c.dhn, c.dhn ? (int64_t)d->B * d->H : 0);               // with dh_n: the carry is scaled too)
+    if (rc != WGNN_OK) return rc;
+    if (L.gen_gru) {
+      rc = launch_split_weight2(p->w_hh, (int)L.G3, (int)L.H, 1, nullptr, 0, b.ws + L.ws_hhp_b, L.np_h, (int)L.Gp, b.status,
+                                b.st);
+      if (rc != WGNN_OK) return rc;
+      return launch_gru_gen_bwd_x3(d->B, d->T, d->H, b.ws + L.ws_hhp_b, L.np_h, b.Y, dY, gates, b.scales, b.dGI, b.dGH,
+                                   (int)L.Gp, b.ws + L.ws_dhz, b.ws + L.ws_dhw, b.ws + L.ws_kp_b, b.ws + L.ws_dc, b.full, b.st, sb);
+    }
+    return launch_grux_bwd(d->B, d->T, d->H, p->w_hh, c.Y, b.fused_loss ? nullptr : dY, b.fused_loss ? c.labels : nullptr,
+                           d->io, gates, L.gi_stash ? b.sf + L.st_GI : nullptr, (int)L.Gp, b.scales, b.dGI, b.dGH, (int)L.Gp,
+                           b.full, stats, (int64_t)L.BT * L.H, c.grad_scale, c.loss, b.scales, b.status, L.dgi1 ? 0 : 1, b.st,
+                           sb);
+  }
+  if (L.gen_gru)
+    return launch_gru_gen_bwd(d->B, d->T, d->H, p->w_hh, b.Y, dY, gates, b.dGI, b.dGH, (int)L.Gp, b.ws + L.ws_dhz,
+                              b.ws + L.ws_dhw, b.st, sb);
+  if (L.small)
+    return launch_gru_small_bwd(d->B, d->T, d->H, p->w_hh, b.Y, b.fused_loss ? nullptr : dY, b.fused_loss ? labels : nullptr,
+                                gates, b.dGI, b.dGH, (int)L.Gp, stats, (int64_t)L.BT * L.H, c.grad_scale, c.loss, b.status,
+                                b.st, sb);
+  // register-resident recurrence: dGHn alone when the dW_hh GEMM has the two-source A operand; fused loss
+  return launch_gru_bwd(d->B, d->T, d->H, p->w_hh, b.Y, b.fused_loss ? nullptr : dY, b.fused_loss ? labels : nullptr, gates,
+                        b.sf + L.st_GI, (int)L.Gp, b.dGI, (int)L.Gp, L.dghn ? b.dGH : nullptr, L.dghn ? nullptr : b.dGH, stats,
+                        (int64_t)L.BT * L.H, c.grad_scale, c.loss, b.status, b.st, sb);
+}
+
+// Part 4: dW_hh | db_hh = dGH^T [Hprev | 1] and dW_ih | db_ih = dGI^T [g | 1] (prods: WGNN_ROWS_HH | WGNN_ROWS_IH, in that
+// order) over gate rows [r0, r0 + rows): the whole products are [0, 3H).  A range (wgnn_bwd_rows: one product, the wide-GRU
+// path only -- no two-source A operand, no gemm32) is an offset on the A operand and a smaller Mout with the whole product's
+// split-K count; its reduction writes those rows of g alone.  Reads only Y, the stash and the workspace.
+int bwd_weights(const Bwd& b, int prods, int r0, int rows) {
+  const wgnn_dims* d = b.d;
+  const Layout& L = b.L;
+  float* part_ih = b.ws + L.ws_part_ih;
+  float* part_hh = b.ws + L.ws_part_hh;
+  const bool sst = b.c.sst;
+  int rc = WGNN_OK;
+  if (L.x3) {
+    const _Float16* dGIh = (const _Float16*)b.dGI + r0;
+    const _Float16* dGHh = (const _Float16*)b.dGH + r0;
+    const _Float16* gh = (const _Float16*)b.gact;
+    const _Float16* yph = (const _Float16*)(b.sf + L.st_yp);
+    const _Float16* ypl = yph + L.plane_rows * L.Hp;
+    const size_t PG = L.BT * L.Gp;
+    if (prods & WGNN_ROWS_HH) {
+      // Hprev row (b,t) = Y-plane row (b,t-1); row B*T stands in at t = 0, or in the state stash row B*T + b, window b's own
+      // [h0 | 1].  Register-resident recurrence: dGH = [dGI_r | dGI_z | dGHn], the A operand takes GEMM rows < msplit from the
+      // dGI planes and rows >= msplit from the dGHn planes; the reduce kernel maps the GEMM rows back to W_hh's rows.
+      if (L.dghn)
+        rc = launch_pgemm_tn(dGIh, L.dgi1 ? nullptr : dGIh + PG, (int)L.Gp, yph, ypl, (int)L.Hp, d->T, (int)L.BT, L.sk_hh,
+                             part_hh, L.m_hh, (int)L.H + 1, b.full, dGHh, L.dgi1 ? nullptr : dGHh + L.BT * (size_t)L.hn, L.hn,
+                             L.msplit, b.st, /*b_stream=*/true, /*per_window=*/sst);
+      else
+        rc = launch_pgemm_tn(dGHh, L.gen2p ? nullptr : dGHh + PG, (int)L.Gp, yph, ypl, (int)L.Hp, d->T, (int)L.BT, L.sk_hh,
+                             part_hh, rows, (int)L.H + 1, b.full, nullptr, nullptr, 0, 0, b.st, /*b_stream=*/false,
+                             /*per_window=*/sst);
+      if (rc != WGNN_OK) return rc;
+    }
+    if (prods & WGNN_ROWS_IH) {
+      // (single-plane dGI: ONE pass, hi(dGI) x hi(g) -- the rounding of g, too, is independent per element and averages
+      // out over the B*T rows this product sums: measured 8.8e-6 of max at B*T = 6144 against 5.9e-6 with g's lo plane.
+      // The same was measured for dW_hh (7e-5: h rows are correlated) and dg (2.8e-4 on the conv gradients: the rounding
+      // of W_ih is the same for every row and does not average) and NOT adopted: they keep hi x (hi + lo).)
+      const bool one_pass_ih = L.dgi1 || L.gen2p;
+      rc = launch_pgemm_tn(dGIh, one_pass_ih ? dGIh : dGIh + PG, (int)L.Gp, gh, gh + L.BT * L.Ip, (int)L.Ip, 0, (int)L.BT,
+                           L.sk_ih, part_ih, rows, (int)L.I + 1, b.full && !one_pass_ih, nullptr, nullptr, 0, 0, b.st,
+                           /*b_stream=*/true);
+    }
+  } else {
+    const float* hp = b.sf + L.st_hprev;   // [Hprev | 1 | 0..] rows written by the forward recurrence (large B*T, state stash)
+    if (prods & WGNN_ROWS_HH) {            // Hprev row (b,t) = Y row (b,t-1), zero at t = 0
+      if (L.g32tn && L.dghn)   // dGH = [dGI_r | dGI_z | dGHn]: GEMM rows < msplit from dGI, the rest from dGHn
+        rc = launch_gemm32_tn(b.dGI, (int)L.Gp, hp, L.hq, (int)L.BT, L.sk_hh, part_hh, L.m_hh, (int)L.H + 1, b.dGH, L.hn,
+                              L.msplit, b.st);
+      else if (L.g32tn)
+        rc = launch_gemm32_tn(b.dGH, (int)L.Gp, hp, L.hq, (int)L.BT, L.sk_hh, part_hh, rows, (int)L.H + 1, nullptr, 0, 0, b.st);
+      else {
+        GemmArgs a = {};
+        a.A = b.dGH + r0; a.lda = (int)L.Gp; a.a_kcontig = 0;
+        a.B = b.Y; a.ldb = (int)L.H; a.b_kcontig = 0; a.ones_col = 1; a.shift_T = d->T;
+        if (sst) { a.B = hp; a.ldb = L.hq; a.shift_T = 0; }   // the state stash's rows, h0 at window starts
+        a.M = rows; a.N = (int)L.H + 1; a.K = (int)L.BT;
+        a.splitk = L.sk_hh; a.partial = part_hh;
+        rc = launch_gemm_f32(a, b.st);
+      }
+      if (rc != WGNN_OK) return rc;
+    }
+    if (prods & WGNN_ROWS_IH) {
+      if (L.g32tn) {     // g carries its ones column (gcn32_fwd)
+        rc = launch_gemm32_tn(b.dGI, (int)L.Gp, b.gact, (int)L.Ip, (int)L.BT, L.sk_ih, part_ih, rows, (int)L.I + 1, nullptr, 0,
+                              0, b.st);
+      } else {
+        GemmArgs a = {};
+        a.A = b.dGI + r0; a.lda = (int)L.Gp; a.a_kcontig = 0;
+        a.B = b.gact; a.ldb = (int)L.Ip; a.b_kcontig = 0; a.ones_col = 1;
+        a.M = rows; a.N = (int)L.I + 1; a.K = (int)L.BT;
+        a.splitk = L.sk_ih; a.partial = part_ih;
+        rc = launch_gemm_f32(a, b.st);
+      }
+    }
+  }
+  if (rc != WGNN_OK || b.defer) return rc;
+  // the reduce-only form of the finish launch; a range's: its product's segment alone, output pointers at row r0
+  FinishArgs a = {};
+  fill_reduce(L, d, b.c.g, b.ws, 4, a);
+  if (prods != (WGNN_ROWS_IH | WGNN_ROWS_HH)) {
+    const bool ih = prods == WGNN_ROWS_IH;
+    FinSeg& s = ih ? a.ih : a.hh;
+    (ih ? a.hh : a.ih) = FinSeg{};
+    s.Mout = s.Mgemm = rows;
+    if (L.x3) pgemm_tn_geom(rows, s.Nout, &s.T, &s.nNb, &s.ntiles);
+    a.g[ih ? 4 : 5] += (size_t)r0 * s.ncols;                         // w_ih / w_hh
+    a.g[ih ? 6 : 7] += r0;                                           // b_ih / b_hh
+  }
+  return launch_finish(a, b.st);
+}
+
+// Part 2: dg = dGI W_ih (split modes: in scaled units), then the GCN backward -> the four conv gradients; wgnn_gru_bwd hands
+// dg to the caller instead
+int bwd_dg(const Bwd& b) {
+  const wgnn_dims* d = b.d;
+  const BwdCall& c = b.c;
+  const Layout& L = b.L;
+  const wgnn_params* p = c.p;
+  const bool kept = p->prepared != nullptr && L.prep_kind != 0;
+  float* img_b = kept ? (float*)p->prepared + L.prep_b : b.ws + L.ws_planes_b;     // staged image of W_ih^T
+  int rc;
+  if (L.x3) {      // against split(W_ih^T) [np_i][Gp]
+    if (!kept) {
+      rc = launch_split_weight2(p->w_ih, (int)L.G3, (int)L.I, 1, nullptr, 0, img_b, L.np_i, (int)L.Gp, b.status, b.st);
+      if (rc != WGNN_OK) return rc;
+    }
+    const _Float16* dGIh = (const _Float16*)b.dGI;
+    const size_t aimg_b = pgemm_nt256_aimg_bytes((int)L.BT, (int)L.I, (int)L.Gp, 2);
+    rc = launch_pgemm_nt(dGIh, (L.dgi1 || L.gen2p) ? nullptr : dGIh + L.BT * L.Gp, (int)L.Gp, (int)L.BT, (int)L.Gp, img_b,
+                         L.np_i, b.dg, (int)L.Id, (int)L.I, nullptr, b.full, nullptr, b.st, L.dg16,
+                         aimg_b ? b.ws + L.ws_aimg_b : nullptr);
+  } else if (L.g32) {   // against a zero-padded copy of W_ih^T [I -> padded][Gp]
+    if (!kept) {
+      rc = launch_pad_weight(p->w_ih, (int)L.G3, (int)L.I, 1, nullptr, img_b, gemm32_nt_rows((int)L.I), (int)L.Gp, b.st);
+      if (rc != WGNN_OK) return rc;
+    }
+    rc = launch_gemm32_nt(b.dGI, (int)L.Gp, (int)L.BT, (int)L.Gp, img_b, b.dg, (int)L.Id, (int)L.I, b.st);
+  } else {
+    GemmArgs a = {};
+    a.A = b.dGI; a.lda = (int)L.Gp; a.a_kcontig = 1;
+    a.B = p->w_ih; a.ldb = (int)L.I; a.b_kcontig = 0;
+    a.C = b.dg; a.ldc = (int)L.Id; a.M = (int)L.BT; a.N = (int)L.I; a.K = (int)L.G3; a.splitk = 1;
+    rc = launch_gemm_f32_nt(a, gemm_f32_nt_splitk(a.M, a.N, a.K) > 1 && L.BT < 65536 ? b.ws + L.ws_ntk_b : nullptr, b.st);
+  }
+  if (rc != WGNN_OK) return rc;
+  if (c.dg_out) return launch_unpack_dg(b.dg, L.BT, (int)L.I, (int)L.Id, c.dg_out, b.st);
+  if (L.gen_gcn)   // split modes: g as its hi plane, dg in scaled units
+    rc = launch_gcn2_csr_bwd((int)L.BT, d->S, d->nnz, c.A, (const float*)c.X, p->conv2_weight, b.sf + L.st_h1,
+                             L.x3 ? nullptr : b.gact, L.x3 ? b.gact : nullptr, L.Ip, b.dg, L.Id, L.x3 ? b.scales : nullptr,
+                             b.ws + L.ws_du, b.ws + L.ws_gcnpart, nullptr, nullptr, nullptr, nullptr, b.st);
+  else if (L.x3)
+    rc = launch_gcnx2_bwd((int)L.BT, d->S, c.A, c.X, d->io, p->conv1_weight, p->conv1_bias, p->conv2_weight, b.gact, (int)L.Ip,
+                          b.dg, (int)L.Id, L.dg16, b.scales, /*scale_in=*/0, b.ws + L.ws_gcnpart, b.full, b.ws + L.ws_xtail_b,
+                          b.st);
+  else
+    rc = launch_gcn32_bwd((int)L.BT, d->S, c.A, (const float*)c.X, p->conv1_weight, p->conv1_bias, p->conv2_weight, b.gact,
+                          (int)L.Ip, b.dg, (int)L.Id, nullptr, nullptr, nullptr, nullptr, b.ws + L.ws_gcnpart,
+                          b.ws + L.ws_xtail_b, b.st);
+  if (rc != WGNN_OK || b.defer) return rc;
+  FinishArgs a = {};   // the reduce-only form of the finish launch
+  fill_reduce(L, d, c.g, b.ws, 2, a);
+  return launch_finish(a, b.st);
+}
+
+int bwd(const wgnn_dims* d, const BwdCall& c) {
+  const int which = c.part;
+  if (which < 1 || which > 31 || (which & 7) == 0) return WGNN_ERR_SHAPE;
+  int rc = check_dims(d);
+  if (rc != WGNN_OK) return rc;
+  if ((!c.dg_out && (!c.A || !c.X)) || !c.p || !c.Y || (!c.dY && !c.labels) || !c.stash || !c.g || !c.workspace)
+    return WGNN_ERR_NULL;
+  if (c.labels && (which & 1) && !c.loss) return WGNN_ERR_NULL;
+  if (!complete(*c.g, !c.dg_out)) return WGNN_ERR_NULL;
+  if (c.dg_out && (d->math != WGNN_MATH_F32 || d->io != WGNN_IO_F32 || d->adj_format != WGNN_ADJ_DENSE || which != 7))
+    return WGNN_ERR_UNSUPPORTED;
+  const Layout L = make_layout(d, c.sst);
+  if (c.workspace_bytes < sizeof(float) * L.bwd_floats) return WGNN_ERR_WORKSPACE;
+  const Bwd b{d, c, L};
+  // 16-bit labels / Y: the statistics must come from wgnn_fwd_loss (the stand-alone pass reads fp32 only)
+  if (d->io != WGNN_IO_F32 && c.labels && (which & 1) && !(b.fused_loss && b.stats_ready)) return WGNN_ERR_UNSUPPORTED;
+  if (which & 1) {
+    rc = bwd_rec(b);
+    if (rc != WGNN_OK) return rc;
+  }
+  if (which & 4) {   // the four GRU gradients are final after it: a data-parallel caller can start reducing them
+    rc = bwd_weights(b, WGNN_ROWS_IH | WGNN_ROWS_HH, 0, (int)L.G3);
+    if (rc != WGNN_OK) return rc;
+  }
+  return (which & 2) ? bwd_dg(b) : WGNN_OK;
+}
+
+// Row ranges of the weight-gradient products (wgnn_bwd_rows / wgnn_finish_rows): the wide-GRU path only, where each product
+// is ONE TN GEMM with a plain A operand -- the register-resident recurrences remap dW_hh's GEMM rows (msplit), and the one-pass
+// fp16 mode is not offered.  The alignment is the GEMM's M tile: a range is an offset on the A operand plus a smaller Mout,
+// and with whole tiles and the whole product's split-K count every element sums the same terms in the same order.
+int rows_align(const wgnn_dims* d, const Layout& L) {
+  if (!L.gen_gru || d->math == WGNN_MATH_F16) return 0;
+  return L.x3 ? TN_BM : 128;
+}
+
+int check_rows(const wgnn_dims* d, const Layout& L, int which, int row0, int rows) {
+  if ((which & ~(WGNN_ROWS_IH | WGNN_ROWS_HH | WGNN_ROWS_STATE)) != 0 ||
+      ((which & 3) != WGNN_ROWS_IH && (which & 3) != WGNN_ROWS_HH))
+    return WGNN_ERR_SHAPE;
+  if (which & WGNN_ROWS_STATE) return WGNN_ERR_UNSUPPORTED;          // per-window dW_hh rows (the state stash)
+  const int al = rows_align(d, L);
+  if (al == 0) return WGNN_ERR_UNSUPPORTED;
+  const int64_t end = (int64_t)row0 + rows;
+  if (row0 < 0 || rows < 1 || end > (int64_t)L.G3 || row0 % al != 0 || (end % al != 0 && end != (int64_t)L.G3))
+    return WGNN_ERR_SHAPE;
+  return WGNN_OK;
+}
+
 }  // namespace
 
 int opt_big_gemm() { return opt(WGNN_OPT_BIG_GEMM); }
@@ -340,20 +871,15 @@ extern "C" {
 
 int wgnn_version(void) { return WGNN_VERSION; }
 
-int wgnn_get_option(int key) {
-  if (key < 0 || key >= WGNN_OPT_COUNT) return WGNN_ERR_SHAPE;
-  init_options();
-  return g_opt[key].load(std::memory_order_relaxed);
-}
+int wgnn_get_option(int key) { return known_option(key) ? opt(key) : WGNN_ERR_SHAPE; }
 
 int wgnn_set_option(int key, int value) {
-  if (key < 0 || key >= WGNN_OPT_COUNT) return WGNN_ERR_SHAPE;
+  if (!known_option(key)) return WGNN_ERR_SHAPE;
   if (key == WGNN_OPT_FUSED_FWD && (value < 0 || value > 2)) return WGNN_ERR_SHAPE;
   if ((key == WGNN_OPT_GG_ROLE_SPLIT && (value < 0 || value > 1)) || (key == WGNN_OPT_GG_GEMM_PRIO && (value < 0 || value > 3)))
     return WGNN_ERR_SHAPE;
   if (key == WGNN_OPT_BIG_GEMM && (value < 0 || value > 1)) return WGNN_ERR_SHAPE;
   if (key == WGNN_OPT_GEMM32_FORM && (value < 0 || value > 34)) return WGNN_ERR_SHAPE;
-  if (key == WGNN_OPT_BWD2_CHUNKS && value != 1 && value != 2 && value != 4 && value != WGNN_BWD2_MAX_CHUNKS) return WGNN_ERR_SHAPE;
   init_options();
   return g_opt[key].exchange(value, std::memory_order_relaxed);
 }
@@ -387,269 +913,60 @@ size_t wgnn_stash_bytes(const wgnn_dims* d) {
   return sizeof(float) * make_layout(d).stash_floats;
 }
 
-// last != nullptr (wgnn_fwd_last): no stash; last[B][H] = Y[:, T-1, :] * y_mul + y_add and Y itself is only written
-// where the kernels cannot skip it (into the workspace, for the exact-fp32 and general-shape recurrences).
-// g_in != nullptr (wgnn_gru_fwd): the recurrent half alone on a caller-supplied g [B*T][S*F]; A, X and the conv slots of p unused.
-// state (wgnn_fwd_state): no stash; the recurrence starts from h0 (nullable = zeros: then exactly wgnn_fwd's kernels) and
-// leaves the unrounded h_{T-1} in hn (nullable); Y may be NULL (then only hn is written).
-// sst (wgnn_fwd_state_stash): the training forward from h0 (nullable) into the state stash (make_layout(d, true)), which also
-// receives h0 itself and the window-start rows of the dW_hh product's B operand; hn nullable.
-static int fwd_impl(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* labels,
-                    void* Y, void* stash, void* workspace, size_t workspace_bytes, void* stream, float* last = nullptr,
-                    float wind_min = 0.f, float wind_max = 1.f, const float* g_in = nullptr, bool state = false,
-                    const float* h0 = nullptr, float* hn = nullptr, bool sst = false) {
-  // every read-out path forms its multiplier the same way, (wind_max - wind_min) in fp32, from the caller's two values
-  const float y_mul = wind_max - wind_min, y_add = wind_min;
-  int rc = check_dims(d);
-  if (rc != WGNN_OK) return rc;
-  if ((!g_in && (!A || !X)) || !p || (!Y && !last && !(state && hn)) || !workspace) return WGNN_ERR_NULL;
-  if ((!g_in && (!p->conv1_weight || !p->conv1_bias || !p->conv2_weight || !p->conv2_bias)) || !p->w_ih || !p->w_hh ||
-      !p->b_ih || !p->b_hh)
-    return WGNN_ERR_NULL;
-  if (g_in && (d->math != WGNN_MATH_F32 || d->io != WGNN_IO_F32 || d->adj_format != WGNN_ADJ_DENSE)) return WGNN_ERR_UNSUPPORTED;
-  const Layout L = make_layout(d, sst);
-  if (workspace_bytes < sizeof(float) * L.fwd_floats) return WGNN_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  float* ws = (float*)workspace;
-  if (last && !(L.x3 && !L.gen_gru) && !L.rec32) Y = ws + L.ws_Ylast;   // these recurrences write every row: then read the last one out
-  // wgnn_fwd_state without Y: the register-resident recurrences write h_n alone (last_only into hn, or no Y rows with 16-bit
-  // I/O); the others write Y into the workspace, like wgnn_fwd_last, and h_n is a copy of its last row
-  const bool y_ws = state && !Y && !(L.x3 && !L.gen_gru) && !L.rec32;
-  if (y_ws) Y = ws + L.ws_Ylast;
-  const bool hn_only = state && !Y;                  // ... the last_only form (fp32 I/O) or the no-Y form (16-bit I/O)
-  auto copy_hn = [&](const float* Yf) -> int {       // h_n = Y[:, T-1, :] (fp32 Y), for the recurrences without an hn output
-    if (!hn) return WGNN_OK;
-    return hipMemcpy2DAsync(hn, (size_t)d->H * 4, Yf + (size_t)(d->T - 1) * d->H, (size_t)d->T * d->H * 4, (size_t)d->H * 4,
-                            d->B, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess ? WGNN_OK : WGNN_ERR_HIP;
-  };
-  unsigned* status = (unsigned*)workspace;           // word 0 of the status block (include/windgnn.h)
-  float* sf = (float*)stash;
-  float* GI = (sf && L.gi_stash) ? sf + L.st_GI : ws + L.ws_GI;
-  float* g = sf ? sf + L.st_g : ws + L.ws_g;
-  float* gates = sf ? sf + L.st_gates : nullptr;
-  const bool x3 = L.x3;                              // fp16-plane kernels
-  const bool full = d->math == WGNN_MATH_F16X3 || d->math == WGNN_MATH_F16X3G;   // three-pass split products (false: one fp16 pass)
-  // the staged image of [W_ih | b_ih]: the caller's (wgnn_prepare_weights / wgnn_finish keep it current) or rebuilt here
-  const bool kept = p->prepared != nullptr && L.prep_kind != 0;
-  float* img_f = kept ? (float*)p->prepared + L.prep_f : ws + L.ws_planes_f;
-  // the state stash: h0 (or zeros) is kept for the backward, and once the recurrence has run, the window-start rows of the
-  // dW_hh product's B operand are set to it (they are written as zeros / [0 | 1] by the recurrence kernels)
-  float* h0c = sst ? sf + L.st_h0 : nullptr;
-  if (sst) {
-    const size_t hb = (size_t)d->B * d->H * sizeof(float);
-    if ((h0 ? hipMemcpyAsync(h0c, h0, hb, hipMemcpyDeviceToDevice, (hipStream_t)stream)
-            : hipMemsetAsync(h0c, 0, hb, (hipStream_t)stream)) != hipSuccess)
-      return WGNN_ERR_HIP;
-  }
-  auto state_rows = [&]() -> int {
-    if (L.x3) {     // B planes rows [h0[b] | 1 | 0..] behind the B*T rows of h_t (pgemm_tn's per-window extra rows)
-      _Float16* yh = (_Float16*)(sf + L.st_yp);
-      return launch_h0_planes(d->B, d->H, (int)L.Hp, h0c, yh + L.BT * L.Hp, yh + (L.plane_rows + L.BT) * L.Hp,
-                              (hipStream_t)stream);
-    }
-    float* hp = sf + L.st_hprev;
-    const size_t hq4 = (size_t)L.hq * 4, h4 = (size_t)d->H * 4;
-    if (L.gen_gru && L.BT > 1 &&       // the general recurrence writes no [Hprev | 1] rows: row k = Y row k - 1 (the ones
-        hipMemcpy2DAsync(hp + L.hq, hq4, Y, h4, h4, L.BT - 1, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
-      return WGNN_ERR_HIP;             // column is gemm_f32's virtual one)
-    return hipMemcpy2DAsync(hp, (size_t)d->T * hq4, h0c, h4, h4, d->B, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess
-               ? WGNN_OK : WGNN_ERR_HIP;
-  };
-  // the register-resident split-fp16 recurrence of a training forward (with labels: wgnn_fwd_loss)
-  auto grux_train = [&]() -> int {
-    const int r = launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, Y, gates, sf ? sf + L.st_yp : nullptr,
-                                  full, status, sf ? labels : nullptr, sf ? sf + L.st_stats : nullptr, d->io, 0, 1.f, 0.f, st,
-                                  h0, hn, sst ? L.plane_rows : 0);
-    return (r != WGNN_OK || !sst) ? r : state_rows();
-  };
+size_t wgnn_state_stash_bytes(const wgnn_dims* d) {
+  if (check_dims(d) != WGNN_OK) return 0;
+  return sizeof(float) * make_layout(d, true).stash_floats;
+}
 
-  if (x3) {
-    // W_ih as stage-major fp16 planes [np_g3][Ip] with b_ih folded into column I (g's ones column)
-    if (!kept) {
-      rc = launch_split_weight2(p->w_ih, (int)L.G3, (int)L.I, 0, p->b_ih, (int)L.I, img_f, L.np_g3, (int)L.Ip, status, st);
-      if (rc != WGNN_OK) return rc;
-    }
-    // Fused front end (gcngi.hip): GCN layers + input projection in one persistent kernel, g through LDS.  The results are
-    // bit-identical to the two launches below (same products, same summation order); WGNN_FUSED_FWD selects (above).
-    const int fmode = fused_fwd_mode();
-    if (!L.gen_gcn && !L.gen_gru && (fmode == 2 || (fmode == 1 && !sf)) && gcngi_supported(d->S, d->H, full)) {
-      const int planes = sf ? ((full && !L.dgi1) ? 2 : 1) : 0;     // what the backward reads of g: hi (mask, one-pass dW_ih), + lo (strict)
-      rc = launch_gcngi_fwd((int)L.BT, d->S, A, X, d->io, p->conv1_weight, p->conv1_bias, p->conv2_weight, p->conv2_bias,
-                            sf ? (void*)g : nullptr, (int)L.Ip, planes, img_f, L.np_g3, GI, (int)L.Gp, (int)L.G3, full, status,
-                            ws + L.ws_xtail_f, st, opt(WGNN_OPT_GG_ROLE_SPLIT), opt(WGNN_OPT_GG_GEMM_PRIO));
-      if (rc != WGNN_OK) return rc;
-      if (last)
-        return launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, last, nullptr, nullptr, full, status,
-                               nullptr, nullptr, 0, 1, y_mul, y_add, st);
-      if (state) {
-        const int lo = hn_only && d->io == WGNN_IO_F32;
-        return launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, lo ? (void*)hn : Y, nullptr, nullptr, full,
-                               status, nullptr, nullptr, d->io, lo, 1.f, 0.f, st, h0, lo ? nullptr : hn);
-      }
-      return grux_train();
-    }
-    if (L.gen_gcn)    // CSR adjacency: fp32 SpMM layers, layer 2 writes the g planes
-      rc = launch_gcn2_csr_fwd((int)L.BT, d->S, d->nnz, A, (const float*)X, p->conv1_weight, p->conv1_bias,
-                               p->conv2_weight, p->conv2_bias, sf ? sf + L.st_h1 : ws + L.ws_h1, nullptr, g, L.Ip, full,
-                               status, st);
-    else
-      rc = launch_gcnx2_fwd((int)L.BT, d->S, A, X, d->io, p->conv1_weight, p->conv1_bias, p->conv2_weight,
-                            p->conv2_bias, g, (int)L.Ip, full, status, ws + L.ws_xtail_f, st);
-    if (rc != WGNN_OK) return rc;
-    const _Float16* ghi = (const _Float16*)g;
-    const size_t aimg_f = pgemm_nt256_aimg_bytes((int)L.BT, (int)L.G3, (int)L.Ip, 2);
-    rc = launch_pgemm_nt(ghi, ghi + L.BT * L.Ip, (int)L.Ip, (int)L.BT, (int)L.Ip, img_f, L.np_g3, GI,
-                         (int)L.Gp, (int)L.G3, nullptr, full, nullptr, st, L.gi16, aimg_f ? ws + L.ws_aimg_f : nullptr);
-    if (rc != WGNN_OK) return rc;
-    if (L.gen_gru) {  // any hidden width: one plane GEMM per step against split(W_hh | b_hh)
-      rc = launch_split_weight2(p->w_hh, (int)L.G3, (int)L.H, 0, p->b_hh, (int)L.H, ws + L.ws_hhp_f, L.np_g3, (int)L.Hp,
-                                status, st);
-      if (rc != WGNN_OK) return rc;
-      rc = launch_gru_gen_fwd_x3(d->B, d->T, d->H, GI, (int)L.Gp, ws + L.ws_hhp_f, L.np_g3, p->b_hh, (float*)Y, gates,
-                                 sf ? sf + L.st_yp : ws + L.ws_yp, ws + L.ws_gh, ws + L.ws_kp_f, ws + L.ws_hc, full,
-                                 st, h0, sst ? L.plane_rows : 0);
-      if (rc == WGNN_OK && state) return copy_hn((const float*)Y);
-      if (rc == WGNN_OK && sst) rc = copy_hn((const float*)Y);
-      if (rc == WGNN_OK && sst) return state_rows();
-      if (rc != WGNN_OK || !last) return rc;
-      return wgnn_predict_last((const float*)Y, d->B, d->T, d->H, wind_min, wind_max, last, stream);
-    }
-    if (last)   // the register-resident recurrence writes the read-out itself
-      return launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, last, nullptr, nullptr, full, status,
-                             nullptr, nullptr, 0, 1, y_mul, y_add, st);
-    if (state) {
-      const int lo = hn_only && d->io == WGNN_IO_F32;
-      return launch_grux_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, lo ? (void*)hn : Y, nullptr, nullptr, full,
-                             status, nullptr, nullptr, d->io, lo, 1.f, 0.f, st, h0, lo ? nullptr : hn);
-    }
-    // labels (wgnn_fwd_loss): the recurrence also leaves the MSE partial sums / maxima of (Y - labels) in the stash
-    // (a stash without labels gets its tag word cleared: bit 8 of a later backward cannot trust stale statistics)
-    return grux_train();
-  }
-  if (L.gen_gcn) {
-    float* h1 = sf ? sf + L.st_h1 : ws + L.ws_h1;    // layer-1 activations: kept for the backward if there is a stash
-    rc = launch_gcn2_csr_fwd((int)L.BT, d->S, d->nnz, A, (const float*)X, p->conv1_weight, p->conv1_bias,
-                             p->conv2_weight, p->conv2_bias, h1, g, nullptr, L.Ip, false, nullptr, st);
-  } else if (g_in) {
-    rc = launch_pack_g(g_in, L.BT, (int)L.I, g, (int)L.Ip, st);
-  } else {
-    rc = launch_gcn32_fwd((int)L.BT, d->S, A, (const float*)X, p->conv1_weight, p->conv1_bias, p->conv2_weight, p->conv2_bias, g,
-                         (int)L.Ip, ws + L.ws_xtail_f, st);
-  }
-  if (rc != WGNN_OK) return rc;
-  if (L.g32) {       // GI = [g|1] [W_ih|b_ih]^T
-    float* wp = img_f;
-    if (!kept) {
-      rc = launch_pad_weight(p->w_ih, (int)L.G3, (int)L.I, 0, p->b_ih, wp, gemm32_nt_rows((int)L.G3), (int)L.Ip, st);
-      if (rc != WGNN_OK) return rc;
-    }
-    rc = launch_gemm32_nt(g, (int)L.Ip, (int)L.BT, (int)L.Ip, wp, GI, (int)L.Gp, (int)L.G3, st);
-  } else {
-    GemmArgs ga = {};
-    ga.A = g; ga.lda = (int)L.Ip; ga.a_kcontig = 1;
-    ga.B = p->w_ih; ga.ldb = (int)L.I; ga.b_kcontig = 1;
-    ga.C = GI; ga.ldc = (int)L.Gp; ga.M = (int)L.BT; ga.N = (int)L.G3; ga.K = (int)L.I;
-    ga.bias = p->b_ih; ga.splitk = 1;
-    // few rows (the reference's own call shape: 168): split-K + a fixed-order sum, so that more than 15 workgroups work
-    rc = launch_gemm_f32_nt(ga, gemm_f32_nt_splitk(ga.M, ga.N, ga.K) > 1 && L.BT < 65536 ? ws + L.ws_ntk_f : nullptr, st);
-  }
-  if (rc != WGNN_OK) return rc;
-  float* hprev = (sf && (L.g32tn || sst)) ? sf + L.st_hprev : nullptr;      // [Hprev | 1 | 0..] rows for the backward's dW_hh GEMM
-  if (L.gen_gru) {
-    rc = launch_gru_gen_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, (float*)Y, gates, ws + L.ws_gh, st, h0);
-    if (rc == WGNN_OK && state) return copy_hn((const float*)Y);
-    if (rc == WGNN_OK && sst) rc = copy_hn((const float*)Y);
-    if (rc == WGNN_OK && sst) return state_rows();
-  } else if (L.small) {   // few windows: one per workgroup instead of sixteen
-    rc = launch_gru_small_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, (float*)Y, gates, hprev, L.hq,
-                              sf ? (const float*)labels : nullptr, sf ? sf + L.st_stats : nullptr, st, h0, hn);
-    if (rc == WGNN_OK && sst) return state_rows();
-  } else if (state)   // the register-resident recurrence: h_n from its registers (and with Y = NULL the last_only form alone)
-    return launch_gru_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, hn_only ? hn : (float*)Y, nullptr, nullptr, nullptr,
-                          nullptr, 0, hn_only ? 1 : 0, 1.f, 0.f, st, h0, hn_only ? nullptr : hn);
-  else if (last)      // the register-resident recurrence writes the read-out itself
-    return launch_gru_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, last, nullptr, nullptr, nullptr, nullptr, 0, 1,
-                          y_mul, y_add, st);
-  else {              // labels (wgnn_fwd_loss): the recurrence also leaves the MSE partial sums of (Y - labels) in the stash
-    rc = launch_gru_fwd(d->B, d->T, d->H, GI, (int)L.Gp, p->w_hh, p->b_hh, (float*)Y, gates,
-                        sf ? (const float*)labels : nullptr, sf ? sf + L.st_stats : nullptr, hprev, L.hq, 0, 1.f, 0.f, st, h0, hn);
-    return (rc != WGNN_OK || !sst) ? rc : state_rows();
-  }
-  if (rc != WGNN_OK || !last) return rc;
-  return wgnn_predict_last((const float*)Y, d->B, d->T, d->H, wind_min, wind_max, last, stream);
+size_t wgnn_prepared_bytes(const wgnn_dims* d) {
+  if (check_dims(d) != WGNN_OK) return 0;
+  return sizeof(float) * make_layout(d).prep_floats;
 }
 
 int wgnn_fwd(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, void* Y, void* stash,
              void* workspace, size_t workspace_bytes, void* stream) {
-  return fwd_impl(d, A, X, p, nullptr, Y, stash, workspace, workspace_bytes, stream);
+  FwdCall c(workspace, workspace_bytes, stream);
+  c.A = A; c.X = X; c.p = p; c.Y = Y; c.stash = stash;
+  return fwd(d, c);
 }
 
 int wgnn_fwd_loss(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* labels,
                   void* Y, void* stash, void* workspace, size_t workspace_bytes, void* stream) {
   if (!labels || !stash) return WGNN_ERR_NULL;
-  return fwd_impl(d, A, X, p, labels, Y, stash, workspace, workspace_bytes, stream);
+  FwdCall c(workspace, workspace_bytes, stream);
+  c.A = A; c.X = X; c.p = p; c.labels = labels; c.Y = Y; c.stash = stash;
+  return fwd(d, c);
 }
 
 int wgnn_fwd_last(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, float wind_min,
                   float wind_max, float* out, void* workspace, size_t workspace_bytes, void* stream) {
   if (!out) return WGNN_ERR_NULL;
   if (d && d->io != WGNN_IO_F32) return WGNN_ERR_UNSUPPORTED;
-  return fwd_impl(d, A, X, p, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream, out, wind_min, wind_max);
+  FwdCall c(workspace, workspace_bytes, stream);
+  c.A = A; c.X = X; c.p = p; c.last = out; c.wind_min = wind_min; c.wind_max = wind_max;
+  return fwd(d, c);
 }
 
 int wgnn_fwd_state(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const float* h0, void* Y,
                    float* h_n, void* workspace, size_t workspace_bytes, void* stream) {
-  int rc = check_dims(d);
-  if (rc != WGNN_OK) return rc;
-  if (!Y && !h_n) return WGNN_ERR_NULL;
-  if (!A || !X || !p || !workspace) return WGNN_ERR_NULL;
-  if (!p->conv1_weight || !p->conv1_bias || !p->conv2_weight || !p->conv2_bias || !p->w_ih || !p->w_hh || !p->b_ih ||
-      !p->b_hh)
-    return WGNN_ERR_NULL;
-  // h0 is read by every workgroup while others already write h_n / Y: the buffers must not overlap
-  const size_t hb = (size_t)d->B * d->H * sizeof(float);
-  const size_t yb = (size_t)d->B * d->T * d->H * (d->io == WGNN_IO_F32 ? 4 : 2);
-  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
-    return a && b && (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
-  };
-  if (overlap(h0, hb, h_n, hb) || overlap(h0, hb, Y, yb) || overlap(Y, yb, h_n, hb)) return WGNN_ERR_UNSUPPORTED;
-  if (workspace_bytes < sizeof(float) * make_layout(d).fwd_floats) return WGNN_ERR_WORKSPACE;
-  // one hour, small batch, the reference's dense graph: the whole step as one launch (csrc/gru_step.hip)
-  if (d->T == 1 && d->adj_format == WGNN_ADJ_DENSE && d->io == WGNN_IO_F32 && gru_step_supported(d->B, d->S, d->H))
-    return launch_gru_step(d->B, d->S, d->H, A, (const float*)X, p->conv1_weight, p->conv1_bias, p->conv2_weight,
-                           p->conv2_bias, p->w_ih, p->b_ih, p->w_hh, p->b_hh, h0, (float*)Y, h_n, (hipStream_t)stream);
-  return fwd_impl(d, A, X, p, nullptr, Y, nullptr, workspace, workspace_bytes, stream, nullptr, 0.f, 1.f, nullptr, true, h0,
-                  h_n);
-}
-
-size_t wgnn_state_stash_bytes(const wgnn_dims* d) {
-  if (check_dims(d) != WGNN_OK) return 0;
-  return sizeof(float) * make_layout(d, true).stash_floats;
+  FwdCall c(workspace, workspace_bytes, stream);
+  c.A = A; c.X = X; c.p = p; c.h0 = h0; c.Y = Y; c.hn = h_n; c.state = true;
+  return fwd(d, c);
 }
 
 int wgnn_fwd_state_stash(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const float* h0, void* Y,
                          float* h_n, void* stash, void* workspace, size_t workspace_bytes, void* stream) {
-  int rc = check_dims(d);
-  if (rc != WGNN_OK) return rc;
-  if (!A || !X || !p || !Y || !stash || !workspace) return WGNN_ERR_NULL;
-  if (!p->conv1_weight || !p->conv1_bias || !p->conv2_weight || !p->conv2_bias || !p->w_ih || !p->w_hh || !p->b_ih ||
-      !p->b_hh)
-    return WGNN_ERR_NULL;
-  // as wgnn_fwd_state: h0 is read while h_n / Y are written
-  const size_t hb = (size_t)d->B * d->H * sizeof(float);
-  const size_t yb = (size_t)d->B * d->T * d->H * (d->io == WGNN_IO_F32 ? 4 : 2);
-  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
-    return a && b && (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
-  };
-  if (overlap(h0, hb, h_n, hb) || overlap(h0, hb, Y, yb) || overlap(Y, yb, h_n, hb)) return WGNN_ERR_UNSUPPORTED;
-  if (workspace_bytes < sizeof(float) * make_layout(d, true).fwd_floats) return WGNN_ERR_WORKSPACE;
-  return fwd_impl(d, A, X, p, nullptr, Y, stash, workspace, workspace_bytes, stream, nullptr, 0.f, 1.f, nullptr, false, h0,
-                  h_n, /*sst=*/true);
+  FwdCall c(workspace, workspace_bytes, stream);
+  c.A = A; c.X = X; c.p = p; c.h0 = h0; c.Y = Y; c.hn = h_n; c.stash = stash; c.sst = true;
+  return fwd(d, c);
 }
 
-size_t wgnn_prepared_bytes(const wgnn_dims* d) {
-  if (check_dims(d) != WGNN_OK) return 0;
-  return sizeof(float) * make_layout(d).prep_floats;
+int wgnn_gru_fwd(const wgnn_dims* d, const float* g, const wgnn_params* p, void* Y, void* stash, void* workspace,
+                 size_t workspace_bytes, void* stream) {
+  if (!g) return WGNN_ERR_NULL;
+  FwdCall c(workspace, workspace_bytes, stream);
+  c.g_in = g; c.p = p; c.Y = Y; c.stash = stash;
+  return fwd(d, c);
 }
 
 int wgnn_prepare_weights(const wgnn_dims* d, const wgnn_params* p, void* workspace, size_t workspace_bytes,
@@ -674,91 +991,54 @@ int wgnn_prepare_weights(const wgnn_dims* d, const wgnn_params* p, void* workspa
   return launch_pad_weight(p->w_ih, (int)L.G3, (int)L.I, 1, nullptr, img_b, gemm32_nt_rows((int)L.I), (int)L.Gp, st);
 }
 
-int wgnn_finish(const wgnn_dims* d, const wgnn_params* p, const wgnn_grads* g, int which, const wgnn_adam* adam,
-                void* workspace, size_t workspace_bytes, void* stream) {
+int wgnn_bwd(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* Y,
+             const float* dY, const void* stash, const wgnn_grads* g, void* workspace, size_t workspace_bytes,
+             void* stream) {
+  return wgnn_bwd_part(d, A, X, p, Y, dY, stash, g, workspace, workspace_bytes, stream, 7);
+}
+
+int wgnn_bwd_part(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* Y,
+                  const float* dY, const void* stash, const wgnn_grads* g, void* workspace, size_t workspace_bytes,
+                  void* stream, int which) {
+  if (!dY) return WGNN_ERR_NULL;
+  BwdCall c(workspace, workspace_bytes, stream);
+  c.A = A; c.X = X; c.p = p; c.Y = Y; c.dY = dY; c.stash = stash; c.g = g; c.part = which;
+  return bwd(d, c);
+}
+
+int wgnn_bwd_mse_part(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* Y,
+                      const void* labels, float grad_scale, float* loss, const void* stash, const wgnn_grads* g,
+                      void* workspace, size_t workspace_bytes, void* stream, int which) {
+  if (!labels) return WGNN_ERR_NULL;
+  BwdCall c(workspace, workspace_bytes, stream);
+  c.A = A; c.X = X; c.p = p; c.Y = Y; c.labels = labels; c.grad_scale = grad_scale; c.loss = loss; c.stash = stash; c.g = g;
+  c.part = which;
+  return bwd(d, c);
+}
+
+int wgnn_bwd_state_part(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* Y,
+                        const float* dY, const float* dh_n, const void* stash, const wgnn_grads* g, float* dh0,
+                        void* workspace, size_t workspace_bytes, void* stream, int part) {
   int rc = check_dims(d);
   if (rc != WGNN_OK) return rc;
-  const int only = which & (WGNN_FINISH_ADAM_GRU | WGNN_FINISH_ADAM_CONV);   // optimiser step of one tensor family
-  if ((which & ~(6 | WGNN_FINISH_ADAM_GRU | WGNN_FINISH_ADAM_CONV)) != 0 || (which == 0 && !adam)) return WGNN_ERR_SHAPE;
-  if (only && (!adam || (which & 6) != 0 || only == (WGNN_FINISH_ADAM_GRU | WGNN_FINISH_ADAM_CONV))) return WGNN_ERR_SHAPE;
-  if (!g || !workspace || (adam && !p)) return WGNN_ERR_NULL;
-  if (!g->conv1_weight || !g->conv1_bias || !g->conv2_weight || !g->conv2_bias || !g->w_ih || !g->w_hh || !g->b_ih ||
-      !g->b_hh)
-    return WGNN_ERR_NULL;
-  const Layout L = make_layout(d);
-  if (workspace_bytes < sizeof(float) * L.bwd_floats) return WGNN_ERR_WORKSPACE;
-  float* ws = (float*)workspace;
-  FinishArgs a = {};
-  fill_reduce(L, d, g, ws, which, a);
-  if (adam) {
-    if (!p->conv1_weight || !p->conv1_bias || !p->conv2_weight || !p->conv2_bias || !p->w_ih || !p->w_hh || !p->b_ih ||
-        !p->b_hh)
-      return WGNN_ERR_NULL;
-    if (adam->step < 1) return WGNN_ERR_SHAPE;
-    const float* ps[8] = {p->conv1_weight, p->conv1_bias, p->conv2_weight, p->conv2_bias, p->w_ih, p->w_hh, p->b_ih, p->b_hh};
-    const wgnn_grads& m = adam->exp_avg;
-    const wgnn_grads& v = adam->exp_avg_sq;
-    float* ms[8] = {m.conv1_weight, m.conv1_bias, m.conv2_weight, m.conv2_bias, m.w_ih, m.w_hh, m.b_ih, m.b_hh};
-    float* vs[8] = {v.conv1_weight, v.conv1_bias, v.conv2_weight, v.conv2_bias, v.w_ih, v.w_hh, v.b_ih, v.b_hh};
-    for (int t = 0; t < 8; ++t) {
-      if (!ms[t] || !vs[t]) return WGNN_ERR_NULL;
-      a.p[t] = const_cast<float*>(ps[t]);          // the optimiser updates the parameters in place
-      a.m[t] = ms[t];
-      a.v[t] = vs[t];
-    }
-    a.adam = 1;
-    const double bc1 = 1.0 - pow((double)adam->beta1, (double)adam->step);
-    const double bc2 = 1.0 - pow((double)adam->beta2, (double)adam->step);
-    a.lr_over_bc1 = (float)(adam->lr / bc1);
-    a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-    a.b1 = adam->beta1; a.b2 = adam->beta2; a.eps = adam->eps;
-    a.elem_mask = ((which & 4) ? 0u : 0xF0u) | ((which & 2) ? 0u : 0x0Fu);   // tensors whose gradient is final in g
-    if (only == WGNN_FINISH_ADAM_GRU) a.elem_mask = 0xF0u;
-    if (only == WGNN_FINISH_ADAM_CONV) a.elem_mask = 0x0Fu;
-    if (p->prepared && L.prep_kind) {
-      a.prep_kind = L.prep_kind;
-      float* img_f = (float*)p->prepared + L.prep_f;
-      float* img_b = (float*)p->prepared + L.prep_b;
-      if (L.prep_kind == 1) {
-        a.pf_hi = (_Float16*)img_f; a.pf_lo = a.pf_hi + (size_t)L.np_g3 * L.Ip;
-        a.pb_hi = (_Float16*)img_b; a.pb_lo = a.pb_hi + (size_t)L.np_i * L.Gp;
-        a.np_g3 = L.np_g3; a.np_i = L.np_i;
-      } else {
-        a.wp = img_f; a.wt = img_b;
-      }
-      a.Ip = (int)L.Ip; a.Gp = (int)L.Gp;
-    }
-  }
-  return launch_finish(a, (hipStream_t)stream);
+  if (!dY) return WGNN_ERR_NULL;
+  // dh0 is written while dY, dh_n and the stash are read
+  const size_t hb = (size_t)d->B * d->H * sizeof(float), yb = (size_t)d->B * d->T * d->H * sizeof(float);
+  if (overlap(dh0, hb, dh_n, hb) || overlap(dh0, hb, dY, yb) || overlap(dh0, hb, stash, wgnn_state_stash_bytes(d)))
+    return WGNN_ERR_UNSUPPORTED;
+  BwdCall c(workspace, workspace_bytes, stream);
+  c.A = A; c.X = X; c.p = p; c.Y = Y; c.dY = dY; c.stash = stash; c.g = g; c.part = part;
+  c.sst = true; c.dhn = dh_n; c.dh0 = dh0;
+  return bwd(d, c);
 }
 
-}  // extern "C"
-
-namespace {
-// Row ranges of the weight-gradient products (wgnn_bwd_rows / wgnn_finish_rows): the wide-GRU path only, where each product
-// is ONE TN GEMM with a plain A operand -- the register-resident recurrences remap dW_hh's GEMM rows (msplit), and the one-pass
-// fp16 mode is not offered.  The alignment is the GEMM's M tile: a range is an offset on the A operand plus a smaller Mout,
-// and with whole tiles and the whole product's split-K count every element sums the same terms in the same order.
-int rows_align(const wgnn_dims* d, const Layout& L) {
-  if (!L.gen_gru || d->math == WGNN_MATH_F16) return 0;
-  return L.x3 ? TN_BM : 128;
+int wgnn_gru_bwd(const wgnn_dims* d, const float* g, const wgnn_params* p, const void* Y, const float* dY, const void* stash,
+                 const wgnn_grads* grads, float* dg, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!g || !dY || !dg) return WGNN_ERR_NULL;
+  BwdCall c(workspace, workspace_bytes, stream);
+  c.p = p; c.Y = Y; c.dY = dY; c.stash = stash; c.g = grads; c.part = 7; c.dg_out = dg;
+  return bwd(d, c);
 }
-
-int check_rows(const wgnn_dims* d, const Layout& L, int which, int row0, int rows) {
-  if ((which & ~(WGNN_ROWS_IH | WGNN_ROWS_HH | WGNN_ROWS_STATE)) != 0 ||
-      ((which & 3) != WGNN_ROWS_IH && (which & 3) != WGNN_ROWS_HH))
-    return WGNN_ERR_SHAPE;
-  if (which & WGNN_ROWS_STATE) return WGNN_ERR_UNSUPPORTED;          // per-window dW_hh rows (the state stash)
-  const int al = rows_align(d, L);
-  if (al == 0) return WGNN_ERR_UNSUPPORTED;
-  const int64_t end = (int64_t)row0 + rows;
-  if (row0 < 0 || rows < 1 || end > (int64_t)L.G3 || row0 % al != 0 || (end % al != 0 && end != (int64_t)L.G3))
-    return WGNN_ERR_SHAPE;
-  return WGNN_OK;
-}
-}  // namespace
-
-extern "C" {
 
 int wgnn_bwd_rows_align(const wgnn_dims* d) {
   if (check_dims(d) != WGNN_OK) return 0;
@@ -776,53 +1056,50 @@ int wgnn_bwd_rows(const wgnn_dims* d, const void* Yv, const void* stash, const w
   rc = check_rows(d, L, which, row0, rows);
   if (rc != WGNN_OK) return rc;
   if (workspace_bytes < sizeof(float) * L.bwd_floats) return WGNN_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  float* ws = (float*)workspace;
-  const float* sf = (const float*)stash;
-  // the reduce half of part 4, narrowed to the range: the other product's segment is off, the output pointers start at row0
-  FinishArgs a = {};
-  fill_reduce(L, d, g, ws, 4, a);
-  FinSeg& s = ih ? a.ih : a.hh;
-  (ih ? a.hh : a.ih) = FinSeg{};
-  s.Mout = s.Mgemm = rows;
-  if (L.x3) pgemm_tn_geom(rows, s.Nout, &s.T, &s.nNb, &s.ntiles);
-  a.g[ih ? 4 : 5] += (size_t)row0 * s.ncols;                         // w_ih / w_hh
-  a.g[ih ? 6 : 7] += row0;                                           // b_ih / b_hh
+  BwdCall c(workspace, workspace_bytes, stream);
+  c.Y = Yv; c.stash = stash; c.g = g;
   // (the A operand is read from column row0 on; the last range's final tile reads columns past 3H exactly as the whole
   // product's does -- any finite data, inside the workspace -- and its rows are never stored)
-  if (L.x3) {
-    const bool full = d->math == WGNN_MATH_F16X3 || d->math == WGNN_MATH_F16X3G;
-    const size_t PG = L.BT * L.Gp;
-    const _Float16* dGIh = (const _Float16*)(ws + L.ws_dGI) + row0;
-    const _Float16* dGHh = (const _Float16*)(ws + L.ws_dGH) + row0;
-    if (ih) {
-      const _Float16* gh = (const _Float16*)(sf + L.st_g);
-      rc = launch_pgemm_tn(dGIh, L.gen2p ? dGIh : dGIh + PG, (int)L.Gp, gh, gh + L.BT * L.Ip, (int)L.Ip, 0, (int)L.BT,
-                           L.sk_ih, ws + L.ws_part_ih, rows, (int)L.I + 1, full && !L.gen2p, nullptr, nullptr, 0, 0, st,
-                           /*b_stream=*/true);
-    } else {
-      const _Float16* yph = (const _Float16*)(sf + L.st_yp);
-      const _Float16* ypl = yph + L.plane_rows * L.Hp;
-      rc = launch_pgemm_tn(dGHh, L.gen2p ? nullptr : dGHh + PG, (int)L.Gp, yph, ypl, (int)L.Hp, d->T, (int)L.BT, L.sk_hh,
-                           ws + L.ws_part_hh, rows, (int)L.H + 1, full, nullptr, nullptr, 0, 0, st, /*b_stream=*/false,
-                           /*per_window=*/false);
-    }
-  } else {
-    GemmArgs b = {};
-    b.a_kcontig = 0; b.b_kcontig = 0; b.ones_col = 1; b.lda = (int)L.Gp; b.M = rows; b.K = (int)L.BT;
-    if (ih) {
-      b.A = ws + L.ws_dGI + row0;
-      b.B = sf + L.st_g; b.ldb = (int)L.Ip; b.N = (int)L.I + 1;
-      b.splitk = L.sk_ih; b.partial = ws + L.ws_part_ih;
-    } else {
-      b.A = ws + L.ws_dGH + row0;
-      b.B = (const float*)Yv; b.ldb = (int)L.H; b.shift_T = d->T; b.N = (int)L.H + 1;
-      b.splitk = L.sk_hh; b.partial = ws + L.ws_part_hh;
-    }
-    rc = launch_gemm_f32(b, st);
-  }
+  return bwd_weights(Bwd{d, c, L}, which & 3, row0, rows);
+}
+
+int wgnn_finish(const wgnn_dims* d, const wgnn_params* p, const wgnn_grads* g, int which, const wgnn_adam* adam,
+                void* workspace, size_t workspace_bytes, void* stream) {
+  int rc = check_dims(d);
   if (rc != WGNN_OK) return rc;
-  return launch_finish(a, st);
+  const int only = which & (WGNN_FINISH_ADAM_GRU | WGNN_FINISH_ADAM_CONV);   // optimiser step of one tensor family
+  if ((which & ~(6 | WGNN_FINISH_ADAM_GRU | WGNN_FINISH_ADAM_CONV)) != 0 || (which == 0 && !adam)) return WGNN_ERR_SHAPE;
+  if (only && (!adam || (which & 6) != 0 || only == (WGNN_FINISH_ADAM_GRU | WGNN_FINISH_ADAM_CONV))) return WGNN_ERR_SHAPE;
+  if (!g || !workspace || (adam && !p)) return WGNN_ERR_NULL;
+  if (!complete(*g)) return WGNN_ERR_NULL;
+  const Layout L = make_layout(d);
+  if (workspace_bytes < sizeof(float) * L.bwd_floats) return WGNN_ERR_WORKSPACE;
+  FinishArgs a = {};
+  fill_reduce(L, d, g, (float*)workspace, which, a);
+  if (adam) {
+    if (!complete(*p)) return WGNN_ERR_NULL;
+    if (adam->step < 1) return WGNN_ERR_SHAPE;
+    if (!complete(adam->exp_avg) || !complete(adam->exp_avg_sq)) return WGNN_ERR_NULL;
+    slots(*p, a.p);                                  // the optimiser updates the parameters in place
+    slots(adam->exp_avg, a.m);
+    slots(adam->exp_avg_sq, a.v);
+    a.adam = 1;
+    set_adam(a, adam);
+    a.elem_mask = ((which & 4) ? 0u : 0xF0u) | ((which & 2) ? 0u : 0x0Fu);   // tensors whose gradient is final in g
+    if (only == WGNN_FINISH_ADAM_GRU) a.elem_mask = 0xF0u;
+    if (only == WGNN_FINISH_ADAM_CONV) a.elem_mask = 0x0Fu;
+    if (p->prepared && L.prep_kind) {
+      a.prep_kind = L.prep_kind;
+      if (L.prep_kind == 1) {
+        set_planes(a, L, p->prepared);
+      } else {
+        a.wp = (float*)p->prepared + L.prep_f;
+        a.wt = (float*)p->prepared + L.prep_b;
+      }
+      a.Ip = (int)L.Ip; a.Gp = (int)L.Gp;
+    }
+  }
+  return launch_finish(a, (hipStream_t)stream);
 }
 
 int wgnn_finish_rows(const wgnn_dims* d, const wgnn_params* p, const wgnn_grads* g, int which, int row0, int rows,
@@ -854,320 +1131,10 @@ int wgnn_finish_rows(const wgnn_dims* d, const wgnn_params* p, const wgnn_grads*
   r.p_b += row0; r.m_b += row0; r.v_b += row0; r.g_b += row0;
   r.row0 = row0;
   r.rows = rows;
-  const double bc1 = 1.0 - pow((double)adam->beta1, (double)adam->step);     // as wgnn_finish
-  const double bc2 = 1.0 - pow((double)adam->beta2, (double)adam->step);
-  r.lr_over_bc1 = (float)(adam->lr / bc1);
-  r.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-  r.b1 = adam->beta1; r.b2 = adam->beta2; r.eps = adam->eps;
+  set_adam(r, adam);
   r.status = (unsigned*)workspace;
-  if (ih && p->prepared && L.prep_kind == 1) {
-    r.pf_hi = (_Float16*)((float*)p->prepared + L.prep_f);
-    r.pf_lo = r.pf_hi + (size_t)L.np_g3 * L.Ip;
-    r.pb_hi = (_Float16*)((float*)p->prepared + L.prep_b);
-    r.pb_lo = r.pb_hi + (size_t)L.np_i * L.Gp;
-    r.np_g3 = L.np_g3; r.np_i = L.np_i;
-  }
+  if (ih && p->prepared && L.prep_kind == 1) set_planes(r, L, p->prepared);
   return launch_adam_rows(r, (hipStream_t)stream);
-}
-
-int wgnn_bwd(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* Y,
-             const float* dY, const void* stash, const wgnn_grads* g, void* workspace, size_t workspace_bytes,
-             void* stream) {
-  return wgnn_bwd_part(d, A, X, p, Y, dY, stash, g, workspace, workspace_bytes, stream, 7);
-}
-
-}  // extern "C"
-
-namespace {
-// The backward behind wgnn_bwd_part (dY given) and wgnn_bwd_mse_part (labels given: dY = 2 (Y - labels) grad_scale / n
-// is never written when the register-resident f16x3 recurrence runs; loss[0] = mean((Y - labels)^2)).
-// dg_out != nullptr (wgnn_gru_bwd): the recurrent half alone -- the four GRU gradients and dg [B*T][S*F]; A, X, the conv slots
-// of p and of g unused.
-int bwd_impl(const wgnn_dims* d, const float* A, const void* Xv, const wgnn_params* p, const void* Yv,
-             const float* dY, const void* labelsv, float grad_scale, float* loss, const void* stash,
-             const wgnn_grads* g, void* workspace, size_t workspace_bytes, void* stream, int which, float* dg_out = nullptr,
-             bool sst = false, const float* dhn = nullptr, float* dh0 = nullptr) {
-  // sst (wgnn_bwd_state_part): the stash is a state stash; the BPTT kernels start from dh_n (nullable) and h0 (the stash's
-  // copy) and leave dh_{-1} in dh0 (nullable); the dW_hh products read h0 at every window start
-  if (which < 1 || which > 31 || (which & 7) == 0) return WGNN_ERR_SHAPE;
-  const bool do_rec = which & 1, do_gcn = which & 2, do_wg = which & 4;
-  const bool defer = which & WGNN_BWD_DEFER;          // partial sums stay in the workspace for wgnn_finish
-  const float* X = (const float*)Xv;                 // io-typed (d->io): only the kernels that take `io` see 16-bit data
-  const float* Y = (const float*)Yv;
-  const float* labels = (const float*)labelsv;
-  const bool stats_ready = (which & 8) && labels;   // wgnn_fwd_loss left the MSE partials in the stash
-  int rc = check_dims(d);
-  if (rc != WGNN_OK) return rc;
-  if ((!dg_out && (!A || !X)) || !p || !Y || (!dY && !labels) || !stash || !g || !workspace) return WGNN_ERR_NULL;
-  if (labels && do_rec && !loss) return WGNN_ERR_NULL;
-  if ((!dg_out && (!g->conv1_weight || !g->conv1_bias || !g->conv2_weight || !g->conv2_bias)) || !g->w_ih || !g->w_hh ||
-      !g->b_ih || !g->b_hh)
-    return WGNN_ERR_NULL;
-  if (dg_out && (d->math != WGNN_MATH_F32 || d->io != WGNN_IO_F32 || d->adj_format != WGNN_ADJ_DENSE || which != 7))
-    return WGNN_ERR_UNSUPPORTED;
-  const Layout L = make_layout(d, sst);
-  if (workspace_bytes < sizeof(float) * L.bwd_floats) return WGNN_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  float* ws = (float*)workspace;
-  unsigned* status = (unsigned*)workspace;
-  const float* sf = (const float*)stash;
-  const BwdState sbs = {sst ? sf + L.st_h0 : nullptr, dhn, dh0};
-  const BwdState* sb = sst ? &sbs : nullptr;
-  const float* gact = sf + L.st_g;
-  const float* gates = sf + L.st_gates;
-  float* dGI = ws + L.ws_dGI;
-  float* dGH = ws + L.ws_dGH;
-  float* dg = ws + L.ws_dg;
-  float* part_ih = ws + L.ws_part_ih;
-  float* part_hh = ws + L.ws_part_hh;
-  const bool kept = p->prepared != nullptr && L.prep_kind != 0;
-  float* img_b = kept ? (float*)p->prepared + L.prep_b : ws + L.ws_planes_b;     // staged image of W_ih^T
-  float* scales = ws + L.ws_scales;          // [0] = 2^k, [1] = 2^-k (f16x3 range scaling), [2] = dY coefficient; partials from 64
-  const bool x3 = L.x3;
-  const bool full = d->math == WGNN_MATH_F16X3 || d->math == WGNN_MATH_F16X3G;
-  auto reduce_now = [&](int parts) {                 // without WGNN_BWD_DEFER: the reduce-only form of the finish launch
-    FinishArgs fa = {};
-    fill_reduce(L, d, g, ws, parts, fa);
-    return launch_finish(fa, st);
-  };
-  // the recurrence kernel forms dY from the labels itself: the fast f16x3 recurrence always (its statistics pass is
-  // cheap), the exact-fp32 register-resident one when the forward left the loss statistics in the stash
-  const bool fused_loss = labels && ((x3 && !L.gen_gru) || ((L.rec32 || L.small) && stats_ready));
-  // 16-bit labels / Y: the statistics must come from wgnn_fwd_loss (the stand-alone pass reads fp32 only)
-  if (d->io != WGNN_IO_F32 && labels && do_rec && !(fused_loss && stats_ready)) return WGNN_ERR_UNSUPPORTED;
-  if (labels && !fused_loss && do_rec) {                   // other kernels: materialise dY in the workspace
-    rc = launch_mse(Y, labels, (int64_t)L.BT * L.H, grad_scale, ws + L.ws_dY, loss, scales + 64, st);
-    if (rc != WGNN_OK) return rc;
-  }
-  if (labels && !fused_loss) dY = ws + L.ws_dY;
-
-  if (x3) {
-    // Everything downstream of dY is linear in it: run it in units scaled by scales[0] = 2^k (so that
-    // fp16 never sees ~1e-9 values) and multiply only the final gradients by scales[1] = 2^-k.
-    _Float16* dGIh = (_Float16*)dGI;
-    _Float16* dGHh = (_Float16*)dGH;
-    const _Float16* gh = (const _Float16*)gact;
-    const _Float16* yph = (const _Float16*)(sf + L.st_yp);
-    const _Float16* ypl = yph + L.plane_rows * L.Hp;
-    const size_t PG = L.BT * L.Gp;
-    const _Float16* dGIlo = L.dgi1 ? nullptr : dGIh + PG;                    // nullptr: single-plane A operand, two passes
-    const _Float16* dGHnlo = L.dgi1 ? nullptr : dGHh + L.BT * (size_t)L.hn;
-    if (do_rec) {
-      if (fused_loss && stats_ready)   // the forward recurrence already reduced (Y - labels): the BPTT kernel finalises
-        rc = WGNN_OK;
-      else if (fused_loss)   // loss, the range scale and the dY coefficient in one pass over Y and the labels
-        rc = launch_mse_stats(Y, labels, (int64_t)L.BT * L.H, grad_scale, loss, scales, scales + 64, st);
-      else
-        rc = launch_amax_scale(dY, (int64_t)L.BT * L.H, scales, scales + 64, st,    // 448 partials after the scales (896
-                               dhn, dhn ? (int64_t)d->B * d->H : 0);                 // with dh_n: the carry is scaled too)
-      if (rc != WGNN_OK) return rc;
-      if (L.gen_gru) {
-        rc = launch_split_weight2(p->w_hh, (int)L.G3, (int)L.H, 1, nullptr, 0, ws + L.ws_hhp_b, L.np_h, (int)L.Gp, status,
-                                  st);
-        if (rc != WGNN_OK) return rc;
-        rc = launch_gru_gen_bwd_x3(d->B, d->T, d->H, ws + L.ws_hhp_b, L.np_h, Y, dY, gates, scales, dGIh, dGHh,
-                                   (int)L.Gp, ws + L.ws_dhz, ws + L.ws_dhw, ws + L.ws_kp_b, ws + L.ws_dc, full, st, sb);
-      } else {
-        rc = launch_grux_bwd(d->B, d->T, d->H, p->w_hh, Yv, fused_loss ? nullptr : dY, fused_loss ? labelsv : nullptr,
-                             d->io, gates, L.gi_stash ? sf + L.st_GI : nullptr, (int)L.Gp, scales, dGIh, dGHh, (int)L.Gp, full,
-                             fused_loss && stats_ready ? sf + L.st_stats : nullptr, (int64_t)L.BT * L.H, grad_scale, loss,
-                             scales, status, L.dgi1 ? 0 : 1, st, sb);
-      }
-      if (rc != WGNN_OK) return rc;
-    }
-    if (do_wg) {
-      // dW_hh | db_hh = dGH^T [Hprev | 1]   (Hprev row (b,t) = Y-plane row (b,t-1); row B*T stands in at t = 0, or in the
-      // state stash row B*T + b, window b's own [h0 | 1]).
-      // Register-resident recurrence: dGH = [dGI_r | dGI_z | dGHn], the A operand takes GEMM rows < msplit from the dGI
-      // planes and rows >= msplit from the dGHn planes; the reduce kernel maps the GEMM rows back to W_hh's rows.
-      if (L.dghn) {
-        rc = launch_pgemm_tn(dGIh, dGIlo, (int)L.Gp, yph, ypl, (int)L.Hp, d->T, (int)L.BT, L.sk_hh, part_hh, L.m_hh,
-                             (int)L.H + 1, full, dGHh, dGHnlo, L.hn, L.msplit, st, /*b_stream=*/true, /*per_window=*/sst);
-      } else {
-        rc = launch_pgemm_tn(dGHh, L.gen2p ? nullptr : dGHh + PG, (int)L.Gp, yph, ypl, (int)L.Hp, d->T, (int)L.BT, L.sk_hh,
-                             part_hh, (int)L.G3, (int)L.H + 1, full, nullptr, nullptr, 0, 0, st, /*b_stream=*/false,
-                             /*per_window=*/sst);
-      }
-      if (rc != WGNN_OK) return rc;
-      // dW_ih | db_ih = dGI^T [g | 1]
-      // (single-plane dGI: ONE pass, hi(dGI) x hi(g) -- the rounding of g, too, is independent per element and averages
-      // out over the B*T rows this product sums: measured 8.8e-6 of max at B*T = 6144 against 5.9e-6 with g's lo plane.
-      // The same was measured for dW_hh (7e-5: h rows are correlated) and dg (2.8e-4 on the conv gradients: the rounding
-      // of W_ih is the same for every row and does not average) and NOT adopted: they keep hi x (hi + lo).)
-      const bool one_pass_ih = L.dgi1 || L.gen2p;
-      rc = launch_pgemm_tn(dGIh, one_pass_ih ? dGIh : dGIh + PG, (int)L.Gp, gh, gh + L.BT * L.Ip, (int)L.Ip, 0, (int)L.BT,
-                           L.sk_ih, part_ih, (int)L.G3, (int)L.I + 1, full && !one_pass_ih, nullptr, nullptr, 0, 0, st,
-                           /*b_stream=*/true);
-      if (rc != WGNN_OK) return rc;
-      if (!defer) rc = reduce_now(4);
-      if (rc != WGNN_OK) return rc;
-    }   // the four GRU gradients are final here: a data-parallel caller can start reducing them now
-    if (!do_gcn) return WGNN_OK;
-    // dg = dGI W_ih   (B operand = split(W_ih^T) [np_i][Gp]); dg stays in scaled units
-    if (!kept) {
-      rc = launch_split_weight2(p->w_ih, (int)L.G3, (int)L.I, 1, nullptr, 0, img_b, L.np_i, (int)L.Gp, status, st);
-      if (rc != WGNN_OK) return rc;
-    }
-    const int chunks = bwd2_chunks(L);
-    if (chunks > 1) {     // producer -> consumer pairs over row chunks (WGNN_OPT_BWD2_CHUNKS); same products, same partial sums per tile
-      const size_t rows = L.BT / chunks;
-      const size_t es = d->io ? 2 : 4, dgs = L.dg16 ? 2 : 4;
-      const int prow = gcnx_bwd_grid((int)rows, d->S, full);
-      for (int c = 0; c < chunks; ++c) {
-        const size_t r0 = (size_t)c * rows;
-        rc = launch_pgemm_nt(dGIh + r0 * L.Gp, dGIlo ? dGIlo + r0 * L.Gp : nullptr, (int)L.Gp, (int)rows, (int)L.Gp, img_b, L.np_i,
-                             (float*)((char*)dg + r0 * L.Id * dgs), (int)L.Id, (int)L.I, nullptr, full, nullptr, st, L.dg16);
-        if (rc != WGNN_OK) return rc;
-        rc = launch_gcnx2_bwd((int)rows, d->S, A, (const char*)Xv + r0 * L.I * es, d->io, p->conv1_weight, p->conv1_bias,
-                              p->conv2_weight, gh + r0 * L.Ip, (int)L.Ip, (const char*)dg + r0 * L.Id * dgs, (int)L.Id, L.dg16,
-                              scales, /*scale_in=*/0, ws + L.ws_gcnpart + (size_t)c * prow * gcnx2_bwd_partial_floats((int)rows) / 256,
-                              full, ws + L.ws_xtail_b, st);
-        if (rc != WGNN_OK) return rc;
-      }
-      if (defer) return WGNN_OK;
-      return reduce_now(2);
-    }
-    const size_t aimg_b = pgemm_nt256_aimg_bytes((int)L.BT, (int)L.I, (int)L.Gp, 2);
-    rc = launch_pgemm_nt(dGIh, L.gen_gru ? (L.gen2p ? nullptr : dGIh + PG) : dGIlo, (int)L.Gp, (int)L.BT, (int)L.Gp, img_b, L.np_i, dg, (int)L.Id,
-                         (int)L.I, nullptr, full, nullptr, st, L.dg16, aimg_b ? ws + L.ws_aimg_b : nullptr);
-    if (rc != WGNN_OK) return rc;
-    if (L.gen_gcn) {
-      rc = launch_gcn2_csr_bwd((int)L.BT, d->S, d->nnz, A, X, p->conv2_weight, sf + L.st_h1, nullptr, gact, L.Ip, dg,
-                                 L.Id, scales, ws + L.ws_du, ws + L.ws_gcnpart, nullptr, nullptr, nullptr, nullptr, st);
-      if (rc != WGNN_OK || defer) return rc;
-      return reduce_now(2);
-    }
-    rc = launch_gcnx2_bwd((int)L.BT, d->S, A, Xv, d->io, p->conv1_weight, p->conv1_bias, p->conv2_weight, gact, (int)L.Ip, dg, (int)L.Id, L.dg16,
-                          scales, /*scale_in=*/0, ws + L.ws_gcnpart, full, ws + L.ws_xtail_b, st);
-    if (rc != WGNN_OK || defer) return rc;
-    return reduce_now(2);
-  }
-
-  if (do_rec) {
-    if (L.gen_gru)
-      rc = launch_gru_gen_bwd(d->B, d->T, d->H, p->w_hh, Y, dY, gates, dGI, dGH, (int)L.Gp, ws + L.ws_dhz,
-                              ws + L.ws_dhw, st, sb);
-    else if (L.small)
-      rc = launch_gru_small_bwd(d->B, d->T, d->H, p->w_hh, Y, fused_loss ? nullptr : dY, fused_loss ? labels : nullptr, gates,
-                                dGI, dGH, (int)L.Gp, fused_loss ? sf + L.st_stats : nullptr, (int64_t)L.BT * L.H, grad_scale,
-                                loss, status, st, sb);
-    else   // register-resident recurrence: dGHn alone when the dW_hh GEMM has the two-source A operand; fused loss
-      rc = launch_gru_bwd(d->B, d->T, d->H, p->w_hh, Y, fused_loss ? nullptr : dY, fused_loss ? labels : nullptr, gates,
-                          sf + L.st_GI, (int)L.Gp, dGI, (int)L.Gp, L.dghn ? dGH : nullptr, L.dghn ? nullptr : dGH,
-                          fused_loss ? sf + L.st_stats : nullptr, (int64_t)L.BT * L.H, grad_scale, loss, status, st, sb);
-    if (rc != WGNN_OK) return rc;
-  }
-  if (do_wg) {
-    // dW_hh = dGH^T Hprev, db_hh = dGH^T 1   (Hprev row (b,t) = Y row (b,t-1), zero at t = 0)
-    if (L.g32tn) {     // [Hprev | 1 | 0..] rows were written by the forward recurrence (stash)
-      const float* hp = sf + L.st_hprev;
-      if (L.dghn)      // dGH = [dGI_r | dGI_z | dGHn]: GEMM rows < msplit from dGI, the rest from dGHn
-        rc = launch_gemm32_tn(dGI, (int)L.Gp, hp, L.hq, (int)L.BT, L.sk_hh, part_hh, L.m_hh, (int)L.H + 1, dGH, L.hn,
-                              L.msplit, st);
-      else
-        rc = launch_gemm32_tn(dGH, (int)L.Gp, hp, L.hq, (int)L.BT, L.sk_hh, part_hh, (int)L.G3, (int)L.H + 1, nullptr, 0, 0,
-                              st);
-    } else {
-      GemmArgs a = {};
-      a.A = dGH; a.lda = (int)L.Gp; a.a_kcontig = 0;
-      a.B = Y; a.ldb = (int)L.H; a.b_kcontig = 0; a.ones_col = 1; a.shift_T = d->T;
-      if (sst) { a.B = sf + L.st_hprev; a.ldb = L.hq; a.shift_T = 0; }   // the state stash's rows, h0 at window starts
-      a.M = (int)L.G3; a.N = (int)L.H + 1; a.K = (int)L.BT;
-      a.splitk = L.sk_hh; a.partial = part_hh;
-      rc = launch_gemm_f32(a, st);
-    }
-    if (rc != WGNN_OK) return rc;
-    // dW_ih = dGI^T g, db_ih = dGI^T 1
-    if (L.g32tn) {     // g carries its ones column (gcn32_fwd)
-      rc = launch_gemm32_tn(dGI, (int)L.Gp, gact, (int)L.Ip, (int)L.BT, L.sk_ih, part_ih, (int)L.G3, (int)L.I + 1, nullptr, 0,
-                            0, st);
-    } else {
-      GemmArgs b = {};
-      b.A = dGI; b.lda = (int)L.Gp; b.a_kcontig = 0;
-      b.B = gact; b.ldb = (int)L.Ip; b.b_kcontig = 0; b.ones_col = 1;
-      b.M = (int)L.G3; b.N = (int)L.I + 1; b.K = (int)L.BT;
-      b.splitk = L.sk_ih; b.partial = part_ih;
-      rc = launch_gemm_f32(b, st);
-    }
-    if (rc != WGNN_OK) return rc;
-    if (!defer) rc = reduce_now(4);
-    if (rc != WGNN_OK) return rc;
-  }
-  if (!do_gcn) return WGNN_OK;
-  {
-    // dg = dGI W_ih
-    if (L.g32) {
-      float* wt = img_b;                  // (W_ih^T) [I -> padded][Gp]
-      if (!kept) {
-        rc = launch_pad_weight(p->w_ih, (int)L.G3, (int)L.I, 1, nullptr, wt, gemm32_nt_rows((int)L.I), (int)L.Gp, st);
-        if (rc != WGNN_OK) return rc;
-      }
-      rc = launch_gemm32_nt(dGI, (int)L.Gp, (int)L.BT, (int)L.Gp, wt, dg, (int)L.Id, (int)L.I, st);
-    } else {
-      GemmArgs c = {};
-      c.A = dGI; c.lda = (int)L.Gp; c.a_kcontig = 1;
-      c.B = p->w_ih; c.ldb = (int)L.I; c.b_kcontig = 0;
-      c.C = dg; c.ldc = (int)L.Id; c.M = (int)L.BT; c.N = (int)L.I; c.K = (int)L.G3; c.splitk = 1;
-      rc = launch_gemm_f32_nt(c, gemm_f32_nt_splitk(c.M, c.N, c.K) > 1 && L.BT < 65536 ? ws + L.ws_ntk_b : nullptr, st);
-    }
-    if (rc != WGNN_OK) return rc;
-  }
-  if (dg_out) return launch_unpack_dg(dg, L.BT, (int)L.I, (int)L.Id, dg_out, st);     // wgnn_gru_bwd: hand dg to the caller
-  if (L.gen_gcn)
-    rc = launch_gcn2_csr_bwd((int)L.BT, d->S, d->nnz, A, X, p->conv2_weight, sf + L.st_h1, gact, nullptr, L.Ip, dg,
-                             L.Id, nullptr, ws + L.ws_du, ws + L.ws_gcnpart, nullptr, nullptr, nullptr, nullptr, st);
-  else
-    rc = launch_gcn32_bwd((int)L.BT, d->S, A, X, p->conv1_weight, p->conv1_bias, p->conv2_weight, gact, (int)L.Ip, dg, (int)L.Id,
-                          nullptr, nullptr, nullptr, nullptr, ws + L.ws_gcnpart, ws + L.ws_xtail_b, st);
-  if (rc != WGNN_OK || defer) return rc;
-  return reduce_now(2);
-}
-}  // namespace
-
-extern "C" {
-
-int wgnn_bwd_part(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* Y,
-                  const float* dY, const void* stash, const wgnn_grads* g, void* workspace, size_t workspace_bytes,
-                  void* stream, int which) {
-  if (!dY) return WGNN_ERR_NULL;
-  return bwd_impl(d, A, X, p, Y, dY, nullptr, 1.f, nullptr, stash, g, workspace, workspace_bytes, stream, which);
-}
-
-int wgnn_bwd_mse_part(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* Y,
-                      const void* labels, float grad_scale, float* loss, const void* stash, const wgnn_grads* g,
-                      void* workspace, size_t workspace_bytes, void* stream, int which) {
-  if (!labels) return WGNN_ERR_NULL;
-  return bwd_impl(d, A, X, p, Y, nullptr, labels, grad_scale, loss, stash, g, workspace, workspace_bytes, stream,
-                  which);
-}
-
-int wgnn_bwd_state_part(const wgnn_dims* d, const float* A, const void* X, const wgnn_params* p, const void* Y,
-                        const float* dY, const float* dh_n, const void* stash, const wgnn_grads* g, float* dh0,
-                        void* workspace, size_t workspace_bytes, void* stream, int part) {
-  int rc = check_dims(d);
-  if (rc != WGNN_OK) return rc;
-  if (!dY) return WGNN_ERR_NULL;
-  // dh0 is written while dY, dh_n and the stash are read
-  const size_t hb = (size_t)d->B * d->H * sizeof(float), yb = (size_t)d->B * d->T * d->H * sizeof(float);
-  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
-    return a && b && (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
-  };
-  if (overlap(dh0, hb, dh_n, hb) || overlap(dh0, hb, dY, yb) || overlap(dh0, hb, stash, wgnn_state_stash_bytes(d)))
-    return WGNN_ERR_UNSUPPORTED;
-  return bwd_impl(d, A, X, p, Y, dY, nullptr, 1.f, nullptr, stash, g, workspace, workspace_bytes, stream, part, nullptr,
-                  /*sst=*/true, dh_n, dh0);
-}
-
-int wgnn_gru_fwd(const wgnn_dims* d, const float* g, const wgnn_params* p, void* Y, void* stash, void* workspace,
-                 size_t workspace_bytes, void* stream) {
-  if (!g) return WGNN_ERR_NULL;
-  return fwd_impl(d, nullptr, nullptr, p, nullptr, Y, stash, workspace, workspace_bytes, stream, nullptr, 0.f, 1.f, g);
-}
-
-int wgnn_gru_bwd(const wgnn_dims* d, const float* g, const wgnn_params* p, const void* Y, const float* dY, const void* stash,
-                 const wgnn_grads* grads, float* dg, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!g || !dY || !dg) return WGNN_ERR_NULL;
-  return bwd_impl(d, nullptr, nullptr, p, Y, dY, nullptr, 1.f, nullptr, stash, grads, workspace, workspace_bytes, stream, 7, dg);
 }
 
 // F == F_out == 13 (the reference's own layers, src/main.py:41): the MFMA kernels of gcn.hip; any other widths: gcn_any.hip

@@ -126,23 +126,43 @@ def check_range_status(device=None) -> None:
                                % (_lib.load().wgnn_strerror(-7).decode(), word, what))
 
 
+def _forward_setup(A, X, params: Sequence[torch.Tensor], math, labels=None, h0=None, h_n=None, B=None):
+    """What every forward checks and sizes before it launches anything: X [B,T,S,F] and the params on the GPU and contiguous
+    (labels: contiguous too; h0 / h_n: [B, H] fp32 on X's device), the adjacency resolved for S stations (_adj), the Dims
+    (X's dtype is the I/O type: Y comes back in it) and the workspace.  B: Dims for another batch size (sizes that do not
+    depend on it).  Returns (adjacency to pass, d, workspace, workspace bytes)."""
+    _require_gpu(X, io_ok=True)
+    _require_gpu(*params)
+    _require_contiguous(X=X, labels=labels, **{"params[%d]" % i: q for i, q in enumerate(params)})
+    if X.dim() != 4:
+        raise RuntimeError("windgnn_amd: X must be [B, T, S, 13], got %s" % (tuple(X.shape),))
+    BX, T, S, F = X.shape
+    B = BX if B is None else B
+    A, fmt, nnz = _adj(A, S)
+    H = params[5].shape[1]
+    for name, t in (("h0", h0), ("h_n", h_n)):
+        if t is None:
+            continue
+        _require_gpu(t)
+        _require_contiguous(**{name: t})
+        if tuple(t.shape) != (B, H) or t.device != X.device:
+            raise RuntimeError("windgnn_amd: %s must be [B, H] = [%d, %d] float32 on %s, got %s on %s"
+                               % (name, B, H, X.device, tuple(t.shape), t.device))
+    d = _lib.Dims(B, T, S, F, H, math, fmt, nnz, _IO_OF[X.dtype])
+    ws_bytes = _lib.load().wgnn_workspace_bytes(C.byref(d))
+    if ws_bytes == 0:      # the library sizes nothing for dims it refuses: name the reason
+        _lib.check(-5 if F == 13 else -2, "wgnn_workspace_bytes(B=%d,T=%d,S=%d,F=%d,H=%d,math=%d,io=%s)"
+                   % (B, T, S, F, H, math, X.dtype))
+    return A, d, _Workspace.get(X.device, ws_bytes), ws_bytes
+
+
 def gcn_gru_forward_raw(A, X, params: Sequence[torch.Tensor], math=_lib.MATH_F32, want_stash=True, labels=None,
                         prepared=None):
     """Y[B,T,H], stash = wgnn_fwd(...).  X is [B,T,S,F].  labels [B,T,H]: wgnn_fwd_loss (the MSE statistics of
     (Y - labels) are left in the stash for gcn_gru_backward_mse_raw(..., part | 8))."""
     lib = _lib.load()
-    _require_gpu(X, io_ok=True)
-    _require_gpu(*params)
-    _require_contiguous(X=X, labels=labels, **{"params[%d]" % i: q for i, q in enumerate(params)})
-    B, T, S, F = X.shape
-    A, fmt, nnz = _adj(A, S)
-    H = params[5].shape[1]
-    d = _lib.Dims(B, T, S, F, H, math, fmt, nnz, _IO_OF[X.dtype])     # X's dtype is the I/O type: Y comes back in it
-    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
-    if ws_bytes == 0:
-        _lib.check(-5 if F == 13 else -2, "wgnn_workspace_bytes(B=%d,T=%d,S=%d,F=%d,H=%d,math=%d,io=%s)"
-                   % (B, T, S, F, H, math, X.dtype))
-    ws = _Workspace.get(X.device, ws_bytes)
+    A, d, ws, ws_bytes = _forward_setup(A, X, params, math, labels=labels)
+    B, T, H = d.B, d.T, d.H
     stash = torch.empty(lib.wgnn_stash_bytes(C.byref(d)), dtype=torch.uint8, device=X.device) if want_stash else None
     Y = torch.empty(B, T, H, dtype=X.dtype, device=X.device)
     ps = _params_struct(_lib.Params, params, prepared)
@@ -168,28 +188,8 @@ def gcn_gru_state(A, X, params: Sequence[torch.Tensor], math=_lib.MATH_F32, h0=N
     [B,T,S,F]; Y comes back in X's dtype.  h_n: optional caller buffer [B,H] fp32 (it must not share memory with h0).
     T == 1 with a dense A (S <= 64), fp32 X, H <= 128 and B <= _lib.STEP_MAX_B is ONE kernel launch."""
     lib = _lib.load()
-    _require_gpu(X, io_ok=True)
-    _require_gpu(*params)
-    _require_contiguous(X=X, **{"params[%d]" % i: q for i, q in enumerate(params)})
-    if X.dim() != 4:
-        raise RuntimeError("windgnn_amd: X must be [B, T, S, 13], got %s" % (tuple(X.shape),))
-    B, T, S, F = X.shape
-    A, fmt, nnz = _adj(A, S)
-    H = params[5].shape[1]
-    for name, t in (("h0", h0), ("h_n", h_n)):
-        if t is None:
-            continue
-        _require_gpu(t)
-        _require_contiguous(**{name: t})
-        if tuple(t.shape) != (B, H) or t.device != X.device:
-            raise RuntimeError("windgnn_amd: %s must be [B, H] = [%d, %d] float32 on %s, got %s on %s"
-                               % (name, B, H, X.device, tuple(t.shape), t.device))
-    d = _lib.Dims(B, T, S, F, H, math, fmt, nnz, _IO_OF[X.dtype])
-    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
-    if ws_bytes == 0:
-        _lib.check(-5 if F == 13 else -2, "wgnn_workspace_bytes(B=%d,T=%d,S=%d,F=%d,H=%d,math=%d,io=%s)"
-                   % (B, T, S, F, H, math, X.dtype))
-    ws = _Workspace.get(X.device, ws_bytes)
+    A, d, ws, ws_bytes = _forward_setup(A, X, params, math, h0=h0, h_n=h_n)
+    B, T, H = d.B, d.T, d.H
     Y = torch.empty(B, T, H, dtype=X.dtype, device=X.device) if want_y else None
     if h_n is None:
         h_n = torch.empty(B, H, dtype=torch.float32, device=X.device)
@@ -259,6 +259,14 @@ def refresh_prepared(d, params, prepared) -> None:
     _lib.check(lib.wgnn_prepare_weights(C.byref(d), C.byref(ps), _ptr(ws), ws.numel(), _stream()), "wgnn_prepare_weights")
 
 
+def _adam_struct(adam):
+    ad = _lib.Adam()
+    ad.exp_avg = _params_struct(_lib.Grads, adam["exp_avg"])
+    ad.exp_avg_sq = _params_struct(_lib.Grads, adam["exp_avg_sq"])
+    ad.step, ad.lr, ad.beta1, ad.beta2, ad.eps = adam["step"], adam["lr"], adam["beta1"], adam["beta2"], adam["eps"]
+    return ad
+
+
 def finish_step(d, params, grads, which: int, adam=None, prepared=None, device=None) -> None:
     """wgnn_finish: reduce the deferred partial sums of the backward parts in `which` (4: GRU, 2: conv) into `grads` and,
     with adam = dict(exp_avg=[8 tensors], exp_avg_sq=[8 tensors], step, lr, beta1, beta2, eps), apply Adam to `params`
@@ -269,23 +277,10 @@ def finish_step(d, params, grads, which: int, adam=None, prepared=None, device=N
     ws = _Workspace.get(device if device is not None else grads[0].device, ws_bytes)
     ps = _params_struct(_lib.Params, params, prepared)
     gs = _params_struct(_lib.Grads, grads)
-    ad = None
-    if adam is not None:
-        ad = _lib.Adam()
-        ad.exp_avg = _params_struct(_lib.Grads, adam["exp_avg"])
-        ad.exp_avg_sq = _params_struct(_lib.Grads, adam["exp_avg_sq"])
-        ad.step, ad.lr, ad.beta1, ad.beta2, ad.eps = adam["step"], adam["lr"], adam["beta1"], adam["beta2"], adam["eps"]
+    ad = _adam_struct(adam) if adam is not None else None
     rc = lib.wgnn_finish(C.byref(d), C.byref(ps), C.byref(gs), which, C.byref(ad) if ad is not None else None, _ptr(ws),
                          ws_bytes, _stream())
     _lib.check(rc, "wgnn_finish(%d%s)" % (which, ", adam" if adam is not None else ""))
-
-
-def _adam_struct(adam):
-    ad = _lib.Adam()
-    ad.exp_avg = _params_struct(_lib.Grads, adam["exp_avg"])
-    ad.exp_avg_sq = _params_struct(_lib.Grads, adam["exp_avg_sq"])
-    ad.step, ad.lr, ad.beta1, ad.beta2, ad.eps = adam["step"], adam["lr"], adam["beta1"], adam["beta2"], adam["eps"]
-    return ad
 
 
 def rows_align(d) -> int:
@@ -334,19 +329,18 @@ class GCNGRUFunction(torch.autograd.Function):
         need = any(ctx.needs_input_grad[3:])
         Y, stash, d = gcn_gru_forward_raw(A, X, params, math, want_stash=need)
         ctx.d = d
-        ctx.stash = stash
-        ctx.save_for_backward(_adj(A)[0], X, Y, *params)   # dense [S,S] or the CSR blob; d.adj_format says which
+        ctx.save_for_backward(_adj(A)[0], X, Y, stash, *params)   # dense [S,S] or the CSR blob; d.adj_format says which
         return Y
 
     @staticmethod
     def backward(ctx, dY):
-        A, X, Y, *params = ctx.saved_tensors
-        if ctx.stash is None:
+        A, X, Y, stash, *params = ctx.saved_tensors
+        if stash is None:
             raise RuntimeError("windgnn_amd: backward called but the forward ran without a stash")
         sizes = [p.numel() for p in params]
         flat = torch.empty(sum(sizes), dtype=torch.float32, device=X.device)
         grads = [g.view_as(p) for g, p in zip(flat.split(sizes), params)]
-        gcn_gru_backward_raw(ctx.d, A, X, params, Y, dY.float().contiguous(), ctx.stash, grads)   # dY is always fp32
+        gcn_gru_backward_raw(ctx.d, A, X, params, Y, dY.float().contiguous(), stash, grads)   # dY is always fp32
         return (None, None, None, *grads)
 
 
@@ -359,28 +353,8 @@ def gcn_gru_state_forward_raw(A, X, params: Sequence[torch.Tensor], math=_lib.MA
     stash the backward (gcn_gru_state_backward_raw) needs; h_n [B,H] fp32 is the unrounded last state (a new tensor unless
     a caller buffer is given; it must not share memory with h0)."""
     lib = _lib.load()
-    _require_gpu(X, io_ok=True)
-    _require_gpu(*params)
-    _require_contiguous(X=X, **{"params[%d]" % i: q for i, q in enumerate(params)})
-    if X.dim() != 4:
-        raise RuntimeError("windgnn_amd: X must be [B, T, S, 13], got %s" % (tuple(X.shape),))
-    B, T, S, F = X.shape
-    A, fmt, nnz = _adj(A, S)
-    H = params[5].shape[1]
-    for name, t in (("h0", h0), ("h_n", h_n)):
-        if t is None:
-            continue
-        _require_gpu(t)
-        _require_contiguous(**{name: t})
-        if tuple(t.shape) != (B, H) or t.device != X.device:
-            raise RuntimeError("windgnn_amd: %s must be [B, H] = [%d, %d] float32 on %s, got %s on %s"
-                               % (name, B, H, X.device, tuple(t.shape), t.device))
-    d = _lib.Dims(B, T, S, F, H, math, fmt, nnz, _IO_OF[X.dtype])
-    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
-    if ws_bytes == 0:
-        _lib.check(-5 if F == 13 else -2, "wgnn_workspace_bytes(B=%d,T=%d,S=%d,F=%d,H=%d,math=%d,io=%s)"
-                   % (B, T, S, F, H, math, X.dtype))
-    ws = _Workspace.get(X.device, ws_bytes)
+    A, d, ws, ws_bytes = _forward_setup(A, X, params, math, h0=h0, h_n=h_n)
+    B, T, H = d.B, d.T, d.H
     stash = torch.empty(lib.wgnn_state_stash_bytes(C.byref(d)), dtype=torch.uint8, device=X.device)
     Y = torch.empty(B, T, H, dtype=X.dtype, device=X.device)
     if h_n is None:
@@ -534,14 +508,14 @@ class GRUFunction(torch.autograd.Function):
         ps.w_ih, ps.w_hh, ps.b_ih, ps.b_hh = (q.data_ptr() for q in params)
         _lib.check(lib.wgnn_gru_fwd(C.byref(d), _ptr(g), C.byref(ps), _ptr(Y), _ptr(stash), _ptr(ws), ws_bytes, _stream()),
                    "wgnn_gru_fwd")
-        ctx.d, ctx.stash = d, stash
-        ctx.save_for_backward(g, Y, *params)
+        ctx.d = d
+        ctx.save_for_backward(g, Y, stash, *params)
         return Y
 
     @staticmethod
     def backward(ctx, dY):
         lib = _lib.load()
-        g, Y, *params = ctx.saved_tensors
+        g, Y, stash, *params = ctx.saved_tensors
         grads = [torch.empty_like(q) for q in params]
         dg = torch.empty_like(g)
         ws_bytes = lib.wgnn_workspace_bytes(C.byref(ctx.d))
@@ -550,7 +524,7 @@ class GRUFunction(torch.autograd.Function):
         ps.w_ih, ps.w_hh, ps.b_ih, ps.b_hh = (q.data_ptr() for q in params)
         gs.w_ih, gs.w_hh, gs.b_ih, gs.b_hh = (q.data_ptr() for q in grads)
         _lib.check(lib.wgnn_gru_bwd(C.byref(ctx.d), _ptr(g), C.byref(ps), _ptr(Y), _ptr(dY.float().contiguous()),
-                                    _ptr(ctx.stash), C.byref(gs), _ptr(dg), _ptr(ws), ws_bytes, _stream()), "wgnn_gru_bwd")
+                                    _ptr(stash), C.byref(gs), _ptr(dg), _ptr(ws), ws_bytes, _stream()), "wgnn_gru_bwd")
         return (dg, None, *grads)
 
 

@@ -37,9 +37,9 @@ import torch
 
 from . import _lib
 from .distributed import HEADER, LOSS_SLOT, BucketExchange, grad_block_plan
-from .functional import (bwd_rows, check_range_status, finish_rows, finish_step, gcn_gru_backward_mse_raw,
-                         gcn_gru_forward_raw, gcn_gru_state_backward_raw, gcn_gru_state_forward_raw, mse_loss_grad,
-                         prepared_weights, refresh_prepared, rows_align)
+from .functional import (_forward_setup, bwd_rows, check_range_status, finish_rows, finish_step,
+                         gcn_gru_backward_mse_raw, gcn_gru_forward_raw, gcn_gru_state_backward_raw,
+                         gcn_gru_state_forward_raw, mse_loss_grad, prepared_weights, refresh_prepared, rows_align)
 from .modules import GCN_GRU
 
 AUTO_GRAD_BLOCKS = 8                # grad_blocks="auto": row blocks per GRU weight ...
@@ -175,11 +175,8 @@ class TrainStep:
         launch(es) on the summed gradient.  Returns (big-batch mean loss, empty Y)."""
         if not self.collective:
             raise RuntimeError("windgnn_amd: TrainStep.step needs at least one window (got a batch of %s)" % (tuple(X.shape),))
-        from .functional import _IO_OF, _adj
-        _, T, S, F = X.shape
-        _, fmt, nnz = _adj(A, S)
-        H = self.p_views[5].shape[1]
-        d = _lib.Dims(1, T, S, F, H, self.model.math, fmt, nnz, _IO_OF[X.dtype])    # sizes the finish launch (B-independent)
+        _, d, _, _ = _forward_setup(A, X, self.p_views, self.model.math, B=1)   # sizes the finish launch (B-independent)
+        T, H = d.T, d.H
         if self._prepared_version != self._param_version():
             self._images(d)
         pre = self._prepared
@@ -249,10 +246,7 @@ class TrainStep:
     def _forward(self, A, X, L):
         # the first call sizes and builds the images from the dims of this batch (they depend on S, H, math only)
         if self._prepared_version != self._param_version():
-            from .functional import _IO_OF, _adj
-            B, T, S, F = X.shape
-            _, fmt, nnz = _adj(A, S)
-            self._images(_lib.Dims(B, T, S, F, self.p_views[5].shape[1], self.model.math, fmt, nnz, _IO_OF[X.dtype]))
+            self._images(_forward_setup(A, X, self.p_views, self.model.math)[1])
         return gcn_gru_forward_raw(A, X, self.p_views, self.model.math, want_stash=True, labels=L, prepared=self._prepared)
 
     @property
@@ -277,10 +271,7 @@ class TrainStep:
                                    "a state is carried; call reset_state() first" % (self._hbuf.shape[1], B))
             self._hbuf = torch.zeros(2, B, H, dtype=torch.float32, device=self.device)
         if self._prepared_version != self._param_version():
-            from .functional import _IO_OF, _adj
-            _, T, S, F = X.shape
-            _, fmt, nnz = _adj(A, S)
-            self._images(_lib.Dims(B, T, S, F, H, self.model.math, fmt, nnz, _IO_OF[X.dtype]))
+            self._images(_forward_setup(A, X, self.p_views, self.model.math)[1])
         h0 = self._hbuf[self._hcur] if self._has_state else None
         Y, _, stash, d = gcn_gru_state_forward_raw(A, X, self.p_views, self.model.math, h0, self._hbuf[1 - self._hcur],
                                                    prepared=self._prepared)
