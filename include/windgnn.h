@@ -50,7 +50,27 @@ extern "C" {
  * handling an error.  The fp16-plane math modes (WGNN_MATH_F16X3 / WGNN_MATH_F16) hold activations and weights as
  * fp16 (hi [+ lo]) and cannot represent magnitudes > 65504 (anything beyond is flagged); the reference's fp32 path has no such limit, so
  * instead of producing inf/NaN (or, behind a ReLU, silently 0) the kernels report it here.  WGNN_MATH_F32 never
- * sets a range bit. */
+ * sets a range bit.
+ *
+ * What the library may touch, and what it may assume (tests/test_gpu_footprint.py holds every entry point to the first two,
+ * and runs X, Y, labels and dY one element off a 256-byte boundary; the parameter views are windgnn_amd.trainer's daily use):
+ *   - Sizes are exact.  No call reads or writes a byte outside [ptr, ptr + n) of any buffer, n being wgnn_*_bytes() for
+ *     workspace, stash, state stash, `prepared` and the layer workspaces and numel * sizeof(element) for every tensor.
+ *     (Where a kernel's widest load would run past a tensor's end -- the pair loads of X when S * 13 is odd -- the launcher
+ *     stages the last tile in the workspace instead.)
+ *   - Scratch may be dirty.  Apart from the status block, no call depends on what workspace, stash, `prepared` or an output
+ *     held before it: every region, padding included, is written by the call that reads it, or earlier in one of the
+ *     sequences marked "on the SAME workspace" below.  Any bytes will do, NaN patterns included; results are bit-identical.
+ *     Between a forward and its backward only the stash (and `prepared`) carries state, never the workspace.
+ *   - Alignment.  Tensors -- A, the CSR buffer, X, Y, labels, dY, h0 / h_n / dh_n / dh0, g / dg, the 8 parameters, gradients
+ *     and Adam moments, loss, every tensor of the layer and training ops: the alignment of their ELEMENT type (4 bytes; 2 for
+ *     fp16 / bf16 X, Y and labels).  A contiguous slice of a larger tensor and the views of one flat parameter buffer
+ *     qualify.  Wider accesses to these tensors are either chosen after testing the address or issued at element alignment
+ *     (gfx9 compute queues serve unaligned global accesses; the pair loads of X at odd S * 13 always were); results do not
+ *     depend on the alignment.  workspace, stash, state stash, `prepared` and the layer workspaces: 256 bytes (what hipMalloc
+ *     and every caching allocator give); their regions are laid out in 256-byte steps and read by LDS-DMA and 16-byte vector
+ *     loads, stored in 64-byte segments.  The entry points do not diagnose a misaligned scratch buffer reliably (some
+ *     launchers return WGNN_ERR_SHAPE); the Python bindings refuse one before the call. */
 #define WGNN_STATUS_BYTES 256
 #define WGNN_STATUS_ACT_RANGE 1u    /* a GCN pre-activation left fp16's range (or was NaN) in the forward */
 #define WGNN_STATUS_WEIGHT_RANGE 2u /* a GRU weight / bias left fp16's range */

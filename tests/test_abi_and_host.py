@@ -219,6 +219,31 @@ def test_csr_adjacency_for_another_graph_is_refused_on_the_host():
         _adj(csr, 20)
 
 
+def test_scratch_buffers_off_a_256_byte_boundary_are_refused_on_the_host():
+    """include/windgnn.h, "Alignment": tensors need their element's alignment (every torch view has it), but the stash and the
+    `prepared` images are read by LDS-DMA and 16-byte loads at offsets laid out from a 256-byte-aligned base.  The bindings
+    refuse a slice of a larger buffer before its pointer reaches a kernel; a buffer of its own passes, and so does None."""
+    from windgnn_amd import _lib
+    from windgnn_amd.functional import SCRATCH_ALIGN, _params_struct, _require_scratch_aligned, _stash_ptr
+    assert SCRATCH_ALIGN == 256
+    big = torch.empty(4096, dtype=torch.uint8)
+    o = (-big.data_ptr()) % 256                                     # host allocations are 64-byte aligned only
+    good = big[o:o + 1024]
+    _require_scratch_aligned(stash=good, prepared=None)
+    assert _stash_ptr(good).value == good.data_ptr() and _stash_ptr(None).value is None
+    for off in (1, 4, 16, 64, 128):
+        with pytest.raises(RuntimeError, match="stash must start on a 256-byte boundary"):
+            _stash_ptr(big[o + off:o + off + 1024])
+    params = [torch.zeros(4) for _ in range(8)]
+    assert _params_struct(_lib.Params, params, good).prepared == good.data_ptr()
+    with pytest.raises(RuntimeError, match="prepared must start on a 256-byte boundary"):
+        _params_struct(_lib.Params, params, big[o + 364:o + 364 + 1024])      # e.g. 364 bytes into its storage
+    # tensors: element alignment is the contract, so a contiguous slice of a batch is taken as it is
+    X = torch.zeros(7, 1, 7, 13)
+    assert X[1:].is_contiguous() and (X[1:].data_ptr() - X.data_ptr()) == 364
+    assert _params_struct(_lib.Grads, [X[1:]] * 8).conv1_weight == X[1:].data_ptr()
+
+
 def test_reference_import_header_resolves_with_the_documented_swap():
     """src/main.py gets `nn`, `torch`, `np` and GraphConvLayer only through its star
     imports (src/main.py:4-8; step6 does `import torch.nn as nn`).  With the documented replacement lines every

@@ -36,8 +36,27 @@ def _require_contiguous(**named: torch.Tensor) -> None:
                                "on it first" % (name, tuple(t.shape), tuple(t.stride())))
 
 
+SCRATCH_ALIGN = 256        # workspace, stash, state stash and `prepared` (include/windgnn.h, "Alignment")
+
+
+def _require_scratch_aligned(**named: torch.Tensor) -> None:
+    """Tensors need the alignment of their element only, which every torch view has.  The stash and the `prepared` images are
+    read by LDS-DMA and 16-byte vector loads at offsets laid out in 256-byte steps from their base: a buffer that starts
+    anywhere else (a slice of a larger allocation) is refused here, not read.  Fresh torch allocations qualify."""
+    for name, t in named.items():
+        if t is not None and t.data_ptr() % SCRATCH_ALIGN != 0:
+            raise RuntimeError("windgnn_amd: %s must start on a %d-byte boundary (its data_ptr() is %d bytes past one): "
+                               "allocate it on its own (torch.empty) instead of slicing a larger buffer"
+                               % (name, SCRATCH_ALIGN, t.data_ptr() % SCRATCH_ALIGN))
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _stash_ptr(stash):
+    _require_scratch_aligned(stash=stash)
+    return _ptr(stash)
 
 
 def _scratch(device, nbytes: int):
@@ -79,6 +98,7 @@ def _params_struct(cls, tensors: Sequence[torch.Tensor], prepared: torch.Tensor 
     for (name, _), t in zip(cls._fields_, tensors):
         setattr(s, name, t.data_ptr())
     if prepared is not None:
+        _require_scratch_aligned(prepared=prepared)
         s.prepared = prepared.data_ptr()      # wgnn_params.prepared: caller-kept images of W_ih
     return s
 
@@ -174,10 +194,10 @@ def gcn_gru_forward_raw(A, X, params: Sequence[torch.Tensor], math=_lib.MATH_F32
             raise RuntimeError("windgnn_amd: wgnn_fwd_loss needs a stash and labels of Y's size, got %s vs %s"
                                % (tuple(labels.shape), tuple(Y.shape)))
         rc = lib.wgnn_fwd_loss(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(labels), _ptr(Y),
-                               _ptr(stash), _ptr(ws), ws_bytes, _stream())
+                               _stash_ptr(stash), _ptr(ws), ws_bytes, _stream())
         _lib.check(rc, "wgnn_fwd_loss")
         return Y, stash, d
-    rc = lib.wgnn_fwd(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(Y), _ptr(stash), _ptr(ws), ws_bytes, _stream())
+    rc = lib.wgnn_fwd(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(Y), _stash_ptr(stash), _ptr(ws), ws_bytes, _stream())
     _lib.check(rc, "wgnn_fwd")
     return Y, stash, d
 
@@ -211,7 +231,7 @@ def gcn_gru_backward_raw(d, A, X, params, Y, dY, stash, grads: Sequence[torch.Te
     ws = _Workspace.get(X.device, ws_bytes)
     ps = _params_struct(_lib.Params, params)
     gs = _params_struct(_lib.Grads, grads)
-    rc = lib.wgnn_bwd_part(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(Y), _ptr(dY), _ptr(stash), C.byref(gs),
+    rc = lib.wgnn_bwd_part(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(Y), _ptr(dY), _stash_ptr(stash), C.byref(gs),
                            _ptr(ws), ws_bytes, _stream() if stream is None else C.c_void_p(stream.cuda_stream), part)
     _lib.check(rc, "wgnn_bwd_part(%d)" % part)
 
@@ -235,7 +255,7 @@ def gcn_gru_backward_mse_raw(d, A, X, params, Y, L, stash, grads: Sequence[torch
     ps = _params_struct(_lib.Params, params, prepared)
     gs = _params_struct(_lib.Grads, grads)
     rc = lib.wgnn_bwd_mse_part(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(Y), _ptr(L), grad_scale,
-                               _ptr(loss), _ptr(stash), C.byref(gs), _ptr(ws), ws_bytes, _stream(), part)
+                               _ptr(loss), _stash_ptr(stash), C.byref(gs), _ptr(ws), ws_bytes, _stream(), part)
     _lib.check(rc, "wgnn_bwd_mse_part(%d)" % part)
 
 
@@ -295,7 +315,7 @@ def bwd_rows(d, Y, stash, grads, which: int, row0: int, rows: int, device=None) 
     ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
     ws = _Workspace.get(device if device is not None else grads[0].device, ws_bytes)
     gs = _params_struct(_lib.Grads, grads)
-    rc = lib.wgnn_bwd_rows(C.byref(d), _ptr(Y), _ptr(stash), C.byref(gs), which, row0, rows, _ptr(ws), ws_bytes, _stream())
+    rc = lib.wgnn_bwd_rows(C.byref(d), _ptr(Y), _stash_ptr(stash), C.byref(gs), which, row0, rows, _ptr(ws), ws_bytes, _stream())
     _lib.check(rc, "wgnn_bwd_rows(%d, %d, %d)" % (which, row0, rows))
 
 
@@ -360,7 +380,7 @@ def gcn_gru_state_forward_raw(A, X, params: Sequence[torch.Tensor], math=_lib.MA
     if h_n is None:
         h_n = torch.empty(B, H, dtype=torch.float32, device=X.device)
     ps = _params_struct(_lib.Params, params, prepared)
-    rc = lib.wgnn_fwd_state_stash(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(h0), _ptr(Y), _ptr(h_n), _ptr(stash),
+    rc = lib.wgnn_fwd_state_stash(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(h0), _ptr(Y), _ptr(h_n), _stash_ptr(stash),
                                   _ptr(ws), ws_bytes, _stream())
     _lib.check(rc, "wgnn_fwd_state_stash")
     return Y, h_n, stash, d
@@ -383,7 +403,7 @@ def gcn_gru_state_backward_raw(d, A, X, params, Y, dY, dh_n, stash, grads: Seque
     ws = _Workspace.get(X.device, ws_bytes)
     ps = _params_struct(_lib.Params, params, prepared)
     gs = _params_struct(_lib.Grads, grads)
-    rc = lib.wgnn_bwd_state_part(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(Y), _ptr(dY), _ptr(dh_n), _ptr(stash),
+    rc = lib.wgnn_bwd_state_part(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(Y), _ptr(dY), _ptr(dh_n), _stash_ptr(stash),
                                  C.byref(gs), _ptr(dh0), _ptr(ws), ws_bytes,
                                  _stream() if stream is None else C.c_void_p(stream.cuda_stream), part)
     _lib.check(rc, "wgnn_bwd_state_part(%d)" % part)
@@ -506,7 +526,7 @@ class GRUFunction(torch.autograd.Function):
         Y = torch.empty(B, T, H, dtype=torch.float32, device=g.device)
         ps = _lib.Params()
         ps.w_ih, ps.w_hh, ps.b_ih, ps.b_hh = (q.data_ptr() for q in params)
-        _lib.check(lib.wgnn_gru_fwd(C.byref(d), _ptr(g), C.byref(ps), _ptr(Y), _ptr(stash), _ptr(ws), ws_bytes, _stream()),
+        _lib.check(lib.wgnn_gru_fwd(C.byref(d), _ptr(g), C.byref(ps), _ptr(Y), _stash_ptr(stash), _ptr(ws), ws_bytes, _stream()),
                    "wgnn_gru_fwd")
         ctx.d = d
         ctx.save_for_backward(g, Y, stash, *params)
@@ -524,7 +544,7 @@ class GRUFunction(torch.autograd.Function):
         ps.w_ih, ps.w_hh, ps.b_ih, ps.b_hh = (q.data_ptr() for q in params)
         gs.w_ih, gs.w_hh, gs.b_ih, gs.b_hh = (q.data_ptr() for q in grads)
         _lib.check(lib.wgnn_gru_bwd(C.byref(ctx.d), _ptr(g), C.byref(ps), _ptr(Y), _ptr(dY.float().contiguous()),
-                                    _ptr(stash), C.byref(gs), _ptr(dg), _ptr(ws), ws_bytes, _stream()), "wgnn_gru_bwd")
+                                    _stash_ptr(stash), C.byref(gs), _ptr(dg), _ptr(ws), ws_bytes, _stream()), "wgnn_gru_bwd")
         return (dg, None, *grads)
 
 
