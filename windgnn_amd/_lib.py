@@ -1,4 +1,4 @@
-"""ctypes binding of libwindgnn_hip.so (the C ABI declared in include/windgnn.h).
+"""ctypes binding of libwindgnn_hip.so (the C ABI declared in include/windgnn.h and include/windgnn_optim.h).
 
 The library is the product: there is no CPU or eager-PyTorch fallback.  If the shared object is
 missing or a call fails this module raises, loudly."""
@@ -119,6 +119,19 @@ EXPORTS = {
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
 }
 
+# include/windgnn_optim.h: clipping by the global gradient norm inside the step tail (a second header and a second table:
+# include/windgnn.h and EXPORTS stay as they are)
+OPTIM_VERSION = 1           # WGNN_OPTIM_VERSION
+CLIP_TOTAL, CLIP_COEF = 0, 1   # float slots of the `clip` buffer: the gradient's L2 norm, min(1, max_norm / (norm + 1e-6))
+EXPORTS_OPTIM = {
+    "wgnn_optim_version": (C.c_int, []),
+    "wgnn_clip_bytes": (C.c_size_t, [C.POINTER(Dims)]),
+    "wgnn_finish_norm": (C.c_int, [C.POINTER(Dims), C.POINTER(Grads), C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                   C.c_size_t, C.c_void_p]),
+    "wgnn_finish_clipped": (C.c_int, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Grads), C.POINTER(Adam), C.c_void_p,
+                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -138,6 +151,16 @@ def load() -> C.CDLL:
         fn.argtypes = args
     if lib.wgnn_version() < 122:
         raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old")
+    if not hasattr(lib, "wgnn_optim_version"):
+        raise RuntimeError("windgnn_amd: %s predates include/windgnn_optim.h (no wgnn_optim_version): rebuild it with "
+                           "`python -m windgnn_amd.build --force`" % LIB_PATH)
+    for name, (res, args) in EXPORTS_OPTIM.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.wgnn_optim_version() < OPTIM_VERSION:
+        raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_optim_version %d < %d)"
+                           % (lib.wgnn_optim_version(), OPTIM_VERSION))
     _lib = lib
     return lib
 

@@ -7,6 +7,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "../../include/windgnn_optim.h"
 
 namespace {
 
@@ -288,6 +289,47 @@ void fill_reduce(const Layout& L, const wgnn_dims* d, const wgnn_grads* g, float
     a.conv_rows = L.gen_gcn ? gcn_csr_bwd_rows()
                             : (L.x3 ? gcnx_bwd_grid((int)L.BT, d->S, three_pass(d)) : gcn32_bwd_grid((int)L.BT, d->S));
   }
+}
+
+// The optimiser half of a finish launch: parameters (updated in place), moments, hyper-parameters and the images to refresh
+void fill_adam(const Layout& L, const wgnn_params* p, const wgnn_adam* adam, FinishArgs& a) {
+  slots(*p, a.p);
+  slots(adam->exp_avg, a.m);
+  slots(adam->exp_avg_sq, a.v);
+  a.adam = 1;
+  set_adam(a, adam);
+  if (p->prepared && L.prep_kind) {
+    a.prep_kind = L.prep_kind;
+    if (L.prep_kind == 1) {
+      set_planes(a, L, p->prepared);
+    } else {
+      a.wp = (float*)p->prepared + L.prep_f;
+      a.wt = (float*)p->prepared + L.prep_b;
+    }
+    a.Ip = (int)L.Ip; a.Gp = (int)L.Gp;
+  }
+}
+
+// wgnn_finish_norm(which): the reduction of `which`, and through elem_mask a read of the other tensors as they stand in g
+void fill_norm(const Layout& L, const wgnn_dims* d, const wgnn_grads* g, float* ws, int which, FinishArgs& a) {
+  fill_reduce(L, d, g, ws, which, a);
+  a.elem_mask = ((which & 4) ? 0u : 0xF0u) | ((which & 2) ? 0u : 0x0Fu);
+}
+
+// floats of `clip`: its header and one partial sum per block of the widest of the four wgnn_finish_norm launches; 0 if one
+// of them exceeds a launch's grid.  Geometry only: the pointers of the FinishArgs built here are never followed.
+size_t clip_floats(const Layout& L, const wgnn_dims* d) {
+  const wgnn_grads none = {};
+  float* const nowhere = reinterpret_cast<float*>((uintptr_t)WGNN_STATUS_BYTES);
+  int64_t most = 0;
+  for (int which = 0; which <= 6; which += 2) {
+    FinishArgs a = {};
+    fill_norm(L, d, &none, nowhere, which, a);
+    int64_t grid;
+    if (finish_grid(a, &grid) != WGNN_OK) return 0;
+    most = grid > most ? grid : most;
+  }
+  return rup((size_t)CLIP_HDR + (size_t)most, 64);
 }
 
 // Process-wide options (wgnn_set_option / wgnn_get_option).  Keys 0, 1, 2 and 5 choose between schedules with bit-identical
@@ -1080,26 +1122,55 @@ int wgnn_finish(const wgnn_dims* d, const wgnn_params* p, const wgnn_grads* g, i
     if (!complete(*p)) return WGNN_ERR_NULL;
     if (adam->step < 1) return WGNN_ERR_SHAPE;
     if (!complete(adam->exp_avg) || !complete(adam->exp_avg_sq)) return WGNN_ERR_NULL;
-    slots(*p, a.p);                                  // the optimiser updates the parameters in place
-    slots(adam->exp_avg, a.m);
-    slots(adam->exp_avg_sq, a.v);
-    a.adam = 1;
-    set_adam(a, adam);
+    fill_adam(L, p, adam, a);
     a.elem_mask = ((which & 4) ? 0u : 0xF0u) | ((which & 2) ? 0u : 0x0Fu);   // tensors whose gradient is final in g
     if (only == WGNN_FINISH_ADAM_GRU) a.elem_mask = 0xF0u;
     if (only == WGNN_FINISH_ADAM_CONV) a.elem_mask = 0x0Fu;
-    if (p->prepared && L.prep_kind) {
-      a.prep_kind = L.prep_kind;
-      if (L.prep_kind == 1) {
-        set_planes(a, L, p->prepared);
-      } else {
-        a.wp = (float*)p->prepared + L.prep_f;
-        a.wt = (float*)p->prepared + L.prep_b;
-      }
-      a.Ip = (int)L.Ip; a.Gp = (int)L.Gp;
-    }
   }
   return launch_finish(a, (hipStream_t)stream);
+}
+
+int wgnn_optim_version(void) { return WGNN_OPTIM_VERSION; }
+
+size_t wgnn_clip_bytes(const wgnn_dims* d) {
+  if (check_dims(d) != WGNN_OK) return 0;
+  return sizeof(float) * clip_floats(make_layout(d), d);
+}
+
+int wgnn_finish_norm(const wgnn_dims* d, const wgnn_grads* g, int which, float max_norm, void* clip, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  int rc = check_dims(d);
+  if (rc != WGNN_OK) return rc;
+  if ((which & ~6) != 0 || !(max_norm > 0.f)) return WGNN_ERR_SHAPE;   // (NaN fails the comparison)
+  if (!g || !clip || !workspace) return WGNN_ERR_NULL;
+  if (!complete(*g)) return WGNN_ERR_NULL;
+  const Layout L = make_layout(d);
+  if (workspace_bytes < sizeof(float) * L.bwd_floats) return WGNN_ERR_WORKSPACE;
+  FinishArgs a = {};
+  fill_norm(L, d, g, (float*)workspace, which, a);
+  a.clip = (float*)clip;
+  a.max_norm = max_norm;
+  // (an internal consistency check of this launch against wgnn_clip_bytes' own arithmetic -- both depend on dims alone -- NOT a
+  // check of the caller's buffer, whose real size the library cannot know: a clip shorter than wgnn_clip_bytes(d) is overrun)
+  int64_t grid;
+  if (finish_grid(a, &grid) != WGNN_OK || (size_t)CLIP_HDR + (size_t)grid > clip_floats(L, d)) return WGNN_ERR_SHAPE;
+  return launch_finish_norm(a, (hipStream_t)stream);
+}
+
+int wgnn_finish_clipped(const wgnn_dims* d, const wgnn_params* p, const wgnn_grads* g, const wgnn_adam* adam, const void* clip,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  int rc = check_dims(d);
+  if (rc != WGNN_OK) return rc;
+  if (!p || !g || !adam || !clip || !workspace) return WGNN_ERR_NULL;
+  if (!complete(*g) || !complete(*p) || !complete(adam->exp_avg) || !complete(adam->exp_avg_sq)) return WGNN_ERR_NULL;
+  if (adam->step < 1) return WGNN_ERR_SHAPE;
+  const Layout L = make_layout(d);
+  if (workspace_bytes < sizeof(float) * L.bwd_floats) return WGNN_ERR_WORKSPACE;
+  FinishArgs a = {};
+  fill_norm(L, d, g, (float*)workspace, 0, a);      // every tensor is read from g
+  fill_adam(L, p, adam, a);
+  a.clip = const_cast<float*>((const float*)clip);  // (read only: clip[1])
+  return launch_finish_clipped(a, (hipStream_t)stream);
 }
 
 int wgnn_finish_rows(const wgnn_dims* d, const wgnn_params* p, const wgnn_grads* g, int which, int row0, int rows,

@@ -339,8 +339,15 @@ struct FinishArgs {
   int np_g3, np_i;
   float *wp, *wt;
   int Ip, Gp, I;
+  // wgnn_finish_norm / wgnn_finish_clipped (include/windgnn_optim.h); unused by launch_finish
+  float* clip;                 // [0] total norm, [1] clip coefficient, from float CLIP_HDR on one partial sum of squares per block
+  float max_norm;
 };
 int launch_finish(FinishArgs a, hipStream_t st);
+constexpr int CLIP_HDR = 64;   // floats of clip ahead of the per-block partial sums (256 bytes)
+int finish_grid(FinishArgs& a, int64_t* grid);                        // fills in the block counts; WGNN_ERR_SHAPE past one launch's grid.x
+int launch_finish_norm(FinishArgs a, hipStream_t st);                  // reduce (+ squares per block), then the fp64 sum: 2 launches
+int launch_finish_clipped(FinishArgs a, hipStream_t st);               // Adam on g * clip[1] for the tensors in elem_mask
 // wgnn_finish_rows: Adam on rows [row0, row0 + rows) of one GRU pair (W [.][ncols] and its bias), the pointers already offset
 // to row row0; pf_hi != null (W_ih with fp16-plane images): the parts of both images those rows own (row0 a multiple of 8)
 struct RowsAdamArgs {

@@ -17,11 +17,15 @@ constexpr int FP = 16, PART = 2 * FP * FP + 2 * FP;   // GCN partial row: dW1 | 
 enum { T_C1W = 0, T_C1B, T_C2W, T_C2B, T_WIH, T_WHH, T_BIH, T_BHH };
 
 // IMG = false: the caller writes the prepared images itself (seg_tn's wide stores); *wout receives the new weight
-template <int ADAM, bool IMG = true>   // ADAM 1: Adam + prepared images after the reduction; 0: reduce only
+// CLIP (wgnn_finish_norm / wgnn_finish_clipped): 0 none; 1 the thread also sums the squares of the gradients it sees (into
+// *clip); 2 every gradient enters Adam times the clip coefficient *clip (g itself keeps the unclipped value)
+template <int ADAM, bool IMG = true, int CLIP = 0>   // ADAM 1: Adam + prepared images after the reduction; 0: reduce only
 __device__ __forceinline__ void emit(const FinishArgs& a, int t, int64_t idx, int row, int col, float gval, bool write_g,
-                                     bool& bad_g, bool& bad_w, float* wout = nullptr) {
+                                     bool& bad_g, bool& bad_w, float* wout = nullptr, float* clip = nullptr) {
   bad_g |= !(__builtin_fabsf(gval) <= 3.0e38f);                       // inf / NaN in a final gradient
   if (write_g) a.g[t][idx] = gval;
+  if (CLIP == 1) *clip = __fmaf_rn(gval, gval, *clip);
+  if (CLIP == 2) gval = __fmul_rn(gval, *clip);
   if (!ADAM) return;
   // torch.optim.Adam, single-tensor formulas in fp32, explicit roundings (the fused and the split launch agree bitwise)
   const float mi = __fmaf_rn(a.b1, a.m[t][idx], __fmul_rn(1.f - a.b1, gval));
@@ -54,9 +58,9 @@ __device__ __forceinline__ void emit(const FinishArgs& a, int t, int64_t idx, in
 }
 
 // ---- split-K partials in pgemm_tn_kernel's own layout [z][tile][wave][i][j][lane][4] (pgemm.hip)
-template <int ADAM>   // 1: Adam + prepared images after the reduction; 0: reduce only
+template <int ADAM, int CLIP = 0>   // 1: Adam + prepared images after the reduction; 0: reduce only
 __device__ __forceinline__ void seg_tn(const FinishArgs& a, const FinSeg& s, int tw, int tb, int blk, bool& bad_g,
-                                       bool& bad_w) {
+                                       bool& bad_w, float* clip = nullptr) {
   const size_t slab4 = (size_t)s.ntiles * TN_WAVES * 5 * s.T * 64;
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;            // 64 quads x 4 z phases per block
   f32x4 v;
@@ -158,15 +162,15 @@ __device__ __forceinline__ void seg_tn(const FinishArgs& a, const FinSeg& s, int
       else if (m >= s.rows1) continue;
     }
     if (m >= s.Mout) continue;
-    if (n < s.ncols) emit<ADAM>(a, tw, (int64_t)m * s.ncols + n, m, n, v[r], true, bad_g, bad_w);
-    else if (n == s.Nout - 1) emit<ADAM>(a, tb, m, m, 0, v[r], true, bad_g, bad_w);
+    if (n < s.ncols) emit<ADAM, true, CLIP>(a, tw, (int64_t)m * s.ncols + n, m, n, v[r], true, bad_g, bad_w, nullptr, clip);
+    else if (n == s.Nout - 1) emit<ADAM, true, CLIP>(a, tb, m, m, 0, v[r], true, bad_g, bad_w, nullptr, clip);
   }
 }
 
 // ---- split-K partials as plain [z][Mout][Nout] (gemm.hip, gemm32.hip)
-template <int ADAM>   // 1: Adam + prepared images after the reduction; 0: reduce only
+template <int ADAM, int CLIP = 0>   // 1: Adam + prepared images after the reduction; 0: reduce only
 __device__ __forceinline__ void seg_plain(const FinishArgs& a, const FinSeg& s, int tw, int tb, int blk, bool& bad_g,
-                                          bool& bad_w) {
+                                          bool& bad_w, float* clip = nullptr) {
   const size_t MN = (size_t)s.Mgemm * s.pitch;                       // Mgemm: rows of the GEMM that wrote the partials
   const size_t i = (size_t)blk * 256 + threadIdx.x;
   if (i >= MN) return;
@@ -193,13 +197,13 @@ __device__ __forceinline__ void seg_plain(const FinishArgs& a, const FinSeg& s, 
     else if (m >= s.rows1) return;
   }
   if (m >= s.Mout) return;
-  if (n < s.ncols) emit<ADAM>(a, tw, (int64_t)m * s.ncols + n, m, n, v, true, bad_g, bad_w);
-  else if (n == s.Nout - 1) emit<ADAM>(a, tb, m, m, 0, v, true, bad_g, bad_w);
+  if (n < s.ncols) emit<ADAM, true, CLIP>(a, tw, (int64_t)m * s.ncols + n, m, n, v, true, bad_g, bad_w, nullptr, clip);
+  else if (n == s.Nout - 1) emit<ADAM, true, CLIP>(a, tb, m, m, 0, v, true, bad_g, bad_w, nullptr, clip);
 }
 
 // ---- per-workgroup partial rows of the GCN backward, [rows][PART]: 32 columns x 8 row groups per block
-template <int ADAM>   // 1: Adam + prepared images after the reduction; 0: reduce only
-__device__ __forceinline__ void seg_conv(const FinishArgs& a, int blk, bool& bad_g, bool& bad_w) {
+template <int ADAM, int CLIP = 0>   // 1: Adam + prepared images after the reduction; 0: reduce only
+__device__ __forceinline__ void seg_conv(const FinishArgs& a, int blk, bool& bad_g, bool& bad_w, float* clip = nullptr) {
   __shared__ float sm[8][33];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const int i = blk * 32 + tx;
@@ -223,22 +227,22 @@ __device__ __forceinline__ void seg_conv(const FinishArgs& a, int blk, bool& bad
   constexpr int F = 13;
   if (i < FP * FP) {
     const int r = i / FP, c = i % FP;
-    if (r < F && c < F) emit<ADAM>(a, T_C1W, r * F + c, r, c, s, true, bad_g, bad_w);
+    if (r < F && c < F) emit<ADAM, true, CLIP>(a, T_C1W, r * F + c, r, c, s, true, bad_g, bad_w, nullptr, clip);
   } else if (i < 2 * FP * FP) {
     const int j = i - FP * FP, r = j / FP, c = j % FP;
-    if (r < F && c < F) emit<ADAM>(a, T_C2W, r * F + c, r, c, s, true, bad_g, bad_w);
+    if (r < F && c < F) emit<ADAM, true, CLIP>(a, T_C2W, r * F + c, r, c, s, true, bad_g, bad_w, nullptr, clip);
   } else if (i < 2 * FP * FP + FP) {
     const int c = i - 2 * FP * FP;
-    if (c < F) emit<ADAM>(a, T_C1B, c, c, 0, s, true, bad_g, bad_w);
+    if (c < F) emit<ADAM, true, CLIP>(a, T_C1B, c, c, 0, s, true, bad_g, bad_w, nullptr, clip);
   } else {
     const int c = i - 2 * FP * FP - FP;
-    if (c < F) emit<ADAM>(a, T_C2B, c, c, 0, s, true, bad_g, bad_w);
+    if (c < F) emit<ADAM, true, CLIP>(a, T_C2B, c, c, 0, s, true, bad_g, bad_w, nullptr, clip);
   }
 }
 
 // ---- tensors whose gradient is already final in g (after an all-reduce, or written directly by their kernel)
-template <int ADAM>   // 1: Adam + prepared images after the reduction; 0: reduce only
-__device__ __forceinline__ void seg_elem(const FinishArgs& a, int blk, bool& bad_g, bool& bad_w) {
+template <int ADAM, int CLIP = 0>   // 1: Adam + prepared images after the reduction; 0: reduce only
+__device__ __forceinline__ void seg_elem(const FinishArgs& a, int blk, bool& bad_g, bool& bad_w, float* clip = nullptr) {
   // 64-bit: the masked tensors TOGETHER may exceed 2^31 elements (configs[4]: W_ih 1.96e9 + W_hh 0.45e9)
   int64_t e = (int64_t)blk * 256 + threadIdx.x;
 #pragma unroll
@@ -246,7 +250,7 @@ __device__ __forceinline__ void seg_elem(const FinishArgs& a, int blk, bool& bad
     if (!((a.elem_mask >> t) & 1)) continue;
     if (e < (int64_t)a.n[t]) {
       const int ncols = t == T_WIH ? a.I : 1;
-      emit<ADAM>(a, t, e, (int)(e / ncols), (int)(e % ncols), a.g[t][e], false, bad_g, bad_w);
+      emit<ADAM, true, CLIP>(a, t, e, (int)(e / ncols), (int)(e % ncols), a.g[t][e], false, bad_g, bad_w, nullptr, clip);
       return;
     }
     e -= a.n[t];
@@ -268,6 +272,69 @@ __global__ void __launch_bounds__(256) finish_kernel(const FinishArgs a) {
   } else {
     seg_elem<ADAM>(a, blk - a.conv_blocks, bad_g, bad_w);
   }
+  report_status(a.status, bad_g, WGNN_STATUS_GRAD_NONFINITE);
+  report_status(a.status, bad_w, WGNN_STATUS_WEIGHT_RANGE);
+}
+
+// ---- wgnn_finish_norm / wgnn_finish_clipped (include/windgnn_optim.h): clipping by the global L2 norm around the same segments.
+// finish_norm_kernel is finish_kernel<0> -- the same grid, the same segments, the same values stored to g -- in which every
+// thread also sums the squares of the gradients it writes (and, for the tensors of elem_mask, of those it reads from g), and
+// every block leaves ONE fp32 sum in clip[CLIP_HDR + blockIdx.x].  The segments' early returns leave seg_*, not the kernel:
+// all 256 threads reach the block's reduction, the idle ones with 0.  Fixed order everywhere (xor butterfly inside the wave:
+// fp32 addition commutes, so all lanes hold the same bits; then the 4 waves in index order): no atomics, bitwise reproducible.
+__global__ void __launch_bounds__(256) finish_norm_kernel(const FinishArgs a) {
+  int blk = blockIdx.x;
+  bool bad_g = false, bad_w = false;
+  float sq = 0.f;
+  if (blk < a.ih.nblocks) {
+    if (a.ih.kind == 2) seg_tn<0, 1>(a, a.ih, T_WIH, T_BIH, blk, bad_g, bad_w, &sq);
+    else seg_plain<0, 1>(a, a.ih, T_WIH, T_BIH, blk, bad_g, bad_w, &sq);
+  } else if ((blk -= a.ih.nblocks) < a.hh.nblocks) {
+    if (a.hh.kind == 2) seg_tn<0, 1>(a, a.hh, T_WHH, T_BHH, blk, bad_g, bad_w, &sq);
+    else seg_plain<0, 1>(a, a.hh, T_WHH, T_BHH, blk, bad_g, bad_w, &sq);
+  } else if ((blk -= a.hh.nblocks) < a.conv_blocks) {
+    seg_conv<0, 1>(a, blk, bad_g, bad_w, &sq);
+  } else {
+    seg_elem<0, 1>(a, blk - a.conv_blocks, bad_g, bad_w, &sq);
+  }
+  report_status(a.status, bad_g, WGNN_STATUS_GRAD_NONFINITE);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) sq += __shfl_xor(sq, o, 64);
+  __shared__ float wsum[4];
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = sq;
+  __syncthreads();
+  if (threadIdx.x == 0) a.clip[CLIP_HDR + blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// The sum over blocks in fp64, one workgroup: thread t adds partials t, t + 1024, .. in order, then a fixed tree over the
+// 1024 threads.  total = sqrt(sum), coef = min(1, max_norm / (total + 1e-6)) evaluated as torch.nn.utils.clip_grad_norm_ does
+// (fp32; a NaN total gives a NaN coef: torch.clamp passes NaN through).  Also fills the rest of clip's header.
+__global__ void __launch_bounds__(1024) clip_coef_kernel(float* clip, int nblocks, float max_norm, unsigned* status) {
+  __shared__ double red[1024];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nblocks; i += 1024) s += (double)clip[CLIP_HDR + i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 512; w >= 1; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x >= CLIP_HDR) return;
+  float out = 0.f;
+  if (threadIdx.x < 2) {
+    const float total = (float)sqrt(red[0]);
+    const float c = __fdiv_rn(max_norm, __fadd_rn(total, 1e-6f));
+    out = threadIdx.x == 0 ? total : (c > 1.f ? 1.f : c);              // (NaN > 1 is false: NaN stays)
+    if (threadIdx.x == 0) report_status(status, !(total <= 3.0e38f), WGNN_STATUS_GRAD_NONFINITE);
+  }
+  clip[threadIdx.x] = out;
+}
+
+// wgnn_finish(0, adam) on g * clip[1]: the tensors of elem_mask, read from g
+__global__ void __launch_bounds__(256) finish_clipped_kernel(const FinishArgs a) {
+  bool bad_g = false, bad_w = false;
+  float coef = a.clip[1];
+  seg_elem<1, 2>(a, blockIdx.x, bad_g, bad_w, &coef);
   report_status(a.status, bad_g, WGNN_STATUS_GRAD_NONFINITE);
   report_status(a.status, bad_w, WGNN_STATUS_WEIGHT_RANGE);
 }
@@ -410,7 +477,7 @@ int finish_seg_blocks(const FinSeg& s) {
 }
 
 // a.ih / a.hh with kind 0 and conv_partial == nullptr are skipped; elem_mask names the tensors read from g.
-int launch_finish(FinishArgs a, hipStream_t st) {
+int finish_grid(FinishArgs& a, int64_t* grid) {
   a.ih.nblocks = finish_seg_blocks(a.ih);
   a.hh.nblocks = finish_seg_blocks(a.hh);
   a.conv_blocks = a.conv_partial ? cdiv_i(PART, 32) : 0;
@@ -418,15 +485,52 @@ int launch_finish(FinishArgs a, hipStream_t st) {
   for (int t = 0; t < 8; ++t)
     if ((a.elem_mask >> t) & 1) ne += a.n[t];
   const int64_t eb = (ne + 255) / 256;
-  const int64_t grid64 = (int64_t)a.ih.nblocks + a.hh.nblocks + a.conv_blocks + eb;
-  if (grid64 > 0x7fffffffll) return WGNN_ERR_SHAPE;                   // one launch's grid.x
+  *grid = (int64_t)a.ih.nblocks + a.hh.nblocks + a.conv_blocks + eb;
+  if (*grid > 0x7fffffffll) return WGNN_ERR_SHAPE;                    // one launch's grid.x
   a.elem_blocks = (int)eb;
-  const int grid = (int)grid64;
-  if (grid < 1) return WGNN_OK;
+  return WGNN_OK;
+}
+
+static double finish_reduce_bytes(const FinishArgs& a) {
   double by = 0.0;
   if (a.ih.kind) by += 4.0 * a.ih.splitk * a.ih.Mout * (double)a.ih.Nout;
   if (a.hh.kind) by += 4.0 * a.hh.splitk * a.hh.Mout * (double)a.hh.Nout;
   if (a.conv_partial) by += 4.0 * a.conv_rows * PART;
+  return by;
+}
+
+int launch_finish_norm(FinishArgs a, hipStream_t st) {
+  int64_t grid64;
+  if (finish_grid(a, &grid64) != WGNN_OK || grid64 < 1) return WGNN_ERR_SHAPE;
+  const int grid = (int)grid64;
+  double np = 0.0;
+  for (int t = 0; t < 8; ++t) np += a.n[t];
+  PROF_LAUNCH("finish_norm_kernel", 3.0 * np, finish_reduce_bytes(a) + 4.0 * np + 4.0 * grid, st,
+              hipLaunchKernelGGL(finish_norm_kernel, dim3(grid), dim3(256), 0, st, a));
+  WGNN_CHECK_LAUNCH();
+  PROF_LAUNCH("clip_coef_kernel", (double)grid, 4.0 * grid, st,
+              hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(1024), 0, st, a.clip, grid, a.max_norm, a.status));
+  WGNN_CHECK_LAUNCH();
+  return WGNN_OK;
+}
+
+int launch_finish_clipped(FinishArgs a, hipStream_t st) {
+  int64_t grid64;
+  if (finish_grid(a, &grid64) != WGNN_OK || grid64 < 1) return WGNN_ERR_SHAPE;
+  double np = 0.0;
+  for (int t = 0; t < 8; ++t) np += a.n[t];
+  PROF_LAUNCH("finish_clipped_kernel", 13.0 * np, (28.0 + (a.prep_kind ? 8.0 : 0.0)) * np, st,
+              hipLaunchKernelGGL(finish_clipped_kernel, dim3((int)grid64), dim3(256), 0, st, a));
+  WGNN_CHECK_LAUNCH();
+  return WGNN_OK;
+}
+
+int launch_finish(FinishArgs a, hipStream_t st) {
+  int64_t grid64;
+  if (finish_grid(a, &grid64) != WGNN_OK) return WGNN_ERR_SHAPE;
+  const int grid = (int)grid64;
+  if (grid < 1) return WGNN_OK;
+  double by = finish_reduce_bytes(a);
   double np = 0.0;
   for (int t = 0; t < 8; ++t) np += a.n[t];
   by += (a.adam ? 28.0 + (a.prep_kind ? 8.0 : 0.0) : 4.0) * np;

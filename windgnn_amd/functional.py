@@ -303,6 +303,66 @@ def finish_step(d, params, grads, which: int, adam=None, prepared=None, device=N
     _lib.check(rc, "wgnn_finish(%d%s)" % (which, ", adam" if adam is not None else ""))
 
 
+_CLIP_BYTES = {}           # wgnn_clip_bytes per dims (it depends on nothing else): one library call per shape, not per step
+
+
+def clip_bytes(d) -> int:
+    """wgnn_clip_bytes(d): bytes of the `clip` buffer of finish_norm / finish_clipped; 0 = dims the library refuses."""
+    key = bytes(d)
+    if key not in _CLIP_BYTES:
+        _CLIP_BYTES[key] = int(_lib.load().wgnn_clip_bytes(C.byref(d)))
+    return _CLIP_BYTES[key]
+
+
+def clip_buffer(d, device) -> torch.Tensor:
+    """A fresh `clip` buffer (fp32, clip_bytes(d) bytes) for finish_norm / finish_clipped: [_lib.CLIP_TOTAL] the gradient's
+    L2 norm, [_lib.CLIP_COEF] the clip coefficient, the rest private to the library."""
+    nbytes = clip_bytes(d)
+    if nbytes == 0:
+        _lib.check(-2, "wgnn_clip_bytes")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+
+
+def _clip_ptr(d, clip):
+    _require_gpu(clip)
+    _require_contiguous(clip=clip)
+    _require_scratch_aligned(clip=clip)
+    need = clip_bytes(d)
+    if need == 0 or clip.numel() * 4 < need:
+        raise RuntimeError("windgnn_amd: clip holds %d bytes, wgnn_clip_bytes says %d (0 = dims the library refuses)"
+                           % (clip.numel() * 4, need))
+    return _ptr(clip)
+
+
+def finish_norm(d, grads, which: int, max_norm: float, clip, device=None) -> None:
+    """wgnn_finish_norm: reduce the deferred partial sums named by `which` (0, 2, 4 or 6) into `grads` exactly as
+    finish_step(d, .., which) does, and leave the L2 norm of all 8 gradients in clip[_lib.CLIP_TOTAL] and
+    min(1, max_norm / (norm + 1e-6)) in clip[_lib.CLIP_COEF] (torch.nn.utils.clip_grad_norm_'s coefficient) -- on the device,
+    deterministic, no host synchronisation.  max_norm > 0; float("inf") only measures.  clip: clip_buffer(d, device)."""
+    lib = _lib.load()
+    cp = _clip_ptr(d, clip)
+    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
+    ws = _Workspace.get(device if device is not None else grads[0].device, ws_bytes)
+    gs = _params_struct(_lib.Grads, grads)
+    rc = lib.wgnn_finish_norm(C.byref(d), C.byref(gs), which, float(max_norm), cp, _ptr(ws), ws_bytes, _stream())
+    _lib.check(rc, "wgnn_finish_norm(%d, max_norm=%r)" % (which, max_norm))
+
+
+def finish_clipped(d, params, grads, adam, clip, prepared=None, device=None) -> None:
+    """wgnn_finish_clipped: finish_step(d, params, grads, 0, adam, prepared) with every gradient element entering Adam times
+    clip[_lib.CLIP_COEF], as the preceding finish_norm left it -- one launch.  `grads` is NOT rewritten (torch's
+    clip_grad_norm_ scales .grad in place; here it keeps the unclipped gradient, and clip holds the norm and the factor)."""
+    lib = _lib.load()
+    cp = _clip_ptr(d, clip)
+    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
+    ws = _Workspace.get(device if device is not None else grads[0].device, ws_bytes)
+    ps = _params_struct(_lib.Params, params, prepared)
+    gs = _params_struct(_lib.Grads, grads)
+    ad = _adam_struct(adam)
+    rc = lib.wgnn_finish_clipped(C.byref(d), C.byref(ps), C.byref(gs), C.byref(ad), cp, _ptr(ws), ws_bytes, _stream())
+    _lib.check(rc, "wgnn_finish_clipped")
+
+
 def rows_align(d) -> int:
     """wgnn_bwd_rows_align: the row alignment of a range of wgnn_bwd_rows / wgnn_finish_rows; 0 = not offered for this shape."""
     return int(_lib.load().wgnn_bwd_rows_align(C.byref(d)))

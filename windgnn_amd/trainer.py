@@ -30,15 +30,23 @@ blocked step is the one-bucket step bit for bit.
 A step that RAISES (a refused launch, a failed collective) leaves the optimiser state undefined: `steps` counts completed
 steps only, but in the two-collective form the GRU tensors and their moments may already have been stepped when a later
 launch of the same step fails, and a retry would then apply the same bias-correction step number to them twice.  Do not
-retry a failed step on the same TrainStep: rebuild it from a checkpoint of the parameters (state_dict) instead."""
+retry a failed step on the same TrainStep: rebuild it from a checkpoint of the parameters (state_dict) instead.
+
+Clipping (`max_grad_norm`, opt-in): where the reference loop would call torch.nn.utils.clip_grad_norm_ between loss.backward()
+and optimizer.step(), the optimiser's wgnn_finish becomes wgnn_finish_norm + wgnn_finish_clipped (include/windgnn_optim.h): the
+global L2 norm of the 8 gradients and min(1, max_grad_norm / (norm + 1e-6)) are formed on the device, and Adam reads
+g * coefficient.  One rank: the norm is taken in the launch that reduces the deferred partial sums.  Data parallel: after the
+all-reduce, over the summed bucket -- which is the same on every rank, and the norm's summation order is fixed, so every rank
+derives the same coefficient without another collective.  The bucket keeps the UNCLIPPED gradient (torch clips .grad in place);
+`grad_norm` and `clip_coef` are views of the device values, overwritten by the next step like the loss."""
 from __future__ import annotations
 
 import torch
 
 from . import _lib
 from .distributed import HEADER, LOSS_SLOT, BucketExchange, grad_block_plan
-from .functional import (_forward_setup, bwd_rows, check_range_status, finish_rows, finish_step,
-                         gcn_gru_backward_mse_raw, gcn_gru_forward_raw, gcn_gru_state_backward_raw,
+from .functional import (_forward_setup, bwd_rows, check_range_status, clip_buffer, clip_bytes, finish_clipped, finish_norm,
+                         finish_rows, finish_step, gcn_gru_backward_mse_raw, gcn_gru_forward_raw, gcn_gru_state_backward_raw,
                          gcn_gru_state_forward_raw, mse_loss_grad, prepared_weights, refresh_prepared, rows_align)
 from .modules import GCN_GRU
 
@@ -49,7 +57,7 @@ AUTO_BLOCK_BYTES = 64 << 20         # ... from a gradient bucket of this size (s
 class TrainStep:
     def __init__(self, model: GCN_GRU, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  process_group=None, check_every: int = 100, overlap_collectives: bool = False, direct_rccl=None,
-                 rccl_loader=None, carry_state: bool = False, grad_blocks=None):
+                 rccl_loader=None, carry_state: bool = False, grad_blocks=None, max_grad_norm=None):
         """carry_state: truncated BPTT over consecutive chunks -- each step starts the recurrence from the h_n of the previous
         step (detached; zeros on the first step and after reset_state()), so a model trained on chunks of a long series
         learns the carried-state regime StreamingForecaster(window=None) serves.  The batch size must stay the same
@@ -60,7 +68,12 @@ class TrainStep:
         (distributed.grad_block_plan), each block's all-reduce started as soon as its weight-gradient GEMM is done (module
         docstring); "auto" = k = AUTO_GRAD_BLOCKS when the bucket reaches
         AUTO_BLOCK_BYTES and the shape has the row-range entry points, else None.  Not with carry_state,
-        overlap_collectives or direct_rccl."""
+        overlap_collectives or direct_rccl.
+
+        max_grad_norm: None = no clipping (the schedules above, launch for launch); a value > 0 = clip the step's gradient
+        by its global L2 norm as torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) would before the optimiser step
+        (module docstring); float("inf") = measure only (`grad_norm`), nothing is scaled.  Not with overlap_collectives or
+        the blocked exchange, which step tensors before the whole bucket has arrived."""
         if not getattr(model, "fused", True):
             raise RuntimeError("windgnn_amd: TrainStep drives the fused hot path, i.e. the reference model's own widths "
                                "(input_dim = hidden_dim = 13, src/main.py:41); a GCN_GRU of other widths trains through "
@@ -77,6 +90,20 @@ class TrainStep:
         # an explicitly passed group runs the collective path even with one rank (the all-reduces execute)
         self.collective = self.world > 1 or process_group is not None
         self.plan = self._grad_block_plan(grad_blocks, sizes, carry_state, overlap_collectives, direct_rccl)
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0.0:                   # (NaN fails the comparison)
+                raise ValueError("windgnn_amd: max_grad_norm must be > 0 (float('inf') = measure only) or None, got %r"
+                                 % (max_grad_norm,))
+            if overlap_collectives or self.plan is not None:
+                raise RuntimeError("windgnn_amd: TrainStep(max_grad_norm=%r) with %s: that schedule steps %s before the "
+                                   "whole gradient bucket has arrived, and the global norm needs all of it; clipping runs "
+                                   "with the one-bucket schedules only"
+                                   % (max_grad_norm, "overlap_collectives=True" if overlap_collectives
+                                      else "grad_blocks=%r" % (grad_blocks,),
+                                      "the GRU tensors" if overlap_collectives else "row blocks"))
+        self.max_grad_norm = max_grad_norm
+        self._clip = None               # wgnn_finish_norm's buffer: sized at the first clipped step (wgnn_clip_bytes needs its dims)
         # gradient bucket with a 4-float header (16-byte aligned bucket): header[3] = the step's loss, so that the loss
         # rides in the conv-gradient all-reduce (the conv gradients are the first 364 floats of the bucket).  The blocked
         # exchange lays it out as its plan says: [header | conv | b_ih | b_hh | w_ih | w_hh]
@@ -170,6 +197,36 @@ class TrainStep:
         return dict(exp_avg=self.m_views, exp_avg_sq=self.v_views, step=self.steps + 1, lr=self.lr, beta1=self.betas[0],
                     beta2=self.betas[1], eps=self.eps)
 
+    def _tail(self, d, which, pre):
+        """The optimiser's end of a step: reduce the deferred partial sums `which` (0: the bucket is final) and step Adam --
+        ONE wgnn_finish, or with max_grad_norm wgnn_finish_norm (the same reduction + the norm) and wgnn_finish_clipped."""
+        if self.max_grad_norm is None:
+            finish_step(d, self.p_views, self.g_views, which, self._adam(), pre, self.device)
+            return
+        if self._clip is None or self._clip.numel() * 4 < clip_bytes(d):
+            self._clip = clip_buffer(d, self.device)
+        finish_norm(d, self.g_views, which, self.max_grad_norm, self._clip, self.device)
+        finish_clipped(d, self.p_views, self.g_views, self._adam(), self._clip, pre, self.device)
+
+    def _clip_word(self, slot, name):
+        if self._clip is None:
+            raise RuntimeError("windgnn_amd: TrainStep.%s is written by a step with max_grad_norm set (float('inf') measures "
+                               "without clipping); %s" % (name, "no such step has run yet" if self.max_grad_norm is not None
+                                                          else "this TrainStep has max_grad_norm=None"))
+        return self._clip[slot]
+
+    @property
+    def grad_norm(self):
+        """The L2 norm of the last step's (summed, unclipped) gradient: a 0-dim VIEW of the device value, overwritten by the
+        next step -- float() or .clone() it to keep it, as with the returned loss."""
+        return self._clip_word(_lib.CLIP_TOTAL, "grad_norm")
+
+    @property
+    def clip_coef(self):
+        """min(1, max_grad_norm / (grad_norm + 1e-6)) of the last step, the factor its gradient entered Adam with: a 0-dim
+        VIEW, overwritten by the next step."""
+        return self._clip_word(_lib.CLIP_COEF, "clip_coef")
+
     def _empty_shard_step(self, A, X, n_global):
         """This rank has no windows in this step: zero bucket, the same collectives as every other rank, the optimiser's
         launch(es) on the summed gradient.  Returns (big-batch mean loss, empty Y)."""
@@ -187,7 +244,7 @@ class TrainStep:
             self._blocked_adam(d, works, self.exchange.start_tail(self.plan, gs), pre)
         elif not self.overlap_collectives:
             self.exchange.all_reduce_all(gs)
-            finish_step(d, self.p_views, self.g_views, 0, self._adam(), pre, self.device)
+            self._tail(d, 0, pre)
         else:
             work = self.exchange.start_gru()
             wconv = self.exchange.start_conv(gs)
@@ -295,7 +352,7 @@ class TrainStep:
                 bwd(part)
             finish_step(d, self.p_views, self.g_views, 6, device=self.device)
             self.exchange.all_reduce_all(gs)
-            finish_step(d, self.p_views, self.g_views, 0, self._adam(), pre, self.device)
+            self._tail(d, 0, pre)
         elif self.collective:
             bwd(1 | 4)
             finish_step(d, self.p_views, self.g_views, 4, device=self.device)
@@ -311,7 +368,7 @@ class TrainStep:
         else:
             for part in (1, 2, 4):
                 bwd(part)
-            finish_step(d, self.p_views, self.g_views, 6, self._adam(), pre, self.device)
+            self._tail(d, 6, pre)
         self._hcur, self._has_state = 1 - self._hcur, True     # h_n of this step is the next step's h0
         return loss, Y
 
@@ -341,7 +398,7 @@ class TrainStep:
                                          prepared=pre)
             finish_step(d, self.p_views, self.g_views, 6, device=self.device)
             self.exchange.all_reduce_all(gs)    # loss: sum of the weighted shard means = the big-batch mean
-            finish_step(d, self.p_views, self.g_views, 0, self._adam(), pre, self.device)      # src/main.py:80
+            self._tail(d, 0, pre)                                                              # src/main.py:80
         elif self.collective:
             # Overlap: the GRU gradients (99.8 % of the bucket) are final after parts 1|4 of the backward, so
             # their all-reduce runs on RCCL's stream while part 2 (dg GEMM + GCN backward, ~30 % of the
@@ -371,7 +428,7 @@ class TrainStep:
             for part in (1 | 8, 2, 4):     # (the order 1, 4, 2 measured the same, 672-680 us either way: round 3)
                 gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, loss, 1.0, part=part | DEFER,
                                          prepared=pre)
-            finish_step(d, self.p_views, self.g_views, 6, self._adam(), pre, self.device)              # :79 tail + :80
+            self._tail(d, 6, pre)                                                                      # :79 tail + :80
         self.steps += 1                         # only a step whose launches were all accepted counts
         if self.check_every and self.steps % self.check_every == 0 and (
                 self.model.math != _lib.MATH_F32 or (self.exchange is not None and self.exchange.direct is not None)):
