@@ -178,7 +178,7 @@ typedef struct wgnn_adam {
 int wgnn_version(void);
 const char* wgnn_strerror(int status);
 
-/* Process-wide options: which of two kernel schedules runs.  Keys 0, 1, 2 and 5 do not change a result bit; key 4 changes the
+/* Process-wide options: which of two kernel schedules runs.  Keys 0, 1, 2, 5 and 6 do not change a result bit; key 4 changes the
  * summation order of some products.  Key 3 (a chunked backward part 2, measured slower) is retired: it is an unknown key now.
  * There is no reference counterpart (the reference has no kernels to choose between).  wgnn_set_option returns the PREVIOUS
  * value (>= 0) or WGNN_ERR_SHAPE for an unknown key / value; it takes effect for calls issued after it returns and is atomic,
@@ -201,7 +201,12 @@ const char* wgnn_strerror(int status);
  * into the other's K loop (v <= 33); 34 the persistent form of the
  * 8-wave kernel (cross-tile prefetch, counted waits).  Same products, same summation order per element: results are bit-identical. */
 #define WGNN_OPT_GEMM32_FORM 5
-#define WGNN_OPT_COUNT 6
+/* The two GRU weight-gradient products of the fp16-plane modes (register-resident recurrence, H <= 127): 1 (default) ONE
+ * launch in which every workgroup runs one work item of dW_ih and then one of dW_hh; 0 one launch per product.  A schedule
+ * choice like WGNN_OPT_FUSED_FWD: both forms run the same tiles over the same K chunks into the same partial sums (the
+ * split-K factors belong to the workspace layout, not to this option), so the results are bit-identical. */
+#define WGNN_OPT_TN_MERGED 6
+#define WGNN_OPT_COUNT 7
 int wgnn_set_option(int key, int value);
 int wgnn_get_option(int key);
 

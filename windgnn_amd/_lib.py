@@ -22,6 +22,7 @@ STEP_MAX_B = 256            # wgnn_fwd_state: T == 1 calls up to this batch (den
 STATUS_BYTES = 256          # WGNN_STATUS_BYTES: status block at the start of every workspace
 OPT_FUSED_FWD = 0           # WGNN_OPT_FUSED_FWD (wgnn_set_option): 0 never / 1 stash-less forwards / 2 every supported forward
 OPT_GG_ROLE_SPLIT, OPT_GG_GEMM_PRIO, OPT_BIG_GEMM, OPT_GEMM32_FORM = 1, 2, 4, 5   # measurement aids (include/windgnn.h; key 3 is retired)
+OPT_TN_MERGED = 6           # WGNN_OPT_TN_MERGED: 1 (default) one launch for both GRU weight-gradient GEMMs / 0 one each; same bits
 
 
 class Dims(C.Structure):
@@ -132,6 +133,15 @@ EXPORTS_OPTIM = {
                                       C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
+# include/windgnn_sched.h: host-only schedule queries (a third header and table, as above)
+class TnSplitInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("sk_ih", "sk_hh", "kchunk_ih", "kchunk_hh", "merged", "workgroups")]
+
+
+EXPORTS_SCHED = {
+    "wgnn_tn_split": (C.c_int, [C.POINTER(Dims), C.c_int, C.POINTER(TnSplitInfo)]),
+}
+
 _lib = None
 
 
@@ -155,6 +165,13 @@ def load() -> C.CDLL:
         raise RuntimeError("windgnn_amd: %s predates include/windgnn_optim.h (no wgnn_optim_version): rebuild it with "
                            "`python -m windgnn_amd.build --force`" % LIB_PATH)
     for name, (res, args) in EXPORTS_OPTIM.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    for name, (res, args) in EXPORTS_SCHED.items():
+        if not hasattr(lib, name):
+            raise RuntimeError("windgnn_amd: %s predates include/windgnn_sched.h (no %s): rebuild it with "
+                               "`python -m windgnn_amd.build --force`" % (LIB_PATH, name))
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -184,6 +201,13 @@ def get_option(key: int) -> int:
     if v < 0:
         check(v, "wgnn_get_option(%d)" % key)
     return v
+
+
+def tn_split(dims: Dims, state: bool = False) -> TnSplitInfo:
+    """wgnn_tn_split: the split-K factors of the two GRU weight-gradient GEMMs for `dims`."""
+    info = TnSplitInfo()
+    check(load().wgnn_tn_split(C.byref(dims), 1 if state else 0, C.byref(info)), "wgnn_tn_split")
+    return info
 
 
 def profile_enable(on: bool) -> None:

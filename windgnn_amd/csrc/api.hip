@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "../../include/windgnn_optim.h"
+#include "../../include/windgnn_sched.h"
 
 namespace {
 
@@ -27,6 +28,7 @@ struct Layout {
   size_t prep_f, prep_b, prep_floats;
   int prep_kind;                                 // 0 none, 1 fp16 planes, 2 padded fp32
   int sk_ih, sk_hh;
+  bool tn_merge;                                 // both products are pgemm_tn_kernel tiles: one launch can run them (pgemm_tn2_kernel)
   // which kernels run: the fp16-plane family needs the dense LDS-resident GCN and the register-resident GRU;
   // shapes beyond the fast kernels (CSR adjacency, wide hidden state) use general.hip in exact fp32
   bool x3, gen_gcn, gen_gru, g32, g32tn;
@@ -167,9 +169,16 @@ Layout make_layout(const wgnn_dims* d, bool state = false) {
   // GEMM rows of the dW_hh product: [dGI_r | dGI_z | pad to msplit | dGHn]
   L.m_hh = L.dghn ? (x3 ? L.msplit + L.hn : L.msplit + (int)L.H) : (int)L.G3;
   if (x3) {
-    L.sk_ih = pick_splitk(L.BT, pgemm_tn_tiles((int)L.G3, (int)L.I + 1), 256, 64);   // one workgroup per CU
+    // one workgroup per CU (256: MI355X) and product.  Register-resident recurrence: both products are pgemm_tn_kernel tiles
+    // and share one launch (bwd_weights, WGNN_OPT_TN_MERGED) in which a workgroup runs one work item of each.  The splits are
+    // a function of the dims alone -- not of the launch form, not of the device: the K chunks are the units finish sums in
+    // a fixed order, so a moved chunk boundary regroups fp32 sums and a training run no longer repeats bit for bit
+    // (profiles/tn_merged_ab.txt section B).
+    L.sk_ih = pick_splitk(L.BT, pgemm_tn_tiles((int)L.G3, (int)L.I + 1), 256, 64);
     L.sk_hh = pick_splitk(L.BT, pgemm_tn_tiles(L.m_hh, (int)L.H + 1), 256, 64);
+    L.tn_merge = L.dghn;
   } else {
+    L.tn_merge = false;
     // K chunks of at least 128 rows (B*T = 6144 at BASELINE configs[1]: with 256-row chunks the dW_hh product had 72 workgroups)
     L.sk_ih = L.g32tn ? pick_splitk(L.BT, gemm32_tn_tiles((int)L.G3, (int)L.I + 1), 256, 64)   // one workgroup per CU
                     : pick_splitk(L.BT, gemm_f32_tiles((int)L.G3, (int)L.I + 1), 1024, 128);
@@ -332,7 +341,7 @@ size_t clip_floats(const Layout& L, const wgnn_dims* d) {
   return rup((size_t)CLIP_HDR + (size_t)most, 64);
 }
 
-// Process-wide options (wgnn_set_option / wgnn_get_option).  Keys 0, 1, 2 and 5 choose between schedules with bit-identical
+// Process-wide options (wgnn_set_option / wgnn_get_option).  Keys 0, 1, 2, 5 and 6 choose between schedules with bit-identical
 // results; key 4 (WGNN_OPT_BIG_GEMM) changes the summation order of the large NT plane products.  Key 3 is retired.
 //
 // WGNN_OPT_FUSED_FWD: which forwards run the fused GCN + projection kernel (gcngi.hip).
@@ -359,6 +368,7 @@ void init_options() {
     for (int k = 0; k < WGNN_OPT_COUNT; ++k) g_opt[k].store(0, std::memory_order_relaxed);
     g_opt[WGNN_OPT_FUSED_FWD].store(env_int("WGNN_FUSED_FWD", 1, 0, 2), std::memory_order_relaxed);
     g_opt[WGNN_OPT_BIG_GEMM].store(1, std::memory_order_relaxed);
+    g_opt[WGNN_OPT_TN_MERGED].store(1, std::memory_order_relaxed);
   });
 }
 
@@ -729,29 +739,42 @@ int bwd_weights(const Bwd& b, int prods, int r0, int rows) {
     const _Float16* yph = (const _Float16*)(b.sf + L.st_yp);
     const _Float16* ypl = yph + L.plane_rows * L.Hp;
     const size_t PG = L.BT * L.Gp;
-    if (prods & WGNN_ROWS_HH) {
-      // Hprev row (b,t) = Y-plane row (b,t-1); row B*T stands in at t = 0, or in the state stash row B*T + b, window b's own
-      // [h0 | 1].  Register-resident recurrence: dGH = [dGI_r | dGI_z | dGHn], the A operand takes GEMM rows < msplit from the
-      // dGI planes and rows >= msplit from the dGHn planes; the reduce kernel maps the GEMM rows back to W_hh's rows.
-      if (L.dghn)
-        rc = launch_pgemm_tn(dGIh, L.dgi1 ? nullptr : dGIh + PG, (int)L.Gp, yph, ypl, (int)L.Hp, d->T, (int)L.BT, L.sk_hh,
-                             part_hh, L.m_hh, (int)L.H + 1, b.full, dGHh, L.dgi1 ? nullptr : dGHh + L.BT * (size_t)L.hn, L.hn,
-                             L.msplit, b.st, /*b_stream=*/true, /*per_window=*/sst);
-      else
-        rc = launch_pgemm_tn(dGHh, L.gen2p ? nullptr : dGHh + PG, (int)L.Gp, yph, ypl, (int)L.Hp, d->T, (int)L.BT, L.sk_hh,
-                             part_hh, rows, (int)L.H + 1, b.full, nullptr, nullptr, 0, 0, b.st, /*b_stream=*/false,
-                             /*per_window=*/sst);
-      if (rc != WGNN_OK) return rc;
+    // Hprev row (b,t) = Y-plane row (b,t-1); row B*T stands in at t = 0, or in the state stash row B*T + b, window b's own
+    // [h0 | 1].  Register-resident recurrence: dGH = [dGI_r | dGI_z | dGHn], the A operand takes GEMM rows < msplit from the
+    // dGI planes and rows >= msplit from the dGHn planes; the reduce kernel maps the GEMM rows back to W_hh's rows.
+    TnProd hh = {};
+    hh.lda = (int)L.Gp; hh.Bhi = yph; hh.Blo = ypl; hh.ldb = (int)L.Hp; hh.shift_T = d->T; hh.splitk = L.sk_hh;
+    hh.partial = part_hh; hh.Nout = (int)L.H + 1; hh.x3 = b.full; hh.per_window = sst;
+    if (L.dghn) {
+      hh.Ahi = dGIh; hh.Alo = L.dgi1 ? nullptr : dGIh + PG; hh.Mout = L.m_hh;
+      hh.A2hi = dGHh; hh.A2lo = L.dgi1 ? nullptr : dGHh + L.BT * (size_t)L.hn; hh.lda2 = L.hn; hh.msplit = L.msplit;
+      hh.b_stream = true;
+    } else {
+      hh.Ahi = dGHh; hh.Alo = L.gen2p ? nullptr : dGHh + PG; hh.Mout = rows;
     }
-    if (prods & WGNN_ROWS_IH) {
-      // (single-plane dGI: ONE pass, hi(dGI) x hi(g) -- the rounding of g, too, is independent per element and averages
-      // out over the B*T rows this product sums: measured 8.8e-6 of max at B*T = 6144 against 5.9e-6 with g's lo plane.
-      // The same was measured for dW_hh (7e-5: h rows are correlated) and dg (2.8e-4 on the conv gradients: the rounding
-      // of W_ih is the same for every row and does not average) and NOT adopted: they keep hi x (hi + lo).)
-      const bool one_pass_ih = L.dgi1 || L.gen2p;
-      rc = launch_pgemm_tn(dGIh, one_pass_ih ? dGIh : dGIh + PG, (int)L.Gp, gh, gh + L.BT * L.Ip, (int)L.Ip, 0, (int)L.BT,
-                           L.sk_ih, part_ih, rows, (int)L.I + 1, b.full && !one_pass_ih, nullptr, nullptr, 0, 0, b.st,
-                           /*b_stream=*/true);
+    // (single-plane dGI: ONE pass, hi(dGI) x hi(g) -- the rounding of g, too, is independent per element and averages
+    // out over the B*T rows this product sums: measured 8.8e-6 of max at B*T = 6144 against 5.9e-6 with g's lo plane.
+    // The same was measured for dW_hh (7e-5: h rows are correlated) and dg (2.8e-4 on the conv gradients: the rounding
+    // of W_ih is the same for every row and does not average) and NOT adopted: they keep hi x (hi + lo).)
+    const bool one_pass_ih = L.dgi1 || L.gen2p;
+    TnProd ih = {};
+    ih.Ahi = dGIh; ih.Alo = one_pass_ih ? dGIh : dGIh + PG; ih.lda = (int)L.Gp;
+    ih.Bhi = gh; ih.Blo = gh + L.BT * L.Ip; ih.ldb = (int)L.Ip; ih.splitk = L.sk_ih;
+    ih.partial = part_ih; ih.Mout = rows; ih.Nout = (int)L.I + 1; ih.x3 = b.full && !one_pass_ih; ih.b_stream = true;
+    auto one = [&](const TnProd& p) {
+      return launch_pgemm_tn(p.Ahi, p.Alo, p.lda, p.Bhi, p.Blo, p.ldb, p.shift_T, (int)L.BT, p.splitk, p.partial, p.Mout, p.Nout,
+                             p.x3, p.A2hi, p.A2lo, p.lda2, p.msplit, b.st, p.b_stream, p.per_window);
+    };
+    // WGNN_OPT_TN_MERGED: both products as one launch whose work items are exactly the workgroups of the two launches
+    // (same tiles, same K chunks, same partial regions: bit-identical)
+    if (prods == (WGNN_ROWS_IH | WGNN_ROWS_HH) && L.tn_merge && opt(WGNN_OPT_TN_MERGED) && pgemm_tn2_covers(ih, hh)) {
+      rc = launch_pgemm_tn2(ih, hh, (int)L.BT, b.st);
+    } else {
+      if (prods & WGNN_ROWS_HH) {
+        rc = one(hh);
+        if (rc != WGNN_OK) return rc;
+      }
+      if (prods & WGNN_ROWS_IH) rc = one(ih);
     }
   } else {
     const float* hp = b.sf + L.st_hprev;   // [Hprev | 1 | 0..] rows written by the forward recurrence (large B*T, state stash)
@@ -920,7 +943,7 @@ int wgnn_set_option(int key, int value) {
   if (key == WGNN_OPT_FUSED_FWD && (value < 0 || value > 2)) return WGNN_ERR_SHAPE;
   if ((key == WGNN_OPT_GG_ROLE_SPLIT && (value < 0 || value > 1)) || (key == WGNN_OPT_GG_GEMM_PRIO && (value < 0 || value > 3)))
     return WGNN_ERR_SHAPE;
-  if (key == WGNN_OPT_BIG_GEMM && (value < 0 || value > 1)) return WGNN_ERR_SHAPE;
+  if ((key == WGNN_OPT_BIG_GEMM || key == WGNN_OPT_TN_MERGED) && (value < 0 || value > 1)) return WGNN_ERR_SHAPE;
   if (key == WGNN_OPT_GEMM32_FORM && (value < 0 || value > 34)) return WGNN_ERR_SHAPE;
   init_options();
   return g_opt[key].exchange(value, std::memory_order_relaxed);
@@ -1131,6 +1154,25 @@ int wgnn_finish(const wgnn_dims* d, const wgnn_params* p, const wgnn_grads* g, i
 }
 
 int wgnn_optim_version(void) { return WGNN_OPTIM_VERSION; }
+
+// include/windgnn_sched.h
+int wgnn_tn_split(const wgnn_dims* d, int state, wgnn_tn_split_info* out) {
+  int rc = check_dims(d);
+  if (rc != WGNN_OK) return rc;
+  if (!out) return WGNN_ERR_NULL;
+  const Layout L = make_layout(d, state != 0);
+  out->sk_ih = L.sk_ih;
+  out->sk_hh = L.sk_hh;
+  out->kchunk_ih = cdiv_i(cdiv_i((int)L.BT, L.sk_ih), 32) * 32;
+  out->kchunk_hh = cdiv_i(cdiv_i((int)L.BT, L.sk_hh), 32) * 32;
+  out->merged = L.tn_merge ? 1 : 0;
+  out->workgroups = 0;
+  if (L.x3) {
+    const int ni = L.sk_ih * pgemm_tn_tiles((int)L.G3, (int)L.I + 1), nh = L.sk_hh * pgemm_tn_tiles(L.m_hh, (int)L.H + 1);
+    out->workgroups = L.tn_merge ? (ni > nh ? ni : nh) : ni + nh;
+  }
+  return WGNN_OK;
+}
 
 size_t wgnn_clip_bytes(const wgnn_dims* d) {
   if (check_dims(d) != WGNN_OK) return 0;

@@ -226,6 +226,22 @@ int launch_pgemm_tn(const void* Ahi, const void* Alo, int lda, const void* Bhi, 
                     int K, int splitk, float* partial, int Mout, int Nout, bool x3, const void* A2hi, const void* A2lo,
                     int lda2, int msplit, hipStream_t st, bool b_stream = false /*B: old read-once data, non-temporal*/,
                     bool per_window = false /*shift_T: window b starts at the extra row K + b, not K*/);
+// Both weight-gradient products of the register-resident split-fp16 recurrence as ONE launch (pgemm_tn2_kernel): each TnProd
+// is the argument list of the launch_pgemm_tn call it replaces, and every workgroup computes what that call's would, so the
+// partials are bit-identical.  pgemm_tn2_covers: the combinations the merged kernel is built for (api.hip falls back to the
+// two launches elsewhere).
+struct TnProd {
+  const void *Ahi, *Alo; int lda;
+  const void *Bhi, *Blo; int ldb;
+  int shift_T, splitk;
+  float* partial;
+  int Mout, Nout;
+  bool x3;
+  const void *A2hi, *A2lo; int lda2, msplit;
+  bool b_stream, per_window;
+};
+bool pgemm_tn2_covers(const TnProd& ih, const TnProd& hh);
+int launch_pgemm_tn2(const TnProd& ih, const TnProd& hh, int K, hipStream_t st);
 // general shapes (general.hip): CSR adjacency (blob layout: see include/windgnn.h) and any hidden width
 size_t gcn_csr_bwd_partial_floats();
 int launch_gcn2_csr_fwd(int ntiles, int S, int nnz, const void* csr, const float* X, const float* W1, const float* b1,

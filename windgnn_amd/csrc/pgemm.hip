@@ -349,16 +349,22 @@ __device__ __forceinline__ int tn_g(int stride32, int r) {   // stride32 = row b
 // ALO (with X3): as in pgemm_nt_kernel -- false: the A operand (dGI [+ dGHn]) is a single fp16 plane, two passes.
 // PW (the state stash, wgnn_bwd_state_part): with shift_T, the row read at a window start k = b shift_T is the extra row
 // K + b (the window's own h0 row) instead of the one shared row K.
+// The tile code is a device function of (z, tile, ntile) = (K chunk, output tile, output tiles per chunk): pgemm_tn_kernel
+// takes them from its grid, pgemm_tn2_kernel (one launch for both weight-gradient products) from a linear work-item index.
+// It has to stay a function with __restrict__ operands that is INLINED into its kernels: the inliner turns the qualifiers into
+// alias scopes on every access of the body, the LDS-DMA stores and the transpose reads included, and only with scopes does
+// the compiler's wait-count pass tell the DMA into the next stage from the reads of the current one.  As a plain kernel
+// body it put an `s_waitcnt vmcnt(0)` between dma_stage and the first ds_read of compute(): every K step then waited for its
+// own prefetch (staging + MFMAs in sequence, T = 7: 99 us); without it the prefetch runs under the MFMAs (78 us).  The
+// synchronisation the stages need is the explicit vmcnt(0) + s_barrier at the top of the loop.  Check after a compiler
+// change: the K loop of the assembly has that wait and the one of the partial last stage, and no third.
 template <int T, bool X3, bool A2, bool ALO, bool PW = false>
-__global__ void __launch_bounds__(64 * TN_WAVES) pgemm_tn_kernel(const _Float16* __restrict__ Ahi,
-                                                                const _Float16* __restrict__ Alo, int lda,
-                                                                const _Float16* __restrict__ Bhi,
-                                                                const _Float16* __restrict__ Blo, int ldb,
-                                                                int shift_T, int K, int kchunk,
-                                                                float* __restrict__ partial, int Mout, int Nout,
-                                                                int nNb, const _Float16* __restrict__ A2hi,
-                                                                const _Float16* __restrict__ A2lo, int lda2,
-                                                                int msplit, int b_stream) {
+__device__ __forceinline__ void pgemm_tn_tile(const _Float16* __restrict__ Ahi, const _Float16* __restrict__ Alo, int lda,
+                                              const _Float16* __restrict__ Bhi, const _Float16* __restrict__ Blo, int ldb,
+                                              int shift_T, int K, int kchunk, float* __restrict__ partial, int Mout,
+                                              int Nout, int nNb, const _Float16* __restrict__ A2hi,
+                                              const _Float16* __restrict__ A2lo, int lda2, int msplit, int b_stream,
+                                              const int z, const int tile, const int ntile) {
   constexpr int BM = TN_BM, BN = 32 * T;
   constexpr int ARB = BM * 2, BRB = BN * 2;                         // row bytes
   constexpr int A_PL = 32 * ARB, B_PL = 32 * BRB, STAGE = 2 * A_PL + 2 * B_PL;
@@ -371,8 +377,7 @@ __global__ void __launch_bounds__(64 * TN_WAVES) pgemm_tn_kernel(const _Float16*
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave & 3, wn = wave >> 2;
-  const int z = blockIdx.x;
-  const int mb = blockIdx.y / nNb, nb = blockIdx.y % nNb;
+  const int mb = tile / nNb, nb = tile % nNb;
   const int m0 = mb * BM, n0 = nb * BN;
   const int kbeg = z * kchunk, kend = min(K, kbeg + kchunk);
   const int nk = kend > kbeg ? (kend - kbeg + 31) / 32 : 0;
@@ -505,13 +510,58 @@ __global__ void __launch_bounds__(64 * TN_WAVES) pgemm_tn_kernel(const _Float16*
   // Partials are stored in the accumulators' own layout, [z][tile][wave][i][j][lane][4]: every store is a
   // full 1 KB wave-instruction (row-major P would be 64-byte segments, 4x the store instructions);
   // finish.hip (seg_tn) undoes the permutation while it sums over z.
-  float* P = partial + (((size_t)z * gridDim.y + blockIdx.y) * TN_WAVES + wave) * (5 * T * 256) + lane * 4;
+  float* P = partial + (((size_t)z * ntile + tile) * TN_WAVES + wave) * (5 * T * 256) + lane * 4;
 #pragma unroll
   for (int i = 0; i < 5; ++i)
 #pragma unroll
     for (int j = 0; j < T; ++j) {
       *(f32x4*)(P + (i * T + j) * 256) = acc[i][j];
     }
+}
+
+template <int T, bool X3, bool A2, bool ALO, bool PW = false>
+__global__ void __launch_bounds__(64 * TN_WAVES) pgemm_tn_kernel(const _Float16* __restrict__ Ahi,
+                                                                const _Float16* __restrict__ Alo, int lda,
+                                                                const _Float16* __restrict__ Bhi,
+                                                                const _Float16* __restrict__ Blo, int ldb,
+                                                                int shift_T, int K, int kchunk,
+                                                                float* __restrict__ partial, int Mout, int Nout,
+                                                                int nNb, const _Float16* __restrict__ A2hi,
+                                                                const _Float16* __restrict__ A2lo, int lda2,
+                                                                int msplit, int b_stream) {
+  pgemm_tn_tile<T, X3, A2, ALO, PW>(Ahi, Alo, lda, Bhi, Blo, ldb, shift_T, K, kchunk, partial, Mout, Nout, nNb, A2hi, A2lo,
+                                    lda2, msplit, b_stream, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y);
+}
+
+// Both weight-gradient products of the register-resident recurrence in ONE launch: workgroup w runs work item w of
+// dW_ih = dGI^T [g | 1] (single-source A) and then work item w of dW_hh = [dGI_r | dGI_z | dGHn]^T [Hprev | 1] (two-source A,
+// shifted B rows).  Each product is split for one workgroup per CU (api.hip), so every CU gets one item of each and goes from
+// the long dW_ih item straight into its dW_hh item: no second launch, and no boundary at which every CU waits for the slowest
+// dW_ih workgroup.  (Nothing of the two items overlaps inside a workgroup: the barrier between them waits for the first
+// item's partial stores.)  Each role keeps its own tile width, K chunk and partial region, i.e. every item runs exactly the
+// code, on exactly the rows, that a workgroup of its stand-alone launch would: the partials are the same bits.
+// item = tile * splitk + z keeps the N tiles of one K chunk on one XCD (splitk a multiple of 8) as the stand-alone grid does.
+// Against option 0 of the same build the form is worth ~7 us of 130.  7 x 4 tile widths x 3 modes x PW are
+// 168 instances (every (I, H) this path accepts can occur), none with scratch, all at 2 waves per SIMD.
+// MODE 0: three passes both (f16x3); 1: dGI / dGHn are ONE fp16 plane -- dW_ih one pass, dW_hh two (f16x3g at large B*T);
+// 2: one pass both (f16).
+struct TnRole {
+  const _Float16 *Ahi, *Alo, *Bhi, *Blo, *A2hi, *A2lo;
+  float* partial;
+  int lda, ldb, lda2, shift_T, K, kchunk, Mout, Nout, nNb, msplit, b_stream, splitk, ntile;
+};
+template <int TI, int TH, int MODE, bool PW>
+__global__ void __launch_bounds__(64 * TN_WAVES) pgemm_tn2_kernel(const TnRole ih, const TnRole hh) {
+  const int item = (int)blockIdx.x;                                 // (both conditions are workgroup-uniform)
+  if (item < ih.splitk * ih.ntile)
+    pgemm_tn_tile<TI, MODE == 0, false, true, false>(ih.Ahi, ih.Alo, ih.lda, ih.Bhi, ih.Blo, ih.ldb, ih.shift_T, ih.K, ih.kchunk,
+                                                     ih.partial, ih.Mout, ih.Nout, ih.nNb, ih.A2hi, ih.A2lo, ih.lda2, ih.msplit,
+                                                     ih.b_stream, item % ih.splitk, item / ih.splitk, ih.ntile);
+  __syncthreads();                                                  // the last stage of the first item has been read
+  if (item < hh.splitk * hh.ntile)
+    pgemm_tn_tile<TH, MODE != 2, true, MODE != 1, PW>(hh.Ahi, hh.Alo, hh.lda, hh.Bhi, hh.Blo, hh.ldb, hh.shift_T, hh.K, hh.kchunk,
+                                                      hh.partial, hh.Mout, hh.Nout, hh.nNb, hh.A2hi, hh.A2lo, hh.lda2, hh.msplit,
+                                                      hh.b_stream, item % hh.splitk, item / hh.splitk, hh.ntile);
 }
 
 // Planes of O[Rp][Cp] (O[r][c] = transpose ? W[c][r] : W[r][c]; optional extra column `bias_col`
@@ -810,6 +860,94 @@ int launch_pgemm_tn(const void* Ahi, const void* Alo, int lda, const void* Bhi, 
                                 lda2, msplit, st, b_stream, per_window);
     TN_CASE(1) TN_CASE(2) TN_CASE(3) TN_CASE(4) TN_CASE(5) TN_CASE(6) TN_CASE(7)
 #undef TN_CASE
+  }
+  return WGNN_ERR_SHAPE;
+}
+
+// ---- both weight-gradient products in one launch (pgemm_tn2_kernel)
+namespace {
+int tn2_mode(const TnProd& ih, const TnProd& hh) {
+  const bool ih3 = ih.x3 && ih.Alo, hh3 = hh.x3 && hh.Alo, hh2 = hh.x3 && !hh.Alo;
+  if (ih3 && hh3) return 0;
+  if (!ih.x3 && hh2) return 1;
+  if (!ih.x3 && !hh.x3) return 2;
+  return -1;
+}
+
+template <int TI, int TH>
+int launch_tn2_t(const TnProd& pi, const TnProd& ph, int K, int mode, int nNi, int nNh, hipStream_t st) {
+  auto role = [K](const TnProd& p, int nNb) {
+    TnRole r;
+    const bool alo = p.Alo != nullptr;             // single-plane A operand: the lo pointers are never read
+    r.Ahi = (const _Float16*)p.Ahi; r.Alo = (const _Float16*)(alo ? p.Alo : p.Ahi);
+    r.Bhi = (const _Float16*)p.Bhi; r.Blo = (const _Float16*)p.Blo;
+    r.A2hi = (const _Float16*)p.A2hi; r.A2lo = (const _Float16*)(alo ? p.A2lo : p.A2hi);
+    r.partial = p.partial;
+    r.lda = p.lda; r.ldb = p.ldb; r.lda2 = p.lda2; r.shift_T = p.shift_T; r.K = K;
+    r.kchunk = cdiv_i(cdiv_i(K, p.splitk), 32) * 32;
+    r.Mout = p.Mout; r.Nout = p.Nout; r.nNb = nNb; r.msplit = p.msplit; r.b_stream = p.b_stream ? 1 : 0;
+    r.splitk = p.splitk; r.ntile = cdiv_i(p.Mout, TN_BM) * nNb;
+    return r;
+  };
+  const TnRole ri = role(pi, nNi), rh = role(ph, nNh);
+  constexpr int TMAX = TI > TH ? TI : TH;
+  const size_t smem = 2 * (size_t)(2 * 32 * 2 * (TN_BM + 32 * TMAX));
+  auto bytes = [K](const TnProd& p) {
+    return ((p.x3 && p.Alo) ? 4.0 : 2.0) * (double)K * p.Mout + (p.x3 ? 4.0 : 2.0) * (double)K * p.Nout +
+           4.0 * (double)p.splitk * p.Mout * p.Nout;
+  };
+  const double fl = 2.0 * K * ((double)pi.Mout * pi.Nout + (double)ph.Mout * ph.Nout), by = bytes(pi) + bytes(ph);
+  static const std::string base = "pgemm_tn_kernel<" + std::to_string(TI) + "+" + std::to_string(TH);
+  static const std::string names[3] = {base + ">", base + ",x2>", base + ",f16>"};
+  const int ni = ri.splitk * ri.ntile, nh = rh.splitk * rh.ntile;
+  const dim3 grid(ni > nh ? ni : nh), block(64 * TN_WAVES);
+#define TN2_GO(MODE, PWV)                                                                                        \
+  do {                                                                                                           \
+    static std::atomic<unsigned long long> done_{0};                                                             \
+    if (ensure_dyn_smem((const void*)pgemm_tn2_kernel<TI, TH, MODE, PWV>, smem, done_) != WGNN_OK) return WGNN_ERR_HIP; \
+    PROF_LAUNCH(names[MODE].c_str(), fl, by, st,                                                                 \
+                hipLaunchKernelGGL((pgemm_tn2_kernel<TI, TH, MODE, PWV>), grid, block, smem, st, ri, rh));       \
+  } while (0)
+  switch (2 * mode + (ph.per_window ? 1 : 0)) {
+    case 0: TN2_GO(0, false); break;
+    case 1: TN2_GO(0, true); break;
+    case 2: TN2_GO(1, false); break;
+    case 3: TN2_GO(1, true); break;
+    case 4: TN2_GO(2, false); break;
+    case 5: TN2_GO(2, true); break;
+    default: return WGNN_ERR_UNSUPPORTED;
+  }
+#undef TN2_GO
+  WGNN_CHECK_LAUNCH();
+  return WGNN_OK;
+}
+}  // namespace
+
+// The merged launch covers: dW_ih with a single-source, unshifted A / B; dW_hh with the two-source A operand (N tile
+// T <= 4, as in launch_tn_t); and the three pass combinations of tn2_mode.  Everything else takes the two launches.
+bool pgemm_tn2_covers(const TnProd& ih, const TnProd& hh) {
+  int nNb, T;
+  tn_shape(hh.Nout, nNb, T);
+  return tn2_mode(ih, hh) >= 0 && !ih.A2hi && ih.shift_T == 0 && !ih.per_window && hh.A2hi && T <= 4 && ih.splitk >= 1 &&
+         hh.splitk >= 1;
+}
+
+int launch_pgemm_tn2(const TnProd& ih, const TnProd& hh, int K, hipStream_t st) {
+  if (!pgemm_tn2_covers(ih, hh)) return WGNN_ERR_UNSUPPORTED;
+  if (ih.lda % 8 != 0 || ih.ldb % 8 != 0 || hh.lda % 8 != 0 || hh.ldb % 8 != 0 || K < 1) return WGNN_ERR_SHAPE;
+  if (hh.per_window && hh.shift_T < 1) return WGNN_ERR_SHAPE;
+  if (hh.lda2 % 8 != 0 || hh.msplit % 8 != 0 || hh.msplit > hh.lda) return WGNN_ERR_SHAPE;
+  int nNi, TI, nNh, TH;
+  tn_shape(ih.Nout, nNi, TI);
+  tn_shape(hh.Nout, nNh, TH);
+  const int mode = tn2_mode(ih, hh);
+  switch (4 * (TI - 1) + (TH - 1)) {
+#define TN2_CASE(ti, th) \
+  case 4 * (ti - 1) + (th - 1): return launch_tn2_t<ti, th>(ih, hh, K, mode, nNi, nNh, st);
+#define TN2_ROW(ti) TN2_CASE(ti, 1) TN2_CASE(ti, 2) TN2_CASE(ti, 3) TN2_CASE(ti, 4)
+    TN2_ROW(1) TN2_ROW(2) TN2_ROW(3) TN2_ROW(4) TN2_ROW(5) TN2_ROW(6) TN2_ROW(7)
+#undef TN2_ROW
+#undef TN2_CASE
   }
   return WGNN_ERR_SHAPE;
 }
