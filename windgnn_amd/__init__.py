@@ -1,6 +1,7 @@
 """windgnn_amd: MI355X-native (gfx950 HIP) implementation of WindGNN's GCN+GRU hot path behind
 the reference's own nn.Module API.  See DESIGN.md / INTEGRATION.md."""
+from .evaluate import Evaluator  # noqa: F401
 from .modules import GCN_GRU, GraphConvLayer  # noqa: F401
 from .streaming import StreamingForecaster  # noqa: F401
 
-__all__ = ["GCN_GRU", "GraphConvLayer", "StreamingForecaster"]
+__all__ = ["Evaluator", "GCN_GRU", "GraphConvLayer", "StreamingForecaster"]

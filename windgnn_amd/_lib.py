@@ -1,4 +1,5 @@
-"""ctypes binding of libwindgnn_hip.so (the C ABI declared in include/windgnn.h and include/windgnn_optim.h).
+"""ctypes binding of libwindgnn_hip.so (the C ABI declared in include/windgnn.h, windgnn_optim.h, windgnn_sched.h and
+windgnn_eval.h).
 
 The library is the product: there is no CPU or eager-PyTorch fallback.  If the shared object is
 missing or a call fails this module raises, loudly."""
@@ -142,6 +143,17 @@ EXPORTS_SCHED = {
     "wgnn_tn_split": (C.c_int, [C.POINTER(Dims), C.c_int, C.POINTER(TnSplitInfo)]),
 }
 
+# include/windgnn_eval.h: the test loop's statistics accumulated on the device (a fourth header and table, as above)
+EVAL_VERSION = 1            # WGNN_EVAL_VERSION
+EVAL_ROWS = ("n", "sum_e2", "sum_abs_e", "sum_a", "sum_a2")   # the fp64 rows [H] at the start of `acc`, in this order
+EXPORTS_EVAL = {
+    "wgnn_eval_version": (C.c_int, []),
+    "wgnn_eval_bytes": (C.c_size_t, [C.c_int32]),
+    "wgnn_eval_accum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "wgnn_eval_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -175,6 +187,16 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    if not hasattr(lib, "wgnn_eval_version"):
+        raise RuntimeError("windgnn_amd: %s predates include/windgnn_eval.h (no wgnn_eval_version): rebuild it with "
+                           "`python -m windgnn_amd.build --force`" % LIB_PATH)
+    for name, (res, args) in EXPORTS_EVAL.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.wgnn_eval_version() < EVAL_VERSION:
+        raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_eval_version %d < %d)"
+                           % (lib.wgnn_eval_version(), EVAL_VERSION))
     if lib.wgnn_optim_version() < OPTIM_VERSION:
         raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_optim_version %d < %d)"
                            % (lib.wgnn_optim_version(), OPTIM_VERSION))
