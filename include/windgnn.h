@@ -178,8 +178,10 @@ typedef struct wgnn_adam {
 int wgnn_version(void);
 const char* wgnn_strerror(int status);
 
-/* Process-wide options: which of two kernel schedules runs.  Keys 0, 1, 2, 5 and 6 do not change a result bit; key 4 changes the
- * summation order of some products.  Key 3 (a chunked backward part 2, measured slower) is retired: it is an unknown key now.
+/* Process-wide options: which of two kernel schedules runs.  Keys 0 and 6 do not change a result bit; key 4 changes the
+ * summation order of some products.  Keys 1, 2 (wave roles per SIMD and s_setprio levels in the fused forward kernel), 3 (a
+ * chunked backward part 2) and 5 (other workgroup forms of the exact-fp32 NT products) never measured better than the
+ * defaults and are retired with their code paths: they are unknown keys now, and their numbers are not reused.
  * There is no reference counterpart (the reference has no kernels to choose between).  wgnn_set_option returns the PREVIOUS
  * value (>= 0) or WGNN_ERR_SHAPE for an unknown key / value; it takes effect for calls issued after it returns and is atomic,
  * but callers that flip an option while other threads launch get either schedule for those launches.
@@ -187,20 +189,11 @@ const char* wgnn_strerror(int status);
  *                       projection kernel (csrc/gcngi.hip).  Initial value: environment variable WGNN_FUSED_FWD, read once at
  *                       the first call that needs it (never again). */
 #define WGNN_OPT_FUSED_FWD 0
-/* Measurement aids (same results, another schedule; defaults 0 / 0): roles of the fused kernel's waves assigned per SIMD
- * instead of per wave index (0 / 1); s_setprio level of its projection waves (0..3). */
-#define WGNN_OPT_GG_ROLE_SPLIT 1
-#define WGNN_OPT_GG_GEMM_PRIO 2
 /* 1 (default): NT plane products with >= 1024 rows, >= 2048 columns and a contraction >= 1024 long (BASELINE configs[4]) run
  * the 256 x 256-tile kernel of csrc/pgemm_big.hip (their activation operand rewritten as an image first); 0: the 192 x 448-tile
  * kernel shaped for the 34-station widths.  The two sum each dot product in a different order (results differ by fp32
  * rounding, inside every stated tolerance). */
 #define WGNN_OPT_BIG_GEMM 4
-/* Exact-fp32 NT products (GI, dg) from 24 576 rows on: 0 one 8-wave workgroup per CU with a 128 x 64 T tile; v >= 1 two 4-wave
- * workgroups per CU with 128 x 32 T tiles, the second of each pair started (v - 1) x 3.4 us late so that one's epilogue falls
- * into the other's K loop (v <= 33); 34 the persistent form of the
- * 8-wave kernel (cross-tile prefetch, counted waits).  Same products, same summation order per element: results are bit-identical. */
-#define WGNN_OPT_GEMM32_FORM 5
 /* The two GRU weight-gradient products of the fp16-plane modes (register-resident recurrence, H <= 127): 1 (default) ONE
  * launch in which every workgroup runs one work item of dW_ih and then one of dW_hh; 0 one launch per product.  A schedule
  * choice like WGNN_OPT_FUSED_FWD: both forms run the same tiles over the same K chunks into the same partial sums (the

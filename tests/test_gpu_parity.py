@@ -1595,15 +1595,13 @@ def test_4096_station_config_full_size_properties_B128_T24(math):
     torch.cuda.empty_cache()
 
 
-def test_exact_fp32_projection_as_two_workgroups_per_cu_is_bitwise_the_one_workgroup_form():
-    """WGNN_OPT_GEMM32_FORM (a schedule option, round 5): the exact-fp32 NT products (GI, dg) from 24 448 rows on as two 4-wave
-    workgroups per CU (128 x 160 tiles; dg's 14 column tiles as slices of 5, 5 and 4) with and without the late start, against
-    the one 8-wave workgroup form: every element is the same fp32 chain, so Y, the loss and all eight gradients are bit-identical;
-    1100 windows x 24 = 26 400 rows leave a ragged last row tile (26 400 = 206 x 128 + 32).  Form 34 is the persistent kernel
-    (cross-tile prefetch, counted waits, stores after the loop); form 0 issues its stores inside the last K step: three
-    different epilogues, one result."""
+def test_exact_fp32_step_on_128row_tiles_with_a_ragged_last_tile_against_oracle():
+    """A whole training step (forward, MSE loss, backward through autograd) in exact fp32 from 24 448 rows on: GI and dg run the
+    128-row form of the LDS-DMA NT kernel (csrc/gemm32.hip: one 8-wave workgroup per CU, the C stores issued inside the last K
+    step), dg's 14 column tiles as one slice of 2 x 7; 1100 windows x 24 = 26 400 rows leave a ragged last row tile (26 400 =
+    206 x 128 + 32).  Y, the loss and all eight gradients of the whole batch against the fp64 oracle at SURVEY 8(c)'s bar.
+    (test_exact_fp32_big_tile_gemms runs the same shape through the raw forward / backward entry points only.)"""
     from oracle import windgnn_oracle as orc
-    from windgnn_amd import _lib
     dev = _dev()
     S, T, H = 34, 24, 102
     p = orc.init_params(S, 13, H, seed=4)
@@ -1612,19 +1610,14 @@ def test_exact_fp32_projection_as_two_workgroups_per_cu_is_bitwise_the_one_workg
     B = 1100
     X = torch.rand(B, T, S, 13, generator=g)
     L = torch.rand(B, T, H, generator=g)
-    res = {}
-    try:
-        for form in (0, 1, 6, 34):
-            _lib.set_option(_lib.OPT_GEMM32_FORM, form)
-            res[form] = _run_step(_model_from(p, S, H, "f32"), A.to(dev), X.to(dev), L.to(dev))
-    finally:
-        _lib.set_option(_lib.OPT_GEMM32_FORM, 0)
-    for form in (1, 6, 34):
-        assert torch.equal(res[0][0], res[form][0]) and res[0][1] == res[form][1]
-        for k in PARAM_KEYS:
-            assert torch.equal(res[0][2][k], res[form][2][k]), (form, k)
-    Yo = orc.forward(A.double(), X[-64:].double(), {k: v.double() for k, v in p.items()}, want_cache=False)[0]
-    assert (res[1][0][-64:].double() - Yo).abs().max().item() <= Y_TOL      # the ragged tile's windows against the fp64 oracle
+    Yo, loss_o, go = orc.train_step(A.double(), X.double(), L.double(), {k: v.double() for k, v in p.items()})
+    out, loss, grads = _run_step(_model_from(p, S, H, "f32"), A.to(dev), X.to(dev), L.to(dev))
+    ey = max_abs(out.reshape(Yo.shape), Yo)
+    worst = {k: rel_to_max(grads[k], go[k]) for k in PARAM_KEYS}
+    print("exact fp32, 26 400 rows: Y %.2e, loss %.8g vs %.8g, grads %s" % (ey, loss, float(loss_o), {k: "%.1e" % v for k, v in worst.items()}))
+    assert ey <= Y_TOL, ey
+    assert abs(loss - float(loss_o)) <= 1e-5 * max(1.0, float(loss_o)), (loss, float(loss_o))
+    assert max(worst.values()) <= G_TOL, worst
 
 
 @pytest.mark.parametrize("math,B", [("f16x3", 48), ("f16x3g", 128)])

@@ -56,6 +56,32 @@ def test_option_key_is_known_and_defaults_to_the_merged_launch():
     assert L.get_option(L.OPT_TN_MERGED) == 1
 
 
+def test_retired_option_keys_are_unknown_and_the_live_ones_keep_their_defaults():
+    """Keys 1, 2, 3 and 5 named schedules that never measured better than the defaults and were removed with their code paths:
+    the library refuses them, neither the header nor the bindings name them, and their numbers are not reused.  The live keys
+    0, 4 and 6 answer 1 in a fresh process (key 0 takes its initial value from WGNN_FUSED_FWD: unset in the child)."""
+    import subprocess
+    import sys
+    L, lib = _lib()
+    WGNN_ERR_SHAPE = -2
+    for k in (1, 2, 3, 5):
+        assert lib.wgnn_set_option(k, 0) == WGNN_ERR_SHAPE, k
+        assert lib.wgnn_get_option(k) == WGNN_ERR_SHAPE, k
+    hdr = open(os.path.join(ROOT, "include", "windgnn.h")).read()
+    assert re.search(r"WGNN_ERR_SHAPE\s*=\s*-2\b", hdr)
+    keys = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define\s+WGNN_OPT_(\w+)\s+(\d+)\b", hdr)}
+    assert keys == {"FUSED_FWD": 0, "BIG_GEMM": 4, "TN_MERGED": 6, "COUNT": 7}, keys
+    opts = {n: getattr(L, n) for n in dir(L) if n.startswith("OPT_")}               # the bindings name the live keys only
+    assert opts == {"OPT_FUSED_FWD": 0, "OPT_BIG_GEMM": 4, "OPT_TN_MERGED": 6}, opts
+    code = ("import sys; sys.path.insert(0, %r); from windgnn_amd import _lib as L; "
+            "print('options', L.get_option(0), L.get_option(4), L.get_option(6))" % ROOT)
+    env = {k: v for k, v in os.environ.items() if k != "WGNN_FUSED_FWD"}
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert [l for l in r.stdout.splitlines() if l.startswith("options")] == ["options 1 1 1"], r.stdout
+
+
 def _bt_sweep():
     """B*T from 1 to 131 072: every small value, then powers of two and their neighbours, then odd strides."""
     vals = set(range(1, 300))

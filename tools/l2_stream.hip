@@ -10,7 +10,7 @@
 //   D     K steps requested ahead (register stages in flight = D; the shipped kernel: 1)
 //   MF    MFMAs (16x16x32 f16) issued per K step on the loaded fragments (0 = loads only; the shipped f16x3 kernel: RT * CT * 3 = 18)
 //   PAT   0: every CU walks the same image in step (the shipped kernel)
-//         1: every CU starts at its own K step (blockIdx * 5 % nk) and wave (staggered: same bytes, different moments)
+//         1: every CU starts at its own K step (blockIdx * 5 % nk) and wave (out of step: same bytes, different moments)
 //         2: every CU has a private copy of the image (256 x 573 KB = 147 MB: served by the Infinity Cache, not L2)
 //         3: the control of tools/l2_rate.hip -- 64 KB blocks hopping through a 2 MB window -- with this kernel's loop
 // Output: us per launch, B/clk/CU at the clock measured in the kernel (s_memtime / s_memrealtime), bytes in flight per CU
@@ -116,7 +116,7 @@ static void run() {
   for (int i = 0; i < 256; ++i) { cyc += (double)h[2 * i]; real += (double)h[2 * i + 1]; }
   const double ghz = cyc / real * 0.1;                             // s_memrealtime ticks at 100 MHz
   const double bytes_cu = (double)ntiles * NK * W * CT * PL * 1024.0;
-  static const char* pat[] = {"same image, in step", "same image, staggered", "private copies (MALL)", "2 MB window, 64 KB hops"};
+  static const char* pat[] = {"same image, in step", "same image, out of step", "private copies (MALL)", "2 MB window, 64 KB hops"};
   printf("W=%2d CT=%d PL=%d D=%d MF=%2d  %-24s in flight %3d KB/CU  %7.1f us  %5.1f B/clk/CU (in-kernel %.2f GHz, %5.1f B/clk by cycles)  %5.2f TB/s\n",
          W, CT, PL, D, MF, pat[PAT], W * D * CT * PL, best * 1e3, bytes_cu / (best * 1e-3 * ghz * 1e9), ghz,
          bytes_cu / (cyc / 256.0), bytes_cu * 256 / best / 1e9);

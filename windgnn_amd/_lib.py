@@ -22,7 +22,7 @@ IO_F32, IO_F16, IO_BF16 = 0, 1, 2   # wgnn_io: element type of X, Y and the labe
 STEP_MAX_B = 256            # wgnn_fwd_state: T == 1 calls up to this batch (dense A, fp32 I/O, H <= 128) run ONE kernel
 STATUS_BYTES = 256          # WGNN_STATUS_BYTES: status block at the start of every workspace
 OPT_FUSED_FWD = 0           # WGNN_OPT_FUSED_FWD (wgnn_set_option): 0 never / 1 stash-less forwards / 2 every supported forward
-OPT_GG_ROLE_SPLIT, OPT_GG_GEMM_PRIO, OPT_BIG_GEMM, OPT_GEMM32_FORM = 1, 2, 4, 5   # measurement aids (include/windgnn.h; key 3 is retired)
+OPT_BIG_GEMM = 4            # WGNN_OPT_BIG_GEMM: 1 (default) the 256 x 256-tile kernel for large NT plane products / 0 off (keys 1, 2, 3, 5 are retired)
 OPT_TN_MERGED = 6           # WGNN_OPT_TN_MERGED: 1 (default) one launch for both GRU weight-gradient GEMMs / 0 one each; same bits
 
 

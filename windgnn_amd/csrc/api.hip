@@ -341,8 +341,9 @@ size_t clip_floats(const Layout& L, const wgnn_dims* d) {
   return rup((size_t)CLIP_HDR + (size_t)most, 64);
 }
 
-// Process-wide options (wgnn_set_option / wgnn_get_option).  Keys 0, 1, 2, 5 and 6 choose between schedules with bit-identical
-// results; key 4 (WGNN_OPT_BIG_GEMM) changes the summation order of the large NT plane products.  Key 3 is retired.
+// Process-wide options (wgnn_set_option / wgnn_get_option).  Keys 0 (WGNN_OPT_FUSED_FWD) and 6 (WGNN_OPT_TN_MERGED) choose
+// between schedules with bit-identical results; key 4 (WGNN_OPT_BIG_GEMM) changes the summation order of the large NT plane
+// products.  Keys 1, 2, 3 and 5 are retired: their other sides never measured better and went with their code paths.
 //
 // WGNN_OPT_FUSED_FWD: which forwards run the fused GCN + projection kernel (gcngi.hip).
 //   1 (default)  forwards WITHOUT a stash (inference: wgnn_fwd(stash = NULL), wgnn_fwd_last) -- where it measured faster
@@ -377,8 +378,8 @@ int opt(int key) {
   return g_opt[key].load(std::memory_order_relaxed);
 }
 
-// option keys wgnn_set_option / wgnn_get_option accept (key 3, the chunked backward part 2, was removed)
-bool known_option(int key) { return key >= 0 && key < WGNN_OPT_COUNT && key != 3; }
+// option keys wgnn_set_option / wgnn_get_option accept (1, 2, 3 and 5 are retired and never reused)
+bool known_option(int key) { return key == WGNN_OPT_FUSED_FWD || key == WGNN_OPT_BIG_GEMM || key == WGNN_OPT_TN_MERGED; }
 
 int check_dims(const wgnn_dims* d) {
   if (!d) return WGNN_ERR_NULL;
@@ -473,7 +474,7 @@ int fwd_front(const Fwd& f) {
     const int planes = f.sf ? ((f.full && !L.dgi1) ? 2 : 1) : 0;   // what the backward reads of g: hi (mask, one-pass dW_ih), + lo (strict)
     return launch_gcngi_fwd((int)L.BT, d->S, c.A, c.X, d->io, p->conv1_weight, p->conv1_bias, p->conv2_weight, p->conv2_bias,
                             f.sf ? (void*)f.g : nullptr, (int)L.Ip, planes, f.img_f, L.np_g3, f.GI, (int)L.Gp, (int)L.G3, f.full,
-                            f.status, f.ws + L.ws_xtail_f, f.st, opt(WGNN_OPT_GG_ROLE_SPLIT), opt(WGNN_OPT_GG_GEMM_PRIO));
+                            f.status, f.ws + L.ws_xtail_f, f.st);
   } else if (L.gen_gcn) {   // CSR adjacency: exact fp32 SpMM layers; layer 2 writes g as fp32 rows, or as the split modes' planes
     rc = launch_gcn2_csr_fwd((int)L.BT, d->S, d->nnz, c.A, (const float*)c.X, p->conv1_weight, p->conv1_bias, p->conv2_weight,
                              p->conv2_bias, f.sf ? f.sf + L.st_h1 : f.ws + L.ws_h1, L.x3 ? nullptr : f.g, L.x3 ? f.g : nullptr,
@@ -930,7 +931,6 @@ int check_rows(const wgnn_dims* d, const Layout& L, int which, int row0, int row
 }  // namespace
 
 int opt_big_gemm() { return opt(WGNN_OPT_BIG_GEMM); }
-int opt_gemm32_form() { return opt(WGNN_OPT_GEMM32_FORM); }
 
 extern "C" {
 
@@ -941,10 +941,7 @@ int wgnn_get_option(int key) { return known_option(key) ? opt(key) : WGNN_ERR_SH
 int wgnn_set_option(int key, int value) {
   if (!known_option(key)) return WGNN_ERR_SHAPE;
   if (key == WGNN_OPT_FUSED_FWD && (value < 0 || value > 2)) return WGNN_ERR_SHAPE;
-  if ((key == WGNN_OPT_GG_ROLE_SPLIT && (value < 0 || value > 1)) || (key == WGNN_OPT_GG_GEMM_PRIO && (value < 0 || value > 3)))
-    return WGNN_ERR_SHAPE;
   if ((key == WGNN_OPT_BIG_GEMM || key == WGNN_OPT_TN_MERGED) && (value < 0 || value > 1)) return WGNN_ERR_SHAPE;
-  if (key == WGNN_OPT_GEMM32_FORM && (value < 0 || value > 34)) return WGNN_ERR_SHAPE;
   init_options();
   return g_opt[key].exchange(value, std::memory_order_relaxed);
 }

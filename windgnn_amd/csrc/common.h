@@ -179,8 +179,7 @@ int launch_gcnx2_bwd(int ntiles, int S, const float* A, const void* X, int io, c
 bool gcngi_supported(int S, int H, bool x3);
 int launch_gcngi_fwd(int ntiles, int S, const float* A, const void* X, int io, const float* W1, const float* b1,
                      const float* W2, const float* b2, void* g_planes, int ldg, int stash_planes, const void* Bplanes,
-                     int Np, void* GI, int ldgi, int N, bool x3, unsigned* status, void* xtail_scratch, hipStream_t st,
-                     int role_split = 0, int gemm_prio = 0);
+                     int Np, void* GI, int ldgi, int N, bool x3, unsigned* status, void* xtail_scratch, hipStream_t st);
 // GraphConvLayer with any feature widths, S <= 64 dense (gcn_any.hip), and the g / dg hand-over of wgnn_gru_fwd / wgnn_gru_bwd
 bool gcn_any_supported(int S, int Fi, int Fo);
 size_t gcn_any_bwd_partial_floats(int ntiles, int Fi, int Fo);
@@ -196,7 +195,6 @@ int launch_pgemm_nt256(const void* Aimg_hi, const void* Aimg_lo, int M, int k0, 
                        size_t bplane, float* C, int ldc, int N, bool accumulate, hipStream_t st);
 size_t pgemm_nt256_aimg_bytes(int M, int N, int Kp, int planes);
 int launch_pgemm_repack_a(const void* Ahi, const void* Alo, int lda, int M, int Kp, void* img, hipStream_t st);
-int opt_gemm32_form(); // WGNN_OPT_GEMM32_FORM: 0 one 8-wave workgroup per CU, v >= 1 two 4-wave ones, stagger v - 1 (gemm32.hip)
 int opt_big_gemm();   // WGNN_OPT_BIG_GEMM: 0 off, 1 on (needs the caller's A-image scratch)
 // ---- The image of a B operand (weights: W_ih | b_ih, W_ih^T, W_hh | b_hh), written by split_weight2_kernel / finish.hip and
 // staged by the NT plane GEMMs and the fused front end: one fp16 plane of B[Np][Kp] is STAGE-major (a 32-deep K step of all

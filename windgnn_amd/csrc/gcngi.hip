@@ -36,8 +36,7 @@ __global__ void __launch_bounds__(64 * (NG + NM)) gcngi_fwd_kernel(
     int ntiles, int S, const float* __restrict__ A, const void* __restrict__ X, const void* __restrict__ xtail, int io,
     const float* __restrict__ W1, const float* __restrict__ b1, const float* __restrict__ W2,
     const float* __restrict__ b2, _Float16* __restrict__ ghi, _Float16* __restrict__ glo, int ldp, int stash_planes,
-    const _Float16* __restrict__ Bpl, size_t bplane, int Np, void* __restrict__ GIv, int ldgi, int N, unsigned* status,
-    int role_split, int gemm_prio) {
+    const _Float16* __restrict__ Bpl, size_t bplane, int Np, void* __restrict__ GIv, int ldgi, int N, unsigned* status) {
   constexpr int KS = (NT + 1) / 2;
   constexpr int SP = 16 * NT;
   constexpr int NP = (SP * F13 / 2 + 63) / 64;
@@ -45,26 +44,16 @@ __global__ void __launch_bounds__(64 * (NG + NM)) gcngi_fwd_kernel(
   constexpr int PL = X3 ? 2 : 1;
   constexpr int RT = R / 16;
   static_assert(R % 16 == 0, "the projection works on 16-row MFMA tiles");
-  constexpr bool CAN_SPLIT = (NG + NM) % 4 == 0 && (4 * NG) % (NG + NM) == 0;   // role_split maps roles to whole SIMD slots
   extern __shared__ __attribute__((aligned(16))) char smem[];
   h8* const sCA = (h8*)smem;                                              // [frag][hi|lo][lane]
   float* const sx = (float*)(smem + (size_t)2 * NF * 64 * 16);            // per GCN wave: [SP][XS] fp32
   char* const gt = smem + (size_t)2 * NF * 64 * 16 + (size_t)NG * SP * XS * 4;
   const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // Which waves play which role.  Default: waves 0..NG-1 GCN, the rest GEMM -- with the hardware's cyclic wave -> SIMD
-  // assignment every SIMD then hosts waves of both roles.  role_split (WGNN_OPT_GG_ROLE_SPLIT, an experiment: VERDICT r4
-  // next 2b) assigns roles by wave % 4 instead, i.e. per SIMD: NG : NM = 1 : 1 -> SIMD slots {0,1} GCN, {2,3} GEMM;
-  // 3 : 1 -> slot 3 GEMM.  gidx / q: the wave's index inside its role.  The results do not depend on it.
-  bool is_gcn = wave < NG;
-  int gidx = wave, q = wave - NG;
-  if (CAN_SPLIT && role_split == 1) {
-    constexpr int GS = CAN_SPLIT ? 4 * NG / (NG + NM) : 1;                // SIMD slots that run GCN waves
-    const int slot = wave & 3, round = wave >> 2;
-    is_gcn = slot < GS;
-    gidx = round * GS + slot;
-    q = round * (4 - GS) + (slot - GS);
-  }
+  // Waves 0..NG-1 are GCN waves, the rest GEMM waves: with the hardware's cyclic wave -> SIMD assignment every SIMD hosts
+  // waves of both roles.  gidx / q: the wave's index inside its role.
+  const bool is_gcn = wave < NG;
+  const int gidx = wave, q = wave - NG;
   const int I = S * F13;
   const int pitch = 2 * ldp + GG_PAD;                                     // bytes per g row in LDS
   const int plane_b = R * pitch, buf_b = PL * plane_b;
@@ -275,11 +264,6 @@ __global__ void __launch_bounds__(64 * (NG + NM)) gcngi_fwd_kernel(
 
   // =============================== GEMM waves: a slice of the 3H columns, all R rows ===============================
   {
-    // (experiment, WGNN_OPT_GG_GEMM_PRIO: the GEMM waves' instructions -- their B loads above all -- win issue arbitration
-    // against the GCN waves of the same SIMD; s_setprio takes an immediate)
-    if (gemm_prio == 1) __builtin_amdgcn_s_setprio(1);
-    else if (gemm_prio == 2) __builtin_amdgcn_s_setprio(2);
-    else if (gemm_prio == 3) __builtin_amdgcn_s_setprio(3);
     const int ntn = (N + 15) / 16;                                          // 16-column tiles of GI
     const int base = ntn / NM, extra = ntn % NM;
     const int nct = base + (q < extra ? 1 : 0);                             // wave-uniform
@@ -456,8 +440,7 @@ bool gcngi_supported(int S, int H, bool x3) {
 // [Kp / 32][Np][32] halfs, hi then lo (launch_split_weight2 / wgnn_prepare_weights), column I = b_ih.
 int launch_gcngi_fwd(int ntiles, int S, const float* A, const void* X, int io, const float* W1, const float* b1,
                      const float* W2, const float* b2, void* g_planes, int ldg, int stash_planes, const void* Bplanes,
-                     int Np, void* GI, int ldgi, int N, bool x3, unsigned* status, void* xtail_scratch, hipStream_t st,
-                     int role_split, int gemm_prio) {
+                     int Np, void* GI, int ldgi, int N, bool x3, unsigned* status, void* xtail_scratch, hipStream_t st) {
   const int NTs = (S + 15) / 16;
   const size_t I = (size_t)S * 13, es = io ? 2 : 4;
   const void* xt = nullptr;
@@ -487,8 +470,7 @@ int launch_gcngi_fwd(int ntiles, int S, const float* A, const void* X, int io, c
     PROF_LAUNCH(NAME, fl, by, st,                                                                                      \
                 hipLaunchKernelGGL((gcngi_fwd_kernel<NT, X3V, IOV, NGV, NMV, RV>), dim3(grid),                         \
                                    dim3(64 * (NGV + NMV)), smem, st, ntiles, S, A, X, xt, io, W1, b1, W2, b2, ghi,     \
-                                   glo, ldg, stash_planes, (const _Float16*)Bplanes, bplane, Np, GI, ldgi, N, status,  \
-                                   role_split, gemm_prio));                                                            \
+                                   glo, ldg, stash_planes, (const _Float16*)Bplanes, bplane, Np, GI, ldgi, N, status)); \
   } while (0)
 #define GG_CASE(NT)                                                                      \
   if (x3 && !io) GG_GO(NT, true, false, 8, 8, 32, "gcngi_fwd_kernel<" #NT ">");          \

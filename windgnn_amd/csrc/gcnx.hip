@@ -249,9 +249,7 @@ __global__ void __launch_bounds__(64 * FWD_WAVES) gcnx_fwd_kernel(int ntiles, in
 // registers (268 vs 136 us) and stays at 12 waves.
 // S = 49..64 (NT = 4) in the split modes needs 172 VGPRs: 12 waves spilled 3-4 registers (16-20 B of scratch) and ran 132.8 us at
 // S = 64, B = 2048 against 118.3 us with 8 waves and no scratch (r4, tools/exp/gcnx_bwd_s64.py, same box)
-#ifndef WGNN_BWD4_WAVES
-#define WGNN_BWD4_WAVES 8
-#endif
+constexpr int WGNN_BWD4_WAVES = 8;
 // DG16 = false in the one-pass mode (fp32 dg: only with a wide GRU behind a dense GCN) needs 131 VGPRs: 12 waves there too
 // (3 spilled registers at 16 waves; 51.0 -> 49.1 us at S = 34, H = 200, B = 2048)
 constexpr int bwd_waves(int NT, bool X3, bool DG16 = true) {

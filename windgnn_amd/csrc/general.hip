@@ -159,6 +159,8 @@ __device__ __forceinline__ void csr_rows(const Csr& c, const CsrItem& it, int S,
   }
 }
 
+constexpr int CSR_FWD_RPT = 2;    // output rows per thread and item of the forward
+constexpr int CSR_FWD_NB = 4;     // column indices per round trip of its gather
 // Out[tile][s][:] = relu((A In[tile])[s][:] W + b); In = [ntiles][S*13].  PLANES: the output row is written as fp16 hi/lo
 // planes [ntiles][ld_out] (the f16x3 interchange format, pgemm.hip) with 1.0 in column S*13 and zeros behind it.  The rows go
 // through LDS once more on their way out, so that the stores are whole 16-byte (planes: 8-byte) pieces of consecutive memory.
@@ -168,12 +170,6 @@ __global__ void __launch_bounds__(CT) csr_layer_fwd_kernel(int ntiles, int S, Cs
                                                            float* __restrict__ Out, size_t ld_out,
                                                            _Float16* __restrict__ Ohi, _Float16* __restrict__ Olo,
                                                            unsigned* status) {
-#ifndef CSR_FWD_RPT
-#define CSR_FWD_RPT 2
-#endif
-#ifndef CSR_FWD_NB
-#define CSR_FWD_NB 4
-#endif
   constexpr int RPT = CSR_FWD_RPT, RB = CT * RPT;              // output rows per item
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* tile = lds;

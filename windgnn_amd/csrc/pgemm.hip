@@ -640,10 +640,7 @@ __global__ void nt_ksum_kernel(const float* __restrict__ part, int nchunks, size
 // C (453 / 654 MB per chunk for GI / dg at B*T = 3072), so half the chunks = 11.7 GB less traffic and half the launches:
 // configs[4] 142.3 -> 132.4 ms per step, with Y / gradients at full width still inside the same bounds
 // (test_4096_station_config_at_full_width_H12288_against_host_fp64; a single 53 248-long chain measured 4e-5 / 2.5e-4)
-#ifndef WGNN_NT_KC
-#define WGNN_NT_KC 4096
-#endif
-constexpr int NT_KC = WGNN_NT_KC;
+constexpr int NT_KC = 4096;
 static int nt_chunks(int Kp) { return Kp > NT_KC + NT_KC / 2 ? cdiv_i(Kp, NT_KC) : 1; }
 static void nt_shape(int M, int N, int Kp, bool splitk, int& nsl, int& T) {
   nsl = cdiv_i(N, 448);

@@ -107,11 +107,7 @@ __global__ void __launch_bounds__(64 * BG_WAVES) pgemm_nt256_kernel(const _Float
     srcB[1] = Bpl + bplane + fb;
   }
   const size_t astep = (size_t)Mp * 32, bstep = (size_t)Np * 32;   // halfs per K step of the images
-#ifndef BG_ABLATE
-#define BG_ABLATE 0      // tools/gemm256_ablate.hip builds this file with parts switched off (bit 0: no steady-state DMA, bit 1: no
-#endif                   // fragment reads after the first, bit 2: no MFMAs, bit 3: no barriers); the library always builds 0
   auto dma = [&](int slot, int hs) {                               // half step hs = 2 kt + s
-    if ((BG_ABLATE & 1) && hs >= NS) return;
     char* base = smem + slot * SLOT + wave * 1024;
     const size_t ao = (size_t)(hs >> 1) * astep + (hs & 1) * 256, bo = (size_t)(hs >> 1) * bstep + (hs & 1) * 256;
 #pragma unroll
@@ -128,13 +124,7 @@ __global__ void __launch_bounds__(64 * BG_WAVES) pgemm_nt256_kernel(const _Float
   const int laneoff = (r32 >> 4) * 512 + hsel * 256 + (r32 & 15) * 16;
   const int offA = 4 * wm * 1024 + laneoff, offB = A_SLOT + 2 * wn * 1024 + laneoff;
   struct Frags { h8 ah[4], al[4], bh[2], bl[2]; };
-  bool first_load = true;
   auto load = [&](Frags& f, int slot) {
-    if (BG_ABLATE & 2) {
-      if (!first_load) return;
-      first_load = false;
-      f = Frags{};
-    }
     const char* st = smem + slot * SLOT;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -148,20 +138,14 @@ __global__ void __launch_bounds__(64 * BG_WAVES) pgemm_nt256_kernel(const _Float
     }
   };
   auto mm = [&](const Frags& f) {
-    if (BG_ABLATE & 4) return;
-    // pass-major: the three products of one accumulator are eight MFMAs apart (BG_ABLATE & 32: accumulator-major, dependent triples)
+    // pass-major: the three products of one accumulator are eight MFMAs apart, not a dependent triple
 #pragma unroll
     for (int pass = 0; pass < 3; ++pass)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          if (BG_ABLATE & 32) {
-            if (pass != 0) continue;
-            if (ALO) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[i], f.bh[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[i], f.bl[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[i], f.bh[j], acc[i][j], 0, 0, 0);
-          } else if (pass == 0) {
+          if (pass == 0) {
             if (ALO) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[i], f.bh[j], acc[i][j], 0, 0, 0);
           } else if (pass == 1) {
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[i], f.bl[j], acc[i][j], 0, 0, 0);
@@ -180,7 +164,7 @@ __global__ void __launch_bounds__(64 * BG_WAVES) pgemm_nt256_kernel(const _Float
   //   * the 24 MFMAs of half step h out of registers,
   // INTERLEAVED (sched_group_barrier: one DS read behind each of the first 12 MFMAs, one DMA behind every second of the next
   // 8): issued as a block in front of the MFMAs they cost the matrix pipe their issue time, because the two waves of a SIMD run
-  // in step between barriers (ablation, tools/gemm256_ablate.hip: MFMAs alone 1.92 ms per K chunk, + fragment reads 2.40, + DMA
+  // in step between barriers (ablation, profiles/r5_c5_big_gemm.txt: MFMAs alone 1.92 ms per K chunk, + fragment reads 2.40, + DMA
   // 2.67 -- the memory instructions' time ADDED to the MFMAs'; barriers removed: no change).  Then: fragments of h + 1 in
   // registers, half step h + 2 landed (its NS - 3 successors may stay in flight), barrier.  Every request has NS - 2 half steps
   // to arrive.  Past the end the DMA re-requests the last half step into a slot nobody reads again and the fragment read
@@ -200,21 +184,19 @@ __global__ void __launch_bounds__(64 * BG_WAVES) pgemm_nt256_kernel(const _Float
     dma(slot_dma, hs_dma < nh ? hs_dma : nh - 1);
     load(nxt, slot_frag);
     mm(cur);
-    if (!(BG_ABLATE & 16)) {
 #pragma unroll
-      for (int k = 0; k < 12; ++k) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);         // 1 MFMA
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);         // 1 DS read
-      }
-#pragma unroll
-      for (int k = 0; k < P; ++k) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);         // 2 MFMAs
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);         // 1 VMEM read (the LDS-DMA)
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 24, 0);          // the rest
+    for (int k = 0; k < 12; ++k) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);           // 1 MFMA
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);           // 1 DS read
     }
+#pragma unroll
+    for (int k = 0; k < P; ++k) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);           // 2 MFMAs
+      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);           // 1 VMEM read (the LDS-DMA)
+    }
+    __builtin_amdgcn_sched_group_barrier(0x008, 24, 0);            // the rest
     BG_WAIT((NS - 3) * P);
-    if (!(BG_ABLATE & 8)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
   };
   int s0 = 0;                                                      // h % NS, h even
   for (int h = 0; h < nh; h += 2) {
