@@ -1,5 +1,5 @@
-"""ctypes binding of libwindgnn_hip.so (the C ABI declared in include/windgnn.h, windgnn_optim.h, windgnn_sched.h and
-windgnn_eval.h).
+"""ctypes binding of libwindgnn_hip.so (the C ABI declared in include/windgnn.h, windgnn_optim.h, windgnn_sched.h,
+windgnn_eval.h and windgnn_best.h).
 
 The library is the product: there is no CPU or eager-PyTorch fallback.  If the shared object is
 missing or a call fails this module raises, loudly."""
@@ -154,6 +154,19 @@ EXPORTS_EVAL = {
     "wgnn_eval_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
+# include/windgnn_best.h: the reference's keep-the-best-model rule on the device (a fifth header and table, as above)
+BEST_VERSION = 1            # WGNN_BEST_VERSION
+# the public words of the record: name -> (byte offset, torch dtype name)
+BEST_WORDS = {"best_loss": (0, "float64"), "best_step": (8, "int64"), "calls": (16, "int64"), "improvements": (24, "int64"),
+              "improved": (32, "int32")}
+EXPORTS_BEST = {
+    "wgnn_best_version": (C.c_int, []),
+    "wgnn_best_bytes": (C.c_size_t, []),
+    "wgnn_best_init": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "wgnn_keep_best": (C.c_int, [C.POINTER(Dims), C.c_void_p, C.POINTER(Params), C.POINTER(Params), C.c_int64, C.c_void_p,
+                                 C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -194,6 +207,16 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    if not hasattr(lib, "wgnn_best_version"):
+        raise RuntimeError("windgnn_amd: %s predates include/windgnn_best.h (no wgnn_best_version): rebuild it with "
+                           "`python -m windgnn_amd.build --force`" % LIB_PATH)
+    for name, (res, args) in EXPORTS_BEST.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.wgnn_best_version() < BEST_VERSION:
+        raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_best_version %d < %d)"
+                           % (lib.wgnn_best_version(), BEST_VERSION))
     if lib.wgnn_eval_version() < EVAL_VERSION:
         raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_eval_version %d < %d)"
                            % (lib.wgnn_eval_version(), EVAL_VERSION))

@@ -363,6 +363,62 @@ def finish_clipped(d, params, grads, adam, clip, prepared=None, device=None) -> 
     _lib.check(rc, "wgnn_finish_clipped")
 
 
+def best_bytes() -> int:
+    """wgnn_best_bytes(): bytes of the record of best_init / keep_best (include/windgnn_best.h)."""
+    return int(_lib.load().wgnn_best_bytes())
+
+
+def best_word(record: torch.Tensor, name: str) -> torch.Tensor:
+    """A 0-dim VIEW of one public word of a best record (uint8 [best_bytes()]): _lib.BEST_WORDS names them."""
+    off, dtype = _lib.BEST_WORDS[name]
+    dtype = getattr(torch, dtype)
+    return record[off:off + torch.empty((), dtype=dtype).element_size()].view(dtype)[0]
+
+
+def _record_ptr(record):
+    if not record.is_cuda:
+        raise RuntimeError("windgnn_amd runs on an MI355X (HIP) only: the best record is on %s. There is no CPU fallback."
+                           % record.device)
+    _require_contiguous(best=record)
+    _require_scratch_aligned(best=record)
+    if record.dtype != torch.uint8 or record.numel() < best_bytes():
+        raise RuntimeError("windgnn_amd: the best record must be a uint8 tensor of wgnn_best_bytes() = %d bytes, got %s %s"
+                           % (best_bytes(), record.dtype, tuple(record.shape)))
+    return _ptr(record)
+
+
+def best_init(record: torch.Tensor, threshold: float) -> None:
+    """wgnn_best_init: every byte of `record` (uint8 [best_bytes()], it may be dirty) written: best_loss = threshold
+    (float("inf"): the first finite loss wins), best_step = -1, counters 0."""
+    _lib.check(_lib.load().wgnn_best_init(_record_ptr(record), float(threshold), _stream()), "wgnn_best_init(%r)" % threshold)
+
+
+def keep_best_args(d, loss: torch.Tensor, params, best_params, record: torch.Tensor):
+    """Everything of a keep_best call but the step number, validated and marshalled once (a caller whose tensors never move --
+    TrainStep -- pays the checks and the two wgnn_params structs at construction, not per step): pass it to keep_best_launch."""
+    _require_gpu(loss, *params, *best_params)
+    _require_contiguous(**{"params[%d]" % i: q for i, q in enumerate(params)},
+                        **{"best_params[%d]" % i: q for i, q in enumerate(best_params)})
+    for i, (q, b) in enumerate(zip(params, best_params)):
+        if q.numel() != b.numel():
+            raise RuntimeError("windgnn_amd: best_params[%d] has %d elements, params[%d] has %d" % (i, b.numel(), i, q.numel()))
+    ps = _params_struct(_lib.Params, params)
+    bs = _params_struct(_lib.Params, best_params)
+    return (_lib.load().wgnn_keep_best, C.byref(d), _ptr(loss), C.byref(ps), C.byref(bs), _record_ptr(record),
+            (d, ps, bs, loss, list(params), list(best_params), record))       # the last entry keeps the memory alive
+
+
+def keep_best_launch(args, step: int) -> None:
+    fn, d, loss, ps, bs, rec, _ = args
+    _lib.check(fn(d, loss, ps, bs, int(step), rec, _stream()), "wgnn_keep_best(step=%d)" % step)
+
+
+def keep_best(d, loss: torch.Tensor, params, best_params, step: int, record: torch.Tensor) -> None:
+    """wgnn_keep_best: the reference's rule (src/main.py:83-86) on the device -- if float64(loss) < record.best_loss, the 8
+    tensors `params` are copied into `best_params` and best_loss / best_step = loss / `step`; no host synchronisation."""
+    keep_best_launch(keep_best_args(d, loss, params, best_params, record), step)
+
+
 def rows_align(d) -> int:
     """wgnn_bwd_rows_align: the row alignment of a range of wgnn_bwd_rows / wgnn_finish_rows; 0 = not offered for this shape."""
     return int(_lib.load().wgnn_bwd_rows_align(C.byref(d)))

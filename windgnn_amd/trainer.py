@@ -38,16 +38,33 @@ global L2 norm of the 8 gradients and min(1, max_grad_norm / (norm + 1e-6)) are 
 g * coefficient.  One rank: the norm is taken in the launch that reduces the deferred partial sums.  Data parallel: after the
 all-reduce, over the summed bucket -- which is the same on every rank, and the norm's summation order is fixed, so every rank
 derives the same coefficient without another collective.  The bucket keeps the UNCLIPPED gradient (torch clips .grad in place);
-`grad_norm` and `clip_coef` are views of the device values, overwritten by the next step like the loss."""
+`grad_norm` and `clip_coef` are views of the device values, overwritten by the next step like the loss.
+
+Best model (`keep_best`, opt-in): the reference keeps the parameters of its best step, src/main.py:83-86
+(`if loss.item() < best_loss: torch.save(model.state_dict(), PATH); best_loss = loss.item()`), which costs a device
+synchronisation and a host-driven copy per step.  With keep_best set every successful step ends with wgnn_keep_best
+(include/windgnn_best.h): the comparison (fp64, as Python's), best_loss / best_step and the copy of the 8 tensors into a second
+flat buffer all happen on the device.  The order is the reference's: the loss of the forward BEFORE the update decides, and the
+parameters AFTER optimizer.step() are what is kept (src/main.py:66-86), so the call follows the optimiser's launches of every
+schedule and carries step = `steps` after the increment.  Under data parallel the loss word is the all-reduced big-batch mean
+on every rank, so every rank takes the same decision without another collective.  `best_loss`, `best_step` and `improved`
+are views of the device record; best_state_dict() / restore_best() read the snapshot.
+
+Checkpoints: state_dict() / load_state_dict() carry what a TrainStep owns besides the parameters -- the Adam moments and step
+count in torch.optim.Adam's own layout (so a run can move between torch.optim.Adam on the drop-in module and TrainStep), the
+best record and snapshot, and the carried GRU state.  The parameters travel through model.state_dict() as before."""
 from __future__ import annotations
+
+import collections
 
 import torch
 
 from . import _lib
 from .distributed import HEADER, LOSS_SLOT, BucketExchange, grad_block_plan
-from .functional import (_forward_setup, bwd_rows, check_range_status, clip_buffer, clip_bytes, finish_clipped, finish_norm,
-                         finish_rows, finish_step, gcn_gru_backward_mse_raw, gcn_gru_forward_raw, gcn_gru_state_backward_raw,
-                         gcn_gru_state_forward_raw, mse_loss_grad, prepared_weights, refresh_prepared, rows_align)
+from .functional import (PARAM_ORDER, _forward_setup, best_bytes, best_init, best_word, bwd_rows, check_range_status,
+                         clip_buffer, clip_bytes, finish_clipped, finish_norm, finish_rows, finish_step,
+                         gcn_gru_backward_mse_raw, gcn_gru_forward_raw, gcn_gru_state_backward_raw, gcn_gru_state_forward_raw,
+                         keep_best_args, keep_best_launch, mse_loss_grad, prepared_weights, refresh_prepared, rows_align)
 from .modules import GCN_GRU
 
 AUTO_GRAD_BLOCKS = 8                # grad_blocks="auto": row blocks per GRU weight ...
@@ -57,7 +74,7 @@ AUTO_BLOCK_BYTES = 64 << 20         # ... from a gradient bucket of this size (s
 class TrainStep:
     def __init__(self, model: GCN_GRU, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  process_group=None, check_every: int = 100, overlap_collectives: bool = False, direct_rccl=None,
-                 rccl_loader=None, carry_state: bool = False, grad_blocks=None, max_grad_norm=None):
+                 rccl_loader=None, carry_state: bool = False, grad_blocks=None, max_grad_norm=None, keep_best=None):
         """carry_state: truncated BPTT over consecutive chunks -- each step starts the recurrence from the h_n of the previous
         step (detached; zeros on the first step and after reset_state()), so a model trained on chunks of a long series
         learns the carried-state regime StreamingForecaster(window=None) serves.  The batch size must stay the same
@@ -73,7 +90,13 @@ class TrainStep:
         max_grad_norm: None = no clipping (the schedules above, launch for launch); a value > 0 = clip the step's gradient
         by its global L2 norm as torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) would before the optimiser step
         (module docstring); float("inf") = measure only (`grad_norm`), nothing is scaled.  Not with overlap_collectives or
-        the blocked exchange, which step tensors before the whole bucket has arrived."""
+        the blocked exchange, which step tensors before the whole bucket has arrived.
+
+        keep_best: None = off (no buffer, no launch: the schedules above, launch for launch); True = keep the parameters of
+        the step with the smallest loss so far (threshold +inf: the first finite loss wins); a float = keep them only once
+        the loss falls below it (0.03 is the reference's initial best_loss, src/main.py:60).  As in the reference the loss
+        of the forward BEFORE the update decides and the parameters AFTER the optimiser step are kept (module docstring).
+        Every schedule takes it, the empty-shard step included."""
         if not getattr(model, "fused", True):
             raise RuntimeError("windgnn_amd: TrainStep drives the fused hot path, i.e. the reference model's own widths "
                                "(input_dim = hidden_dim = 13, src/main.py:41); a GCN_GRU of other widths trains through "
@@ -103,6 +126,13 @@ class TrainStep:
                                       else "grad_blocks=%r" % (grad_blocks,),
                                       "the GRU tensors" if overlap_collectives else "row blocks"))
         self.max_grad_norm = max_grad_norm
+        if keep_best is False:                          # off, as a user means it (not the threshold 0.0)
+            keep_best = None
+        if keep_best is not None:
+            keep_best = float("inf") if keep_best is True else float(keep_best)
+            if keep_best != keep_best:
+                raise ValueError("windgnn_amd: keep_best must be None, True or a loss threshold, got NaN")
+        self.keep_best = keep_best
         self._clip = None               # wgnn_finish_norm's buffer: sized at the first clipped step (wgnn_clip_bytes needs its dims)
         # gradient bucket with a 4-float header (16-byte aligned bucket): header[3] = the step's loss, so that the loss
         # rides in the conv-gradient all-reduce (the conv gradients are the first 364 floats of the bucket).  The blocked
@@ -131,6 +161,18 @@ class TrainStep:
         self.n_conv = sum(sizes[:4])
         self.lr, self.betas, self.eps = lr, betas, eps
         self.steps = 0
+        # keep_best: the snapshot (one more flat buffer, the 8 tensors at flat_p's offsets) and the device record
+        self._best = self._best_p = self._best_views = self._best_dims = self._best_call = None
+        if keep_best is not None:
+            self._best_p = torch.zeros_like(self.flat_p)
+            self._best_views = [t.view_as(p) for t, p in zip(self._best_p.split(sizes), self.params)]
+            self._best = torch.zeros(best_bytes(), dtype=torch.uint8, device=dev)
+            # sizes the 8 tensors for wgnn_keep_best (S, H and F only: B, T, the adjacency and the math mode do not enter)
+            self._best_dims = _lib.Dims(1, 1, self.params[4].shape[1] // 13, 13, self.params[5].shape[1], _lib.MATH_F32,
+                                        _lib.ADJ_CSR, 1, _lib.IO_F32)
+            self._reset_best(keep_best)
+            # the call's arguments but the step number: the views never move, so they are checked and marshalled once
+            self._best_call = keep_best_args(self._best_dims, self._loss, self.p_views, self._best_views, self._best)
         self.overlap_collectives = overlap_collectives
         # direct_rccl: None = only if WGNN_RCCL_DIRECT=1 (opt-in: distributed.DirectRccl); the two-collective form overlaps
         # through torch.distributed's own stream by design and never takes it
@@ -227,6 +269,150 @@ class TrainStep:
         VIEW, overwritten by the next step."""
         return self._clip_word(_lib.CLIP_COEF, "clip_coef")
 
+    def _reset_best(self, threshold, words=None):
+        """wgnn_best_init for `threshold`; `words`: public words to set after that (a checkpoint's)."""
+        best_init(self._best, threshold)
+        for name, value in (words or {}).items():
+            best_word(self._best, name).copy_(torch.as_tensor(value).reshape(()))
+
+    def _keep_best(self):
+        if self._best_call is not None:
+            keep_best_launch(self._best_call, self.steps)
+
+    def _best_word(self, name):
+        if self._best is None:
+            raise RuntimeError("windgnn_amd: TrainStep.%s is kept by a step with keep_best set (True, or a loss threshold); "
+                               "this TrainStep has keep_best=None" % name)
+        return best_word(self._best, name)
+
+    @property
+    def best_loss(self):
+        """The smallest loss that won so far (the threshold until one did): a 0-dim fp64 VIEW of the device record."""
+        return self._best_word("best_loss")
+
+    @property
+    def best_step(self):
+        """`steps` at the end of the step whose parameters are kept; -1: none yet.  A 0-dim int64 VIEW of the device record
+        (one read per epoch serves the reference's patience counter)."""
+        return self._best_word("best_step")
+
+    @property
+    def improved(self):
+        """1 if the last step's loss won, else 0: a 0-dim int32 VIEW of the device record, overwritten by the next step."""
+        return self._best_word("improved")
+
+    def best_state_dict(self):
+        """The kept parameters under the reference's eight keys in its order (clones: torch.save(tr.best_state_dict(), PATH)
+        writes what the reference's load_state_dict(torch.load(PATH)) takes), or None while nothing was kept.  One host
+        read (best_step): not for the per-step path."""
+        if int(self._best_word("best_step")) < 0:
+            return None
+        return collections.OrderedDict((k, v.clone()) for k, v in zip(PARAM_ORDER, self._best_views))
+
+    def restore_best(self):
+        """Copy the kept parameters over the model's (moments and step count stay); the staged W_ih images are rebuilt on
+        the next step.  Raises if nothing was kept."""
+        if int(self._best_word("best_step")) < 0:
+            raise RuntimeError("windgnn_amd: TrainStep.restore_best(): no step has beaten the threshold %r yet" % self.keep_best)
+        self.flat_p.copy_(self._best_p)
+        self.refresh()
+
+    def state_dict(self):
+        """What this step owns besides the parameters, as clones on its device:
+        "optimizer": torch.optim.Adam(model.parameters(), lr, betas, eps).state_dict()'s layout (state[i] = {step, exp_avg,
+        exp_avg_sq} for i in 0..7, one param group; hot_path_parameters() is in model.parameters() order);
+        "steps"; "best": None or the record's public words plus the snapshot under the reference's keys; "carry": the
+        carried [B, H] state or None.  The parameters are model.state_dict()'s."""
+        opt = torch.optim.Adam(self.params, lr=self.lr, betas=tuple(self.betas), eps=self.eps).state_dict()
+        opt["state"] = {i: {"step": torch.tensor(float(self.steps)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+                        for i, (m, v) in enumerate(zip(self.m_views, self.v_views))}
+        best = None
+        if self._best is not None:
+            best = {name: best_word(self._best, name).clone() for name in _lib.BEST_WORDS}
+            best.update((k, v.clone()) for k, v in zip(PARAM_ORDER, self._best_views))
+        return {"optimizer": opt, "steps": self.steps, "best": best, "carry": self.state}
+
+    def load_state_dict(self, sd):
+        """Takes state_dict()'s output or a bare torch.optim.Adam state dict (all eight `step` values must agree; an empty
+        `state` is step 0).  Moments are written into the existing flat buffers, lr / betas / eps restored, and from the full
+        form the best record + snapshot and the carried state.  Load the parameters with model.load_state_dict."""
+        full = "param_groups" not in sd
+        opt = sd["optimizer"] if full else sd
+        groups = opt["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != 8:
+            raise ValueError("windgnn_amd: TrainStep.load_state_dict: expected one Adam param group of 8 parameters, got %s"
+                             % [len(g["params"]) for g in groups])
+        grp = groups[0]
+        if grp.get("weight_decay", 0) != 0 or grp.get("amsgrad", False) or grp.get("maximize", False):
+            raise ValueError("windgnn_amd: TrainStep runs plain Adam (weight_decay = 0, amsgrad = maximize = False), got "
+                             "weight_decay=%r amsgrad=%r maximize=%r"
+                             % (grp.get("weight_decay"), grp.get("amsgrad"), grp.get("maximize")))
+        state = opt["state"]
+        steps = 0
+        if len(state):
+            if sorted(state) != list(range(8)):
+                raise ValueError("windgnn_amd: TrainStep.load_state_dict: Adam state for parameters %s, expected 0..7"
+                                 % sorted(state))
+            counts = [int(round(float(state[i]["step"]))) for i in range(8)]
+            if len(set(counts)) != 1:
+                raise ValueError("windgnn_amd: TrainStep.load_state_dict: the Adam `step` values disagree (%s): TrainStep "
+                                 "steps all 8 tensors together" % dict(zip(PARAM_ORDER, counts)))
+            steps = counts[0]
+            for i, key in enumerate(PARAM_ORDER):
+                for name, views in (("exp_avg", self.m_views), ("exp_avg_sq", self.v_views)):
+                    if tuple(state[i][name].shape) != tuple(views[i].shape):
+                        raise ValueError("windgnn_amd: TrainStep.load_state_dict: %s of %s is %s, expected %s"
+                                         % (name, key, tuple(state[i][name].shape), tuple(views[i].shape)))
+        if full and len(state) and int(sd["steps"]) != steps:
+            raise ValueError("windgnn_amd: TrainStep.load_state_dict: steps = %r but the Adam state is at step %d"
+                             % (sd["steps"], steps))
+        best, carry = (sd.get("best"), sd.get("carry")) if full else (None, None)
+        if best is not None:
+            if self._best is None:
+                raise RuntimeError("windgnn_amd: TrainStep.load_state_dict: the checkpoint carries a best record, but this "
+                                   "TrainStep has keep_best=None")
+            missing = [k for k in list(_lib.BEST_WORDS) + list(PARAM_ORDER) if k not in best]
+            if missing:
+                raise ValueError("windgnn_amd: TrainStep.load_state_dict: the best record lacks %s" % ", ".join(missing))
+            if float(best["best_loss"]) != float(best["best_loss"]):
+                raise ValueError("windgnn_amd: TrainStep.load_state_dict: the best record's best_loss is NaN")
+            for key, view in zip(PARAM_ORDER, self._best_views):
+                if tuple(best[key].shape) != tuple(view.shape):
+                    raise ValueError("windgnn_amd: TrainStep.load_state_dict: best %s is %s, expected %s"
+                                     % (key, tuple(best[key].shape), tuple(view.shape)))
+        if carry is not None:
+            H = self.p_views[5].shape[1]
+            if not self.carry_state:
+                raise RuntimeError("windgnn_amd: TrainStep.load_state_dict: the checkpoint carries a GRU state, but this "
+                                   "TrainStep has carry_state=False")
+            if carry.dim() != 2 or carry.shape[1] != H:
+                raise ValueError("windgnn_amd: TrainStep.load_state_dict: carry is %s, expected [B, %d]" % (tuple(carry.shape), H))
+        # everything checked: write
+        if len(state):
+            for i in range(8):
+                self.m_views[i].copy_(state[i]["exp_avg"])
+                self.v_views[i].copy_(state[i]["exp_avg_sq"])
+        else:
+            self.exp_avg.zero_()
+            self.exp_avg_sq.zero_()
+        self.steps = int(sd["steps"]) if full and not len(state) else steps
+        self.lr, self.betas, self.eps = grp["lr"], tuple(grp["betas"]), grp["eps"]
+        if self._best is not None and full:
+            if best is None:
+                self._reset_best(self.keep_best)
+            else:
+                self._reset_best(float(best["best_loss"]), {name: best[name] for name in _lib.BEST_WORDS})
+                for key, view in zip(PARAM_ORDER, self._best_views):
+                    view.copy_(best[key])
+        if full and self.carry_state:
+            if carry is None:
+                self._has_state = False
+            else:
+                if self._hbuf is None or self._hbuf.shape[1] != carry.shape[0]:
+                    self._hbuf = torch.zeros(2, carry.shape[0], carry.shape[1], dtype=torch.float32, device=self.device)
+                self._hbuf[self._hcur].copy_(carry)
+                self._has_state = True
+
     def _empty_shard_step(self, A, X, n_global):
         """This rank has no windows in this step: zero bucket, the same collectives as every other rank, the optimiser's
         launch(es) on the summed gradient.  Returns (big-batch mean loss, empty Y)."""
@@ -254,6 +440,7 @@ class TrainStep:
             wconv.wait()
             finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_CONV, adam, pre, self.device)
         self.steps += 1
+        self._keep_best()
         return self._loss, torch.empty(0, T, H, dtype=X.dtype, device=X.device)
 
     def _blocked_adam(self, d, works, wtail, pre):
@@ -430,6 +617,7 @@ class TrainStep:
                                          prepared=pre)
             self._tail(d, 6, pre)                                                                      # :79 tail + :80
         self.steps += 1                         # only a step whose launches were all accepted counts
+        self._keep_best()                       # src/main.py:83-86, after the optimiser's launches of every schedule
         if self.check_every and self.steps % self.check_every == 0 and (
                 self.model.math != _lib.MATH_F32 or (self.exchange is not None and self.exchange.direct is not None)):
             self.check()
