@@ -1,0 +1,237 @@
+"""The per-instance table of tests/instance_cases.py without a GPU: every instance key of every family is claimed by exactly
+one case (or listed as unreachable, with the line of api.hip that excludes it), the integer lists of the table are the lists
+in the launcher sources (extracted as text: a pattern that stops matching fails), and the Python selection formulas put every
+case on the key it claims.  The library's host-only queries confirm what they can: it sizes a workspace for every case's
+dims, refuses the refused ones, and its split-K counts are the formulas'."""
+import ctypes
+import os
+import re
+
+import pytest
+
+import instance_cases as ic
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "windgnn_amd", "csrc")
+MATH = {"f32": 0, "f16x3": 1, "f16": 2, "f16x3g": 3}
+IO = {"f32": 0, "f16": 1, "bf16": 2}
+# (T, B) of the cases: the plain pair, the first batch of gru.hip's recurrences, and the thresholds named above CASES
+PLAIN_TB = {(2, 17), (3, 17), (2, 33)}          # (2, 33): one-pass fp16 cases grown once (see F16_EXCEPTIONS)
+THRESHOLD_TB = {(2, 769), (2, 2049), (2, 3073), (3, 1025), (3, 5473), (3, 8161), (24, 1537)}
+
+
+def _read(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return f.read()
+
+
+def _body(src, signature):
+    """The text of the function whose definition starts with `signature`, up to its closing brace in column 0."""
+    i = src.find(signature)
+    assert i >= 0, "no %r in the source any more" % signature
+    j = src.find("\n}\n", i)
+    assert j > i, signature
+    return src[i:j]
+
+
+def _ints(pattern, text, what):
+    found = re.findall(pattern, text)
+    assert found, "the pattern for %s matches nothing any more: %r" % (what, pattern)
+    return [int(x) for x in found]
+
+
+def source_lists(read=_read):
+    """name of a list of tests/instance_cases.py -> that list as the launcher sources have it."""
+    gru, grux, small, gcnx, gcngi, gcn32, pgemm, gemm32 = (read(n + ".hip") for n in (
+        "gru", "grux", "gru_small", "gcnx", "gcngi", "gcn32", "pgemm", "gemm32"))
+    out = {}
+    for name in ("FWD_KS", "BWD_KS3"):
+        init = re.search(r"const int %s\[\] = \{([^}]*)\};" % name, gru)
+        assert init, "no initialiser of %s in gru.hip any more" % name
+        out["GRU_" + name] = [int(x) for x in init.group(1).split(",")]
+    out["GRU_FWD_KS cases"] = _ints(r"FCASE\((\d+)\);", _body(gru, "int launch_gru_fwd("), "gru.hip FCASE")
+    out["GRU_BWD_KS3 cases"] = _ints(r"BCASE\((\d+)\);", _body(gru, "int launch_gru_bwd("), "gru.hip BCASE")
+    out["GRUX_FWD_K"] = _ints(r"case (\d+): FCASE\(\1\);", _body(grux, "int launch_grux_fwd("), "grux.hip FCASE")
+    out["GRUX_BWD_K"] = _ints(r"case (\d+): BCASE\(\1\);", _body(grux, "int launch_grux_bwd("), "grux.hip BCASE")
+    hmax = re.search(r"static int small_hmax\(int H\) \{ return ([^;]*); \}", small)
+    assert hmax, "no one-line small_hmax in gru_small.hip any more"
+    pairs = re.findall(r"H <= (\d+) \? (\d+) :", hmax.group(1))
+    assert pairs and re.fullmatch(r"(?:H <= \d+ \? \d+ : )+\d+", hmax.group(1)), hmax.group(1)
+    out["SMALL_HMAX_UPTO"] = [int(a) for a, _ in pairs]
+    out["SMALL_HMAX"] = [int(b) for _, b in pairs] + [int(hmax.group(1).rsplit(":", 1)[1])]
+    dispatch = _body(small, "#define SMALL_DISPATCH(KERNEL, ...)")
+    out["SMALL_HMAX cases"] = (_ints(r"case (\d+): SMALL_GO\(KERNEL, \1,", dispatch, "gru_small.hip SMALL_GO")
+                               + _ints(r"default: SMALL_GO\(KERNEL, (\d+),", dispatch, "gru_small.hip SMALL_GO default"))
+    out["GCNX_NT"] = _ints(r"case (\d+): FWD_CASE\(\1\);", _body(gcnx, "int launch_gcnx2_fwd("), "gcnx.hip FWD_CASE")
+    out["GCNX_NT bwd"] = _ints(r"case (\d+): BWD_CASE\(\1\);", _body(gcnx, "int launch_gcnx2_bwd("), "gcnx.hip BWD_CASE")
+    out["GCNGI_NT"] = _ints(r"case (\d+): GG_CASE\(\1\);", _body(gcngi, "int launch_gcngi_fwd("), "gcngi.hip GG_CASE")
+    out["GCN32_NT"] = _ints(r"case (\d+): FCASE\(\1\);", _body(gcn32, "int launch_gcn32_fwd("), "gcn32.hip FCASE")
+    bwd32 = _body(gcn32, "int launch_gcn32_bwd(")
+    out["GCN32_NT bwd"] = _ints(r"case (\d+): (?:BCASE\(\1\)|BLAUNCH\(\1, 12\));", bwd32, "gcn32.hip BCASE")
+    out["GCN32 16 waves"] = _ints(r"case (\d+): BCASE\(\1\);", bwd32, "gcn32.hip BCASE")
+    out["PGEMM_NT_T"] = _ints(r"NT_CASE\((\d+)\)", _body(pgemm, "int launch_pgemm_nt("), "pgemm.hip NT_CASE")
+    out["PGEMM_TN_T"] = _ints(r"TN_CASE\((\d+)\)", _body(pgemm, "int launch_pgemm_tn("), "pgemm.hip TN_CASE")
+    tn2 = _body(pgemm, "int launch_pgemm_tn2(")
+    out["TN2_TI"] = _ints(r"TN2_ROW\((\d+)\)", tn2, "pgemm.hip TN2_ROW")
+    out["TN2_TH"] = _ints(r"TN2_CASE\(ti, (\d+)\)", tn2, "pgemm.hip TN2_CASE")
+    out["two-source A: T <="] = _ints(r"if constexpr \(T <= (\d+)\)", _body(pgemm, "static int launch_tn_t("), "pgemm.hip a2")
+    nt32 = _body(gemm32, "int launch_gemm32_nt(")
+    head, found, forms = nt32.partition("if (big) {")
+    big, _, small32 = forms.partition("return WGNN_ERR_SHAPE;")
+    assert found and "launch_nt_t<4, 2, t>" in big and "launch_nt_t<1, t, 1>" in small32
+    out["GEMM32_NT_BIG_T"] = _ints(r"NT_CASE\((\d+)\)", big, "gemm32.hip NT_CASE (128 rows)")
+    out["GEMM32_NT_SMALL_T"] = _ints(r"NT_CASE\((\d+)\)", small32, "gemm32.hip NT_CASE (32 rows)")
+    out["GEMM32_TN_T"] = _ints(r"TN_CASE\((\d+)\)", _body(gemm32, "int launch_gemm32_tn("), "gemm32.hip TN_CASE")
+    return out
+
+
+def table_lists():
+    """The same names from the table."""
+    t = {n: getattr(ic, n) for n in ("GRU_FWD_KS", "GRU_BWD_KS3", "GRUX_FWD_K", "GRUX_BWD_K", "SMALL_HMAX_UPTO", "SMALL_HMAX",
+                                     "GCNX_NT", "GCNGI_NT", "GCN32_NT", "PGEMM_NT_T", "PGEMM_TN_T", "TN2_TI", "TN2_TH",
+                                     "GEMM32_NT_BIG_T", "GEMM32_NT_SMALL_T", "GEMM32_TN_T")}
+    t["GRU_FWD_KS cases"], t["GRU_BWD_KS3 cases"] = ic.GRU_FWD_KS, ic.GRU_BWD_KS3
+    t["SMALL_HMAX cases"], t["GCNX_NT bwd"], t["GCN32_NT bwd"] = ic.SMALL_HMAX, ic.GCNX_NT, ic.GCN32_NT
+    t["GCN32 16 waves"] = sorted({int(re.search(r"<(\d+)>", k).group(1)) for k in ic.FAMILIES["gcn32_bwd_kernel"] if "w=16" in k})
+    t["two-source A: T <="] = [max(int(re.search(r"<(\d+)", k).group(1)) for k in ic.FAMILIES["pgemm_tn_kernel"] if "a2=1" in k)]
+    return t
+
+
+def coverage_problems(cases):
+    """What is wrong with `cases` as a cover of ic.FAMILIES: a list of sentences, empty when every key is claimed once."""
+    bad = []
+    claimed = {}
+    for c in cases:
+        fam, key = c[0], c[1]
+        if ic.family_of(key) != fam or key not in ic.FAMILIES.get(fam, ()):
+            bad.append("%s is no key of family %s" % (key, fam))
+        if key in claimed:
+            bad.append("%s is claimed twice" % key)
+        claimed[key] = c
+    for fam, keys in ic.FAMILIES.items():
+        if len(set(keys)) != len(keys):
+            bad.append("family %s lists a key twice" % fam)
+        for key in keys:
+            where = [n for n, d in (("CASES", claimed), ("UNREACHABLE", ic.UNREACHABLE), ("BEYOND_BUDGET", ic.BEYOND_BUDGET))
+                     if key in d]
+            if fam == "pgemm_tn2_kernel" and key not in ic.TN2_REQUIRED:
+                continue                                           # all 28 pairs are not required (see below)
+            if len(where) != 1:
+                bad.append("%s is in %s" % (key, where or "no list"))
+    for key in list(ic.UNREACHABLE) + list(ic.BEYOND_BUDGET):
+        if not any(key in keys for keys in ic.FAMILIES.values()):
+            bad.append("%s is excluded but no family lists it" % key)
+    # the merged launch: every TI and every TH at least once per pass mode and per-window form, TI > TH and TI < TH among them
+    for sfx in ("", ",x2", ",f16"):
+        for pw in (0, 1):
+            pairs = [tuple(int(x) for x in m.groups()) for m in
+                     (re.fullmatch(r"pgemm_tn_kernel<(\d+)\+(\d+)%s>\|pw=%d" % (sfx, pw), k) for k in claimed) if m]
+            if {a for a, _ in pairs} != set(ic.TN2_TI) or {b for _, b in pairs} != set(ic.TN2_TH):
+                bad.append("merged launch %r pw=%d: not every TI and TH is run: %s" % (sfx, pw, pairs))
+            if not any(a > b for a, b in pairs) or not any(a < b for a, b in pairs):
+                bad.append("merged launch %r pw=%d: TI > TH and TI < TH must both occur" % (sfx, pw))
+    return bad
+
+
+def test_every_instance_key_is_claimed_by_exactly_one_case():
+    assert coverage_problems(ic.CASES) == []
+    assert len(ic.CASES) == len({c[1] for c in ic.CASES})
+    assert set(ic.TN2_REQUIRED) <= set(ic.FAMILIES["pgemm_tn2_kernel"])
+
+
+def test_the_integer_lists_are_those_of_the_launcher_sources():
+    src, tab = source_lists(), table_lists()
+    assert set(src) == set(tab)
+    for name in src:
+        assert src[name] == tab[name], (name, src[name], tab[name])
+    # the name launch_gemm_f32 builds at run time
+    assert '"gemm_f32_kernel<%d,%d>[%s%s%s]"' in _read("gemm.hip")
+    for n in ic.GEMM_F32_NAMES:
+        assert re.fullmatch(r"gemm_f32_kernel<(64|128),(64|128)>\[(kk|kn|tn)(,ones)?(,shift)?\]", n), n
+
+
+def test_the_checks_notice_a_deleted_case_and_a_new_instantiation():
+    for i in (0, len(ic.CASES) // 2, len(ic.CASES) - 1):
+        assert coverage_problems(ic.CASES[:i] + ic.CASES[i + 1:]), ic.CASES[i]
+    assert coverage_problems(ic.CASES + [ic.CASES[0]])
+
+    def grown(name):                                             # gru.hip with one more entry in FWD_KS
+        text = _read(name)
+        return text.replace("26, 28, 32};", "26, 28, 32, 36};") if name == "gru.hip" else text
+    assert grown("gru.hip") != _read("gru.hip")
+    assert source_lists(grown)["GRU_FWD_KS"] != table_lists()["GRU_FWD_KS"]
+    with pytest.raises(AssertionError):                          # a launcher that no longer reads as the pattern expects
+        source_lists(lambda name: _read(name).replace("NT_CASE(", "NT_ROW("))
+
+
+def test_selection_formulas_put_every_case_on_its_key():
+    for fam, key, S, T, B, H, math, io, state, route in ic.CASES:
+        assert ic.refusal(S, T, B, H, math, io) is None, key
+        keys = ic.plan(S, T, B, H, math, io, state, route)
+        assert key in keys, (key, keys)
+        assert all(any(k in f for f in ic.FAMILIES.values()) for k in keys), (key, keys)
+        assert not set(keys) & set(ic.UNREACHABLE), key
+        # the shape rules: T = 2 or 3 and B = 17 unless a threshold selects; B = 1 (mod 16) always
+        assert B % 16 == 1 and ((T, B) in PLAIN_TB or (T, B) in THRESHOLD_TB), key
+        assert route in ic.ROUTES and not (state and route in ("fused", "infer")), key
+    for key, (S, T, B, H, math) in ic.BEYOND_BUDGET.items():
+        assert key in ic.plan(S, T, B, H, math), key
+    # every H and S the fast kernels take selects an instance the launchers have
+    for H in range(1, 129):
+        assert ic.gru_fwd_k(H) in ic.GRU_FWD_KS and ic.gru_bwd_k(H) in ic.GRU_BWD_KS3 and ic.small_hmax(H) in ic.SMALL_HMAX
+        if H <= 127:
+            assert ic.grux_fwd_k(H) in ic.GRUX_FWD_K and ic.grux_bwd_k(H) in ic.GRUX_BWD_K
+            assert ic.pgemm_tn_shape(H + 1)[1] in ic.TN2_TH
+    for S in range(1, 65):
+        assert ic.gcn_nt(S) in ic.GCNX_NT and ic.pgemm_tn_shape(13 * S + 1)[1] in ic.TN2_TI
+        assert not ic.gcngi_supported(S, 4, False) or ic.gcn_nt(S) in ic.GCNGI_NT
+        assert not ic.gcngi_supported(S, 4, True) or ic.gcngi_supported(S, 4, False)      # (the split modes' g rows are twice as long)
+
+
+def test_no_call_form_reaches_an_excluded_key():
+    """A grid over the thresholds of every selection: nothing plan() emits is listed as unreachable, and everything it emits
+    is a key of a family.  The lines of api.hip the exclusions cite still say what they are cited for."""
+    api = _read("api.hip").splitlines()
+    for key, (why, line, word) in ic.UNREACHABLE.items():
+        assert word in api[line - 1], (key, line, api[line - 1])
+    allkeys = {k for keys in ic.FAMILIES.values() for k in keys}
+    for T, B in sorted(PLAIN_TB | THRESHOLD_TB):
+        for S in (1, 5, 17, 33, 34, 35, 49, 60, 64):
+            for H in (4, 31, 64, 100, 127, 128, 129, 160, 225, 240):
+                for math in ic.MATHS:
+                    for io in ("f32", "bf16"):
+                        if ic.refusal(S, T, B, H, math, io):
+                            continue
+                        for state, route in ((0, "train"), (0, "unmerged"), (0, "fused"), (0, "infer"), (1, "train"), (1, "unmerged")):
+                            keys = set(ic.plan(S, T, B, H, math, io, bool(state), route))
+                            assert keys <= allkeys and not keys & set(ic.UNREACHABLE), (S, T, B, H, math, io, state, route)
+
+
+def test_the_library_accepts_every_case_and_splits_k_as_the_formulas_do():
+    from windgnn_amd import _lib as L
+    from windgnn_amd import build
+    build.build(verbose=False)
+    lib = L.load()
+    seen = set()
+    for fam, key, S, T, B, H, math, io, state, route in ic.CASES:
+        dims = (S, T, B, H, math, io, state)
+        if dims in seen:
+            continue
+        seen.add(dims)
+        d = L.Dims(B, T, S, 13, H, MATH[math], 0, 0, IO[io])
+        assert lib.wgnn_workspace_bytes(ctypes.byref(d)) > 0, key
+        if math == "f32":
+            continue
+        i = L.tn_split(d, state=state)
+        BT, I, G3 = B * T, 13 * S, 3 * H
+        reg = H <= 127                                            # the register-resident recurrence: [dGI_r | dGI_z | pad | dGHn]
+        m_hh = 8 * ic.cdiv(2 * H, 8) + 8 * ic.cdiv(H, 8) if reg else G3
+        tiles_ih = ic.cdiv(G3, 320) * ic.pgemm_tn_shape(I + 1)[0]
+        tiles_hh = ic.cdiv(m_hh, 320) * ic.pgemm_tn_shape(H + 1)[0]
+        assert (i.sk_ih, i.sk_hh) == (ic.pick_splitk(BT, tiles_ih, 256, 64), ic.pick_splitk(BT, tiles_hh, 256, 64)), key
+        assert i.merged == int(reg), key
+    # refused by design: 16-bit I/O outside the fp16-plane family with the register-resident GRU, a dense graph above 64
+    for S, T, B, H, math, io in ((1, 2, 17, 128, "f16", "bf16"), (1, 2, 17, 128, "f16x3", "f16"), (1, 2, 17, 4, "f32", "bf16"),
+                                 (65, 2, 17, 4, "f16x3", "f32")):
+        assert ic.refusal(S, T, B, H, math, io)
+        assert lib.wgnn_workspace_bytes(ctypes.byref(L.Dims(B, T, S, 13, H, MATH[math], 0, 0, IO[io]))) == 0
