@@ -1,5 +1,5 @@
 """ctypes binding of libwindgnn_hip.so (the C ABI declared in include/windgnn.h, windgnn_optim.h, windgnn_sched.h,
-windgnn_eval.h and windgnn_best.h).
+windgnn_eval.h, windgnn_best.h and windgnn_series.h).
 
 The library is the product: there is no CPU or eager-PyTorch fallback.  If the shared object is
 missing or a call fails this module raises, loudly."""
@@ -167,6 +167,27 @@ EXPORTS_BEST = {
                                  C.c_void_p]),
 }
 
+# include/windgnn_series.h: the model on the sliding windows of one series (a sixth header and table, as above)
+SERIES_VERSION = 1          # WGNN_SERIES_VERSION
+
+
+class SeriesDims(C.Structure):
+    # wgnn_series_dims
+    _fields_ = [(n, C.c_int32) for n in ("rows", "T", "stride", "n", "S", "F", "H", "math", "adj_format", "nnz", "io")]
+
+
+EXPORTS_SERIES = {
+    "wgnn_series_version": (C.c_int, []),
+    "wgnn_series_workspace_bytes": (C.c_size_t, [C.POINTER(SeriesDims)]),
+    "wgnn_series_stash_bytes": (C.c_size_t, [C.POINTER(SeriesDims)]),
+    "wgnn_series_fwd": (C.c_int, [C.POINTER(SeriesDims), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wgnn_series_fwd_last": (C.c_int, [C.POINTER(SeriesDims), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_float, C.c_float,
+                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wgnn_series_bwd": (C.c_int, [C.POINTER(SeriesDims), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.POINTER(Grads), C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -214,6 +235,16 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    if not hasattr(lib, "wgnn_series_version"):
+        raise RuntimeError("windgnn_amd: %s predates include/windgnn_series.h (no wgnn_series_version): rebuild it with "
+                           "`python -m windgnn_amd.build --force`" % LIB_PATH)
+    for name, (res, args) in EXPORTS_SERIES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.wgnn_series_version() < SERIES_VERSION:
+        raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_series_version %d < %d)"
+                           % (lib.wgnn_series_version(), SERIES_VERSION))
     if lib.wgnn_best_version() < BEST_VERSION:
         raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_best_version %d < %d)"
                            % (lib.wgnn_best_version(), BEST_VERSION))

@@ -10,10 +10,11 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libwindgnn_hip.so")
-SOURCES = ["api.hip", "finish.hip", "gcn.hip", "gemm.hip", "gru.hip", "train_ops.hip", "prof.hip", "gcnx.hip", "grux.hip", "pgemm.hip", "data_ops.hip", "general.hip", "gru_small.hip", "gcn32.hip", "gemm32.hip", "gcngi.hip", "pgemm_big.hip", "gcn_any.hip", "gru_step.hip", "eval.hip", "best.hip"]
+SOURCES = ["api.hip", "finish.hip", "gcn.hip", "gemm.hip", "gru.hip", "train_ops.hip", "prof.hip", "gcnx.hip", "grux.hip", "pgemm.hip", "data_ops.hip", "general.hip", "gru_small.hip", "gcn32.hip", "gemm32.hip", "gcngi.hip", "pgemm_big.hip", "gcn_any.hip", "gru_step.hip", "eval.hip", "best.hip", "series.hip"]
 HEADERS = ["common.h", "gcnx_dev.h", os.path.join("..", "..", "include", "windgnn.h"),
            os.path.join("..", "..", "include", "windgnn_optim.h"), os.path.join("..", "..", "include", "windgnn_sched.h"),
-           os.path.join("..", "..", "include", "windgnn_eval.h"), os.path.join("..", "..", "include", "windgnn_best.h")]
+           os.path.join("..", "..", "include", "windgnn_eval.h"), os.path.join("..", "..", "include", "windgnn_best.h"),
+           os.path.join("..", "..", "include", "windgnn_series.h")]
 # -amdgpu-mfma-vgpr-form: MFMA accumulators live in VGPRs, so no v_accvgpr_read per value in the VALU-bound
 # GCN/GRU kernels (gcnx_bwd -8 %).  Safe only because every first read of an MFMA result is a compiler-visible
 # instruction (see split2 in gcnx.hip).

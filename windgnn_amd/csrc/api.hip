@@ -70,7 +70,7 @@ int pick_splitk(size_t BT, int tiles, int target_wgs, int min_rows) {
 // the split-fp16 modes whose products take three passes (hi x hi + hi x lo + lo x hi); f16 takes one, f32 none
 bool three_pass(const wgnn_dims* d) { return d->math == WGNN_MATH_F16X3 || d->math == WGNN_MATH_F16X3G; }
 
-Layout make_layout(const wgnn_dims* d, bool state = false) {
+Layout make_layout(const wgnn_dims* d, bool state = false, int series = SER_NONE /*SER_FRONT / SER_REC: common.h*/) {
   Layout L;
   L.state = state;
   L.x3 = d->math != WGNN_MATH_F32;                                      // the fp16-plane kernel family
@@ -91,21 +91,21 @@ Layout make_layout(const wgnn_dims* d, bool state = false) {
   // exact fp32 at large B*T: the big-tile GEMMs of gemm32.hip on zero-padded copies of W_ih / W_ih^T
   L.g32 = !x3 && !L.gen_gcn && !L.gen_gru && gemm32_nt_supported(L.BT, (int)L.Ip, (int)L.Gp);
   L.g32tn = L.g32 && gemm32_tn_supported(L.BT);          // the split-K dW products (same threshold today)
-  L.small = !x3 && !L.gen_gru && gru_small_supported(d->B, d->H);
+  L.small = !x3 && !L.gen_gru && !series && gru_small_supported(d->B, d->H);
   L.rec32 = !x3 && !L.gen_gru && !L.small;
   // the images of W_ih the GEMMs stage: sized from S and H alone (the exact-fp32 ones are USED from B*T >= 4096 only),
   // so that a caller-kept copy (wgnn_params.prepared) serves every batch size
   const bool g32_shape = !x3 && !L.gen_gcn && !L.gen_gru && gemm32_nt_supported(1u << 30, (int)L.Ip, (int)L.Gp);
-  const size_t planes_f = x3 ? (size_t)L.np_g3 * L.Ip : (g32_shape ? (size_t)gemm32_nt_rows((int)L.G3) * L.Ip : 0);   // 2 planes of halfs = that many floats
-  const size_t planes_b = x3 ? (size_t)L.np_i * L.Gp : (g32_shape ? (size_t)gemm32_nt_rows((int)L.I) * L.Gp : 0);
+  const size_t planes_f = ser_front(series, x3 ? (size_t)L.np_g3 * L.Ip : (g32_shape ? (size_t)gemm32_nt_rows((int)L.G3) * L.Ip : 0));   // 2 planes of halfs = that many floats
+  const size_t planes_b = ser_front(series, x3 ? (size_t)L.np_i * L.Gp : (g32_shape ? (size_t)gemm32_nt_rows((int)L.I) * L.Gp : 0));
   L.prep_kind = x3 ? 1 : (g32_shape ? 2 : 0);
   L.prep_f = 0;
   L.prep_b = al(planes_f);
   L.prep_floats = L.prep_kind ? al(planes_f) + al(planes_b) : 0;
   constexpr size_t HDR = WGNN_STATUS_BYTES / sizeof(float);   // status block at the start of the workspace
   size_t o = HDR;
-  L.ws_GI = o; o += al(L.BT * L.Gp);   // rows padded to 128-B multiples
-  L.ws_g = o; o += al(L.BT * L.Ip);    // fp32 g (f32 mode) or its two fp16 planes (f16x3): same bytes
+  L.ws_GI = o; o += al(ser_front(series, L.BT * L.Gp));   // rows padded to 128-B multiples
+  L.ws_g = o; o += al(ser_front(series, L.BT * L.Ip));    // fp32 g (f32 mode) or its two fp16 planes (f16x3): same bytes
   L.ws_planes_f = o; o += al(planes_f);
   L.np_h = pgemm_nt_np((int)L.H);
   L.ws_gh = o; o += al(L.gen_gru ? (size_t)d->B * L.Gp : 0);
@@ -114,7 +114,7 @@ Layout make_layout(const wgnn_dims* d, bool state = false) {
   L.ws_hhp_f = o; o += al(L.gen_gru && x3 ? (size_t)L.np_g3 * L.Hp : 0);    // split(W_hh | b_hh)
   L.ws_kp_f = o; o += al(L.gen_gru && x3 ? pgemm_nt_kpart_floats(d->B, (int)L.Gp, (int)L.Hp) : 0);
   L.ws_hc = o; o += al(L.gen_gru && x3 ? (size_t)d->B * L.Hp : 0);          // compact planes of h_{t-1}
-  L.ws_xtail_f = o; o += al((L.I & 1) && !L.gen_gcn ? L.I + 1 : 0);        // private copy of X's last tile (odd S*13: see xtail_copy)
+  L.ws_xtail_f = o; o += al(ser_front(series, (L.I & 1) && !L.gen_gcn ? L.I + 1 : 0));        // private copy of X's last tile (odd S*13: see xtail_copy)
   // wgnn_fwd_last where the recurrence writes all of Y: wgnn_fwd_last has no stash, so g lives in ws_g and is dead once GI
   // is formed -- Y aliases it whenever it fits (H <= Ip: always when H = 3S), and only otherwise gets a region of its own
   if ((x3 && !L.gen_gru) || L.rec32 || L.H <= L.Ip) { L.ws_Ylast = L.ws_g; }
@@ -123,30 +123,30 @@ Layout make_layout(const wgnn_dims* d, bool state = false) {
   L.ws_aimg_f = o; o += al(x3 ? pgemm_nt256_aimg_bytes((int)L.BT, (int)L.G3, (int)L.Ip, 2) / 4 : 0);
   {
     const int sk = (!x3 && !L.g32 && L.BT < 65536) ? gemm_f32_nt_splitk((int)L.BT, (int)L.G3, (int)L.I) : 1;
-    L.ws_ntk_f = o; o += al(sk > 1 ? (size_t)sk * L.BT * L.G3 : 0);
+    L.ws_ntk_f = o; o += al(ser_front(series, sk > 1 ? (size_t)sk * L.BT * L.G3 : 0));
   }
   L.fwd_floats = o;
   o = 0;
-  L.st_g = o; o += al(L.BT * L.Ip);
+  L.st_g = o; o += al(ser_front(series, L.BT * L.Ip));
   {  // r, z, n, gh_n of every step: [B*T][4H] fp32, or the register-resident recurrences' own record layout
-    const size_t plain = L.BT * 4 * L.H, rec = (x3 && !L.gen_gru) ? grux_gates_floats(d->B, d->T, d->H, d->io)
+    const size_t plain = L.BT * 4 * L.H, grec = (x3 && !L.gen_gru) ? grux_gates_floats(d->B, d->T, d->H, d->io)
                                                                    : (L.rec32 ? gru_gates_floats(d->B, d->T, d->H) : 0);
-    L.st_gates = o; o += al(plain > rec ? plain : rec);
+    L.st_gates = o; o += al(series == SER_FRONT ? 0 : series == SER_REC ? grec : (plain > grec ? plain : grec));
   }
   L.plane_rows = L.BT + (state ? (size_t)d->B : 1);
   L.st_yp = o; o += al(L.plane_rows * L.Hp);   // two planes of B*T + 1 rows (state stash: B*T + B)
   L.st_h1 = o; o += al(L.gen_gcn ? L.BT * L.I : 0);
   {  // partial pairs (sum | max) + the tag word: one pair per workgroup of the forward recurrence (B / 16, or B for gru_small)
     const size_t nb = L.small ? (size_t)gru_small_blocks(d->B) : (size_t)grux_blocks(d->B);
-    L.st_stats = o; o += al(2 * nb + 4);
+    L.st_stats = o; o += al(series ? 0 : 2 * nb + 4);   // (the series entry points take dY: no fused loss)
   }
   // split fp16 modes with the register-resident recurrence: the gate records hold r | z | gh_n only and the BPTT kernel forms
   // n = tanh(gi_n + r gh_n) from GI, so GI (which the projection GEMM writes anyway) goes into the stash, not the workspace
   L.gi_stash = (x3 && !L.gen_gru && three_pass(d)) || L.rec32;   // (and gru.hip's)
-  L.st_GI = o; o += al(L.gi_stash ? L.BT * L.Gp : 0);
+  L.st_GI = o; o += al(ser_front(series, L.gi_stash ? L.BT * L.Gp : 0));
   L.hq = (int)rup(L.H + 1, 16);
   const bool hprev_rows = L.g32tn || (state && !x3);                // (the state stash: every exact-fp32 path)
-  L.st_hprev = o; o += al(hprev_rows ? L.BT * (size_t)L.hq : 0);   // [Hprev|1] with 16-byte aligned rows (exact fp32, large B*T)
+  L.st_hprev = o; o += al(ser_rec(series, hprev_rows ? L.BT * (size_t)L.hq : 0));   // [Hprev|1] with 16-byte aligned rows (exact fp32, large B*T)
   L.st_h0 = o; o += al(state ? (size_t)d->B * L.H : 0);
   L.stash_floats = o;
   L.dghn = (x3 && !L.gen_gru) || (L.rec32 && L.g32tn);
@@ -193,14 +193,14 @@ Layout make_layout(const wgnn_dims* d, bool state = false) {
   }
   o = HDR;
   L.ws_dGI = o; o += al(L.BT * L.Gp);   // fp32, or hi+lo fp16 planes (same bytes)
-  L.ws_dGH = o; o += al(L.dghn ? L.BT * (size_t)L.hn : L.BT * L.Gp);   // dGHn planes, or full dGH (general GRU / f32)
-  L.ws_dg = o; o += al(L.BT * L.Id);
-  L.ws_part_ih = o; o += al(part_ih);     // separate regions: with WGNN_BWD_DEFER both stay live until wgnn_finish
-  L.ws_part_hh = o; o += al(part_hh);
+  L.ws_dGH = o; o += al(ser_rec(series, L.dghn ? L.BT * (size_t)L.hn : L.BT * L.Gp));   // dGHn planes, or full dGH (general GRU / f32)
+  L.ws_dg = o; o += al(ser_front(series, L.BT * L.Id));
+  L.ws_part_ih = o; o += al(ser_front(series, part_ih));     // separate regions: with WGNN_BWD_DEFER both stay live until wgnn_finish
+  L.ws_part_hh = o; o += al(ser_rec(series, part_hh));
   {
     size_t a = gcn32_bwd_partial_floats((int)L.BT), b = gcnx2_bwd_partial_floats((int)L.BT);
     if (L.gen_gcn) a = gcn_csr_bwd_partial_floats();
-    L.ws_gcnpart = o; o += al(a > b ? a : b);
+    L.ws_gcnpart = o; o += al(ser_front(series, a > b ? a : b));
   }
   L.ws_du = o; o += al(L.gen_gcn ? L.BT * L.I : 0);
   L.ws_dhz = o; o += al(L.gen_gru ? (size_t)d->B * L.H : 0);
@@ -210,12 +210,12 @@ Layout make_layout(const wgnn_dims* d, bool state = false) {
   L.ws_dc = o; o += al(L.gen_gru && x3 ? (size_t)d->B * L.Gp : 0);          // compact planes of dgh_t
   L.ws_planes_b = o; o += al(planes_b);
   L.ws_scales = o; o += al(4096);          // 3 scales, then up to 2 x 1024 block partials from offset 64
-  L.ws_dY = o; o += al(L.BT * L.H);          // wgnn_bwd_mse_part outside the fused kernel: dY lives here
-  L.ws_xtail_b = o; o += al((L.I & 1) && !L.gen_gcn ? L.I + 1 : 0);
+  L.ws_dY = o; o += al(series ? 0 : L.BT * L.H);          // wgnn_bwd_mse_part outside the fused kernel: dY lives here
+  L.ws_xtail_b = o; o += al(ser_front(series, (L.I & 1) && !L.gen_gcn ? L.I + 1 : 0));
   L.ws_aimg_b = o; o += al(x3 ? pgemm_nt256_aimg_bytes((int)L.BT, (int)L.I, (int)L.Gp, 2) / 4 : 0);   // dGI's planes as an image (dg GEMM)
   {
     const int sk = (!x3 && !L.g32 && L.BT < 65536) ? gemm_f32_nt_splitk((int)L.BT, (int)L.I, (int)L.G3) : 1;
-    L.ws_ntk_b = o; o += al(sk > 1 ? (size_t)sk * L.BT * L.I : 0);
+    L.ws_ntk_b = o; o += al(ser_front(series, sk > 1 ? (size_t)sk * L.BT * L.I : 0));
   }
   L.bwd_floats = o;
   return L;
@@ -818,8 +818,10 @@ int bwd_weights(const Bwd& b, int prods, int r0, int rows) {
     const bool ih = prods == WGNN_ROWS_IH;
     FinSeg& s = ih ? a.ih : a.hh;
     (ih ? a.hh : a.ih) = FinSeg{};
-    s.Mout = s.Mgemm = rows;
-    if (L.x3) pgemm_tn_geom(rows, s.Nout, &s.T, &s.nNb, &s.ntiles);
+    if (rows != (int)L.G3) {   // (a whole product alone -- the series backward's -- keeps fill_reduce's segment, two-source rows included)
+      s.Mout = s.Mgemm = rows;
+      if (L.x3) pgemm_tn_geom(rows, s.Nout, &s.T, &s.nNb, &s.ntiles);
+    }
     a.g[ih ? 4 : 5] += (size_t)r0 * s.ncols;                         // w_ih / w_hh
     a.g[ih ? 6 : 7] += r0;                                           // b_ih / b_hh
   }
@@ -931,6 +933,71 @@ int check_rows(const wgnn_dims* d, const Layout& L, int which, int row0, int row
 }  // namespace
 
 int opt_big_gemm() { return opt(WGNN_OPT_BIG_GEMM); }
+
+// ---- series mode (series.hip validates and sizes; the launches live here, next to the layouts and the parts they reuse) ----
+// Workspace: [front | rec], each a workspace of its layout with a status block of its own; stash: [front | rec] likewise.
+int series_plan(const wgnn_dims* df, const wgnn_dims* dr, SeriesPlan* sp) {
+  int rc = check_dims(df);
+  if (rc == WGNN_OK) rc = check_dims(dr);
+  if (rc != WGNN_OK) return rc;
+  const Layout Lf = make_layout(df, false, SER_FRONT), Lr = make_layout(dr, false, SER_REC);
+  if ((int64_t)Lf.BT * (int64_t)Lf.Gp >= (1ll << 31)) return WGNN_ERR_SHAPE;   // 32-bit row offsets into GI_s (gru.hip)
+  sp->ws_front = Lf.fwd_floats > Lf.bwd_floats ? Lf.fwd_floats : Lf.bwd_floats;
+  sp->ws_rec = Lr.fwd_floats > Lr.bwd_floats ? Lr.fwd_floats : Lr.bwd_floats;
+  sp->st_front = Lf.stash_floats;
+  sp->st_rec = Lr.stash_floats;
+  sp->st_g = Lf.BT * Lf.Ip; sp->st_GI = Lf.BT * Lf.Gp;
+  sp->st_gates = gru_gates_floats(dr->B, dr->T, dr->H);
+  sp->st_hprev = Lr.g32tn ? Lr.BT * (size_t)Lr.hq : 0;
+  return WGNN_OK;
+}
+
+int series_fwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
+               float* Y, float* last, float wind_min, float wind_max, void* stash, void* workspace, const SeriesPlan& sp,
+               void* stream) {
+  const Layout Lf = make_layout(df, false, SER_FRONT), Lr = make_layout(dr, false, SER_REC);
+  FwdCall cf(workspace, sizeof(float) * sp.ws_front, stream);
+  cf.A = A; cf.X = Xs; cf.p = p; cf.stash = stash;
+  const Fwd f{df, cf, Lf};
+  int rc = fwd_front(f);                 // g_s and GI_s, once per hour (into the stash if there is one)
+  if (rc != WGNN_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int ld = (int)Lf.Gp;
+  if (last)
+    return launch_gru_fwd(dr->B, dr->T, dr->H, f.GI, ld, p->w_hh, p->b_hh, last, nullptr, nullptr, nullptr, nullptr, 0, 1,
+                          wind_max - wind_min, wind_min, st, nullptr, nullptr, stride);
+  float* sr = stash ? (float*)stash + sp.st_front : nullptr;
+  return launch_gru_fwd(dr->B, dr->T, dr->H, f.GI, ld, p->w_hh, p->b_hh, Y, sr ? sr + Lr.st_gates : nullptr, nullptr, nullptr,
+                        sr && Lr.g32tn ? sr + Lr.st_hprev : nullptr, Lr.hq, 0, 1.f, 0.f, st, nullptr, nullptr, stride);
+}
+
+int series_bwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
+               const float* Y, const float* dY, const void* stash, const wgnn_grads* g, void* workspace, const SeriesPlan& sp,
+               void* stream) {
+  const Layout Lf = make_layout(df, false, SER_FRONT), Lr = make_layout(dr, false, SER_REC);
+  const float* sff = (const float*)stash;
+  BwdCall cr((float*)workspace + sp.ws_front, sizeof(float) * sp.ws_rec, stream);
+  cr.p = p; cr.Y = Y; cr.dY = dY; cr.stash = sff + sp.st_front; cr.g = g; cr.part = 7;
+  const Bwd br{dr, cr, Lr};
+  BwdCall cf(workspace, sizeof(float) * sp.ws_front, stream);
+  cf.A = A; cf.X = Xs; cf.p = p; cf.Y = Y; cf.dY = dY; cf.stash = stash; cf.g = g; cf.part = 7;
+  const Bwd bf{df, cf, Lf};
+  // 1. BPTT per window: n is recomputed from GI_s rows w * stride + t; dGI / dGHn (or dGH) come out window-major
+  int rc = launch_gru_bwd(dr->B, dr->T, dr->H, p->w_hh, Y, dY, nullptr, br.sf + Lr.st_gates, sff + Lf.st_GI, (int)Lf.Gp, br.dGI,
+                          (int)Lr.Gp, Lr.dghn ? br.dGH : nullptr, Lr.dghn ? nullptr : br.dGH, nullptr, (int64_t)Lr.BT * Lr.H, 1.f,
+                          nullptr, nullptr, br.st, nullptr, stride);
+  if (rc != WGNN_OK) return rc;
+  // 2. dW_hh | db_hh over the n * T window-major rows
+  rc = bwd_weights(br, WGNN_ROWS_HH, 0, (int)Lr.G3);
+  if (rc != WGNN_OK) return rc;
+  // 3. dGI_s[tau] = sum over the windows that cover tau
+  rc = launch_series_fold(br.dGI, dr->B, dr->T, stride, df->T, (int)Lf.G3, (int)Lf.Gp, bf.dGI, bf.st);
+  if (rc != WGNN_OK) return rc;
+  // 4. + 5. dW_ih | db_ih, dg and the GCN backward over the `rows` hours, each with its reduction
+  rc = bwd_weights(bf, WGNN_ROWS_IH, 0, (int)Lf.G3);
+  if (rc != WGNN_OK) return rc;
+  return bwd_dg(bf);
+}
 
 extern "C" {
 

@@ -92,6 +92,12 @@ __device__ __forceinline__ BwdState bwd_state(S... s) {
   else return BwdState{s...};
 }
 
+// Series mode (include/windgnn_series.h): window w of a recurrence reads its GI rows at row w * stride + t of ONE series
+// GI_s [rows][ldgi] instead of row w * T + t of a window-major GI.  gru.hip's kernels take it the way the BPTT kernels take
+// BwdState, as an optional trailing argument pack: the instances without it keep their argument list and their code.
+struct SeriesRows { int stride; };
+__device__ __forceinline__ BwdState bwd_state(SeriesRows) { return BwdState{nullptr, nullptr, nullptr}; }
+
 // ---- internal launchers (defined in the .hip files, used by api.hip) -------------------------
 struct GemmArgs {
   const float* A; int lda; int a_kcontig;   // A(m,k) = a_kcontig ? A[m*lda+k] : A[k*lda+m]
@@ -281,13 +287,15 @@ int launch_gcn1_bwd(int ntiles, int S, const float* A, const float* X, const flo
 //   last_only: Y is [B][H] and receives only h_{T-1} * y_mul + y_add
 int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
                    float* gates, const float* labels, float* stat_part, float* hprev, int hq, int last_only, float y_mul,
-                   float y_add, hipStream_t st, const float* h0 = nullptr, float* hn = nullptr);
+                   float y_add, hipStream_t st, const float* h0 = nullptr, float* hn = nullptr,
+                   int series_stride = 0 /*> 0: GI is one series [rows][ldgi], window w at rows w * stride + t (no labels, no h0)*/);
 //   backward: exactly one of dY / labels; dGI [B*T][ldd] and EITHER dGHn [B*T][gru_hn(H)] (dGH's r and z thirds equal
 //   dGI's) OR the full dGH [B*T][ldd]; stat_part (nullable, with labels): loss[0] is finalised from the forward's partials
 int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
                    const float* gates, const float* GI /*forward's GI rows (stash): n is recomputed*/, int ldgi, float* dGI, int ldd, float* dGHn, float* dGH, const float* stat_part,
                    int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st,
-                   const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given*/);
+                   const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given*/,
+                   int series_stride = 0 /*> 0: GI is one series, as in launch_gru_fwd (dY given, no state)*/);
 bool gru_shape_supported(int H);
 size_t gru_gates_floats(int B, int T, int H);
 int gru_blocks(int B);
@@ -305,6 +313,31 @@ int launch_gru_small_bwd(int B, int T, int H, const float* Whh, const float* Y, 
                          const float* gates, float* dGI, float* dGH, int ldd, const float* stat_part, int64_t n_loss,
                          float grad_scale, float* loss, unsigned* status, hipStream_t st,
                          const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given*/);
+
+// ---- series mode (include/windgnn_series.h): series.hip holds the entry points, their validation and the fold kernel;
+// api.hip runs the launches on two of its layouts -- front: dims {B = 1, T = rows}, rec: dims {B = n, T} (float counts below)
+// A Layout of api.hip sizes one half of a series step: SER_FRONT, of dims {B = 1, T = rows}, what depends on the hour alone
+// (g_s, GI_s, dGI_s, dg, the dW_ih partials); SER_REC, of dims {B = n, T}, what is per window (gate records, [Hprev | 1] rows,
+// dGI, dGH, the dW_hh partials).  Each sizes the other's regions as empty -- no window-major g / GI / dg exists -- and both
+// take gru.hip's 16-window recurrence at every n.
+enum { SER_NONE = 0, SER_FRONT = 1, SER_REC = 2 };
+static inline size_t ser_front(int series, size_t n) { return series == SER_REC ? 0 : n; }    // a region of the hour-major half
+static inline size_t ser_rec(int series, size_t n) { return series == SER_FRONT ? 0 : n; }    // a region of the window-major half
+struct SeriesPlan {
+  size_t ws_front, ws_rec;     // the two sub-workspaces, front first
+  size_t st_front, st_rec;     // the two sub-stashes, front first
+  size_t st_g, st_GI, st_gates, st_hprev;   // what the stash holds, unpadded: g_s, GI_s | gate records, [Hprev | 1] rows
+};
+int series_plan(const wgnn_dims* front, const wgnn_dims* rec, SeriesPlan* sp);   // check_dims of both + the sizes
+int series_fwd(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs, const wgnn_params* p,
+               float* Y, float* last /*one of Y / last*/, float wind_min, float wind_max, void* stash /*nullable*/,
+               void* workspace, const SeriesPlan& sp, void* stream);
+int series_bwd(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs, const wgnn_params* p,
+               const float* Y, const float* dY, const void* stash, const wgnn_grads* g, void* workspace, const SeriesPlan& sp,
+               void* stream);
+// dGIs [rows][ld] = the sum, in ascending w, of the window-major rows dGI [(w, tau - w * stride)][ld] that cover hour tau;
+// uncovered rows and the columns [G3, ld) are written as zeros (series.hip)
+int launch_series_fold(const float* dGI, int n, int T, int stride, int rows, int G3, int ld, float* dGIs, hipStream_t st);
 
 // one hour of carried-state inference as ONE launch (gru_step.hip): T = 1, dense A with S <= 64, F = 13, H <= 128, B <= WGNN_STEP_MAX_B;
 // exact fp32 VALU arithmetic in every math mode.  Y [B][H] and hn [B][H] nullable (not both).

@@ -22,6 +22,8 @@
 //   backward -- with labels: dY = 2 (Y - labels) grad_scale / n formed from the h_prev it loads anyway (no dY tensor, no
 //               mse_kernel), the loss finalised by workgroup 0; of dGH only the n third is stored (dGHn): its r and z thirds
 //               equal dGI's and the dW_hh GEMM takes them from there (two-source A operand, gemm32.hip).
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -48,20 +50,31 @@ __device__ __forceinline__ void lds_row(const float* p, float (&a)[N]) {
   }
 }
 
+// GI rows between the first rows of two consecutive windows: T (window-major GI), or the stride of a SeriesRows
+template <typename... S>
+__device__ __forceinline__ int gi_window_rows(int T, S... s) {
+  if constexpr ((std::is_same<S, SeriesRows>::value || ...)) return SeriesRows{s...}.stride;
+  else return T;
+}
+
 // gate stash: grux.hip's layout, [workgroup][t][wave][r | z | n | gh_n][lane] x float4 (the 4 window rows a lane owns):
 // one 16-byte access per lane and component, 1 KB per wave-instruction
 __host__ __device__ inline size_t gate_floats(int B, int T, int H) {
   return (size_t)((B + MB - 1) / MB) * T * ((H + 15) / 16) * 4 * 64 * 4;
 }
 
-template <int KS, bool ST = false>   // k steps of 4 over the hidden index, 4 KS >= H, KS even; ST: the wgnn_fwd_state instance
+// Sr (empty, or one SeriesRows: wgnn_series_fwd): GI is one series and window w reads row w * stride + t of it; everything
+// the kernel writes stays window-major.
+template <int KS, bool ST = false, typename... Sr>   // k steps of 4 over the hidden index, 4 KS >= H, KS even; ST: the wgnn_fwd_state instance
 __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, const float* __restrict__ GI, int ldgi,
                                                            const float* __restrict__ Whh,
                                                            const float* __restrict__ bhh, float* __restrict__ Y,
                                                            float* __restrict__ gates, const float* __restrict__ Lab,
                                                            float* __restrict__ stat_part, float* __restrict__ hprev,
                                                            int hq, int last_only, float y_mul, float y_add,
-                                                           const float* __restrict__ h0, float* __restrict__ hn) {
+                                                           const float* __restrict__ h0, float* __restrict__ hn,
+                                                           Sr... series) {
+  constexpr bool SR = sizeof...(Sr) > 0;
   // h0 (nullable, wgnn_fwd_state): [B][H] initial state instead of zeros; hn (nullable): h_{T-1} [B][H], unrounded
   if (!ST) { h0 = nullptr; hn = nullptr; }       // (the plain forward's instance compiles exactly as before)
   constexpr int KP = 4 * KS, HS = KP + 4;          // row stride: 16-byte aligned rows
@@ -104,7 +117,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
     }
   const float bh_r = bhh[jc], bh_z = bhh[H + jc], bh_n = bhh[2 * H + jc];
 
-  const float* GIw = GI + (size_t)b0 * T * ldgi;
+  const float* GIw = GI + (size_t)b0 * gi_window_rows(T, series...) * ldgi;
   float* Yw = Y + (size_t)b0 * T * H;
   const float* Labw = Lab ? Lab + (size_t)b0 * T * H : nullptr;
   float* Hpw = hprev ? hprev + (size_t)b0 * T * hq : nullptr;
@@ -113,19 +126,21 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
   // stays in the stash (round 4, as in grux.hip: the recurrences are bound by their bytes)
   f32x4* gatesw = gates ? (f32x4*)gates + ((size_t)blockIdx.x * T * NW + wave) * 3 * 64 + lane : nullptr;
   int rowt[4];            // (local window row) * T, clamped to the last valid window
+  int rowg[4];            // series: (local window row) * stride, the window's first GI row
   bool rowok[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int m = 4 * lk + r;
     rowok[r] = jv && b0 + m < B;
     rowt[r] = (b0 + m < B ? m : B - 1 - b0) * T;
+    if constexpr (SR) rowg[r] = (b0 + m < B ? m : B - 1 - b0) * gi_window_rows(T, series...);
   }
   float gi[3][4], gin[3][4], lab[4] = {0.f, 0.f, 0.f, 0.f}, labn[4] = {0.f, 0.f, 0.f, 0.f};
   auto load_gi = [&](int t, float (&dst)[3][4], float (&ldst)[4]) {
     const int tc = t < T ? t : T - 1;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int o = (rowt[r] + tc) * ldgi + jc;
+      const int o = ((SR ? rowg[r] : rowt[r]) + tc) * ldgi + jc;
       dst[0][r] = GIw[o];
       dst[1][r] = GIw[o + H];
       dst[2][r] = GIw[o + 2 * H];
@@ -234,7 +249,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
 //   dh_next = dh z + dgh W_hh
 // Outputs for the GEMMs that follow: dGI rows [B*T][ldd] (3H layout, zero K padding) and dGHn = dnt r rows [B*T][hn].
 // St (empty, or one BwdState: wgnn_bwd_state_part): h_{-1} = h0, the carry starts at dh_n, and the step at t = 0 also forms
-// dh_{-1} = dh z + dgh W_hh into dh0.
+// dh_{-1} = dh z + dgh W_hh into dh0.  Or one SeriesRows (wgnn_series_bwd): GIn is one series, as in the forward.
 template <int KS3, typename... St>   // k steps of 4 over the gate-row index, 4 KS3 >= 3H, KS3 even
 __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, const float* __restrict__ Whh,
                                                            const float* __restrict__ Y, const float* __restrict__ dY,
@@ -247,7 +262,8 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
                                                            const float* __restrict__ stat_part, int nstat, float inv_n,
                                                            float coef_lab, float* __restrict__ loss_out,
                                                            unsigned* status, St... state) {
-  constexpr bool ST = sizeof...(St) > 0;
+  constexpr bool SR = (std::is_same<St, SeriesRows>::value || ...);
+  constexpr bool ST = sizeof...(St) > 0 && !SR;
   const BwdState sb = bwd_state(state...);
   constexpr int KP = 4 * KS3, DS = KP + 4;
   __shared__ __attribute__((aligned(16))) float dbuf[2 * MB * DS];   // dgh rows [dar | daz | dnr | 0..], by step parity
@@ -299,7 +315,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
   }
   const int NW = (H + 15) / 16;
   const f32x4* gatesw = (const f32x4*)gates + ((size_t)blockIdx.x * T * NW + (active ? wave : 0)) * 3 * 64 + lane;
-  const float* GIw = GIn + (size_t)b0 * T * ldgi + 2 * H;          // n third of this workgroup's GI rows (stash)
+  const float* GIw = GIn + (size_t)b0 * gi_window_rows(T, state...) * ldgi + 2 * H;   // n third of this workgroup's GI rows (stash)
   const float* Yw = Y + (size_t)b0 * T * H;
   const float* dYw = dY ? dY + (size_t)b0 * T * H : nullptr;
   const float* Labw = Lab ? Lab + (size_t)b0 * T * H : nullptr;
@@ -307,12 +323,14 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
   float* dGNw = dGN ? dGN + (size_t)b0 * T * hn : nullptr;
   float* dGHw = dGH ? dGH + (size_t)b0 * T * ldd : nullptr;
   int rowt[4];
+  int rowg[4];            // series: (local window row) * stride
   bool rowok[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int m = 4 * lk + r;
     rowok[r] = jv && b0 + m < B;
     rowt[r] = (b0 + m < B ? m : B - 1 - b0) * T;
+    if constexpr (SR) rowg[r] = (b0 + m < B ? m : B - 1 - b0) * gi_window_rows(T, state...);
   }
   // h0 in registers before the loop: a load under `tc == 0` inside load_step would make the compiler wait for all of
   // the step's prefetches at the join
@@ -332,7 +350,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
       s.dy[r] = Lab ? Labw[bt * H + jc] : dYw[bt * H + jc];       // the label, or dY itself
       s.r[r] = r4[r];
       s.z[r] = z4[r];
-      s.n[r] = GIw[bt * ldgi + jc];                                // gi_n: n itself is formed in the step
+      s.n[r] = GIw[(SR ? rowg[r] + tc : bt) * ldgi + jc];          // gi_n: n itself is formed in the step
       s.ghn[r] = g4[r];
       const float hp = Yw[(bt - (tc > 0 ? 1 : 0)) * H + jc];
       s.hp[r] = tc > 0 ? hp : 0.f;
@@ -449,9 +467,10 @@ int gru_msplit(int H) { return 4 * cdiv_i(2 * H, 4); }   // first GEMM row of th
 
 int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
                    float* gates, const float* labels, float* stat_part, float* hprev, int hq, int last_only, float y_mul,
-                   float y_add, hipStream_t st, const float* h0, float* hn) {
+                   float y_add, hipStream_t st, const float* h0, float* hn, int series_stride) {
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
   if (last_only && (gates || labels || hprev)) return WGNN_ERR_UNSUPPORTED;
+  if (series_stride < 0 || (series_stride && (labels || h0 || hn))) return WGNN_ERR_UNSUPPORTED;
   if (hprev && (hq < H + 1 || hq % 4 != 0)) return WGNN_ERR_SHAPE;
   const int ks = pick_ks(cdiv_i(H, 4), FWD_KS, (int)(sizeof(FWD_KS) / sizeof(int)));
   const double bt = (double)B * T;
@@ -461,7 +480,10 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
 #define FCASE(K)                                                                                                  \
   case K:                                                                                                         \
     PROF_LAUNCH("gru_fwd_kernel<" #K ">", fl, by, st,                                                             \
-                if (h0 || hn) hipLaunchKernelGGL((gru_fwd_kernel<K, true>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, \
+                if (series_stride) hipLaunchKernelGGL((gru_fwd_kernel<K, false, SeriesRows>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, \
+                                                      st, B, T, H, GI, ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq,       \
+                                                      last_only, y_mul, y_add, nullptr, nullptr, SeriesRows{series_stride});        \
+                else if (h0 || hn) hipLaunchKernelGGL((gru_fwd_kernel<K, true>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, \
                                                  GI, ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq, last_only, y_mul,  \
                                                  y_add, h0, hn);                                                                \
                 else hipLaunchKernelGGL((gru_fwd_kernel<K, false>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, GI,    \
@@ -481,9 +503,11 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
 // with stat_part (the forward's partial sums + tag) workgroup 0 also writes loss[0] = mean((Y - labels)^2).
 int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
                    const float* gates, const float* GI /*the forward's GI rows [B*T][ldgi] (stash)*/, int ldgi, float* dGI, int ldd, float* dGHn, float* dGH, const float* stat_part,
-                   int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st, const BwdState* state) {
+                   int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st, const BwdState* state,
+                   int series_stride) {
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
   if (state && (!state->h0 || labels)) return WGNN_ERR_UNSUPPORTED;
+  if (series_stride < 0 || (series_stride && (labels || state))) return WGNN_ERR_UNSUPPORTED;
   if ((dY == nullptr) == (labels == nullptr) || ldd < 3 * H || (dGHn == nullptr) == (dGH == nullptr)) return WGNN_ERR_SHAPE;
   if (stat_part && (!labels || !loss)) return WGNN_ERR_NULL;
   if (!GI || ldgi < 3 * H) return WGNN_ERR_NULL;
@@ -496,7 +520,10 @@ int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const 
 #define BCASE(K)                                                                                                  \
   case K:                                                                                                         \
     PROF_LAUNCH("gru_bwd_kernel<" #K ">", fl, by, st,                                                             \
-                if (state) hipLaunchKernelGGL((gru_bwd_kernel<K, BwdState>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, \
+                if (series_stride) hipLaunchKernelGGL((gru_bwd_kernel<K, SeriesRows>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, \
+                                                      T, H, Whh, Y, dY, labels, gates, GI, ldgi, dGI, ldd, dGHn, hn, dGH, stat_part,  \
+                                                      gru_blocks(B), inv_n, coef, loss, status, SeriesRows{series_stride});           \
+                else if (state) hipLaunchKernelGGL((gru_bwd_kernel<K, BwdState>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, \
                                               Whh, Y, dY, labels, gates, GI, ldgi, dGI, ldd, dGHn, hn, dGH, stat_part,            \
                                               gru_blocks(B), inv_n, coef, loss, status, *state);                                   \
                 else hipLaunchKernelGGL(gru_bwd_kernel<K>, dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY,  \

@@ -100,6 +100,18 @@ class GCN_GRU(nn.Module):
             check_range_status(out.device)
         return out.squeeze(0)            # step6:26
 
+    def forward_series(self, adj_matrix, series, seq_len, stride=1, n_windows=None):
+        """[n, seq_len, gru_hidden_dim]: forward() on every window of `series` [rows, S, 13] -- window w covers rows
+        w*stride .. w*stride + seq_len - 1, n = n_windows or (rows - seq_len) // stride + 1, h0 = 0 each -- without building them:
+        the graph convolutions and the input projection run once per hour (windgnn_amd/series.py).  Differentiable in the
+        parameters.  The reference model's 13 / 13 widths in exact fp32 with a dense adjacency only; raises otherwise."""
+        from .series import _require_fused, gcn_gru_series
+        _require_fused(self, "GCN_GRU.forward_series")
+        if series.dim() != 3 or series.shape[2] != NUM_FEATURES or series.shape[1] * NUM_FEATURES != self.gru.input_size:
+            raise RuntimeError("GCN_GRU.forward_series: series must be [rows, %d, 13], got %s"
+                               % (self.gru.input_size // NUM_FEATURES, tuple(series.shape)))
+        return gcn_gru_series(adj_matrix, series, seq_len, stride, self.hot_path_parameters(), self.math, n_windows)
+
     def forward_state(self, adj_matrix, attr_matrix, hx=None):
         """(out, h_n) with nn.GRU(batch_first=True)'s state convention: hx / h_n are [1, B, H] (hx may also be [B, H]; None =
         zeros, i.e. exactly forward()); out is what forward() returns.  Inference only: no autograd graph is built, so with
