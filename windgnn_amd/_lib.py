@@ -1,5 +1,5 @@
 """ctypes binding of libwindgnn_hip.so (the C ABI declared in include/windgnn.h, windgnn_optim.h, windgnn_sched.h,
-windgnn_eval.h, windgnn_best.h and windgnn_series.h).
+windgnn_eval.h, windgnn_best.h, windgnn_series.h and windgnn_series_train.h).
 
 The library is the product: there is no CPU or eager-PyTorch fallback.  If the shared object is
 missing or a call fails this module raises, loudly."""
@@ -188,6 +188,19 @@ EXPORTS_SERIES = {
                                   C.c_void_p, C.POINTER(Grads), C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
+# include/windgnn_series_train.h: the MSE loss fused into the series recurrences (a seventh header and table, as above)
+SERIES_TRAIN_VERSION = 1    # WGNN_SERIES_TRAIN_VERSION
+EXPORTS_SERIES_TRAIN = {
+    "wgnn_series_train_version": (C.c_int, []),
+    "wgnn_series_loss_bytes": (C.c_size_t, [C.POINTER(SeriesDims)]),
+    "wgnn_series_status_offset": (C.c_size_t, [C.POINTER(SeriesDims)]),
+    "wgnn_series_fwd_loss": (C.c_int, [C.POINTER(SeriesDims), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wgnn_series_bwd_mse": (C.c_int, [C.POINTER(SeriesDims), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,
+                                      C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Grads), C.c_void_p,
+                                      C.c_size_t, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -242,6 +255,16 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    if not hasattr(lib, "wgnn_series_train_version"):
+        raise RuntimeError("windgnn_amd: %s predates include/windgnn_series_train.h (no wgnn_series_train_version): rebuild it "
+                           "with `python -m windgnn_amd.build --force`" % LIB_PATH)
+    for name, (res, args) in EXPORTS_SERIES_TRAIN.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.wgnn_series_train_version() < SERIES_TRAIN_VERSION:
+        raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_series_train_version %d < %d)"
+                           % (lib.wgnn_series_train_version(), SERIES_TRAIN_VERSION))
     if lib.wgnn_series_version() < SERIES_VERSION:
         raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_series_version %d < %d)"
                            % (lib.wgnn_series_version(), SERIES_VERSION))

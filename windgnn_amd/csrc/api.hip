@@ -138,7 +138,7 @@ Layout make_layout(const wgnn_dims* d, bool state = false, int series = SER_NONE
   L.st_h1 = o; o += al(L.gen_gcn ? L.BT * L.I : 0);
   {  // partial pairs (sum | max) + the tag word: one pair per workgroup of the forward recurrence (B / 16, or B for gru_small)
     const size_t nb = L.small ? (size_t)gru_small_blocks(d->B) : (size_t)grux_blocks(d->B);
-    L.st_stats = o; o += al(series ? 0 : 2 * nb + 4);   // (the series entry points take dY: no fused loss)
+    L.st_stats = o; o += al(series ? 0 : 2 * nb + 4);   // (series mode keeps them in the caller's loss_buf: windgnn_series_train.h)
   }
   // split fp16 modes with the register-resident recurrence: the gate records hold r | z | gh_n only and the BPTT kernel forms
   // n = tanh(gi_n + r gh_n) from GI, so GI (which the projection GEMM writes anyway) goes into the stash, not the workspace
@@ -952,9 +952,13 @@ int series_plan(const wgnn_dims* df, const wgnn_dims* dr, SeriesPlan* sp) {
   return WGNN_OK;
 }
 
-int series_fwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
-               float* Y, float* last, float wind_min, float wind_max, void* stash, void* workspace, const SeriesPlan& sp,
-               void* stream) {
+namespace {
+
+// Ls / loss_buf (wgnn_series_fwd_loss, both or neither): the recurrence also reads the label series and leaves the MSE partial
+// pairs and the tag in loss_buf; Y and the stash are the same either way
+int series_forward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
+                   float* Y, float* last, float wind_min, float wind_max, void* stash, void* workspace, const SeriesPlan& sp,
+                   void* stream, const float* Ls, int64_t ls_rows, float* loss_buf) {
   const Layout Lf = make_layout(df, false, SER_FRONT), Lr = make_layout(dr, false, SER_REC);
   FwdCall cf(workspace, sizeof(float) * sp.ws_front, stream);
   cf.A = A; cf.X = Xs; cf.p = p; cf.stash = stash;
@@ -967,13 +971,15 @@ int series_fwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float
     return launch_gru_fwd(dr->B, dr->T, dr->H, f.GI, ld, p->w_hh, p->b_hh, last, nullptr, nullptr, nullptr, nullptr, 0, 1,
                           wind_max - wind_min, wind_min, st, nullptr, nullptr, stride);
   float* sr = stash ? (float*)stash + sp.st_front : nullptr;
-  return launch_gru_fwd(dr->B, dr->T, dr->H, f.GI, ld, p->w_hh, p->b_hh, Y, sr ? sr + Lr.st_gates : nullptr, nullptr, nullptr,
-                        sr && Lr.g32tn ? sr + Lr.st_hprev : nullptr, Lr.hq, 0, 1.f, 0.f, st, nullptr, nullptr, stride);
+  return launch_gru_fwd(dr->B, dr->T, dr->H, f.GI, ld, p->w_hh, p->b_hh, Y, sr ? sr + Lr.st_gates : nullptr, Ls, loss_buf,
+                        sr && Lr.g32tn ? sr + Lr.st_hprev : nullptr, Lr.hq, 0, 1.f, 0.f, st, nullptr, nullptr, stride, ls_rows);
 }
 
-int series_bwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
-               const float* Y, const float* dY, const void* stash, const wgnn_grads* g, void* workspace, const SeriesPlan& sp,
-               void* stream) {
+// dY, or Ls with the forward's loss_buf (wgnn_series_bwd_mse): BPTT forms dY = (Y - label) 2 grad_scale / (n T H) itself and its
+// workgroup 0 finalises loss[0]; a missing tag sets WGNN_STATUS_NO_LOSS_STATS in the rec half's status block
+int series_backward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
+                    const float* Y, const float* dY, const void* stash, const wgnn_grads* g, void* workspace, const SeriesPlan& sp,
+                    void* stream, const float* Ls, int64_t ls_rows, float grad_scale, const float* loss_buf, float* loss) {
   const Layout Lf = make_layout(df, false, SER_FRONT), Lr = make_layout(dr, false, SER_REC);
   const float* sff = (const float*)stash;
   BwdCall cr((float*)workspace + sp.ws_front, sizeof(float) * sp.ws_rec, stream);
@@ -983,9 +989,9 @@ int series_bwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float
   cf.A = A; cf.X = Xs; cf.p = p; cf.Y = Y; cf.dY = dY; cf.stash = stash; cf.g = g; cf.part = 7;
   const Bwd bf{df, cf, Lf};
   // 1. BPTT per window: n is recomputed from GI_s rows w * stride + t; dGI / dGHn (or dGH) come out window-major
-  int rc = launch_gru_bwd(dr->B, dr->T, dr->H, p->w_hh, Y, dY, nullptr, br.sf + Lr.st_gates, sff + Lf.st_GI, (int)Lf.Gp, br.dGI,
-                          (int)Lr.Gp, Lr.dghn ? br.dGH : nullptr, Lr.dghn ? nullptr : br.dGH, nullptr, (int64_t)Lr.BT * Lr.H, 1.f,
-                          nullptr, nullptr, br.st, nullptr, stride);
+  int rc = launch_gru_bwd(dr->B, dr->T, dr->H, p->w_hh, Y, dY, Ls, br.sf + Lr.st_gates, sff + Lf.st_GI, (int)Lf.Gp, br.dGI,
+                          (int)Lr.Gp, Lr.dghn ? br.dGH : nullptr, Lr.dghn ? nullptr : br.dGH, loss_buf, (int64_t)Lr.BT * Lr.H,
+                          grad_scale, loss, Ls ? br.status : nullptr, br.st, nullptr, stride, ls_rows);
   if (rc != WGNN_OK) return rc;
   // 2. dW_hh | db_hh over the n * T window-major rows
   rc = bwd_weights(br, WGNN_ROWS_HH, 0, (int)Lr.G3);
@@ -997,6 +1003,35 @@ int series_bwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float
   rc = bwd_weights(bf, WGNN_ROWS_IH, 0, (int)Lf.G3);
   if (rc != WGNN_OK) return rc;
   return bwd_dg(bf);
+}
+
+}  // namespace
+
+int series_fwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
+               float* Y, float* last, float wind_min, float wind_max, void* stash, void* workspace, const SeriesPlan& sp,
+               void* stream) {
+  return series_forward(df, dr, stride, A, Xs, p, Y, last, wind_min, wind_max, stash, workspace, sp, stream, nullptr, 0, nullptr);
+}
+
+int series_bwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
+               const float* Y, const float* dY, const void* stash, const wgnn_grads* g, void* workspace, const SeriesPlan& sp,
+               void* stream) {
+  return series_backward(df, dr, stride, A, Xs, p, Y, dY, stash, g, workspace, sp, stream, nullptr, 0, 1.f, nullptr, nullptr);
+}
+
+size_t series_loss_floats(int n) { return 2 * (size_t)gru_blocks(n) + 4; }   // pairs, tag, 3 spare words (as Layout::st_stats)
+
+int series_fwd_loss(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
+                    const float* Ls, int64_t ls_rows, float* Y, void* stash, float* loss_buf, void* workspace,
+                    const SeriesPlan& sp, void* stream) {
+  return series_forward(df, dr, stride, A, Xs, p, Y, nullptr, 0.f, 1.f, stash, workspace, sp, stream, Ls, ls_rows, loss_buf);
+}
+
+int series_bwd_mse(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
+                   const float* Y, const float* Ls, int64_t ls_rows, float grad_scale, const void* stash, const float* loss_buf,
+                   float* loss, const wgnn_grads* g, void* workspace, const SeriesPlan& sp, void* stream) {
+  return series_backward(df, dr, stride, A, Xs, p, Y, nullptr, stash, g, workspace, sp, stream, Ls, ls_rows, grad_scale, loss_buf,
+                         loss);
 }
 
 extern "C" {

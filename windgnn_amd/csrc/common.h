@@ -288,14 +288,16 @@ int launch_gcn1_bwd(int ntiles, int S, const float* A, const float* X, const flo
 int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
                    float* gates, const float* labels, float* stat_part, float* hprev, int hq, int last_only, float y_mul,
                    float y_add, hipStream_t st, const float* h0 = nullptr, float* hn = nullptr,
-                   int series_stride = 0 /*> 0: GI is one series [rows][ldgi], window w at rows w * stride + t (no labels, no h0)*/);
+                   int series_stride = 0 /*> 0: GI is one series [rows][ldgi], window w at rows w * stride + t (no h0)*/,
+                   int64_t ls_rows = 0 /*series with labels: they are one series too, Ls [ls_rows][H], read at the same rows*/);
 //   backward: exactly one of dY / labels; dGI [B*T][ldd] and EITHER dGHn [B*T][gru_hn(H)] (dGH's r and z thirds equal
 //   dGI's) OR the full dGH [B*T][ldd]; stat_part (nullable, with labels): loss[0] is finalised from the forward's partials
 int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
                    const float* gates, const float* GI /*forward's GI rows (stash): n is recomputed*/, int ldgi, float* dGI, int ldd, float* dGHn, float* dGH, const float* stat_part,
                    int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st,
                    const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given*/,
-                   int series_stride = 0 /*> 0: GI is one series, as in launch_gru_fwd (dY given, no state)*/);
+                   int series_stride = 0 /*> 0: GI is one series, as in launch_gru_fwd (no state)*/,
+                   int64_t ls_rows = 0 /*series with labels: Ls [ls_rows][H], as in launch_gru_fwd*/);
 bool gru_shape_supported(int H);
 size_t gru_gates_floats(int B, int T, int H);
 int gru_blocks(int B);
@@ -335,6 +337,15 @@ int series_fwd(const wgnn_dims* front, const wgnn_dims* rec, int stride, const f
 int series_bwd(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs, const wgnn_params* p,
                const float* Y, const float* dY, const void* stash, const wgnn_grads* g, void* workspace, const SeriesPlan& sp,
                void* stream);
+// include/windgnn_series_train.h (series_train.hip validates): the same two sequences with the labels as a series Ls [ls_rows][H]
+// in the recurrences; loss_buf = 2 * gru_blocks(n) partials (sum | max) + the tag word, series_loss_floats(n) floats in all
+size_t series_loss_floats(int n);
+int series_fwd_loss(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs,
+                    const wgnn_params* p, const float* Ls, int64_t ls_rows, float* Y, void* stash /*nullable*/, float* loss_buf,
+                    void* workspace, const SeriesPlan& sp, void* stream);
+int series_bwd_mse(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs,
+                   const wgnn_params* p, const float* Y, const float* Ls, int64_t ls_rows, float grad_scale, const void* stash,
+                   const float* loss_buf, float* loss, const wgnn_grads* g, void* workspace, const SeriesPlan& sp, void* stream);
 // dGIs [rows][ld] = the sum, in ascending w, of the window-major rows dGI [(w, tau - w * stride)][ld] that cover hour tau;
 // uncovered rows and the columns [G3, ld) are written as zeros (series.hip)
 int launch_series_fold(const float* dGI, int n, int T, int stride, int rows, int G3, int ld, float* dGIs, hipStream_t st);

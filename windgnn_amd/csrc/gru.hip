@@ -63,8 +63,8 @@ __host__ __device__ inline size_t gate_floats(int B, int T, int H) {
   return (size_t)((B + MB - 1) / MB) * T * ((H + 15) / 16) * 4 * 64 * 4;
 }
 
-// Sr (empty, or one SeriesRows: wgnn_series_fwd): GI is one series and window w reads row w * stride + t of it; everything
-// the kernel writes stays window-major.
+// Sr (empty, or one SeriesRows: wgnn_series_fwd): GI is one series and window w reads row w * stride + t of it, and so are the
+// labels (wgnn_series_fwd_loss: Lab = Ls [ls_rows][H], the same row); everything the kernel writes stays window-major.
 template <int KS, bool ST = false, typename... Sr>   // k steps of 4 over the hidden index, 4 KS >= H, KS even; ST: the wgnn_fwd_state instance
 __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, const float* __restrict__ GI, int ldgi,
                                                            const float* __restrict__ Whh,
@@ -119,7 +119,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
 
   const float* GIw = GI + (size_t)b0 * gi_window_rows(T, series...) * ldgi;
   float* Yw = Y + (size_t)b0 * T * H;
-  const float* Labw = Lab ? Lab + (size_t)b0 * T * H : nullptr;
+  const float* Labw = Lab ? Lab + (size_t)b0 * gi_window_rows(T, series...) * H : nullptr;   // series: Ls [ls_rows][H], hour-major
   float* Hpw = hprev ? hprev + (size_t)b0 * T * hq : nullptr;
   const int NW = (H + 15) / 16;
   // three components per record, r | z | gh_n: the BPTT kernel recomputes n = tanh(gi_n + r gh_n) from GI's n third, which
@@ -144,7 +144,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
       dst[0][r] = GIw[o];
       dst[1][r] = GIw[o + H];
       dst[2][r] = GIw[o + 2 * H];
-      if (Lab) ldst[r] = Labw[(rowt[r] + tc) * H + jc];
+      if (Lab) ldst[r] = Labw[((SR ? rowg[r] : rowt[r]) + tc) * H + jc];   // the label row is the GI row
     }
   };
   load_gi(0, gi, lab);
@@ -249,7 +249,8 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
 //   dh_next = dh z + dgh W_hh
 // Outputs for the GEMMs that follow: dGI rows [B*T][ldd] (3H layout, zero K padding) and dGHn = dnt r rows [B*T][hn].
 // St (empty, or one BwdState: wgnn_bwd_state_part): h_{-1} = h0, the carry starts at dh_n, and the step at t = 0 also forms
-// dh_{-1} = dh z + dgh W_hh into dh0.  Or one SeriesRows (wgnn_series_bwd): GIn is one series, as in the forward.
+// dh_{-1} = dh z + dgh W_hh into dh0.  Or one SeriesRows (wgnn_series_bwd / wgnn_series_bwd_mse): GIn, and Lab if given, are
+// one series each, as in the forward.
 template <int KS3, typename... St>   // k steps of 4 over the gate-row index, 4 KS3 >= 3H, KS3 even
 __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, const float* __restrict__ Whh,
                                                            const float* __restrict__ Y, const float* __restrict__ dY,
@@ -318,7 +319,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
   const float* GIw = GIn + (size_t)b0 * gi_window_rows(T, state...) * ldgi + 2 * H;   // n third of this workgroup's GI rows (stash)
   const float* Yw = Y + (size_t)b0 * T * H;
   const float* dYw = dY ? dY + (size_t)b0 * T * H : nullptr;
-  const float* Labw = Lab ? Lab + (size_t)b0 * T * H : nullptr;
+  const float* Labw = Lab ? Lab + (size_t)b0 * gi_window_rows(T, state...) * H : nullptr;   // series: Ls, hour-major
   float* dGIw = dGI + (size_t)b0 * T * ldd;
   float* dGNw = dGN ? dGN + (size_t)b0 * T * hn : nullptr;
   float* dGHw = dGH ? dGH + (size_t)b0 * T * ldd : nullptr;
@@ -347,7 +348,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int bt = rowt[r] + tc;
-      s.dy[r] = Lab ? Labw[bt * H + jc] : dYw[bt * H + jc];       // the label, or dY itself
+      s.dy[r] = Lab ? Labw[(SR ? rowg[r] + tc : bt) * H + jc] : dYw[bt * H + jc];   // the label (series: at the GI row), or dY itself
       s.r[r] = r4[r];
       s.z[r] = z4[r];
       s.n[r] = GIw[(SR ? rowg[r] + tc : bt) * ldgi + jc];          // gi_n: n itself is formed in the step
@@ -467,10 +468,11 @@ int gru_msplit(int H) { return 4 * cdiv_i(2 * H, 4); }   // first GEMM row of th
 
 int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
                    float* gates, const float* labels, float* stat_part, float* hprev, int hq, int last_only, float y_mul,
-                   float y_add, hipStream_t st, const float* h0, float* hn, int series_stride) {
+                   float y_add, hipStream_t st, const float* h0, float* hn, int series_stride, int64_t ls_rows) {
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
   if (last_only && (gates || labels || hprev)) return WGNN_ERR_UNSUPPORTED;
-  if (series_stride < 0 || (series_stride && (labels || h0 || hn))) return WGNN_ERR_UNSUPPORTED;
+  if (series_stride < 0 || (series_stride && (h0 || hn))) return WGNN_ERR_UNSUPPORTED;
+  if (series_stride && labels && ls_rows * H >= (1ll << 31)) return WGNN_ERR_SHAPE;   // 32-bit offsets into Ls
   if (hprev && (hq < H + 1 || hq % 4 != 0)) return WGNN_ERR_SHAPE;
   const int ks = pick_ks(cdiv_i(H, 4), FWD_KS, (int)(sizeof(FWD_KS) / sizeof(int)));
   const double bt = (double)B * T;
@@ -504,10 +506,11 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
 int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
                    const float* gates, const float* GI /*the forward's GI rows [B*T][ldgi] (stash)*/, int ldgi, float* dGI, int ldd, float* dGHn, float* dGH, const float* stat_part,
                    int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st, const BwdState* state,
-                   int series_stride) {
+                   int series_stride, int64_t ls_rows) {
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
   if (state && (!state->h0 || labels)) return WGNN_ERR_UNSUPPORTED;
-  if (series_stride < 0 || (series_stride && (labels || state))) return WGNN_ERR_UNSUPPORTED;
+  if (series_stride < 0 || (series_stride && state)) return WGNN_ERR_UNSUPPORTED;
+  if (series_stride && labels && ls_rows * H >= (1ll << 31)) return WGNN_ERR_SHAPE;   // 32-bit offsets into Ls
   if ((dY == nullptr) == (labels == nullptr) || ldd < 3 * H || (dGHn == nullptr) == (dGH == nullptr)) return WGNN_ERR_SHAPE;
   if (stat_part && (!labels || !loss)) return WGNN_ERR_NULL;
   if (!GI || ldgi < 3 * H) return WGNN_ERR_NULL;

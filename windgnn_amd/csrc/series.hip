@@ -1,8 +1,12 @@
-// Series mode (include/windgnn_series.h): the entry points, their validation, and the fold kernel of the backward.
+// Series mode (include/windgnn_series.h, include/windgnn_series_train.h): the entry points, their validation, and the fold
+// kernel of the backward.
 // The launches themselves are api.hip's (series_fwd / series_bwd): they run the materialised path's own front end, weight-gradient
 // products and GCN backward on two of its layouts, with gru.hip's recurrences reading GI at series rows.
 #include "common.h"
 #include "../../include/windgnn_series.h"
+#include "../../include/windgnn_series_train.h"
+
+#include <cmath>
 
 namespace {
 
@@ -120,6 +124,49 @@ int wgnn_series_bwd(const wgnn_series_dims* sd, const float* A, const float* Xs,
   if (!A || !Xs || !p || !Y || !dY || !stash || !grads || !workspace || !complete(p) || !complete(grads)) return WGNN_ERR_NULL;
   if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
   return series_bwd(&pl.front, &pl.rec, sd->stride, A, Xs, p, Y, dY, stash, grads, workspace, pl.sp, stream);
+}
+
+// ---- include/windgnn_series_train.h ----
+int wgnn_series_train_version(void) { return WGNN_SERIES_TRAIN_VERSION; }
+
+size_t wgnn_series_loss_bytes(const wgnn_series_dims* sd) {
+  Plan pl;
+  return plan(sd, &pl) == WGNN_OK ? sizeof(float) * series_loss_floats(sd->n) : 0;
+}
+
+int wgnn_series_fwd_loss(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, const float* Ls,
+                         int64_t ls_rows, float* Y, void* stash, void* loss_buf, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  if (sd && !Y) return WGNN_ERR_NULL;      // before the dims, as in wgnn_series_fwd
+  Plan pl;
+  const int rc = plan(sd, &pl);
+  if (rc != WGNN_OK) return rc;
+  if (!A || !Xs || !p || !Ls || !loss_buf || !workspace || !complete(p)) return WGNN_ERR_NULL;
+  if (ls_rows < (int64_t)(sd->n - 1) * sd->stride + sd->T || ls_rows * sd->H >= (1ll << 31)) return WGNN_ERR_SHAPE;
+  if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
+  return series_fwd_loss(&pl.front, &pl.rec, sd->stride, A, Xs, p, Ls, ls_rows, Y, stash, (float*)loss_buf, workspace, pl.sp,
+                         stream);
+}
+
+int wgnn_series_bwd_mse(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, const float* Y,
+                        const float* Ls, int64_t ls_rows, float grad_scale, const void* stash, const void* loss_buf, float* loss,
+                        const wgnn_grads* grads, void* workspace, size_t workspace_bytes, void* stream) {
+  Plan pl;
+  const int rc = plan(sd, &pl);
+  if (rc != WGNN_OK) return rc;
+  if (!A || !Xs || !p || !Y || !Ls || !stash || !loss_buf || !loss || !grads || !workspace || !complete(p) || !complete(grads))
+    return WGNN_ERR_NULL;
+  if (ls_rows < (int64_t)(sd->n - 1) * sd->stride + sd->T || ls_rows * sd->H >= (1ll << 31) || !std::isfinite(grad_scale) ||
+      !(grad_scale > 0.f))
+    return WGNN_ERR_SHAPE;
+  if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
+  return series_bwd_mse(&pl.front, &pl.rec, sd->stride, A, Xs, p, Y, Ls, ls_rows, grad_scale, stash, (const float*)loss_buf,
+                        loss, grads, workspace, pl.sp, stream);
+}
+
+size_t wgnn_series_status_offset(const wgnn_series_dims* sd) {
+  Plan pl;
+  return plan(sd, &pl) == WGNN_OK ? sizeof(float) * pl.sp.ws_front : 0;
 }
 
 }  // extern "C"

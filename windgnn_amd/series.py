@@ -99,6 +99,58 @@ def series_backward_raw(sd, A, series, params, Y, dY, stash, grads: Sequence[tor
     _lib.check(rc, "wgnn_series_bwd")
 
 
+def _check_label_series(Ls, sd) -> None:
+    """Ls as series_labels returns it: contiguous [rows, H] fp32 on the GPU with a row for every hour a window covers."""
+    need = (sd.n - 1) * sd.stride + sd.T
+    if Ls.dim() != 2 or Ls.shape[1] != sd.H or Ls.shape[0] < need:
+        raise RuntimeError("windgnn_amd: the label series Ls must be [rows >= (n - 1) * stride + seq_len = %d, H = %d] (what "
+                           "series_labels(feat, seq_len, stride, n_windows)[0] returns; its window view L is not needed), got %s"
+                           % (need, sd.H, tuple(Ls.shape)))
+    _require_gpu(Ls)
+    _require_contiguous(Ls=Ls)
+
+
+def series_forward_loss_raw(A, series, Ls, seq_len, stride, params, math=_lib.MATH_F32, n_windows=None, prepared=None):
+    """Y [n, T, H], stash, loss_buf, dims = wgnn_series_fwd_loss(...): series_forward_raw with the MSE statistics of (Y - labels)
+    left in loss_buf for series_backward_mse_raw.  Ls [rows - 3, H]: the label SERIES (series_labels' first result); window w,
+    step t reads its row w * stride + t."""
+    lib = _lib.load()
+    A, sd, ws, ws_bytes = _series_setup(A, series, seq_len, stride, params, math, n_windows)
+    _check_label_series(Ls, sd)
+    stash = torch.empty(lib.wgnn_series_stash_bytes(C.byref(sd)), dtype=torch.uint8, device=series.device)
+    loss_buf = torch.empty(lib.wgnn_series_loss_bytes(C.byref(sd)) // 4, dtype=torch.float32, device=series.device)
+    Y = torch.empty(sd.n, sd.T, sd.H, dtype=torch.float32, device=series.device)
+    ps = _params_struct(_lib.Params, params, prepared)
+    rc = lib.wgnn_series_fwd_loss(C.byref(sd), _ptr(A), _ptr(series), C.byref(ps), _ptr(Ls), Ls.shape[0], _ptr(Y),
+                                  _stash_ptr(stash), _ptr(loss_buf), _ptr(ws), ws_bytes, _stream())
+    _lib.check(rc, "wgnn_series_fwd_loss")
+    return Y, stash, loss_buf, sd
+
+
+def series_backward_mse_raw(sd, A, series, params, Y, Ls, stash, loss_buf, grads: Sequence[torch.Tensor], loss: torch.Tensor,
+                            grad_scale: float = 1.0, prepared=None) -> None:
+    """wgnn_series_bwd_mse: the 8 gradients of grad_scale * mean((Y - labels)^2) into `grads` (overwritten, final) and the
+    unweighted mean into `loss` (a 0-dim fp32 device tensor), without a dY tensor.  Y, stash, loss_buf: as
+    series_forward_loss_raw returned them for the same inputs."""
+    lib = _lib.load()
+    _check_label_series(Ls, sd)
+    _require_gpu(loss, loss_buf)
+    _require_contiguous(series=series, Y=Y, adj_matrix=A, loss_buf=loss_buf,
+                        **{"grads[%d]" % i: q for i, q in enumerate(grads)},
+                        **{"params[%d]" % i: q for i, q in enumerate(params)})
+    if loss_buf.numel() * 4 < lib.wgnn_series_loss_bytes(C.byref(sd)):
+        raise RuntimeError("windgnn_amd: loss_buf holds %d bytes, wgnn_series_loss_bytes says %d"
+                           % (loss_buf.numel() * 4, lib.wgnn_series_loss_bytes(C.byref(sd))))
+    ws_bytes = lib.wgnn_series_workspace_bytes(C.byref(sd))
+    ws = _Workspace.get(series.device, ws_bytes)
+    ps = _params_struct(_lib.Params, params, prepared)
+    gs = _params_struct(_lib.Grads, grads)
+    rc = lib.wgnn_series_bwd_mse(C.byref(sd), _ptr(A), _ptr(series), C.byref(ps), _ptr(Y), _ptr(Ls), Ls.shape[0],
+                                 float(grad_scale), _stash_ptr(stash), _ptr(loss_buf), _ptr(loss), C.byref(gs), _ptr(ws), ws_bytes,
+                                 _stream())
+    _lib.check(rc, "wgnn_series_bwd_mse")
+
+
 class SeriesFunction(torch.autograd.Function):
     """Y [n, T, H] = GCN_GRU on every window of the series.  Gradients flow to the 8 parameters only, as in GCNGRUFunction."""
 

@@ -52,7 +52,15 @@ are views of the device record; best_state_dict() / restore_best() read the snap
 
 Checkpoints: state_dict() / load_state_dict() carry what a TrainStep owns besides the parameters -- the Adam moments and step
 count in torch.optim.Adam's own layout (so a run can move between torch.optim.Adam on the drop-in module and TrainStep), the
-best record and snapshot, and the carried GRU state.  The parameters travel through model.state_dict() as before."""
+best record and snapshot, and the carried GRU state.  The parameters travel through model.state_dict() as before.
+
+Series mode (step_series / forward_backward_series; include/windgnn_series_train.h): the same step on the sliding windows of ONE
+hourly series, without materialising windows, labels or dY.  The label of window w at step t is row w * stride + t of the label
+series Ls (series.series_labels' first result), which the recurrence kernels read beside the GI row: wgnn_series_fwd_loss leaves
+the MSE partial sums in a small buffer, wgnn_series_bwd_mse forms dY inside BPTT, finalises the loss into the bucket's header
+word and leaves FINAL gradients in the bucket (series mode does not defer its partial sums), so the tail is _tail(d, 0, pre) --
+one wgnn_finish that only steps Adam and refreshes the W_ih images.  With a process group the one all-reduce sits between the
+backward and that tail.  Exact fp32, a dense adjacency, the one-bucket schedules; the rest is refused with the alternative."""
 from __future__ import annotations
 
 import collections
@@ -61,11 +69,12 @@ import torch
 
 from . import _lib
 from .distributed import HEADER, LOSS_SLOT, BucketExchange, grad_block_plan
-from .functional import (PARAM_ORDER, _forward_setup, best_bytes, best_init, best_word, bwd_rows, check_range_status,
+from .functional import (PARAM_ORDER, _forward_setup, _require_gpu, best_bytes, best_init, best_word, bwd_rows, check_range_status,
                          clip_buffer, clip_bytes, finish_clipped, finish_norm, finish_rows, finish_step,
                          gcn_gru_backward_mse_raw, gcn_gru_forward_raw, gcn_gru_state_backward_raw, gcn_gru_state_forward_raw,
                          keep_best_args, keep_best_launch, mse_loss_grad, prepared_weights, refresh_prepared, rows_align)
 from .modules import GCN_GRU
+from .series import n_series_windows, series_backward_mse_raw, series_forward_loss_raw
 
 AUTO_GRAD_BLOCKS = 8                # grad_blocks="auto": row blocks per GRU weight ...
 AUTO_BLOCK_BYTES = 64 << 20         # ... from a gradient bucket of this size (smaller ones are latency-bound: one bucket)
@@ -485,6 +494,105 @@ class TrainStep:
         loss = self._loss
         gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, loss, 1.0, part=7 | 8,
                                  prepared=self._prepared)
+        return loss, Y
+
+    def _series_refusals(self, A, series, seq_len, stride):
+        """What step_series / forward_backward_series refuse, each before any launch and with the alternative."""
+        windows = ("materialise the windows and labels (windgnn_amd.data.make_windows(feat, seq_len, starts=...)) and call "
+                   "TrainStep.step(A, X, L) on them")
+        why = None
+        if self.carry_state:
+            why = ("carry_state=True: every window of series mode starts from h = 0; for truncated BPTT over consecutive chunks "
+                   + windows)
+        elif self.plan is not None:
+            why = "grad_blocks: the blocked exchange needs the row-range weight gradients (wgnn_bwd_rows); " + windows
+        elif self.overlap_collectives:
+            why = ("overlap_collectives=True: series mode runs the one-bucket schedule (one all-reduce after the backward); build "
+                   "the TrainStep with overlap_collectives=False, or " + windows)
+        elif self.model.math != _lib.MATH_F32:
+            why = "math != 'f32': series mode is exact fp32 only; build the model with math='f32', or " + windows
+        elif hasattr(A, "blob"):
+            why = "a CsrAdjacency: series mode takes a dense adjacency (S <= 64); pass the dense matrix, or " + windows
+        elif not getattr(self.model, "fused", False):
+            why = "a model of other widths than the reference's 13 / 13: train it through autograd (loss.backward())"
+        if why is not None:
+            raise RuntimeError("windgnn_amd: TrainStep.step_series with " + why)
+        if series.dim() != 3 or series.shape[2] != 13:
+            raise RuntimeError("windgnn_amd: TrainStep.step_series: series must be [rows, S, 13], got %s" % (tuple(series.shape),))
+        if int(seq_len) < 1 or int(stride) < 1:
+            raise ValueError("windgnn_amd: TrainStep.step_series: seq_len and stride must be >= 1, got %r and %r"
+                             % (seq_len, stride))
+
+    def _series_forward(self, A, series, Ls, seq_len, stride, n):
+        """The W_ih images, then wgnn_series_fwd_loss: (Y, stash, loss_buf, sd, d); d = the B-independent dims of the
+        tail, as in _empty_shard_step."""
+        _require_gpu(series, Ls, *self.p_views)      # before the images: nothing is launched on host memory
+        S, H = series.shape[1], self.p_views[5].shape[1]
+        d = _lib.Dims(1, seq_len, S, 13, H, _lib.MATH_F32, _lib.ADJ_DENSE, 0, _lib.IO_F32)
+        if self._prepared_version != self._param_version():
+            self._images(d)
+        Y, stash, loss_buf, sd = series_forward_loss_raw(A, series, Ls, seq_len, stride, self.p_views, _lib.MATH_F32,
+                                                         n_windows=n, prepared=self._prepared)
+        return Y, stash, loss_buf, sd, d
+
+    def _series_count(self, series, Ls, seq_len, stride, n_windows):
+        """The window count of this call, with n_windows and Ls checked against it."""
+        fit = n_series_windows(series.shape[0], seq_len, stride)
+        n = fit if n_windows is None else int(n_windows)
+        if n < 0 or n > fit:
+            raise RuntimeError("windgnn_amd: TrainStep.step_series: n_windows = %d, but a series of %d rows holds %d windows of "
+                               "%d rows at stride %d" % (n, series.shape[0], fit, seq_len, stride))
+        need = (n - 1) * stride + seq_len
+        H = self.p_views[5].shape[1]
+        if n > 0 and (Ls.dim() != 2 or Ls.shape[1] != H or Ls.shape[0] < need):
+            raise RuntimeError("windgnn_amd: TrainStep.step_series: the label series Ls must be [rows >= (n - 1) * stride + "
+                               "seq_len = %d, H = %d] (series_labels(feat, seq_len, stride, n_windows)[0]; its window view L is "
+                               "for TrainStep.step on materialised windows), got %s" % (need, H, tuple(Ls.shape)))
+        return n
+
+    def forward_backward_series(self, A, series, Ls, seq_len, stride=1, n_windows=None):
+        """forward_backward on the first n_windows sliding windows of `series` [rows, S, 13] with the label series Ls
+        [>= (n - 1) * stride + seq_len, H]: returns (loss, Y [n, seq_len, H]); the gradients land in the flat bucket, final (no
+        optimiser step).  `loss` is a view of the bucket's header word."""
+        seq_len, stride = int(seq_len), int(stride)
+        self._series_refusals(A, series, seq_len, stride)
+        series, Ls = series.contiguous(), Ls.contiguous()
+        n = self._series_count(series, Ls, seq_len, stride, n_windows)
+        if n == 0:
+            raise RuntimeError("windgnn_amd: TrainStep.forward_backward_series needs at least one window (a series of %d rows, "
+                               "seq_len %d, n_windows %r)" % (series.shape[0], seq_len, n_windows))
+        Y, stash, loss_buf, sd, _ = self._series_forward(A, series, Ls, seq_len, stride, n)
+        series_backward_mse_raw(sd, A, series, self.p_views, Y, Ls, stash, loss_buf, self.g_views, self._loss, 1.0,
+                                prepared=self._prepared)
+        return self._loss, Y
+
+    def step_series(self, A, series, Ls, seq_len, stride=1, n_windows=None, n_global=None):
+        """One optimiser step on the first `n_windows` (default: all that fit) sliding windows of this rank's `series`
+        [rows, S, 13]: window w covers rows w * stride .. w * stride + seq_len - 1 and starts from h = 0, as step() on the
+        materialised windows would.  Ls [>= (n - 1) * stride + seq_len, H]: the label SERIES (series_labels(feat, seq_len,
+        stride, n_windows)[0]), read at the rows the windows cover; no window-major labels and no dY exist.  `n_global`: as in
+        step().  Returns (loss, Y [n, seq_len, H]); the loss is the same 0-dim VIEW of the bucket's header word.  Under a
+        process group every rank passes its own sub-series (the caller's slicing: consecutive ranks' rows overlap by
+        seq_len - stride); a rank with no window takes the empty-shard step."""
+        seq_len, stride = int(seq_len), int(stride)
+        self._series_refusals(A, series, seq_len, stride)
+        series, Ls = series.contiguous(), Ls.contiguous()
+        n = self._series_count(series, Ls, seq_len, stride, n_windows)
+        if n == 0:
+            return self._empty_shard_step(A, series.new_empty((0, seq_len) + tuple(series.shape[1:])), n_global)
+        loss = self._loss
+        gs = self.exchange.shard_weight(n, n_global) if self.collective else 1.0
+        Y, stash, loss_buf, sd, d = self._series_forward(A, series, Ls, seq_len, stride, n)
+        pre = self._prepared
+        series_backward_mse_raw(sd, A, series, self.p_views, Y, Ls, stash, loss_buf, self.g_views, loss, gs, prepared=pre)
+        if self.collective:
+            self.exchange.all_reduce_all(gs)    # loss: sum of the weighted shard means = the big-batch mean
+        self._tail(d, 0, pre)                   # the bucket is final: Adam (+ the norm with max_grad_norm) and the W_ih images
+        self.steps += 1
+        self._keep_best()
+        if self.check_every and self.steps % self.check_every == 0 and (
+                self.exchange is not None and self.exchange.direct is not None):
+            self.check()
         return loss, Y
 
     def _forward(self, A, X, L):
