@@ -16,7 +16,12 @@ A case is (family, key, S, T, B, H, math, io, state, route):
          'fused'     the same with WGNN_OPT_FUSED_FWD = 2               (gcngi_fwd_kernel writes the stash planes of g)
          'infer'     wgnn_fwd without a stash                           (gcngi_fwd_kernel, no plane of g written)
 Shapes are the smallest that select the instance: T = 2 or 3, the smallest S / H of the wanted tile count, B = 17 (B = 1 mod 16:
-the last workgroup of a recurrence is ragged), and the threshold itself where a threshold selects (see CASES)."""
+the last workgroup of a recurrence is ragged), and the threshold itself where a threshold selects (see CASES).
+
+The series entry points (wgnn_series_*) have their own half: SERIES_FAMILIES, series_plan() and SERIES_CASES, whose cases are
+(family, key, S, H, rows, T, stride, n, seed, route) with route 'series' (wgnn_series_fwd + wgnn_series_bwd with a signed
+random dY), 'series_mse' (wgnn_series_fwd_loss + wgnn_series_bwd_mse) or 'series_last' (wgnn_series_fwd_last);
+tests/test_gpu_series_instances.py proves them on the GPU."""
 import re
 
 MATHS = ("f32", "f16x3", "f16", "f16x3g")
@@ -169,6 +174,51 @@ def refusal(S, T, B, H, math, io):
     return None
 
 
+def g32_rows(BT, S, H):
+    """api.hip make_layout, L.g32 (and L.g32tn: gemm32_tn_supported is the same threshold) of an exact-fp32 layout of BT rows
+    with gru.hip's or gru_small.hip's recurrence: gemm32.hip's products instead of gemm.hip's."""
+    return BT >= 4096 and rup(13 * S + 1, 32) <= 512 and rup(3 * H, 32) <= 512
+
+
+def gemm32_nt_name(BT, N):
+    big = cdiv(BT, 128) >= 192
+    _, t = gemm32_nt_shape(N, big)
+    return "gemm32_nt_kernel<%dx%d>" % ((128, 64 * t) if big else (32, 32 * t))
+
+
+# The exact-fp32 family's parts of a step over a layout of BT rows (api.hip fwd_front, bwd_weights, bwd_dg); g32 = g32_rows of
+# THAT layout.  plan() runs all four on B*T rows; series_plan() the front end, dW_ih and dg on the series' rows and dW_hh on n*T.
+def f32_front(S, H, BT, g32):
+    I, G3 = 13 * S, 3 * H
+    if g32:
+        return ["gcn32_fwd_kernel<%d>" % gcn_nt(S), gemm32_nt_name(BT, G3)]
+    sk = gemm_f32_nt_splitk(BT, G3, I) if BT < 65536 else 1
+    return ["gcn32_fwd_kernel<%d>" % gcn_nt(S), gemm_f32_name(BT, G3, sk, "kk")]
+
+
+def f32_dw_hh(H, BT, g32, dghn, state):
+    if g32:
+        return "gemm32_tn_kernel<%d>|a2=%d" % (gemm32_tn_shape(H + 1)[1], dghn)
+    sk_hh = pick_splitk(BT, gemm_f32_tiles(3 * H, H + 1), 1024, 128)
+    return gemm_f32_name(3 * H, H + 1, sk_hh, "tn,ones" if state else "tn,ones,shift")
+
+
+def f32_dw_ih(S, H, BT, g32):
+    I, G3 = 13 * S, 3 * H
+    if g32:
+        return "gemm32_tn_kernel<%d>|a2=0" % gemm32_tn_shape(I + 1)[1]
+    return gemm_f32_name(G3, I + 1, pick_splitk(BT, gemm_f32_tiles(G3, I + 1), 1024, 128), "tn,ones")
+
+
+def f32_dg(S, H, BT, g32):
+    I, G3 = 13 * S, 3 * H
+    if g32:
+        gemm = gemm32_nt_name(BT, I)
+    else:
+        gemm = gemm_f32_name(BT, I, gemm_f32_nt_splitk(BT, I, G3) if BT < 65536 else 1, "kn")
+    return [gemm, "gcn32_bwd_kernel<%d>|w=%d" % (gcn_nt(S), 16 if (S <= 48 and BT >= 16384) else 12)]
+
+
 def plan(S, T, B, H, math, io="f32", state=False, route="train"):
     """Every key of the tabled families that one step of this call form launches, in launch order (a dense adjacency)."""
     assert refusal(S, T, B, H, math, io) is None, (S, T, B, H, math, io)
@@ -178,7 +228,7 @@ def plan(S, T, B, H, math, io="f32", state=False, route="train"):
     gen = H > 127 if x3f else H > 128                       # gen_gru
     BT, I, G3 = B * T, 13 * S, 3 * H
     Ip, Gp, Hp = rup(I + 1, 32), rup(G3, 32), 32 * cdiv(H + 1, 32)
-    g32 = not x3f and not gen and BT >= 4096 and Ip <= 512 and Gp <= 512
+    g32 = not x3f and not gen and g32_rows(BT, S, H)
     small = not x3f and not gen and B <= 768
     rec32 = not x3f and not gen and not small
     dghn = (x3f and not gen) or (rec32 and g32)
@@ -206,14 +256,7 @@ def plan(S, T, B, H, math, io="f32", state=False, route="train"):
         out.append("gcnx_fwd_kernel<%d%s>%s" % (gcn_nt(S), mode, iok))
         nt(BT, G3, Ip, True, gi16)
     else:
-        out.append("gcn32_fwd_kernel<%d>" % gcn_nt(S))
-        if g32:
-            big = cdiv(BT, 128) >= 192
-            _, t = gemm32_nt_shape(G3, big)
-            out.append("gemm32_nt_kernel<%dx%d>" % ((128, 64 * t) if big else (32, 32 * t)))
-        else:
-            sk = gemm_f32_nt_splitk(BT, G3, I) if BT < 65536 else 1
-            out.append(gemm_f32_name(BT, G3, sk, "kk"))
+        out += f32_front(S, H, BT, g32)
     # ---- forward recurrence
     h0 = state
     if x3f and not gen:
@@ -262,28 +305,44 @@ def plan(S, T, B, H, math, io="f32", state=False, route="train"):
         else:
             out.append("pgemm_tn_kernel<%d%s>|a2=%d%s" % (th, hh_sfx, dghn, pw))
             out.append("pgemm_tn_kernel<%d%s>|a2=0|pw=0" % (ti, "" if ih_x3 else ",f16"))
-    elif g32:
-        out.append("gemm32_tn_kernel<%d>|a2=%d" % (gemm32_tn_shape(H + 1)[1], dghn))
-        out.append("gemm32_tn_kernel<%d>|a2=0" % gemm32_tn_shape(I + 1)[1])
     else:
-        sk_ih = pick_splitk(BT, gemm_f32_tiles(G3, I + 1), 1024, 128)
-        sk_hh = pick_splitk(BT, gemm_f32_tiles(G3, H + 1), 1024, 128)
-        out.append(gemm_f32_name(G3, H + 1, sk_hh, "tn,ones" if state else "tn,ones,shift"))
-        out.append(gemm_f32_name(G3, I + 1, sk_ih, "tn,ones"))
+        out.append(f32_dw_hh(H, BT, g32, dghn, state))
+        out.append(f32_dw_ih(S, H, BT, g32))
     # ---- dg and the GCN backward
     if x3f:
         nt(BT, I, Gp, not (dgi1 or gen2p), dg16)
         out.append("gcnx_bwd_kernel<%d%s>%s|dg16=%d" % (gcn_nt(S), mode, iok, dg16))
     else:
-        if g32:
-            big = cdiv(BT, 128) >= 192
-            _, t = gemm32_nt_shape(I, big)
-            out.append("gemm32_nt_kernel<%dx%d>" % ((128, 64 * t) if big else (32, 32 * t)))
-        else:
-            sk = gemm_f32_nt_splitk(BT, I, G3) if BT < 65536 else 1
-            out.append(gemm_f32_name(BT, I, sk, "kn"))
-        out.append("gcn32_bwd_kernel<%d>|w=%d" % (gcn_nt(S), 16 if (S <= 48 and BT >= 16384) else 12))
+        out += f32_dg(S, H, BT, g32)
     return out
+
+
+SERIES_ROUTES = ("series", "series_mse", "series_last")
+
+
+def fold_terms(T, stride):
+    """How many windows cover an hour away from the two ends of the series: series_fold_kernel's trip count w_lo .. w_hi."""
+    if stride == 1:
+        return "T"
+    return "%d..%d" % (T // stride, cdiv(T, stride))
+
+
+def series_plan(S, H, rows, T, stride, n, route):
+    """api.hip series_forward / series_backward restated: every tabled key one series step of `route` launches, in launch order.
+    Two exact-fp32 layouts (series.hip plan): the front {B = 1, T = rows} -- both graph convolutions, the input projection, dW_ih,
+    dg and the GCN backward, once per hour -- and the recurrence {B = n, T} -- gru.hip's kernels and dW_hh over the n*T
+    window-major rows.  Each consults gemm32's threshold with its own row count; gru_small_supported is not consulted."""
+    assert route in SERIES_ROUTES and (n - 1) * stride + T <= rows and 1 <= S <= 64 and 1 <= H <= 128, (S, H, rows, T, stride, n)
+    g32_f, g32_r = g32_rows(rows, S, H), g32_rows(n * T, S, H)       # Lf.g32 = Lf.g32tn; Lr.g32tn = Lr.dghn = the [Hprev | 1] rows
+    out = f32_front(S, H, rows, g32_f)
+    out.append("gru_fwd_kernel<%d>|series|%s" % (gru_fwd_k(H), {"series": "y", "series_mse": "loss", "series_last": "last"}[route]))
+    if route == "series_last":
+        return out
+    out.append("gru_bwd_kernel<%d>|series|%s|%s" % (gru_bwd_k(H), "dY" if route == "series" else "mse", "dGHn" if g32_r else "dGH"))
+    out.append(f32_dw_hh(H, n * T, g32_r, g32_r, False))
+    out.append("series_fold_kernel|terms=%s" % fold_terms(T, stride))
+    out.append(f32_dw_ih(S, H, rows, g32_f))
+    return out + f32_dg(S, H, rows, g32_f)
 
 
 def name_of(key):
@@ -359,6 +418,25 @@ FAMILIES = {
     "gemm32_tn_kernel": _keys("gemm32_tn_kernel<%d>|a2=%d", GEMM32_TN_T, _BIT),
     # gemm.hip: <bm / 64, bn / 64> and the operand forms of the name
     "gemm_f32_kernel": GEMM_F32_NAMES,
+}
+
+# The series entry points (include/windgnn_series.h, windgnn_series_train.h).  Their recurrences are further instances of
+# gru.hip's two templates with the SAME profiler names as the window-major ones (FCASE / BCASE print K alone): the entry point
+# fixes the SeriesRows argument -- every wgnn_series_* call passes a non-zero stride, no other call does -- and the call form the
+# run-time paths behind it, so a name launched by a series route IS the series instance.
+SERIES_FAMILIES = {
+    # gru.hip gru_fwd_kernel<K, false, SeriesRows>: GI (and the labels) read at series rows w*stride + t.  y: wgnn_series_fwd
+    # (Y and the gate records); loss: wgnn_series_fwd_loss (+ the label series and the statistics pair per workgroup);
+    # last: wgnn_series_fwd_last (last_only: no Y, no records, the de-normalised last row).  The [Hprev | 1] rows are written
+    # by y / loss when n*T >= 4096, which is when the BPTT kernel's key says dGHn
+    "gru_fwd_kernel": _keys("gru_fwd_kernel<%d>|series|%s", GRU_FWD_KS, ["y", "loss", "last"]),
+    # gru.hip gru_bwd_kernel<K3, SeriesRows>: dY: wgnn_series_bwd; mse: wgnn_series_bwd_mse (dY formed from Y and the label
+    # series, the loss finalised); dGHn: the n third of dGH alone (n*T >= 4096 and S <= 39, dW_hh by gemm32_tn_kernel's
+    # two-source form), dGH: all of it (dW_hh by gemm_f32_kernel[tn,ones,shift])
+    "gru_bwd_kernel": _keys("gru_bwd_kernel<%d>|series|%s|%s", GRU_BWD_KS3, ["dY", "mse"], ["dGH", "dGHn"]),
+    # series.hip: one kernel; terms = how many windows cover an interior hour (the loop's trip count): 0..1 with stride > T
+    # (uncovered hours come out as zero rows), 1..2 with T = 3 at stride 2, T at stride 1
+    "series_fold_kernel": ["series_fold_kernel|terms=%s" % t for t in ("0..1", "1..2", "T")],
 }
 
 # pgemm_tn2_kernel: 7 x 4 pairs per mode and per-window form; required: every TI and every TH at least once per mode and
@@ -1043,4 +1121,86 @@ CASES = [
     ("gemm_f32_kernel", "gemm_f32_kernel<128,64>[kk]", 1, 3, 8161, 192, "f32", "f32", False, "train"),
     ("gemm_f32_kernel", "gemm_f32_kernel<128,128>[kk]", 1, 24, 1537, 129, "f32", "f32", False, "train"),
     ("gemm_f32_kernel", "gemm_f32_kernel<128,128>[kn]", 52, 3, 8161, 4, "f32", "f32", False, "train"),
+]
+
+# ---- the series entry points -------------------------------------------------------------------------------------------
+# (family, key, S, H, rows, T, stride, n, seed, route); the inputs are tests/test_gpu_series.py's _draw(S, H, rows, T, stride, n,
+# seed).  n = 1 (mod 16): the last workgroup of a recurrence is ragged, with one valid window.
+# Shape A: rows 36, T 3, stride 2, n 17 -- n*T = 51, both layouts below 4096: the full dGH, no [Hprev | 1] rows; coverage
+#   alternates between 1 and 2, one spare row; H at the TOP of each K's range (4 K: every k slot of the instance in use).
+# Shape B: rows 272, T 16, stride 1, n 257 -- n*T = 4112 >= 4096 with the front layout (272 rows) below: dGHn and the
+#   [Hprev | 1] rows of rup(H + 1, 16) floats; H at the BOTTOM of each range (4 K_prev + 1).
+# The fold's zero rows: tests/test_gpu_series.py's `gaps` shape (stride 5 > T 3: hours 3, 4, 8, 9 are covered by no window).
+# Seeds: the smallest at which no ReLU pre-activation of the fp64 reference lies within 1e-5 (relative) of zero and the
+# reference's own fp32 evaluation agrees with its fp64 one to 1e-5 (tests/test_instance_table_host.py asserts both).
+SERIES_CASES = [
+    # ---- gru_fwd_kernel
+    ("gru_fwd_kernel", "gru_fwd_kernel<4>|series|y", 2, 16, 36, 3, 2, 17, 0, "series"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<4>|series|loss", 2, 16, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<4>|series|last", 2, 16, 36, 3, 2, 17, 0, "series_last"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<8>|series|y", 2, 32, 36, 3, 2, 17, 0, "series"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<8>|series|loss", 2, 32, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<8>|series|last", 2, 32, 36, 3, 2, 17, 0, "series_last"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<12>|series|y", 2, 48, 36, 3, 2, 17, 0, "series"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<12>|series|loss", 2, 48, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<12>|series|last", 2, 48, 36, 3, 2, 17, 0, "series_last"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<16>|series|y", 2, 64, 36, 3, 2, 17, 0, "series"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<16>|series|loss", 2, 64, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<16>|series|last", 2, 64, 36, 3, 2, 17, 0, "series_last"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<20>|series|y", 2, 80, 36, 3, 2, 17, 0, "series"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<20>|series|loss", 2, 80, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<20>|series|last", 2, 80, 36, 3, 2, 17, 0, "series_last"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<24>|series|y", 2, 96, 36, 3, 2, 17, 0, "series"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<24>|series|loss", 2, 96, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<24>|series|last", 2, 96, 36, 3, 2, 17, 0, "series_last"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<26>|series|y", 2, 104, 36, 3, 2, 17, 0, "series"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<26>|series|loss", 2, 104, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<26>|series|last", 2, 104, 36, 3, 2, 17, 0, "series_last"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<28>|series|y", 2, 112, 36, 3, 2, 17, 0, "series"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<28>|series|loss", 2, 112, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<28>|series|last", 2, 112, 36, 3, 2, 17, 0, "series_last"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<32>|series|y", 2, 128, 36, 3, 2, 17, 0, "series"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<32>|series|loss", 2, 128, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_fwd_kernel", "gru_fwd_kernel<32>|series|last", 2, 128, 36, 3, 2, 17, 0, "series_last"),
+    # ---- gru_bwd_kernel
+    ("gru_bwd_kernel", "gru_bwd_kernel<12>|series|dY|dGH", 2, 16, 36, 3, 2, 17, 0, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<12>|series|dY|dGHn", 2, 4, 272, 16, 1, 257, 0, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<12>|series|mse|dGH", 2, 16, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<12>|series|mse|dGHn", 2, 4, 272, 16, 1, 257, 0, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<24>|series|dY|dGH", 2, 32, 36, 3, 2, 17, 0, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<24>|series|dY|dGHn", 2, 17, 272, 16, 1, 257, 7, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<24>|series|mse|dGH", 2, 32, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<24>|series|mse|dGHn", 2, 17, 272, 16, 1, 257, 7, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<36>|series|dY|dGH", 2, 48, 36, 3, 2, 17, 0, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<36>|series|dY|dGHn", 2, 33, 272, 16, 1, 257, 1, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<36>|series|mse|dGH", 2, 48, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<36>|series|mse|dGHn", 2, 33, 272, 16, 1, 257, 1, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<48>|series|dY|dGH", 2, 64, 36, 3, 2, 17, 0, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<48>|series|dY|dGHn", 2, 49, 272, 16, 1, 257, 0, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<48>|series|mse|dGH", 2, 64, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<48>|series|mse|dGHn", 2, 49, 272, 16, 1, 257, 0, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<60>|series|dY|dGH", 2, 80, 36, 3, 2, 17, 0, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<60>|series|dY|dGHn", 2, 65, 272, 16, 1, 257, 5, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<60>|series|mse|dGH", 2, 80, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<60>|series|mse|dGHn", 2, 65, 272, 16, 1, 257, 5, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<72>|series|dY|dGH", 2, 96, 36, 3, 2, 17, 0, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<72>|series|dY|dGHn", 2, 81, 272, 16, 1, 257, 0, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<72>|series|mse|dGH", 2, 96, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<72>|series|mse|dGHn", 2, 81, 272, 16, 1, 257, 0, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<78>|series|dY|dGH", 2, 104, 36, 3, 2, 17, 0, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<78>|series|dY|dGHn", 2, 97, 272, 16, 1, 257, 1, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<78>|series|mse|dGH", 2, 104, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<78>|series|mse|dGHn", 2, 97, 272, 16, 1, 257, 1, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<84>|series|dY|dGH", 2, 112, 36, 3, 2, 17, 0, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<84>|series|dY|dGHn", 2, 105, 272, 16, 1, 257, 0, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<84>|series|mse|dGH", 2, 112, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<84>|series|mse|dGHn", 2, 105, 272, 16, 1, 257, 0, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<96>|series|dY|dGH", 2, 128, 36, 3, 2, 17, 0, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<96>|series|dY|dGHn", 2, 113, 272, 16, 1, 257, 0, "series"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<96>|series|mse|dGH", 2, 128, 36, 3, 2, 17, 0, "series_mse"),
+    ("gru_bwd_kernel", "gru_bwd_kernel<96>|series|mse|dGHn", 2, 113, 272, 16, 1, 257, 0, "series_mse"),
+    # ---- series_fold_kernel
+    ("series_fold_kernel", "series_fold_kernel|terms=0..1", 7, 21, 13, 3, 5, 3, 0, "series"),
+    ("series_fold_kernel", "series_fold_kernel|terms=1..2", 2, 16, 36, 3, 2, 17, 0, "series"),
+    ("series_fold_kernel", "series_fold_kernel|terms=T", 2, 4, 272, 16, 1, 257, 0, "series"),
 ]

@@ -2,7 +2,9 @@
 one case (or listed as unreachable, with the line of api.hip that excludes it), the integer lists of the table are the lists
 in the launcher sources (extracted as text: a pattern that stops matching fails), and the Python selection formulas put every
 case on the key it claims.  The library's host-only queries confirm what they can: it sizes a workspace for every case's
-dims, refuses the refused ones, and its split-K counts are the formulas'."""
+dims, refuses the refused ones, and its split-K counts are the formulas'.  The series half (SERIES_FAMILIES / SERIES_CASES) is
+held to the same rules, and its inputs are measured on the fp64 oracle alone: tie-free, well conditioned in fp32, and able to
+tell an off-by-one row."""
 import ctypes
 import os
 import re
@@ -17,6 +19,7 @@ MATH = {"f32": 0, "f16x3": 1, "f16": 2, "f16x3g": 3}
 IO = {"f32": 0, "f16": 1, "bf16": 2}
 # (T, B) of the cases: the plain pair, the first batch of gru.hip's recurrences, and the thresholds named above CASES
 PLAIN_TB = {(2, 17), (3, 17), (2, 33)}          # (2, 33): one-pass fp16 cases grown once (see F16_EXCEPTIONS)
+ALL_CASES = ic.CASES + ic.SERIES_CASES
 THRESHOLD_TB = {(2, 769), (2, 2049), (2, 3073), (3, 1025), (3, 5473), (3, 8161), (24, 1537)}
 
 
@@ -98,17 +101,21 @@ def table_lists():
 
 
 def coverage_problems(cases):
-    """What is wrong with `cases` as a cover of ic.FAMILIES: a list of sentences, empty when every key is claimed once."""
+    """What is wrong with `cases` (window-major and series cases together) as a cover of ic.FAMILIES and ic.SERIES_FAMILIES: a
+    list of sentences, empty when every key is claimed once."""
     bad = []
     claimed = {}
+    families = {fam: list(ic.FAMILIES.get(fam, ())) + list(ic.SERIES_FAMILIES.get(fam, ()))
+                for fam in list(ic.FAMILIES) + [f for f in ic.SERIES_FAMILIES if f not in ic.FAMILIES]}
     for c in cases:
         fam, key = c[0], c[1]
-        if ic.family_of(key) != fam or key not in ic.FAMILIES.get(fam, ()):
+        table = ic.SERIES_FAMILIES if c[-1] in ic.SERIES_ROUTES else ic.FAMILIES       # a case claims a key of its own table
+        if ic.family_of(key) != fam or key not in table.get(fam, ()):
             bad.append("%s is no key of family %s" % (key, fam))
         if key in claimed:
             bad.append("%s is claimed twice" % key)
         claimed[key] = c
-    for fam, keys in ic.FAMILIES.items():
+    for fam, keys in families.items():
         if len(set(keys)) != len(keys):
             bad.append("family %s lists a key twice" % fam)
         for key in keys:
@@ -119,7 +126,7 @@ def coverage_problems(cases):
             if len(where) != 1:
                 bad.append("%s is in %s" % (key, where or "no list"))
     for key in list(ic.UNREACHABLE) + list(ic.BEYOND_BUDGET):
-        if not any(key in keys for keys in ic.FAMILIES.values()):
+        if not any(key in keys for keys in families.values()):
             bad.append("%s is excluded but no family lists it" % key)
     # the merged launch: every TI and every TH at least once per pass mode and per-window form, TI > TH and TI < TH among them
     for sfx in ("", ",x2", ",f16"):
@@ -134,8 +141,11 @@ def coverage_problems(cases):
 
 
 def test_every_instance_key_is_claimed_by_exactly_one_case():
-    assert coverage_problems(ic.CASES) == []
-    assert len(ic.CASES) == len({c[1] for c in ic.CASES})
+    assert coverage_problems(ALL_CASES) == []
+    assert len(ALL_CASES) == len({c[1] for c in ALL_CASES})
+    for fam, count in (("gru_fwd_kernel", 27), ("gru_bwd_kernel", 36), ("series_fold_kernel", 3)):
+        assert len(ic.SERIES_FAMILIES[fam]) == count == len([c for c in ic.SERIES_CASES if c[0] == fam]), fam
+    assert not {k for keys in ic.FAMILIES.values() for k in keys} & {k for keys in ic.SERIES_FAMILIES.values() for k in keys}
     assert set(ic.TN2_REQUIRED) <= set(ic.FAMILIES["pgemm_tn2_kernel"])
 
 
@@ -152,8 +162,14 @@ def test_the_integer_lists_are_those_of_the_launcher_sources():
 
 def test_the_checks_notice_a_deleted_case_and_a_new_instantiation():
     for i in (0, len(ic.CASES) // 2, len(ic.CASES) - 1):
-        assert coverage_problems(ic.CASES[:i] + ic.CASES[i + 1:]), ic.CASES[i]
-    assert coverage_problems(ic.CASES + [ic.CASES[0]])
+        assert coverage_problems(ic.CASES[:i] + ic.CASES[i + 1:] + ic.SERIES_CASES), ic.CASES[i]
+    for i in range(len(ic.SERIES_CASES)):                        # every one of them: each is the only claim of its key
+        gone = coverage_problems(ic.CASES + ic.SERIES_CASES[:i] + ic.SERIES_CASES[i + 1:])
+        assert gone == ["%s is in no list" % ic.SERIES_CASES[i][1]], (ic.SERIES_CASES[i], gone)
+    assert coverage_problems(ALL_CASES + [ic.CASES[0]]) and coverage_problems(ALL_CASES + [ic.SERIES_CASES[0]])
+    assert coverage_problems(ic.CASES)                           # the window-major table alone no longer covers the keys
+    moved = ("gru_fwd_kernel", "gru_fwd_kernel<4>|st=0") + ic.SERIES_CASES[0][2:]      # a series case claims no window-major key
+    assert coverage_problems([c for c in ALL_CASES if c[1] != moved[1]] + [moved])
 
     def grown(name):                                             # gru.hip with one more entry in FWD_KS
         text = _read(name)
@@ -235,3 +251,154 @@ def test_the_library_accepts_every_case_and_splits_k_as_the_formulas_do():
                                  (65, 2, 17, 4, "f16x3", "f32")):
         assert ic.refusal(S, T, B, H, math, io)
         assert lib.wgnn_workspace_bytes(ctypes.byref(L.Dims(B, T, S, 13, H, MATH[math], 0, 0, IO[io]))) == 0
+
+
+# ---- the series half of the table ------------------------------------------------------------------------------------------
+FOLD_ZERO_ROWS = "series_fold_kernel|terms=0..1"
+SHAPE_A = (2, 36, 3, 2, 17)          # (S, rows, T, stride, n): both layouts below gemm32's threshold
+SHAPE_B = (2, 272, 16, 1, 257)       # the recurrence layout above it, the front layout below
+TOPS = [4 * k for k in ic.GRU_FWD_KS]                                 # H with every k slot of the instance in use
+BOTTOMS = [4] + [4 * k + 1 for k in ic.GRU_FWD_KS[:-1]]               # the first H of each instance
+
+
+def test_series_plan_puts_every_series_case_on_its_key():
+    allkeys = {k for keys in list(ic.FAMILIES.values()) + list(ic.SERIES_FAMILIES.values()) for k in keys}
+    for fam, key, S, H, rows, T, stride, n, seed, route in ic.SERIES_CASES:
+        keys = ic.series_plan(S, H, rows, T, stride, n, route)
+        assert key in keys and set(keys) <= allkeys and not set(keys) & set(ic.UNREACHABLE), (key, keys)
+        assert [k for k in keys if "|series|" in k or k.startswith("series_fold")] == \
+            [k for k in keys if any(k in f for f in ic.SERIES_FAMILIES.values())], key
+        assert (n - 1) * stride + T <= rows and route in ic.SERIES_ROUTES, key
+        if key == FOLD_ZERO_ROWS:
+            assert stride > T, key
+            continue
+        # the shape rules: n = 1 (mod 16), one of the two shapes, H at the top (A) or at the bottom (B) of its instance's range
+        assert n % 16 == 1 and (S, rows, T, stride, n) in (SHAPE_A, SHAPE_B), key
+        assert H in (TOPS if (S, rows, T, stride, n) == SHAPE_A else BOTTOMS), key
+        assert ("dGHn" in key) == ((S, rows, T, stride, n) == SHAPE_B) or fam != "gru_bwd_kernel", key
+    # shape A: a ragged second workgroup with one window, coverage 1 and 2, one spare row; shape B: on the two sides of 4096
+    S, rows, T, stride, n = SHAPE_A
+    assert n == 16 + 1 and rows == (n - 1) * stride + T + 1 and n * T < 4096 and ic.fold_terms(T, stride) == "1..2"
+    S, rows, T, stride, n = SHAPE_B
+    assert n % 16 == 1 and rows < 4096 <= n * T and (n - 16) * T < 4096 and ic.fold_terms(T, stride) == "T"   # the first such n
+    assert TOPS == [16, 32, 48, 64, 80, 96, 104, 112, 128] and BOTTOMS == [4, 17, 33, 49, 65, 81, 97, 105, 113]
+    for Ht, Hb, K, K3 in zip(TOPS, BOTTOMS, ic.GRU_FWD_KS, ic.GRU_BWD_KS3):
+        assert ic.gru_fwd_k(Ht) == ic.gru_fwd_k(Hb) == K and ic.gru_bwd_k(Ht) == ic.gru_bwd_k(Hb) == K3
+    # the two layouts decide apart: each product follows the row count of its own layout
+    for rows, nT, want in ((4095, 4095, (0, 0)), (4096, 2048, (1, 0)), (2050, 4096, (0, 1)), (4097, 8192, (1, 1))):
+        keys = ic.series_plan(7, 21, rows, 2, 1 if nT >= rows - 1 else 2, nT // 2, "series")
+        assert ("gemm32_nt_kernel<32x64>" in keys, "gru_bwd_kernel<24>|series|dY|dGHn" in keys) == tuple(map(bool, want)), keys
+        assert ("gemm32_tn_kernel<3>|a2=0" in keys, "gemm32_tn_kernel<1>|a2=1" in keys) == tuple(map(bool, want)), keys
+
+
+def test_series_plan_decides_where_the_sources_do():
+    gemm32, api, series, gru = (_read(n + ".hip") for n in ("gemm32", "api", "series", "gru"))
+    nt = re.search(r"bool gemm32_nt_supported\(size_t BT, int Kp_f, int Kp_b\) \{\s*return ([^;]*);", gemm32)
+    assert nt and nt.group(1) == "BT >= 4096 && Kp_f % 32 == 0 && Kp_b % 32 == 0 && Kp_f <= 512 && Kp_b <= 512", nt
+    assert "bool gemm32_tn_supported(size_t BT) { return BT >= 4096; }" in gemm32
+    assert ic.g32_rows(4096, 39, 128) and not ic.g32_rows(4095, 1, 4) and not ic.g32_rows(1 << 20, 40, 4)
+    assert "constexpr int MB = 16;" in gru                         # 16 windows per workgroup: n = 1 (mod 16) is ragged
+    # series mode never takes gru_small, and each layout is made with its own row count
+    assert "L.small = !x3 && !L.gen_gru && !series && gru_small_supported(d->B, d->H);" in api
+    assert "L.dghn = (x3 && !L.gen_gru) || (L.rec32 && L.g32tn);" in api
+    assert "pl->front = wgnn_dims{1, sd->rows, sd->S," in series and "pl->rec = wgnn_dims{sd->n, sd->T, sd->S," in series
+    # the launch order of series_backward, and which layout each part runs on
+    bwd = _body(api, "int series_backward(")
+    order = ["launch_gru_bwd(dr->B, dr->T, dr->H", "bwd_weights(br, WGNN_ROWS_HH", "launch_series_fold(br.dGI",
+             "bwd_weights(bf, WGNN_ROWS_IH", "bwd_dg(bf)"]
+    at = [bwd.find(x) for x in order]
+    assert min(at) >= 0 and at == sorted(at), at
+    assert "Lr.dghn ? br.dGH : nullptr, Lr.dghn ? nullptr : br.dGH" in bwd
+    fwd = _body(api, "int series_forward(")
+    assert "fwd_front(f)" in fwd and "sr && Lr.g32tn ? sr + Lr.st_hprev : nullptr" in fwd
+    assert fwd.count("st, nullptr, nullptr, stride") == 2         # both launch_gru_fwd calls (last_only and Y) pass the stride
+    # a non-zero stride selects the SeriesRows instances, under the window-major instances' names
+    assert gru.count("if (series_stride) hipLaunchKernelGGL((gru_fwd_kernel<K, false, SeriesRows>)") == 1
+    assert gru.count("if (series_stride) hipLaunchKernelGGL((gru_bwd_kernel<K, SeriesRows>)") == 1
+    assert 'PROF_LAUNCH("gru_fwd_kernel<" #K ">"' in gru and 'PROF_LAUNCH("gru_bwd_kernel<" #K ">"' in gru
+    assert 'PROF_LAUNCH("series_fold_kernel"' in series
+    assert "if (sd->rows < 1 || sd->T < 1 || sd->stride < 1" in series         # no entry point passes a zero stride on
+
+
+def test_the_library_accepts_every_series_case():
+    from windgnn_amd import _lib as L
+    from windgnn_amd import build
+    build.build(verbose=False)
+    lib = L.load()
+    for fam, key, S, H, rows, T, stride, n, seed, route in ic.SERIES_CASES:
+        sd = L.SeriesDims(rows, T, stride, n, S, 13, H, 0, 0, 0, 0)
+        for size in (lib.wgnn_series_workspace_bytes, lib.wgnn_series_stash_bytes, lib.wgnn_series_loss_bytes):
+            assert size(ctypes.byref(sd)) > 0, key
+    # ... and refuses H past the register-resident recurrence, which series_plan refuses too
+    assert lib.wgnn_series_workspace_bytes(ctypes.byref(L.SeriesDims(36, 3, 2, 17, 2, 13, 129, 0, 0, 0, 0))) == 0
+    with pytest.raises(AssertionError):
+        ic.series_plan(2, 129, 36, 3, 2, 17, "series")
+
+
+def _series_shapes():
+    """The distinct (S, H, rows, T, stride, n, seed) of the series cases, in table order."""
+    return list(dict.fromkeys(c[2:9] for c in ic.SERIES_CASES))
+
+
+def input_problems(shape):
+    """What is wrong with the inputs of a series shape, measured on the reference alone: a list of sentences."""
+    from oracle import windgnn_oracle as orc
+    from test_gpu_series_instances import reference
+    from test_gpu_series import TOL
+    from conftest import PARAM_KEYS, rel_to_max
+    r = reference(*shape)
+    if not r.margin > 1e-5:                                       # the series suites' tie rule
+        return ["%s: a ReLU pre-activation within %.1e of zero (relative): pick another seed" % (shape, r.margin)]
+    # the oracle in fp32 against itself in fp64: a draw on which rounding alone costs a tenth of the bar proves nothing
+    Y32, cache = orc.forward(r.A, r.X, r.p)
+    g32 = orc.backward(r.A, r.X, r.p, Y32, cache, r.dY)
+    _, loss32, m32 = orc.train_step(r.A, r.X, r.L, r.p)
+    gap = {"Y": rel_to_max(Y32, r.Yo), "loss": abs(float(loss32) - r.loss_o) / r.loss_o}
+    for k in PARAM_KEYS:
+        gap[k] = max(rel_to_max(g32[k], r.go[k]), rel_to_max(m32[k], r.gm[k]))
+    worst = max(gap, key=gap.get)
+    print("%s: margin %.1e, fp32 against fp64 at most %.1e (%s)" % (shape, r.margin, gap[worst], worst))
+    return ["%s: %s in fp32 is %.1e off the fp64 oracle: pick another seed" % (shape, k, e) for k, e in gap.items() if e > TOL / 10]
+
+
+def test_series_inputs_are_tie_free_and_well_conditioned():
+    shapes = _series_shapes()
+    assert len(shapes) == 9 + 9 + 1
+    for shape in shapes:
+        assert input_problems(shape) == []
+    # the check notices a seed with a ReLU tie: shape B at H = 17 with seed 0 has a pre-activation 2e-6 (relative) from zero
+    tied = (2, 17) + SHAPE_B[1:] + (0,)
+    assert tied not in shapes and "ReLU" in input_problems(tied)[0]
+
+
+def test_series_inputs_can_tell_an_off_by_one_row():
+    """On the oracle alone, per shape of a series_mse case.  (a) Labels read one series row late move the loss and some gradient
+    by more than 100 TOL (the SPARE row behind the last covered hour alone does).  (b) Windows started one hour late move Y, the
+    de-normalised last rows and some gradient of the signed random dY by more than 100 TOL.  The MSE of (b) is printed, not
+    asserted: against independent uniform labels it is the labels' own variance, and measured 1e-5 ... 2e-2 of the loss."""
+    from oracle import windgnn_oracle as orc
+    from test_gpu_series_instances import reference, windows
+    from test_gpu_series import TOL
+    from conftest import PARAM_KEYS, rel_to_max
+    from windgnn_amd.series import series_coverage
+    shapes = list(dict.fromkeys(c[2:9] for c in ic.SERIES_CASES if c[9] == "series_mse"))
+    assert len(shapes) == 18
+    for shape in shapes:
+        S, H, rows, T, stride, n, seed = shape
+        r = reference(*shape)
+        A, p64 = r.A.double(), {k: v.double() for k, v in r.p.items()}
+        _, loss, g = orc.train_step(A, r.X.double(), windows(r.Ls, T, stride, n, first=1).double(), p64)
+        lab = (abs(float(loss) - r.loss_o) / r.loss_o, max(rel_to_max(g[k], r.gm[k]) for k in PARAM_KEYS))
+        Xl = windows(r.feat, T, stride, n, first=1).double()         # (feat has three more hours than the series)
+        Yl, cache = orc.forward(A, Xl, p64)
+        gl = orc.backward(A, Xl, p64, Yl, cache, r.dY.double())
+        _, loss_l, _ = orc.train_step(A, Xl, r.L.double(), p64)
+        late = (rel_to_max(Yl, r.Yo), rel_to_max(Yl[:, -1], r.Yo[:, -1]), max(rel_to_max(gl[k], r.go[k]) for k in PARAM_KEYS))
+        print("%s: labels one row late: loss %.1e grad %.1e; windows one hour late: Y %.1e last %.1e grad %.1e (loss %.1e)"
+              % ((shape,) + lab + late + (abs(float(loss_l) - r.loss_o) / r.loss_o,)))
+        assert min(lab) > 100 * TOL and min(late) > 100 * TOL, (shape, lab, late)
+    # the fold's zero-row case: some hour inside the windows' span really is covered by no window
+    fam, key, S, H, rows, T, stride, n, seed, route = next(c for c in ic.SERIES_CASES if c[1] == FOLD_ZERO_ROWS)
+    cover = series_coverage(rows, T, stride, n)
+    assert any(lo > hi for lo, hi in cover[:(n - 1) * stride + T]) and ic.fold_terms(T, stride) == "0..1"
+    assert {hi - lo + 1 for lo, hi in series_coverage(*SHAPE_A[1:])[2:-1]} == {1, 2}
