@@ -29,11 +29,15 @@ def _require_gpu(*tensors: torch.Tensor, io_ok: bool = False) -> None:
 
 def _require_contiguous(**named: torch.Tensor) -> None:
     """The C ABI reads dense row-major memory from data_ptr(): a strided view (e.g. a batch slice X[::2], a transposed
-    label tensor) would be read as if it were dense.  The raw entry points refuse it; callers own the .contiguous()."""
+    label tensor) would be read as if it were dense.  The raw entry points refuse it; callers own the .contiguous().
+    A list of tensors (params=..., grads=...) is checked tensor by tensor; the message names the one, as params[3]."""
     for name, t in named.items():
-        if t is not None and not t.is_contiguous():
-            raise RuntimeError("windgnn_amd: %s must be contiguous (got shape %s with strides %s): call .contiguous() "
-                               "on it first" % (name, tuple(t.shape), tuple(t.stride())))
+        is_list = isinstance(t, (list, tuple))
+        for i, q in enumerate(t if is_list else (t,)):
+            if q is not None and not q.is_contiguous():
+                raise RuntimeError("windgnn_amd: %s must be contiguous (got shape %s with strides %s): call .contiguous() "
+                                   "on it first"
+                                   % ("%s[%d]" % (name, i) if is_list else name, tuple(q.shape), tuple(q.stride())))
 
 
 SCRATCH_ALIGN = 256        # workspace, stash, state stash and `prepared` (include/windgnn.h, "Alignment")
@@ -122,6 +126,39 @@ class _Workspace:
         return buf
 
 
+_WORKSPACE_BYTES = {_lib.Dims: "wgnn_workspace_bytes", _lib.SeriesDims: "wgnn_series_workspace_bytes"}
+
+
+def _workspace(d, device, refused=None):
+    """(workspace, bytes to pass) of the dims struct `d` (wgnn_dims or wgnn_series_dims) on `device`: one size query of the
+    library per call, then this stream's shared buffer, grown if need be.  The library sizes nothing (0) for dims it refuses:
+    with `refused` (the call, for the message) that is raised here with its reason; without, the entry point reports it."""
+    ws_bytes = getattr(_lib.load(), _WORKSPACE_BYTES[type(d)])(C.byref(d))
+    if ws_bytes == 0 and refused is not None:
+        _lib.check(-5 if d.F == 13 else -2, refused)
+    return _Workspace.get(device, ws_bytes), ws_bytes
+
+
+def _grads_device(grads, device):
+    """The device of the finish_* / bwd_rows family, which take no input tensor: the caller's, else the gradients'."""
+    return device if device is not None else grads[0].device
+
+
+def _gru_struct(cls, tensors):
+    """wgnn_params / wgnn_grads of the GRU-only entry points (wgnn_gru_fwd / wgnn_gru_bwd): the four GRU slots from
+    (w_ih, w_hh, b_ih, b_hh), the conv slots NULL."""
+    s = cls()
+    s.w_ih, s.w_hh, s.b_ih, s.b_hh = (q.data_ptr() for q in tensors)
+    return s
+
+
+def _flat_grads(params, device):
+    """Gradients for `params` as views, shaped like them, of ONE new fp32 buffer (one allocation per autograd backward)."""
+    sizes = [p.numel() for p in params]
+    flat = torch.empty(sum(sizes), dtype=torch.float32, device=device)
+    return [g.view_as(p) for g, p in zip(flat.split(sizes), params)]
+
+
 _STATUS_TEXT = {1: "a graph-convolution pre-activation left fp16's range (|x| > 65504) or was NaN",
                 2: "a GRU weight or bias lies outside fp16's range",
                 4: "a gradient came out inf / NaN",
@@ -153,7 +190,7 @@ def _forward_setup(A, X, params: Sequence[torch.Tensor], math, labels=None, h0=N
     depend on it).  Returns (adjacency to pass, d, workspace, workspace bytes)."""
     _require_gpu(X, io_ok=True)
     _require_gpu(*params)
-    _require_contiguous(X=X, labels=labels, **{"params[%d]" % i: q for i, q in enumerate(params)})
+    _require_contiguous(X=X, labels=labels, params=params)
     if X.dim() != 4:
         raise RuntimeError("windgnn_amd: X must be [B, T, S, 13], got %s" % (tuple(X.shape),))
     BX, T, S, F = X.shape
@@ -169,11 +206,9 @@ def _forward_setup(A, X, params: Sequence[torch.Tensor], math, labels=None, h0=N
             raise RuntimeError("windgnn_amd: %s must be [B, H] = [%d, %d] float32 on %s, got %s on %s"
                                % (name, B, H, X.device, tuple(t.shape), t.device))
     d = _lib.Dims(B, T, S, F, H, math, fmt, nnz, _IO_OF[X.dtype])
-    ws_bytes = _lib.load().wgnn_workspace_bytes(C.byref(d))
-    if ws_bytes == 0:      # the library sizes nothing for dims it refuses: name the reason
-        _lib.check(-5 if F == 13 else -2, "wgnn_workspace_bytes(B=%d,T=%d,S=%d,F=%d,H=%d,math=%d,io=%s)"
-                   % (B, T, S, F, H, math, X.dtype))
-    return A, d, _Workspace.get(X.device, ws_bytes), ws_bytes
+    ws, ws_bytes = _workspace(d, X.device, refused="wgnn_workspace_bytes(B=%d,T=%d,S=%d,F=%d,H=%d,math=%d,io=%s)"
+                              % (B, T, S, F, H, math, X.dtype))
+    return A, d, ws, ws_bytes
 
 
 def gcn_gru_forward_raw(A, X, params: Sequence[torch.Tensor], math=_lib.MATH_F32, want_stash=True, labels=None,
@@ -223,12 +258,10 @@ def gcn_gru_state(A, X, params: Sequence[torch.Tensor], math=_lib.MATH_F32, h0=N
 def gcn_gru_backward_raw(d, A, X, params, Y, dY, stash, grads: Sequence[torch.Tensor], part: int = 7, stream=None):
     """part bit mask (wgnn_bwd_part): 1 = BPTT recurrence, 4 = GRU weight-gradient GEMMs, 2 = dg + GCN backward."""
     lib = _lib.load()
-    _require_contiguous(X=X, Y=Y, dY=dY, **{"grads[%d]" % i: q for i, q in enumerate(grads)},
-                        **{"params[%d]" % i: q for i, q in enumerate(params)})
+    _require_contiguous(X=X, Y=Y, dY=dY, grads=grads, params=params)
     A = getattr(A, "blob", A)              # CsrAdjacency -> its device buffer (d.adj_format says which it is)
     _require_contiguous(adj_matrix=A)
-    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
-    ws = _Workspace.get(X.device, ws_bytes)
+    ws, ws_bytes = _workspace(d, X.device)
     ps = _params_struct(_lib.Params, params)
     gs = _params_struct(_lib.Grads, grads)
     rc = lib.wgnn_bwd_part(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(Y), _ptr(dY), _stash_ptr(stash), C.byref(gs),
@@ -246,12 +279,10 @@ def gcn_gru_backward_mse_raw(d, A, X, params, Y, L, stash, grads: Sequence[torch
         raise RuntimeError("windgnn_amd: labels are %s but Y is %s (one I/O type per call)" % (L.dtype, Y.dtype))
     if L.numel() != Y.numel():
         raise RuntimeError("windgnn_amd: MSE operands differ in size: %s vs %s" % (tuple(Y.shape), tuple(L.shape)))
-    _require_contiguous(X=X, Y=Y, labels=L, **{"grads[%d]" % i: q for i, q in enumerate(grads)},
-                        **{"params[%d]" % i: q for i, q in enumerate(params)})
+    _require_contiguous(X=X, Y=Y, labels=L, grads=grads, params=params)
     A = getattr(A, "blob", A)
     _require_contiguous(adj_matrix=A)
-    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
-    ws = _Workspace.get(X.device, ws_bytes)
+    ws, ws_bytes = _workspace(d, X.device)
     ps = _params_struct(_lib.Params, params, prepared)
     gs = _params_struct(_lib.Grads, grads)
     rc = lib.wgnn_bwd_mse_part(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(Y), _ptr(L), grad_scale,
@@ -293,8 +324,7 @@ def finish_step(d, params, grads, which: int, adam=None, prepared=None, device=N
     in place (and refresh `prepared`) -- one launch.  `which` = _lib.FINISH_ADAM_GRU / FINISH_ADAM_CONV (with adam, no
     reduce bit): the optimiser step of that tensor family only."""
     lib = _lib.load()
-    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
-    ws = _Workspace.get(device if device is not None else grads[0].device, ws_bytes)
+    ws, ws_bytes = _workspace(d, _grads_device(grads, device))
     ps = _params_struct(_lib.Params, params, prepared)
     gs = _params_struct(_lib.Grads, grads)
     ad = _adam_struct(adam) if adam is not None else None
@@ -341,8 +371,7 @@ def finish_norm(d, grads, which: int, max_norm: float, clip, device=None) -> Non
     deterministic, no host synchronisation.  max_norm > 0; float("inf") only measures.  clip: clip_buffer(d, device)."""
     lib = _lib.load()
     cp = _clip_ptr(d, clip)
-    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
-    ws = _Workspace.get(device if device is not None else grads[0].device, ws_bytes)
+    ws, ws_bytes = _workspace(d, _grads_device(grads, device))
     gs = _params_struct(_lib.Grads, grads)
     rc = lib.wgnn_finish_norm(C.byref(d), C.byref(gs), which, float(max_norm), cp, _ptr(ws), ws_bytes, _stream())
     _lib.check(rc, "wgnn_finish_norm(%d, max_norm=%r)" % (which, max_norm))
@@ -354,8 +383,7 @@ def finish_clipped(d, params, grads, adam, clip, prepared=None, device=None) -> 
     clip_grad_norm_ scales .grad in place; here it keeps the unclipped gradient, and clip holds the norm and the factor)."""
     lib = _lib.load()
     cp = _clip_ptr(d, clip)
-    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
-    ws = _Workspace.get(device if device is not None else grads[0].device, ws_bytes)
+    ws, ws_bytes = _workspace(d, _grads_device(grads, device))
     ps = _params_struct(_lib.Params, params, prepared)
     gs = _params_struct(_lib.Grads, grads)
     ad = _adam_struct(adam)
@@ -397,8 +425,7 @@ def keep_best_args(d, loss: torch.Tensor, params, best_params, record: torch.Ten
     """Everything of a keep_best call but the step number, validated and marshalled once (a caller whose tensors never move --
     TrainStep -- pays the checks and the two wgnn_params structs at construction, not per step): pass it to keep_best_launch."""
     _require_gpu(loss, *params, *best_params)
-    _require_contiguous(**{"params[%d]" % i: q for i, q in enumerate(params)},
-                        **{"best_params[%d]" % i: q for i, q in enumerate(best_params)})
+    _require_contiguous(params=params, best_params=best_params)
     for i, (q, b) in enumerate(zip(params, best_params)):
         if q.numel() != b.numel():
             raise RuntimeError("windgnn_amd: best_params[%d] has %d elements, params[%d] has %d" % (i, b.numel(), i, q.numel()))
@@ -428,8 +455,7 @@ def bwd_rows(d, Y, stash, grads, which: int, row0: int, rows: int, device=None) 
     """wgnn_bwd_rows: part 4 of the backward (weight-gradient GEMMs + their reduction) for gate rows [row0, row0 + rows) of
     the pair `which` (_lib.ROWS_IH: w_ih / b_ih, _lib.ROWS_HH: w_hh / b_hh), after part 1 on the same workspace."""
     lib = _lib.load()
-    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
-    ws = _Workspace.get(device if device is not None else grads[0].device, ws_bytes)
+    ws, ws_bytes = _workspace(d, _grads_device(grads, device))
     gs = _params_struct(_lib.Grads, grads)
     rc = lib.wgnn_bwd_rows(C.byref(d), _ptr(Y), _stash_ptr(stash), C.byref(gs), which, row0, rows, _ptr(ws), ws_bytes, _stream())
     _lib.check(rc, "wgnn_bwd_rows(%d, %d, %d)" % (which, row0, rows))
@@ -439,7 +465,7 @@ def finish_rows(d, params, grads, which: int, row0: int, rows: int, adam, prepar
     """wgnn_finish_rows: Adam (adam: as finish_step) on rows [row0, row0 + rows) of the pair `which`, and the parts of
     `prepared` those rows own."""
     lib = _lib.load()
-    ws = _Workspace.get(device if device is not None else grads[0].device, _lib.STATUS_BYTES)
+    ws = _Workspace.get(_grads_device(grads, device), _lib.STATUS_BYTES)
     ps = _params_struct(_lib.Params, params, prepared)
     gs = _params_struct(_lib.Grads, grads)
     ad = _adam_struct(adam)
@@ -473,9 +499,7 @@ class GCNGRUFunction(torch.autograd.Function):
         A, X, Y, stash, *params = ctx.saved_tensors
         if stash is None:
             raise RuntimeError("windgnn_amd: backward called but the forward ran without a stash")
-        sizes = [p.numel() for p in params]
-        flat = torch.empty(sum(sizes), dtype=torch.float32, device=X.device)
-        grads = [g.view_as(p) for g, p in zip(flat.split(sizes), params)]
+        grads = _flat_grads(params, X.device)
         gcn_gru_backward_raw(ctx.d, A, X, params, Y, dY.float().contiguous(), stash, grads)   # dY is always fp32
         return (None, None, None, *grads)
 
@@ -507,16 +531,14 @@ def gcn_gru_state_backward_raw(d, A, X, params, Y, dY, dh_n, stash, grads: Seque
     """wgnn_bwd_state_part: the gradients of sum(Y dY) + sum(h_n dh_n) (dh_n None = zeros) into `grads`, and dh0 [B,H]
     (None = not computed) w.r.t. the h0 recorded in the state stash.  Parts as gcn_gru_backward_raw."""
     lib = _lib.load()
-    _require_contiguous(X=X, Y=Y, dY=dY, dh_n=dh_n, dh0=dh0, **{"grads[%d]" % i: q for i, q in enumerate(grads)},
-                        **{"params[%d]" % i: q for i, q in enumerate(params)})
+    _require_contiguous(X=X, Y=Y, dY=dY, dh_n=dh_n, dh0=dh0, grads=grads, params=params)
     for name, t in (("dh_n", dh_n), ("dh0", dh0)):
         if t is not None and (tuple(t.shape) != (d.B, d.H) or t.dtype != torch.float32 or t.device != X.device):
             raise RuntimeError("windgnn_amd: %s must be [B, H] = [%d, %d] float32 on %s, got %s %s on %s"
                                % (name, d.B, d.H, X.device, tuple(t.shape), t.dtype, t.device))
     A = getattr(A, "blob", A)
     _require_contiguous(adj_matrix=A)
-    ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
-    ws = _Workspace.get(X.device, ws_bytes)
+    ws, ws_bytes = _workspace(d, X.device)
     ps = _params_struct(_lib.Params, params, prepared)
     gs = _params_struct(_lib.Grads, grads)
     rc = lib.wgnn_bwd_state_part(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(Y), _ptr(dY), _ptr(dh_n), _stash_ptr(stash),
@@ -550,9 +572,7 @@ class GCNGRUStateFunction(torch.autograd.Function):
         A, X, Y, stash, *params = ctx.saved_tensors
         if dY is None:                     # a loss on h_n alone
             dY = torch.zeros(Y.shape, dtype=torch.float32, device=Y.device)
-        sizes = [p.numel() for p in params]
-        flat = torch.empty(sum(sizes), dtype=torch.float32, device=X.device)
-        grads = [g.view_as(p) for g, p in zip(flat.split(sizes), params)]
+        grads = _flat_grads(params, X.device)
         want_dh0 = ctx.has_h0 and ctx.needs_input_grad[3]
         dh0 = torch.empty(ctx.d.B, ctx.d.H, dtype=torch.float32, device=X.device) if want_dh0 else None
         gcn_gru_state_backward_raw(ctx.d, A, X, params, Y, dY.float().contiguous(),
@@ -633,15 +653,14 @@ class GRUFunction(torch.autograd.Function):
         B, T, I = g.shape
         H = w_hh.shape[1]
         d = _lib.Dims(B, T, S, 13, H, _lib.MATH_F32, _lib.ADJ_DENSE, 0, _lib.IO_F32)
-        ws_bytes = lib.wgnn_workspace_bytes(C.byref(d))
-        if ws_bytes == 0 or I != S * 13:
-            _lib.check(-5 if I == S * 13 else -2, "wgnn_gru_fwd(B=%d,T=%d,S=%d,I=%d,H=%d)" % (B, T, S, I, H))
-        ws = _Workspace.get(g.device, ws_bytes)
+        call = "wgnn_gru_fwd(B=%d,T=%d,S=%d,I=%d,H=%d)" % (B, T, S, I, H)
+        if I != S * 13:
+            _lib.check(-2, call)
+        ws, ws_bytes = _workspace(d, g.device, refused=call)
         need = any(ctx.needs_input_grad)
         stash = torch.empty(lib.wgnn_stash_bytes(C.byref(d)), dtype=torch.uint8, device=g.device) if need else None
         Y = torch.empty(B, T, H, dtype=torch.float32, device=g.device)
-        ps = _lib.Params()
-        ps.w_ih, ps.w_hh, ps.b_ih, ps.b_hh = (q.data_ptr() for q in params)
+        ps = _gru_struct(_lib.Params, params)
         _lib.check(lib.wgnn_gru_fwd(C.byref(d), _ptr(g), C.byref(ps), _ptr(Y), _stash_ptr(stash), _ptr(ws), ws_bytes, _stream()),
                    "wgnn_gru_fwd")
         ctx.d = d
@@ -654,11 +673,8 @@ class GRUFunction(torch.autograd.Function):
         g, Y, stash, *params = ctx.saved_tensors
         grads = [torch.empty_like(q) for q in params]
         dg = torch.empty_like(g)
-        ws_bytes = lib.wgnn_workspace_bytes(C.byref(ctx.d))
-        ws = _Workspace.get(g.device, ws_bytes)
-        ps, gs = _lib.Params(), _lib.Grads()
-        ps.w_ih, ps.w_hh, ps.b_ih, ps.b_hh = (q.data_ptr() for q in params)
-        gs.w_ih, gs.w_hh, gs.b_ih, gs.b_hh = (q.data_ptr() for q in grads)
+        ws, ws_bytes = _workspace(ctx.d, g.device)
+        ps, gs = _gru_struct(_lib.Params, params), _gru_struct(_lib.Grads, grads)
         _lib.check(lib.wgnn_gru_bwd(C.byref(ctx.d), _ptr(g), C.byref(ps), _ptr(Y), _ptr(dY.float().contiguous()),
                                     _stash_ptr(stash), C.byref(gs), _ptr(dg), _ptr(ws), ws_bytes, _stream()), "wgnn_gru_bwd")
         return (dg, None, *grads)

@@ -14,7 +14,8 @@ from typing import List, Sequence, Tuple
 import torch
 
 from . import _lib
-from .functional import (_Workspace, _adj, _params_struct, _ptr, _require_contiguous, _require_gpu, _stash_ptr, _stream)
+from .functional import (_adj, _flat_grads, _params_struct, _ptr, _require_contiguous, _require_gpu, _stash_ptr, _stream,
+                         _workspace)
 
 _MATERIALISED = ("materialise the windows (windgnn_amd.data.make_windows(feat, seq_len, starts=...)) and call "
                  "GCN_GRU.forward / forward_last on them instead")
@@ -50,7 +51,7 @@ def _series_setup(A, series, seq_len: int, stride: int, params: Sequence[torch.T
                            "(f16x3 / f16x3g / f16): " + _MATERIALISED)
     _require_gpu(series)
     _require_gpu(*params)
-    _require_contiguous(series=series, **{"params[%d]" % i: q for i, q in enumerate(params)})
+    _require_contiguous(series=series, params=params)
     if series.dim() != 3:
         raise RuntimeError("windgnn_amd: series must be [rows, S, 13], got %s" % (tuple(series.shape),))
     rows, S, F = series.shape
@@ -64,11 +65,10 @@ def _series_setup(A, series, seq_len: int, stride: int, params: Sequence[torch.T
     A, fmt, nnz = _adj(A, S)
     H = params[5].shape[1]
     sd = _lib.SeriesDims(rows, seq_len, stride, n, S, F, H, math, fmt, nnz, _lib.IO_F32)
-    ws_bytes = _lib.load().wgnn_series_workspace_bytes(C.byref(sd))
-    if ws_bytes == 0:
-        _lib.check(-5 if F == 13 else -2, "wgnn_series_workspace_bytes(rows=%d,T=%d,stride=%d,n=%d,S=%d,F=%d,H=%d) [%s]"
-                   % (rows, seq_len, stride, n, S, F, H, _MATERIALISED))
-    return A, sd, _Workspace.get(series.device, ws_bytes), ws_bytes
+    ws, ws_bytes = _workspace(sd, series.device,
+                              refused="wgnn_series_workspace_bytes(rows=%d,T=%d,stride=%d,n=%d,S=%d,F=%d,H=%d) [%s]"
+                              % (rows, seq_len, stride, n, S, F, H, _MATERIALISED))
+    return A, sd, ws, ws_bytes
 
 
 def series_forward_raw(A, series, seq_len, stride, params, math=_lib.MATH_F32, want_stash=True, n_windows=None):
@@ -88,10 +88,8 @@ def series_forward_raw(A, series, seq_len, stride, params, math=_lib.MATH_F32, w
 def series_backward_raw(sd, A, series, params, Y, dY, stash, grads: Sequence[torch.Tensor]) -> None:
     """wgnn_series_bwd: the 8 gradients of sum(Y * dY), summed over all windows, into `grads` (overwritten)."""
     lib = _lib.load()
-    _require_contiguous(series=series, Y=Y, dY=dY, adj_matrix=A, **{"grads[%d]" % i: q for i, q in enumerate(grads)},
-                        **{"params[%d]" % i: q for i, q in enumerate(params)})
-    ws_bytes = lib.wgnn_series_workspace_bytes(C.byref(sd))
-    ws = _Workspace.get(series.device, ws_bytes)
+    _require_contiguous(series=series, Y=Y, dY=dY, adj_matrix=A, grads=grads, params=params)
+    ws, ws_bytes = _workspace(sd, series.device)
     ps = _params_struct(_lib.Params, params)
     gs = _params_struct(_lib.Grads, grads)
     rc = lib.wgnn_series_bwd(C.byref(sd), _ptr(A), _ptr(series), C.byref(ps), _ptr(Y), _ptr(dY), _stash_ptr(stash), C.byref(gs),
@@ -135,14 +133,11 @@ def series_backward_mse_raw(sd, A, series, params, Y, Ls, stash, loss_buf, grads
     lib = _lib.load()
     _check_label_series(Ls, sd)
     _require_gpu(loss, loss_buf)
-    _require_contiguous(series=series, Y=Y, adj_matrix=A, loss_buf=loss_buf,
-                        **{"grads[%d]" % i: q for i, q in enumerate(grads)},
-                        **{"params[%d]" % i: q for i, q in enumerate(params)})
+    _require_contiguous(series=series, Y=Y, adj_matrix=A, loss_buf=loss_buf, grads=grads, params=params)
     if loss_buf.numel() * 4 < lib.wgnn_series_loss_bytes(C.byref(sd)):
         raise RuntimeError("windgnn_amd: loss_buf holds %d bytes, wgnn_series_loss_bytes says %d"
                            % (loss_buf.numel() * 4, lib.wgnn_series_loss_bytes(C.byref(sd))))
-    ws_bytes = lib.wgnn_series_workspace_bytes(C.byref(sd))
-    ws = _Workspace.get(series.device, ws_bytes)
+    ws, ws_bytes = _workspace(sd, series.device)
     ps = _params_struct(_lib.Params, params, prepared)
     gs = _params_struct(_lib.Grads, grads)
     rc = lib.wgnn_series_bwd_mse(C.byref(sd), _ptr(A), _ptr(series), C.byref(ps), _ptr(Y), _ptr(Ls), Ls.shape[0],
@@ -172,9 +167,7 @@ class SeriesFunction(torch.autograd.Function):
         A, series, Y, stash, *params = ctx.saved_tensors
         if stash is None:
             raise RuntimeError("windgnn_amd: backward called but the forward ran without a stash")
-        sizes = [p.numel() for p in params]
-        flat = torch.empty(sum(sizes), dtype=torch.float32, device=series.device)
-        grads = [g.view_as(p) for g, p in zip(flat.split(sizes), params)]
+        grads = _flat_grads(params, series.device)
         series_backward_raw(ctx.sd, A, series, params, Y, dY.float().contiguous(), stash, grads)
         return (None, None, None, None, None, None, *grads)
 

@@ -12,11 +12,16 @@ equal shards) so the summed bucket equals the gradient of the big-batch mean los
 loss on every rank.  The collectives themselves live in distributed.BucketExchange (every rank issues every collective on
 every step).
 
+Schedules: how the backward's parts, the collectives and the optimiser's launches of a step are ordered -- one rank, one
+bucket, two collectives (`overlap_collectives`), blocked (`grad_blocks`) -- is written once, in TrainStep._run_schedule.  A step
+kind hands it what it enqueues: the plain and the carried-state step their deferred backward parts (_Deferred), the empty-shard
+and the series step a bucket that is final already (_FINAL), for which the same orderings reduce to the collectives and Adam.
+
 The loss a step returns is a 0-dim VIEW of the bucket's header (no clone launch per step): read it (float(loss)) or
 `.clone()` it before the next step -- a list of kept losses would all show the latest value.
 
-A rank whose shard is EMPTY (fewer windows than ranks) still issues every collective of the step: it contributes a zero
-bucket and runs the optimiser's launch on the summed gradient, so no rank is left waiting in an all-reduce.
+A rank whose shard is EMPTY (fewer windows than ranks) still issues every collective of the step, in every schedule: it
+contributes a zero bucket and runs the optimiser's launch(es) on the summed gradient, so no rank is left waiting in an all-reduce.
 
 Blocked exchange (`grad_blocks`, opt-in, for buckets of GB: BASELINE configs[4] has 9.66 GB): the weight-gradient GEMMs run
 per row block of w_ih, then of w_hh (wgnn_bwd_rows), and each block's all-reduce starts as soon as its rows are final, so the
@@ -58,9 +63,9 @@ Series mode (step_series / forward_backward_series; include/windgnn_series_train
 hourly series, without materialising windows, labels or dY.  The label of window w at step t is row w * stride + t of the label
 series Ls (series.series_labels' first result), which the recurrence kernels read beside the GI row: wgnn_series_fwd_loss leaves
 the MSE partial sums in a small buffer, wgnn_series_bwd_mse forms dY inside BPTT, finalises the loss into the bucket's header
-word and leaves FINAL gradients in the bucket (series mode does not defer its partial sums), so the tail is _tail(d, 0, pre) --
-one wgnn_finish that only steps Adam and refreshes the W_ih images.  With a process group the one all-reduce sits between the
-backward and that tail.  Exact fp32, a dense adjacency, the one-bucket schedules; the rest is refused with the alternative."""
+word and leaves FINAL gradients in the bucket (series mode does not defer its partial sums), so the schedule runs on _FINAL:
+its tail is one wgnn_finish(0, adam) that only steps Adam and refreshes the W_ih images.  With a process group the one
+all-reduce sits between the backward and that tail.  Exact fp32, a dense adjacency, the one-bucket schedules; the rest is refused with the alternative."""
 from __future__ import annotations
 
 import collections
@@ -78,6 +83,44 @@ from .series import n_series_windows, series_backward_mse_raw, series_forward_lo
 
 AUTO_GRAD_BLOCKS = 8                # grad_blocks="auto": row blocks per GRU weight ...
 AUTO_BLOCK_BYTES = 64 << 20         # ... from a gradient bucket of this size (smaller ones are latency-bound: one bucket)
+
+
+_ROWS = {"ih": _lib.ROWS_IH, "hh": _lib.ROWS_HH}          # GradBlock.tensor -> `which` of wgnn_bwd_rows / wgnn_finish_rows
+
+
+class _Deferred:
+    """The backward of a step as its schedule enqueues it (TrainStep._run_schedule): parts of the backward with their
+    split-K partial sums left deferred, the reduce-only wgnn_finish of those, and the blocked exchange's weight gradients per
+    row block.  `parts(mask)` is the step kind's own: it enqueues the parts in `mask` (1 BPTT, 2 dg + GCN, 4 weight gradients)
+    with WGNN_BWD_DEFER through its entry point (wgnn_bwd_mse_part or wgnn_bwd_state_part)."""
+    pending = 6                     # what the optimiser's wgnn_finish still has to reduce when nothing else did: parts 2 | 4
+
+    def __init__(self, tr, d, parts, Y, stash):
+        self.tr, self.d, self.parts, self.Y, self.stash = tr, d, parts, Y, stash
+
+    def reduce(self, which):
+        finish_step(self.d, self.tr.p_views, self.tr.g_views, which, device=self.tr.device)
+
+    def rows(self, b):
+        bwd_rows(self.d, self.Y, self.stash, self.tr.g_views, _ROWS[b.tensor], b.row0, b.rows, self.tr.device)
+
+
+class _Final:
+    """The same for a bucket that is final before the schedule starts -- an empty shard's zeros, series mode's
+    wgnn_series_bwd_mse (which reduces its own partial sums): nothing to enqueue and nothing to reduce."""
+    pending = 0
+
+    def parts(self, mask):
+        pass
+
+    def reduce(self, which):
+        pass
+
+    def rows(self, b):
+        pass
+
+
+_FINAL = _Final()
 
 
 class TrainStep:
@@ -422,69 +465,94 @@ class TrainStep:
                 self._hbuf[self._hcur].copy_(carry)
                 self._has_state = True
 
+    def _ensure_images(self, dims):
+        """Build or rebuild the staged W_ih images if someone else wrote the parameters since they were last current.
+        dims: () -> the Dims that size them (S, H and the math mode only), asked for only then."""
+        if self._prepared_version != self._param_version():
+            self._images(dims())
+
+    def _run_schedule(self, d, bwd, gs):
+        """The backward, the exchange and the optimiser of one step, in the order of this TrainStep's schedule (module
+        docstring) -- the ONE place that orders them.  bwd: what the step kind enqueues (_Deferred), or _FINAL for a bucket
+        that is final already; gs: this shard's weight, which the exchange scales the loss word with."""
+        pre, ex = self._prepared, self.exchange
+        if self.plan is not None:
+            # Blocked: part 1, then per row block its weight-gradient GEMM + reduction and the start of its all-reduce, then
+            # part 2 under the last blocks' collectives, the tail's all-reduce and the blocked Adam.
+            bwd.parts(1)
+            works = []
+            for b in self.plan.blocks:
+                bwd.rows(b)
+                works.append(ex.start_block(b))
+            # HAZARD: part 2 reads W_ih through its W_ih^T image, and the blocks' Adam (_blocked_adam, the only place that
+            # enqueues wgnn_finish_rows) rewrites both in place.  Part 2 is enqueued here, after every block's GEMM and before
+            # ANY block's Adam; a wgnn_finish_rows above this line gives a wrong dg (and wrong conv gradients) with no error.
+            bwd.parts(2)
+            bwd.reduce(2)
+            self._blocked_adam(d, works, ex.start_tail(self.plan, gs), pre)    # loss: the big-batch mean
+        elif not self.collective:
+            # One rank: BPTT, then the dg GEMM + GCN backward, and the weight-gradient GEMMs LAST, so that wgnn_finish reads
+            # their split-K partial sums (115 MB at B = 4096) while they still sit in the Infinity Cache; deferring them
+            # across the dg GEMM and the GCN backward (0.8 GB of traffic) had them come back from HBM (finish 35 us)
+            for part in (1, 2, 4):         # (the order 1, 4, 2 measured the same, 672-680 us either way: round 3)
+                bwd.parts(part)
+            self._tail(d, bwd.pending, pre)                                                    # src/main.py:79 tail + :80
+        elif not self.overlap_collectives:
+            # the single-rank schedule, with ONE all-reduce of [loss | conv | GRU gradients] between the reduce-only finish and
+            # the optimiser's: one collective, one stream dependency each way per step
+            for part in (1, 2, 4):
+                bwd.parts(part)
+            bwd.reduce(6)
+            ex.all_reduce_all(gs)           # loss: sum of the weighted shard means = the big-batch mean
+            self._tail(d, 0, pre)                                                              # src/main.py:80
+        else:
+            # Overlap: the GRU gradients (99.8 % of the bucket) are final after parts 1|4 of the backward, so
+            # their all-reduce runs on RCCL's stream while part 2 (dg GEMM + GCN backward, ~30 % of the
+            # step) still computes; the 364 conv gradients and the loss follow in a second, tiny all-reduce.
+            bwd.parts(1 | 4)
+            bwd.reduce(4)
+            work = ex.start_gru()
+            bwd.parts(2)
+            bwd.reduce(2)
+            # the conv gradients' (tiny, latency-bound) all-reduce runs under the GRU tensors' optimiser step
+            wconv = ex.start_conv(gs)       # loss: sum of the weighted shard means = the big-batch mean
+            work.wait()
+            adam = self._adam()
+            finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_GRU, adam, pre, self.device)   # src/main.py:80
+            wconv.wait()
+            finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_CONV, adam, pre, self.device)
+
+    def _blocked_adam(self, d, works, wtail, pre):
+        """The optimiser half of the blocked step: Adam per row block once its all-reduce (and the tail's) has arrived, then
+        the conv tensors.  Every wgnn_finish_rows rewrites W_ih and its images in place, so this runs after part 2 of the
+        backward (the HAZARD in _run_schedule)."""
+        wtail.wait()                    # b_ih / b_hh ride in the tail, and every block's Adam steps its rows' biases
+        adam = self._adam()
+        for b, work in zip(self.plan.blocks, works):
+            work.wait()
+            finish_rows(d, self.p_views, self.g_views, _ROWS[b.tensor], b.row0, b.rows, adam, pre, self.device)
+        finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_CONV, adam, pre, self.device)
+
+    def _end_step(self, check=True):
+        """What follows the optimiser's launches of every schedule: the count, keep_best, the periodic check()."""
+        self.steps += 1                         # only a step whose launches were all accepted counts
+        self._keep_best()                       # src/main.py:83-86
+        if check and self.check_every and self.steps % self.check_every == 0 and (
+                self.model.math != _lib.MATH_F32 or (self.exchange is not None and self.exchange.direct is not None)):
+            self.check()
+
     def _empty_shard_step(self, A, X, n_global):
         """This rank has no windows in this step: zero bucket, the same collectives as every other rank, the optimiser's
         launch(es) on the summed gradient.  Returns (big-batch mean loss, empty Y)."""
         if not self.collective:
             raise RuntimeError("windgnn_amd: TrainStep.step needs at least one window (got a batch of %s)" % (tuple(X.shape),))
         _, d, _, _ = _forward_setup(A, X, self.p_views, self.model.math, B=1)   # sizes the finish launch (B-independent)
-        T, H = d.T, d.H
-        if self._prepared_version != self._param_version():
-            self._images(d)
-        pre = self._prepared
+        self._ensure_images(lambda: d)
         gs = self.exchange.shard_weight(0, n_global)                   # 0.0; the count collective, if any, is issued
         self._gbuf.zero_()
-        if self.plan is not None:
-            works = [self.exchange.start_block(b) for b in self.plan.blocks]
-            self._blocked_adam(d, works, self.exchange.start_tail(self.plan, gs), pre)
-        elif not self.overlap_collectives:
-            self.exchange.all_reduce_all(gs)
-            self._tail(d, 0, pre)
-        else:
-            work = self.exchange.start_gru()
-            wconv = self.exchange.start_conv(gs)
-            work.wait()
-            adam = self._adam()
-            finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_GRU, adam, pre, self.device)
-            wconv.wait()
-            finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_CONV, adam, pre, self.device)
-        self.steps += 1
-        self._keep_best()
-        return self._loss, torch.empty(0, T, H, dtype=X.dtype, device=X.device)
-
-    def _blocked_adam(self, d, works, wtail, pre):
-        """The optimiser half of the blocked step: Adam per row block once its all-reduce (and the tail's) has arrived, then
-        the conv tensors."""
-        wtail.wait()                    # b_ih / b_hh ride in the tail, and every block's Adam steps its rows' biases
-        adam = self._adam()
-        for b, work in zip(self.plan.blocks, works):
-            work.wait()
-            finish_rows(d, self.p_views, self.g_views, _lib.ROWS_IH if b.tensor == "ih" else _lib.ROWS_HH, b.row0, b.rows,
-                        adam, pre, self.device)
-        finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_CONV, adam, pre, self.device)
-
-    def _blocked_step(self, A, X, L, n_global):
-        """step() with grad_blocks: part 1, then per row block its weight-gradient GEMM + reduction and the start of its
-        all-reduce, then part 2 under the last blocks' collectives, the tail's all-reduce and the blocked Adam."""
-        DEFER = _lib.BWD_DEFER
-        loss = self._loss
-        gs = self.exchange.shard_weight(X.shape[0], n_global)
-        Y, stash, d = self._forward(A, X, L)
-        pre = self._prepared
-        gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, loss, gs, part=1 | 8 | DEFER,
-                                 prepared=pre)
-        works = []
-        for b in self.plan.blocks:
-            bwd_rows(d, Y, stash, self.g_views, _lib.ROWS_IH if b.tensor == "ih" else _lib.ROWS_HH, b.row0, b.rows,
-                     self.device)
-            works.append(self.exchange.start_block(b))
-        # HAZARD: part 2 reads W_ih through its W_ih^T image, and the blocks' Adam rewrites both in place.  Part 2 is enqueued
-        # here, after every block's GEMM and before ANY block's Adam; moving a wgnn_finish_rows above this line gives a wrong
-        # dg (and wrong conv gradients) with no error.
-        gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, loss, gs, part=2 | DEFER, prepared=pre)
-        finish_step(d, self.p_views, self.g_views, 2, device=self.device)
-        self._blocked_adam(d, works, self.exchange.start_tail(self.plan, gs), pre)   # loss: the big-batch mean
-        return loss, Y
+        self._run_schedule(d, _FINAL, gs)
+        self._end_step(check=False)             # no host read on this path: the next step with windows checks
+        return self._loss, torch.empty(0, d.T, d.H, dtype=X.dtype, device=X.device)
 
     def forward_backward(self, A, X, L):
         """src/main.py:66,72,79: returns (loss, Y); gradients land in the flat bucket (no optimiser step).  `loss` is a
@@ -529,8 +597,7 @@ class TrainStep:
         _require_gpu(series, Ls, *self.p_views)      # before the images: nothing is launched on host memory
         S, H = series.shape[1], self.p_views[5].shape[1]
         d = _lib.Dims(1, seq_len, S, 13, H, _lib.MATH_F32, _lib.ADJ_DENSE, 0, _lib.IO_F32)
-        if self._prepared_version != self._param_version():
-            self._images(d)
+        self._ensure_images(lambda: d)
         Y, stash, loss_buf, sd = series_forward_loss_raw(A, series, Ls, seq_len, stride, self.p_views, _lib.MATH_F32,
                                                          n_windows=n, prepared=self._prepared)
         return Y, stash, loss_buf, sd, d
@@ -580,25 +647,17 @@ class TrainStep:
         n = self._series_count(series, Ls, seq_len, stride, n_windows)
         if n == 0:
             return self._empty_shard_step(A, series.new_empty((0, seq_len) + tuple(series.shape[1:])), n_global)
-        loss = self._loss
         gs = self.exchange.shard_weight(n, n_global) if self.collective else 1.0
         Y, stash, loss_buf, sd, d = self._series_forward(A, series, Ls, seq_len, stride, n)
-        pre = self._prepared
-        series_backward_mse_raw(sd, A, series, self.p_views, Y, Ls, stash, loss_buf, self.g_views, loss, gs, prepared=pre)
-        if self.collective:
-            self.exchange.all_reduce_all(gs)    # loss: sum of the weighted shard means = the big-batch mean
-        self._tail(d, 0, pre)                   # the bucket is final: Adam (+ the norm with max_grad_norm) and the W_ih images
-        self.steps += 1
-        self._keep_best()
-        if self.check_every and self.steps % self.check_every == 0 and (
-                self.exchange is not None and self.exchange.direct is not None):
-            self.check()
-        return loss, Y
+        series_backward_mse_raw(sd, A, series, self.p_views, Y, Ls, stash, loss_buf, self.g_views, self._loss, gs,
+                                prepared=self._prepared)
+        self._run_schedule(d, _FINAL, gs)       # the bucket is final: (the all-reduce,) Adam and the W_ih images
+        self._end_step()
+        return self._loss, Y
 
     def _forward(self, A, X, L):
         # the first call sizes and builds the images from the dims of this batch (they depend on S, H, math only)
-        if self._prepared_version != self._param_version():
-            self._images(_forward_setup(A, X, self.p_views, self.model.math)[1])
+        self._ensure_images(lambda: _forward_setup(A, X, self.p_views, self.model.math)[1])
         return gcn_gru_forward_raw(A, X, self.p_views, self.model.math, want_stash=True, labels=L, prepared=self._prepared)
 
     @property
@@ -622,50 +681,34 @@ class TrainStep:
                 raise RuntimeError("windgnn_amd: TrainStep(carry_state=True): the batch changed from %d to %d windows while "
                                    "a state is carried; call reset_state() first" % (self._hbuf.shape[1], B))
             self._hbuf = torch.zeros(2, B, H, dtype=torch.float32, device=self.device)
-        if self._prepared_version != self._param_version():
-            self._images(_forward_setup(A, X, self.p_views, self.model.math)[1])
+        self._ensure_images(lambda: _forward_setup(A, X, self.p_views, self.model.math)[1])
         h0 = self._hbuf[self._hcur] if self._has_state else None
         Y, _, stash, d = gcn_gru_state_forward_raw(A, X, self.p_views, self.model.math, h0, self._hbuf[1 - self._hcur],
                                                    prepared=self._prepared)
         return Y, stash, d
 
-    def _state_step(self, A, X, L, n_global):
-        """step() with carry_state=True: the same schedule, with the loss and dY from wgnn_mse_loss_grad (into the bucket's
-        loss slot) and the backward through wgnn_bwd_state_part (dh_n = 0, no dh0: the carried state is detached)."""
-        DEFER = _lib.BWD_DEFER
-        loss = self._loss
-        gs = self.exchange.shard_weight(X.shape[0], n_global) if self.collective else 1.0
+    def _state_step(self, A, X, L, gs):
+        """The carry_state=True step: the loss and dY from wgnn_mse_loss_grad (into the bucket's loss slot) and the backward
+        through wgnn_bwd_state_part (dh_n = 0, no dh0: the carried state is detached)."""
         Y, stash, d = self._state_forward(A, X, L)
-        pre = self._prepared
-        _, dY = mse_loss_grad(Y, L, gs, loss=loss)    # the unweighted shard mean: the exchange weights it, as in step()
+        _, dY = mse_loss_grad(Y, L, gs, loss=self._loss)    # the unweighted shard mean: the exchange weights it
 
-        def bwd(part):
-            gcn_gru_state_backward_raw(d, A, X, self.p_views, Y, dY, None, stash, self.g_views, part=part | DEFER,
-                                       prepared=pre)
-        if self.collective and not self.overlap_collectives:
-            for part in (1, 2, 4):
-                bwd(part)
-            finish_step(d, self.p_views, self.g_views, 6, device=self.device)
-            self.exchange.all_reduce_all(gs)
-            self._tail(d, 0, pre)
-        elif self.collective:
-            bwd(1 | 4)
-            finish_step(d, self.p_views, self.g_views, 4, device=self.device)
-            work = self.exchange.start_gru()
-            bwd(2)
-            finish_step(d, self.p_views, self.g_views, 2, device=self.device)
-            wconv = self.exchange.start_conv(gs)
-            work.wait()
-            adam = self._adam()
-            finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_GRU, adam, pre, self.device)
-            wconv.wait()
-            finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_CONV, adam, pre, self.device)
-        else:
-            for part in (1, 2, 4):
-                bwd(part)
-            self._tail(d, 6, pre)
+        def parts(mask):
+            gcn_gru_state_backward_raw(d, A, X, self.p_views, Y, dY, None, stash, self.g_views, part=mask | _lib.BWD_DEFER,
+                                       prepared=self._prepared)
+        self._run_schedule(d, _Deferred(self, d, parts, Y, stash), gs)
         self._hcur, self._has_state = 1 - self._hcur, True     # h_n of this step is the next step's h0
-        return loss, Y
+        return Y
+
+    def _plain_step(self, A, X, L, gs):
+        """The step from h = 0: wgnn_fwd_loss, then wgnn_bwd_mse_part, whose part 1 also finalises the loss (bit 8)."""
+        Y, stash, d = self._forward(A, X, L)
+
+        def parts(mask):
+            gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, self._loss, gs,
+                                     part=mask | (mask & 1) << 3 | _lib.BWD_DEFER, prepared=self._prepared)
+        self._run_schedule(d, _Deferred(self, d, parts, Y, stash), gs)
+        return Y
 
     def step(self, A, X, L, n_global=None):
         """One optimiser step on this rank's windows (src/main.py:66-80).  `n_global`: windows of ALL ranks in this step,
@@ -674,62 +717,12 @@ class TrainStep:
         with a process group two of them around the one all-reduce.  The returned loss is a VIEW of the gradient bucket's
         header word, overwritten by the next step (module docstring): float() or .clone() it to keep it."""
         X, L = X.contiguous(), L.contiguous()   # a strided batch slice is copied here, never read as if dense
-        DEFER = _lib.BWD_DEFER
         if X.shape[0] == 0:
             return self._empty_shard_step(A, X, n_global)
-        loss = self._loss
-        if self.carry_state:
-            loss, Y = self._state_step(A, X, L, n_global)
-        elif self.plan is not None:
-            loss, Y = self._blocked_step(A, X, L, n_global)
-        elif self.collective and not self.overlap_collectives:
-            # the single-rank schedule, with ONE all-reduce of [loss | conv | GRU gradients] between the reduce-only finish and
-            # the optimiser's: one collective, one stream dependency each way per step
-            gs = self.exchange.shard_weight(X.shape[0], n_global)
-            Y, stash, d = self._forward(A, X, L)
-            pre = self._prepared
-            for part in (1 | 8, 2, 4):
-                gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, loss, gs, part=part | DEFER,
-                                         prepared=pre)
-            finish_step(d, self.p_views, self.g_views, 6, device=self.device)
-            self.exchange.all_reduce_all(gs)    # loss: sum of the weighted shard means = the big-batch mean
-            self._tail(d, 0, pre)                                                              # src/main.py:80
-        elif self.collective:
-            # Overlap: the GRU gradients (99.8 % of the bucket) are final after parts 1|4 of the backward, so
-            # their all-reduce runs on RCCL's stream while part 2 (dg GEMM + GCN backward, ~30 % of the
-            # step) still computes; the 364 conv gradients and the loss follow in a second, tiny all-reduce.
-            gs = self.exchange.shard_weight(X.shape[0], n_global)
-            Y, stash, d = self._forward(A, X, L)
-            pre = self._prepared
-            gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, loss, gs, part=1 | 4 | 8 | DEFER,
-                                     prepared=pre)
-            finish_step(d, self.p_views, self.g_views, 4, device=self.device)
-            work = self.exchange.start_gru()
-            gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, loss, gs, part=2 | DEFER, prepared=pre)
-            finish_step(d, self.p_views, self.g_views, 2, device=self.device)
-            # the conv gradients' (tiny, latency-bound) all-reduce runs under the GRU tensors' optimiser step
-            wconv = self.exchange.start_conv(gs)     # loss: sum of the weighted shard means = the big-batch mean
-            work.wait()
-            adam = self._adam()
-            finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_GRU, adam, pre, self.device)   # src/main.py:80
-            wconv.wait()
-            finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_CONV, adam, pre, self.device)
-        else:
-            # One rank: BPTT, then the dg GEMM + GCN backward, and the weight-gradient GEMMs LAST, so that wgnn_finish reads
-            # their split-K partial sums (115 MB at B = 4096) while they still sit in the Infinity Cache; deferring them
-            # across the dg GEMM and the GCN backward (0.8 GB of traffic) had them come back from HBM (finish 35 us)
-            Y, stash, d = self._forward(A, X, L)
-            pre = self._prepared
-            for part in (1 | 8, 2, 4):     # (the order 1, 4, 2 measured the same, 672-680 us either way: round 3)
-                gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, loss, 1.0, part=part | DEFER,
-                                         prepared=pre)
-            self._tail(d, 6, pre)                                                                      # :79 tail + :80
-        self.steps += 1                         # only a step whose launches were all accepted counts
-        self._keep_best()                       # src/main.py:83-86, after the optimiser's launches of every schedule
-        if self.check_every and self.steps % self.check_every == 0 and (
-                self.model.math != _lib.MATH_F32 or (self.exchange is not None and self.exchange.direct is not None)):
-            self.check()
-        return loss, Y
+        gs = self.exchange.shard_weight(X.shape[0], n_global) if self.collective else 1.0
+        Y = (self._state_step if self.carry_state else self._plain_step)(A, X, L, gs)
+        self._end_step()
+        return self._loss, Y
 
     def close(self):
         """Release the step's own RCCL communicator, if it has one (before torch.distributed.destroy_process_group).
