@@ -4,12 +4,14 @@ in the launcher sources (extracted as text: a pattern that stops matching fails)
 case on the key it claims.  The library's host-only queries confirm what they can: it sizes a workspace for every case's
 dims, refuses the refused ones, and its split-K counts are the formulas'.  The series half (SERIES_FAMILIES / SERIES_CASES) is
 held to the same rules, and its inputs are measured on the fp64 oracle alone: tie-free, well conditioned in fp32, and able to
-tell an off-by-one row."""
+tell an off-by-one row.  The edge half of the recurrence families (EDGE_CASES) is re-derived -- every H the top of its
+bracket, T odd and >= 5 -- and its inputs must tell three mistakes planted into a restated fp64 GRU."""
 import ctypes
 import os
 import re
 
 import pytest
+import torch
 
 import instance_cases as ic
 from conftest import ROOT
@@ -402,3 +404,165 @@ def test_series_inputs_can_tell_an_off_by_one_row():
     cover = series_coverage(rows, T, stride, n)
     assert any(lo > hi for lo, hi in cover[:(n - 1) * stride + T]) and ic.fold_terms(T, stride) == "0..1"
     assert {hi - lo + 1 for lo, hi in series_coverage(*SHAPE_A[1:])[2:-1]} == {1, 2}
+
+
+# ---- the edge half of the recurrence families ------------------------------------------------------------------------------
+EDGE_B = {17: 17, 33: 33, 769: 769, 2049: 833}      # B of the key's CASES entry -> B of its edge case (see above EDGE_CASES)
+Y_BAR = 1e-4                                         # the fp32-grade bar on Y (tests/test_gpu_parity.py Y_TOL), F16_Y_BAR the one-pass one
+F16_Y_BAR = 2e-2
+
+
+def edge_problems(edges):
+    """What is wrong with `edges` as the edge half of the table: a list of sentences, empty when every key of the six recurrence
+    families is claimed once, at the top of its bracket, at an odd T >= 5 and B = 1 (mod 16) by the rule."""
+    bad = []
+    base = {c[1]: c for c in ic.CASES if c[0] in ic.EDGE_FAMILIES}
+    want = [k for fam in ic.EDGE_FAMILIES for k in ic.FAMILIES[fam]]
+    assert sorted(base) == sorted(want)                           # (CASES claims every recurrence key: none is unreachable)
+    claimed = [c[1] for c in edges]
+    for key in want:
+        if claimed.count(key) != 1:
+            bad.append("%s is claimed %d times in EDGE_CASES" % (key, claimed.count(key)))
+    for fam, key, S, T, B, H, math, io, state, route in edges:
+        if key not in base:
+            bad.append("%s is no key of a recurrence family" % key)
+            continue
+        _, _, S0, T0, B0, H0, math0, io0, state0, route0 = base[key]
+        if (fam, S, math, io, state, route) != (base[key][0], S0, math0, io0, state0, route0):
+            bad.append("%s: family, S, math, io, state and route are not those of its case in CASES" % key)
+            continue
+        if ic.refusal(S, T, B, H, math, io) is not None or key not in ic.plan(S, T, B, H, math, io, state, route):
+            bad.append("%s: plan() at H = %d does not contain the key" % (key, H))
+            continue
+        if T < 5 or T % 2 == 0:
+            bad.append("%s: T = %d is not odd and >= 5" % (key, T))
+        elif T != ic.EDGE_T_OTHER.get((S, B, H), ic.EDGE_T):
+            bad.append("%s: T = %d, the rule says %d" % (key, T, ic.EDGE_T_OTHER.get((S, B, H), ic.EDGE_T)))
+        want_b = ic.EDGE_B_MOVED.get(key, EDGE_B[B0])
+        if B % 16 != 1 or B != want_b:
+            bad.append("%s: B = %d, the rule says %d" % (key, B, want_b))
+        top = ic.bracket_top(key, S, T, B, math, io, state, route)
+        beyond = H + 1 > ic.H_SCAN or ic.refusal(S, T, B, H + 1, math, io) is not None
+        if H != top or not (beyond or key not in ic.plan(S, T, B, H + 1, math, io, state, route)):
+            bad.append("%s: H = %d is not the top of its bracket (%s)" % (key, H, top))
+        bottom = min(h for h in range(1, ic.H_SCAN + 1) if ic.refusal(S, T, B, h, math, io) is None
+                     and key in ic.plan(S, T, B, h, math, io, state, route))
+        if not (H > H0 or bottom == top):
+            bad.append("%s: H = %d is not above the %d of its case in CASES" % (key, H, H0))
+    return bad
+
+
+def test_edge_cases_claim_every_recurrence_key_at_the_top_of_its_bracket():
+    assert edge_problems(ic.EDGE_CASES) == []
+    assert len(ic.EDGE_CASES) == 254 == sum(len(ic.FAMILIES[f]) for f in ic.EDGE_FAMILIES)
+    assert len(_edge_shapes()) == 47 + 2 and ic.EDGE_T == 5 and ic.EDGE_T_OTHER == {(1, 17, 106): 7}
+    assert [c[1] for c in ic.EDGE_CASES if c[3] != ic.EDGE_T] == ["gru_small_%s_kernel|hmax=108|st=%d" % (d, st)
+                                                                 for d in ("fwd", "bwd") for st in (0, 1)]
+    tops = lambda fam: sorted({c[5] for c in ic.EDGE_CASES if c[0] == fam})
+    assert tops("grux_fwd_kernel") == [31, 63, 95, 127]
+    assert tops("gru_fwd_kernel") == [4 * k for k in ic.GRU_FWD_KS] == tops("gru_bwd_kernel")
+    assert tops("gru_small_fwd_kernel") == ic.SMALL_HMAX_UPTO + [128] == tops("gru_small_bwd_kernel")
+    assert tops("grux_bwd_kernel") == [max(h for h in range(1, 128) if ic.grux_bwd_k(h) == k) for k in ic.GRUX_BWD_K]
+    # the three thresholds B follows
+    assert 5 * 833 >= 4096 > 5 * (833 - 16) and "L.small = !x3 && !L.gen_gru && !series && gru_small_supported(d->B, d->H);" in _read("api.hip")
+    # only one-pass fp16 cases may leave B = 17 for more rows, to 33 or 65
+    assert all(",f16>" in k and b in (33, 65) for k, b in ic.EDGE_B_MOVED.items()) and len(ic.EDGE_B_MOVED) == 2
+    for c in ic.EDGE_CASES:
+        assert (c[4] == 833) == any(w in c[1] for w in ("dGHn", "lo=0")), c[1]
+        assert (c[4] == 769) == (c[0] in ("gru_fwd_kernel", "gru_bwd_kernel") and "dGHn" not in c[1]), c[1]
+    # the library sizes a workspace for every edge shape
+    from windgnn_amd import _lib as L
+    from windgnn_amd import build
+    build.build(verbose=False)
+    lib = L.load()
+    for dims in dict.fromkeys((c[2:8]) for c in ic.EDGE_CASES):
+        S, T, B, H, math, io = dims
+        assert lib.wgnn_workspace_bytes(ctypes.byref(L.Dims(B, T, S, 13, H, MATH[math], 0, 0, IO[io]))) > 0, dims
+
+
+def test_the_edge_checks_notice_a_mis_tabled_entry():
+    i = next(n for n, c in enumerate(ic.EDGE_CASES) if c[1] == "grux_bwd_kernel<10>|io=32|st=0|lo=1")
+
+    def with_(**kw):
+        c = dict(zip(("fam", "key", "S", "T", "B", "H", "math", "io", "state", "route"), ic.EDGE_CASES[i]))
+        c.update(kw)
+        return ic.EDGE_CASES[:i] + [tuple(c.values())] + ic.EDGE_CASES[i + 1:]
+    H = ic.EDGE_CASES[i][5]
+    assert H == 104
+    assert edge_problems(with_(H=H - 1)) == ["grux_bwd_kernel<10>|io=32|st=0|lo=1: H = 103 is not the top of its bracket (104)"]
+    assert edge_problems(with_(H=H + 1)) == ["grux_bwd_kernel<10>|io=32|st=0|lo=1: plan() at H = 105 does not contain the key"]
+    assert edge_problems(with_(T=2)) == ["grux_bwd_kernel<10>|io=32|st=0|lo=1: T = 2 is not odd and >= 5"]
+    assert edge_problems(with_(T=7)) == ["grux_bwd_kernel<10>|io=32|st=0|lo=1: T = 7, the rule says 5"]
+    assert edge_problems(with_(T=6)) and edge_problems(with_(B=18)) and edge_problems(with_(B=33)) and edge_problems(with_(S=2))
+    for j in (0, i, len(ic.EDGE_CASES) - 1):                      # a recurrence key left out, and one claimed twice
+        gone = edge_problems(ic.EDGE_CASES[:j] + ic.EDGE_CASES[j + 1:])
+        assert gone == ["%s is claimed 0 times in EDGE_CASES" % ic.EDGE_CASES[j][1]], gone
+    assert edge_problems(ic.EDGE_CASES + [ic.EDGE_CASES[i]])
+    assert edge_problems(ic.EDGE_CASES + [c for c in ic.CASES if c[0] == "gcnx_fwd_kernel"][:1])
+    # a bracket of one width would be excused from "above the case in CASES", no other: the bottom-of-bracket entry is not
+    assert edge_problems(ic.EDGE_CASES[:i] + [ic.EDGE_CASES[i][:3] + (5, 17, 97) + ic.EDGE_CASES[i][6:]] + ic.EDGE_CASES[i + 1:])
+
+
+def _edge_shapes():
+    """The distinct (S, T, B, H) of the edge cases, in table order."""
+    return list(dict.fromkeys(c[2:6] for c in ic.EDGE_CASES))
+
+
+def restated_gru(r, mistake=None):
+    """Y of the fp64 GRU restated step by step on the oracle's own g, with one of three mistakes a recurrence kernel can make
+    planted: 'parity' -- from t = 2 on the W_hh product reads h_{t-2} (the other parity's state buffer); 'column' -- hidden
+    column H - 1 is dropped from the W_hh product; 'prefetch' -- on interior steps GI of step t + 1 is consumed at step t."""
+    from oracle import windgnn_oracle as orc
+    A, X, p = r["A"].double(), r["X"].double(), {k: v.double() for k, v in r["p"].items()}
+    g, _ = orc.gcn2_forward(A, X, p)
+    Wih, Whh, bih, bhh = (p["gru." + n] for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"))
+    B, T, H = X.shape[0], X.shape[1], Whh.shape[1]
+    GI = torch.matmul(g, Wih.t()) + bih
+    hs = [torch.zeros(B, H, dtype=torch.float64)]                 # hs[t] = h_{t-1}
+    for t in range(T):
+        h = hs[t]
+        hw = hs[t - 1] if (mistake == "parity" and t >= 2) else h
+        if mistake == "column":
+            gh = torch.matmul(hw[:, :H - 1], Whh[:, :H - 1].t()) + bhh
+        else:
+            gh = torch.matmul(hw, Whh.t()) + bhh
+        gi = GI[:, t + 1] if (mistake == "prefetch" and 1 <= t <= T - 2) else GI[:, t]
+        rg = torch.sigmoid(gi[:, 0:H] + gh[:, 0:H])
+        z = torch.sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
+        n = torch.tanh(gi[:, 2 * H:] + rg * gh[:, 2 * H:])
+        hs.append((1.0 - z) * n + z * h)
+    return torch.stack(hs[1:], 1)
+
+
+def edge_input_problems(shape):
+    """What is wrong with the inputs of an edge shape, measured on the oracle alone: a list of sentences."""
+    from oracle import windgnn_oracle as orc
+    from conftest import PARAM_KEYS, max_abs, rel_to_max
+    from test_gpu_instances import _reference
+    S, T, B, H = shape
+    r = _reference(S, T, B, H, "f32", False)
+    bad = []
+    # the oracle in fp32 against itself in fp64: a draw on which rounding alone costs a tenth of the bar proves nothing
+    Y32, _, g32 = orc.train_step(r["A"], r["X"], r["L"], r["p"])
+    gap = {"Y": rel_to_max(Y32, r["Y"])}
+    gap.update({k: rel_to_max(g32[k], r["grads"][k]) for k in PARAM_KEYS})
+    bad += ["%s: %s in fp32 is %.1e off the fp64 oracle: pick another seed" % (shape, k, e) for k, e in gap.items() if e > 1e-5]
+    # the restated GRU is the oracle's, bit for bit; each planted mistake moves Y by more than 10 fp32-grade bars
+    assert torch.equal(restated_gru(r), r["Y"]), shape
+    moved = {m: max_abs(restated_gru(r, m), r["Y"]) for m in ("parity", "column", "prefetch")}
+    print("%s: seed %d, max|Y| %.2f, fp32 against fp64 at most %.1e; planted parity %.1e column %.1e prefetch %.1e "
+          "(in one-pass bars of 2e-2: %.2f %.2f %.2f)" % ((shape, ic.param_seed(S, H), float(r["Y"].abs().max()), max(gap.values()))
+                                                         + tuple(moved.values()) + tuple(v / F16_Y_BAR for v in moved.values())))
+    bad += ["%s: the planted %s mistake moves Y by %.1e only: pick another seed" % (shape, m, v) for m, v in moved.items()
+            if not v > 10 * Y_BAR]
+    return bad
+
+
+def test_edge_inputs_are_well_conditioned_and_can_tell_the_planted_mistakes():
+    """Per distinct edge shape, on the oracle alone (the inputs are tests/test_gpu_instances.py's _reference draw, which the
+    one-pass cases share with their f16x3 siblings): fp32 against fp64 within a tenth of the bar on Y and every gradient, and
+    each planted mistake of restated_gru above 10 x 1e-4 on Y.  Against the one-pass bar of 2e-2 the mistakes are printed only."""
+    shapes = _edge_shapes()
+    assert len(shapes) == 49
+    for shape in shapes:
+        assert edge_input_problems(shape) == []
