@@ -5,7 +5,10 @@ case on the key it claims.  The library's host-only queries confirm what they ca
 dims, refuses the refused ones, and its split-K counts are the formulas'.  The series half (SERIES_FAMILIES / SERIES_CASES) is
 held to the same rules, and its inputs are measured on the fp64 oracle alone: tie-free, well conditioned in fp32, and able to
 tell an off-by-one row.  The edge half of the recurrence families (EDGE_CASES) is re-derived -- every H the top of its
-bracket, T odd and >= 5 -- and its inputs must tell three mistakes planted into a restated fp64 GRU."""
+bracket, T odd and >= 5 -- and its inputs must tell three mistakes planted into a restated fp64 GRU.  The K-loop half of the two NT
+GEMM families (KLOOP_CASES) likewise: nt_products() is held to plan(), every entry is re-derived -- on its key through the product
+of the same role, seven K stages, dims by the rule -- and its inputs must tell three K-loop mistakes planted into the input
+projection of a restated fp64 step."""
 import ctypes
 import os
 import re
@@ -14,7 +17,7 @@ import pytest
 import torch
 
 import instance_cases as ic
-from conftest import ROOT
+from conftest import PARAM_KEYS, ROOT
 
 CSRC = os.path.join(ROOT, "windgnn_amd", "csrc")
 MATH = {"f32": 0, "f16x3": 1, "f16": 2, "f16x3g": 3}
@@ -231,7 +234,7 @@ def test_the_library_accepts_every_case_and_splits_k_as_the_formulas_do():
     build.build(verbose=False)
     lib = L.load()
     seen = set()
-    for fam, key, S, T, B, H, math, io, state, route in ic.CASES:
+    for fam, key, S, T, B, H, math, io, state, route in ic.CASES + ic.KLOOP_CASES:
         dims = (S, T, B, H, math, io, state)
         if dims in seen:
             continue
@@ -566,3 +569,346 @@ def test_edge_inputs_are_well_conditioned_and_can_tell_the_planted_mistakes():
     assert len(shapes) == 49
     for shape in shapes:
         assert edge_input_problems(shape) == []
+
+
+# ---- the K-loop half of the two NT GEMM families ---------------------------------------------------------------------------
+G_BAR = 1e-3                                         # the widest fp32-grade gradient bar (single-plane f16x3g), F16_G_BAR the one-pass one
+F16_G_BAR = 5e-2
+ALL_WINDOW_TABLES = (("CASES", ic.CASES), ("EDGE_CASES", ic.EDGE_CASES), ("KLOOP_CASES", ic.KLOOP_CASES))
+
+
+def _nt_keys(keys):
+    return [k for k in keys if ic.family_of(k) in ic.NT_FAMILIES]
+
+
+def test_nt_products_names_exactly_the_nt_launches_of_plan():
+    """plan() is the authority for names; nt_products() restates its NT launches with their contraction.  For every case of
+    every window-major table, and over a grid of the thresholds, the two give the same keys in the same order."""
+    for name, table in ALL_WINDOW_TABLES:
+        for fam, key, S, T, B, H, math, io, state, route in table:
+            prods = ic.nt_products(S, T, B, H, math, io, state, route)
+            assert [p[0] for p in prods] == _nt_keys(ic.plan(S, T, B, H, math, io, state, route)), (name, key)
+            assert all(p[1] in ic.NT_ROLES and p[4] >= 1 for p in prods), (name, key, prods)
+    for key, (S, T, B, H, math) in ic.BEYOND_BUDGET.items():
+        assert [p[0] for p in ic.nt_products(S, T, B, H, math)] == _nt_keys(ic.plan(S, T, B, H, math)), key
+    for T, B in sorted(PLAIN_TB | THRESHOLD_TB):
+        for S in (1, 17, 34, 60):
+            for H in (4, 74, 127, 128, 129, 225):
+                for math in ic.MATHS:
+                    for state, route in ((0, "train"), (0, "fused"), (0, "infer"), (1, "train"), (1, "unmerged")):
+                        if ic.refusal(S, T, B, H, math, "f32"):
+                            continue
+                        prods = ic.nt_products(S, T, B, H, math, "f32", bool(state), route)
+                        assert [p[0] for p in prods] == _nt_keys(ic.plan(S, T, B, H, math, "f32", bool(state), route)), (S, T, B, H, math, route)
+    # the contraction: 32 columns a stage in both families, as the kernels count them
+    assert "const int nk = Kp / 32;" in _read("pgemm.hip") and "const int nk = Kp / 32;" in _read("gemm32.hip")
+    assert "const int nloop = FUSE_EPI ? nk - 1 : nk;" in _read("gemm32.hip")
+    assert ic.nt_products(17, 2, 17, 74, "f16x3") == [("pgemm_nt_kernel<1>|out16=0|narrow", "GI", 34, 222, 7),
+                                                       ("pgemm_nt_kernel<1>|out16=0|narrow", "dg", 34, 221, 7)]
+
+
+def kloop_problems(kloops):
+    """What is wrong with `kloops` as the K-loop half of the table: a list of sentences, empty when every key of the two NT GEMM
+    families whose keyed product runs fewer than ic.KLOOP_STAGES stages in CASES is claimed once, on its key, through the product
+    of the same role, at an odd count of at least ic.KLOOP_STAGES stages and at the rule's dims."""
+    bad = []
+    base = {c[1]: c for c in ic.CASES if c[0] in ic.NT_FAMILIES}
+    claimed = [c[1] for c in kloops]
+    bad += ["%s is claimed %d times in KLOOP_CASES" % (k, claimed.count(k)) for k in dict.fromkeys(claimed) if claimed.count(k) > 1]
+    most = {key: ic.keyed_product(key, *c[2:])[3] for key, c in base.items()}      # the most stages the key's product runs anywhere
+    for c in kloops:
+        fam, key, S, T, B, H, math, io, state, route = c
+        if key not in base:
+            bad.append("%s is no key CASES claims for an NT GEMM family" % key)
+            continue
+        _, _, S0, T0, B0, H0, math0, io0, state0, route0 = base[key]
+        if (fam, T, B, math, io, state, route) != (base[key][0], T0, B0, math0, io0, state0, route0):
+            bad.append("%s: family, T, B, math, io, state and route are not those of its case in CASES" % key)
+            continue
+        if ic.refusal(S, T, B, H, math, io) is not None or key not in ic.plan(S, T, B, H, math, io, state, route):
+            bad.append("%s: plan() at S = %d, H = %d does not contain the key" % (key, S, H))
+            continue
+        role0, _, _, stages0 = ic.keyed_product(key, *base[key][2:])
+        if stages0 >= ic.KLOOP_STAGES:
+            bad.append("%s: its case in CASES already runs %d K stages" % (key, stages0))
+            continue
+        mine = ic.keyed_product(key, S, T, B, H, math, io, state, route, role=role0)
+        if mine is None:
+            bad.append("%s: at S = %d, H = %d the key is not carried by the %s product that carries it in CASES" % (key, S, H, role0))
+            continue
+        stages = mine[3]
+        if stages < ic.KLOOP_STAGES or stages % 2 == 0:
+            bad.append("%s: the %s product runs %d K stages, not an odd count >= %d" % (key, role0, stages, ic.KLOOP_STAGES))
+        want = (S0, ic.KLOOP_H) if role0 == "dg" else (ic.KLOOP_S, H0)
+        if (S, H) != want:
+            bad.append("%s: S = %d, H = %d, the rule says %d, %d" % ((key, S, H) + want))
+        most[key] = max(most[key], stages)
+    bad += ["%s runs at most %d K stages in CASES and KLOOP_CASES" % (k, n) for k, n in most.items() if n < ic.KLOOP_STAGES]
+    return bad
+
+
+def _kloop_shapes():
+    """The distinct (S, T, B, H, io, state) of the K-loop cases, in table order, each with the roles of its keyed products."""
+    out = {}
+    for fam, key, S, T, B, H, math, io, state, route in ic.KLOOP_CASES:
+        role = ic.keyed_product(key, *next(c for c in ic.CASES if c[1] == key)[2:])[0]
+        out.setdefault((S, T, B, H, io, state), set()).add(role)
+    return out
+
+
+def test_kloop_cases_give_every_nt_key_a_k_loop_of_seven_stages():
+    assert kloop_problems(ic.KLOOP_CASES) == []
+    assert ic.KLOOP_STAGES == 7 and (ic.KLOOP_H, ic.KLOOP_S) == (74, 17) and ic.NT_BK == 32
+    assert ic.rup(3 * ic.KLOOP_H, 32) == 7 * 32 == ic.rup(13 * ic.KLOOP_S + 1, 32) and 3 * ic.KLOOP_H == 222 == 13 * ic.KLOOP_S + 1
+    # every reachable key of the two families is in CASES (the two BEYOND_BUDGET keys are the K-chunked form's), and no key
+    # leaves the rule: kloop_problems() knows no exemption
+    for fam in ic.NT_FAMILIES:
+        assert {k for k in ic.FAMILIES[fam] if k not in ic.UNREACHABLE and k not in ic.BEYOND_BUDGET} == {c[1] for c in ic.CASES if c[0] == fam}
+    # which half of which family needed the second case: by (family, wide-GRU path, role, stages of the CASES entry)
+    census = {}
+    for c in ic.CASES:
+        if c[0] in ic.NT_FAMILIES:
+            role, _, _, stages = ic.keyed_product(c[1], *c[2:])
+            census.setdefault((c[0], c[5] > 127, role, stages), []).append(c[1])
+    assert {k: len(v) for k, v in census.items()} == {
+        ("pgemm_nt_kernel", False, "GI", 1): 4, ("pgemm_nt_kernel", False, "dg", 1): 65, ("pgemm_nt_kernel", True, "GI", 1): 13,
+        ("pgemm_nt_kernel", True, "dg", 12): 32, ("pgemm_nt_kernel", True, "bptt", 12): 1,
+        ("gemm32_nt_kernel", False, "GI", 1): 2, ("gemm32_nt_kernel", False, "dg", 1): 19}
+    assert len(ic.KLOOP_CASES) == 4 + 65 + 13 + 2 + 19 == 103 and len(_kloop_shapes()) == 53
+    assert {c[1] for c in ic.KLOOP_CASES} == {k for (_, _, _, stages), keys in census.items() for k in keys if stages < ic.KLOOP_STAGES}
+    # one role per shape: H = 74 carries dg keys alone, S = 17 GI keys alone
+    assert all(len(roles) == 1 for roles in _kloop_shapes().values())
+    assert all((roles == {"dg"}) == (shape[3] == ic.KLOOP_H) and (roles == {"GI"}) == (shape[0] == ic.KLOOP_S and shape[3] != ic.KLOOP_H)
+               for shape, roles in _kloop_shapes().items())
+    # a pinned one-pass figure belongs to a one-pass K-loop case (none is pinned: every case is inside the imported bars)
+    assert all(k in {c[1] for c in ic.KLOOP_CASES if c[6] == "f16"} and t in ["Y", "loss"] + list(PARAM_KEYS)
+               for k, t in ic.KLOOP_F16_EXCEPTIONS) and ic.KLOOP_F16_EXCEPTIONS == {}
+    # all fp32 I/O, no carried state, the training route -- as their cases in CASES; rows from 34 to 36 888
+    assert {c[7:] for c in ic.KLOOP_CASES} == {("f32", False, "train")}
+    assert sorted({c[3] * c[4] for c in ic.KLOOP_CASES}) == [34, 4098, 6146, 16419, 24483, 36888]
+
+
+def test_the_kloop_checks_notice_a_mis_tabled_entry():
+    dg_key, gi_key = "gemm32_nt_kernel<128x128>", "pgemm_nt_kernel<1>|out16=0|narrow"
+    at = {k: next(n for n, c in enumerate(ic.KLOOP_CASES) if c[1] == k) for k in (dg_key, gi_key)}
+
+    def with_(key, **kw):
+        i = at[key]
+        c = dict(zip(("fam", "key", "S", "T", "B", "H", "math", "io", "state", "route"), ic.KLOOP_CASES[i]))
+        c.update(kw)
+        return ic.KLOOP_CASES[:i] + [tuple(c.values())] + ic.KLOOP_CASES[i + 1:]
+    assert ic.KLOOP_CASES[at[dg_key]][2:6] == (5, 3, 8161, 74) and ic.KLOOP_CASES[at[gi_key]][2:6] == (17, 2, 17, 4)
+    # a deleted case: the first, one in the middle, the last
+    for j in (0, at[dg_key], len(ic.KLOOP_CASES) - 1):
+        gone = kloop_problems(ic.KLOOP_CASES[:j] + ic.KLOOP_CASES[j + 1:])
+        assert gone == ["%s runs at most 1 K stages in CASES and KLOOP_CASES" % ic.KLOOP_CASES[j][1]], gone
+    # H = 4 put back: the CASES entry itself
+    assert kloop_problems(with_(dg_key, H=4)) == [
+        "gemm32_nt_kernel<128x128>: the dg product runs 1 K stages, not an odd count >= 7",
+        "gemm32_nt_kernel<128x128>: S = 5, H = 4, the rule says 5, 74",
+        "gemm32_nt_kernel<128x128> runs at most 1 K stages in CASES and KLOOP_CASES"]
+    # six stages: 3 H = 192
+    assert kloop_problems(with_(dg_key, H=64)) == [
+        "gemm32_nt_kernel<128x128>: the dg product runs 6 K stages, not an odd count >= 7",
+        "gemm32_nt_kernel<128x128>: S = 5, H = 64, the rule says 5, 74",
+        "gemm32_nt_kernel<128x128> runs at most 6 K stages in CASES and KLOOP_CASES"]
+    # eight stages is past seven but even; nine is odd but not the rule's
+    assert kloop_problems(with_(dg_key, H=85))[0] == "gemm32_nt_kernel<128x128>: the dg product runs 8 K stages, not an odd count >= 7"
+    assert kloop_problems(with_(dg_key, H=96)) == ["gemm32_nt_kernel<128x128>: S = 5, H = 96, the rule says 5, 74"]
+    # the wrong role: at S = 17, H = 32 the key is launched, with seven stages -- by GI (N = 96), where CASES keys it through dg
+    wrong = with_(dg_key, S=17, H=32)
+    assert dg_key in ic.plan(17, 3, 8161, 32, "f32") and ic.keyed_product(dg_key, 17, 3, 8161, 32, "f32") == ("GI", 24483, 96, 7)
+    assert kloop_problems(wrong) == [
+        "gemm32_nt_kernel<128x128>: at S = 17, H = 32 the key is not carried by the dg product that carries it in CASES",
+        "gemm32_nt_kernel<128x128> runs at most 1 K stages in CASES and KLOOP_CASES"]
+    # ... and a GI key moved along H instead of S: the GI product still carries it, for one stage
+    assert kloop_problems(with_(gi_key, S=1, H=74))[0] == "pgemm_nt_kernel<1>|out16=0|narrow: the GI product runs 1 K stages, not an odd count >= 7"
+    # a key lost, a key claimed twice, a key that needs no second case, another family's, another call form
+    assert kloop_problems(with_(dg_key, S=17))[0] == "gemm32_nt_kernel<128x128>: plan() at S = 17, H = 74 does not contain the key"
+    assert kloop_problems(ic.KLOOP_CASES + [ic.KLOOP_CASES[0]])[0] == "%s is claimed 2 times in KLOOP_CASES" % ic.KLOOP_CASES[0][1]
+    twelve = next(c for c in ic.CASES if c[1] == "pgemm_nt_kernel<1,x2>|out16=0|wide")
+    assert kloop_problems(ic.KLOOP_CASES + [twelve]) == ["pgemm_nt_kernel<1,x2>|out16=0|wide: its case in CASES already runs 12 K stages"]
+    assert kloop_problems(ic.KLOOP_CASES + [c for c in ic.CASES if c[0] == "gcnx_fwd_kernel"][:1])
+    assert kloop_problems(with_(dg_key, T=2)) and kloop_problems(with_(dg_key, B=8177)) and kloop_problems(with_(gi_key, math="f16"))
+
+
+def test_the_tables_before_kloop_cases_ran_gemm32_128x128_for_one_stage():
+    """The blind spot, asserted once: over CASES and EDGE_CASES together every launch of gemm32_nt_kernel<128x128> -- the keyed one
+    or a sibling's -- contracts over 32 padded columns, so nloop = nk - 1 = 0 and the 128-row form's main loop never ran; the
+    K-loop case runs it for six trips before the fused last step."""
+    key = "gemm32_nt_kernel<128x128>"
+    seen = [p for _, table in ALL_WINDOW_TABLES[:2] for c in table for p in ic.nt_products(*c[2:]) if p[0] == key]
+    assert seen and {p[4] for p in seen} == {1}, seen
+    case = next(c for c in ic.KLOOP_CASES if c[1] == key)
+    assert ic.keyed_product(key, *case[2:]) == ("dg", 3 * 8161, 13 * 5, 7)
+    # ... and so for most keys: those that NO launch of the two tables takes past one stage, by family and path (by the keyed
+    # product of the CASES entry alone the count is 69 of 69, 21 of 21 and 13 of 46: the census of the test above; thirteen pgemm_nt
+    # keys and two gemm32_nt keys get a longer loop as a sibling, mostly as GI of a case at S >= 30 and H = 4, where N = 12)
+    most = {}
+    for _, table in ALL_WINDOW_TABLES[:2]:
+        for c in table:
+            for k, role, M, N, stages in ic.nt_products(*c[2:]):
+                most[k] = max(most.get(k, 0), stages)
+    wide_gru = {c[1] for c in ic.CASES if c[0] == "pgemm_nt_kernel" and c[5] > 127}
+    one = lambda keys: sum(most[k] == 1 for k in keys)
+    reg = {c[1] for c in ic.CASES if c[0] == "pgemm_nt_kernel"} - wide_gru
+    g32 = {c[1] for c in ic.CASES if c[0] == "gemm32_nt_kernel"}
+    print("one-stage keys: pgemm_nt (H <= 127) %d of %d, gemm32_nt %d of %d, pgemm_nt (wide GRU) %d of %d"
+          % (one(reg), len(reg), one(g32), len(g32), one(wide_gru), len(wide_gru)))
+    assert (one(reg), len(reg)) == (60, 69) and (one(g32), len(g32)) == (19, 21) and (one(wide_gru), len(wide_gru)) == (9, 46)
+
+
+KLOOP_WINDOWS = 64                                   # the inputs are qualified on the first min(B, 64) windows of the case's draw
+KLOOP_MISTAKES = ("slab 3 of A from slab 2", "slab 3 of B from slab 2", "last slab left out")
+
+
+def _slab_delta(Aop, Bop, mistake):
+    """What a mistake of the K loop adds to C = Aop Bop^T, the operands [rows, K] cut into slabs of ic.NT_BK columns: an interior
+    slab of one operand read from the slab before it (a stage consumed before its DMA landed: the slot still holds the stage
+    two trips back in a two-slot ring; the previous slab stands for a stale one), or the last slab never accumulated."""
+    K, bk = Aop.shape[1], ic.NT_BK
+    assert K == Bop.shape[1] and K % bk == 0 and K // bk >= ic.KLOOP_STAGES          # slab 3 is interior
+    s2, s3, last = slice(2 * bk, 3 * bk), slice(3 * bk, 4 * bk), slice(K - bk, K)
+    if mistake == KLOOP_MISTAKES[0]:
+        return torch.matmul(Aop[:, s2] - Aop[:, s3], Bop[:, s3].t())
+    if mistake == KLOOP_MISTAKES[1]:
+        return torch.matmul(Aop[:, s3], (Bop[:, s2] - Bop[:, s3]).t())
+    assert mistake == KLOOP_MISTAKES[2]
+    return -torch.matmul(Aop[:, last], Bop[:, last].t())
+
+
+def _padded(t, K):
+    return torch.cat([t, torch.zeros(t.shape[0], K - t.shape[1], dtype=t.dtype)], 1)
+
+
+class _InputProjection(torch.autograd.Function):
+    """The input projection as the oracle computes it -- forward GI = [g | 1] [W_ih | b_ih]^T, backward dg = dGI W_ih (and dW_ih,
+    db_ih) -- with one mistake of KLOOP_MISTAKES planted into ONE of the two products: plant = (role, mistake) or None.  The
+    operands are the kernels': K = Ip (g, the ones column, zero pad) for GI, K = Gp (the 3 H gate columns, zero pad) for dg."""
+
+    @staticmethod
+    def forward(ctx, g, Wih, bih, plant):
+        ctx.save_for_backward(g, Wih)
+        ctx.plant = plant
+        GI = torch.matmul(g, Wih.t()) + bih
+        if plant and plant[0] == "GI":
+            g2 = g.reshape(-1, g.shape[-1])
+            Ip = ic.rup(g2.shape[1] + 1, 32)
+            Aop = _padded(torch.cat([g2, torch.ones(g2.shape[0], 1, dtype=g.dtype)], 1), Ip)
+            Bop = _padded(torch.cat([Wih, bih[:, None]], 1), Ip)
+            GI = GI + _slab_delta(Aop, Bop, plant[1]).reshape(GI.shape)
+        return GI
+
+    @staticmethod
+    def backward(ctx, dGI):
+        g, Wih = ctx.saved_tensors
+        dGI2 = dGI.reshape(-1, dGI.shape[-1])
+        dW = dGI2.t() @ g.reshape(-1, g.shape[-1])
+        db = dGI2.sum(0)
+        dg = dGI2 @ Wih
+        if ctx.plant and ctx.plant[0] == "dg":
+            Gp = ic.rup(dGI2.shape[1], 32)
+            dg = dg + _slab_delta(_padded(dGI2, Gp), _padded(Wih.t(), Gp), ctx.plant[1])
+        return dg.reshape(g.shape), dW, db, None
+
+
+def kloop_step(r, plant=None):
+    """Y, the loss and the 8 gradients of the oracle's training step restated in fp64 around _InputProjection: the oracle's own
+    graph convolutions, recurrence, BPTT and GCN backward, with GI and (dg, dW_ih, db_ih) taken from the Function."""
+    from oracle import windgnn_oracle as orc
+    A, X, L = r["A"].double(), r["X"].double(), r["L"].double()
+    p = {k: v.double() for k, v in r["p"].items()}
+    Whh, bhh = p["gru.weight_hh_l0"], p["gru.bias_hh_l0"]
+    B, T, S, F = X.shape
+    H = Whh.shape[1]
+    g, cache = orc.gcn2_forward(A, X, p)
+    gl, Wl, bl = (t.detach().clone().requires_grad_(True) for t in (g, p["gru.weight_ih_l0"], p["gru.bias_ih_l0"]))
+    GIa = _InputProjection.apply(gl, Wl, bl, plant)
+    GI = GIa.detach()
+    h = torch.zeros(B, H, dtype=torch.float64)
+    Y, R, Z, N, GHN = (torch.empty(B, T, H, dtype=torch.float64) for _ in range(5))
+    for t in range(T):                                            # orc.forward's loop
+        gh = torch.matmul(h, Whh.t()) + bhh
+        rg = torch.sigmoid(GI[:, t, 0:H] + gh[:, 0:H])
+        z = torch.sigmoid(GI[:, t, H:2 * H] + gh[:, H:2 * H])
+        n = torch.tanh(GI[:, t, 2 * H:] + rg * gh[:, 2 * H:])
+        h = (1.0 - z) * n + z * h
+        Y[:, t], R[:, t], Z[:, t], N[:, t], GHN[:, t] = h, rg, z, n, gh[:, 2 * H:]
+    loss, dY = orc.mse_loss_and_grad(Y, L)
+    dGI, dGH = (torch.empty(B, T, 3 * H, dtype=torch.float64) for _ in range(2))
+    dh_next = torch.zeros(B, H, dtype=torch.float64)
+    for t in range(T - 1, -1, -1):                                # orc.backward's loop
+        hprev = Y[:, t - 1] if t > 0 else torch.zeros(B, H, dtype=torch.float64)
+        rg, z, n = R[:, t], Z[:, t], N[:, t]
+        dh = dY[:, t] + dh_next
+        dn = dh * (1.0 - z)
+        dz = dh * (hprev - n)
+        dnt = dn * (1.0 - n * n)
+        dr = dnt * GHN[:, t]
+        dar = dr * rg * (1.0 - rg)
+        daz = dz * z * (1.0 - z)
+        dGI[:, t, 0:H], dGI[:, t, H:2 * H], dGI[:, t, 2 * H:] = dar, daz, dnt
+        dGH[:, t, 0:H], dGH[:, t, H:2 * H], dGH[:, t, 2 * H:] = dar, daz, dnt * rg
+        dh_next = dh * z + torch.matmul(dGH[:, t], Whh)
+    GIa.backward(dGI)
+    Hprev = torch.cat([torch.zeros(B, 1, H, dtype=torch.float64), Y[:, :-1]], dim=1)
+    dGH2 = dGH.reshape(B * T, 3 * H)
+    grads = {"gru.weight_ih_l0": Wl.grad, "gru.bias_ih_l0": bl.grad,
+             "gru.weight_hh_l0": dGH2.t() @ Hprev.reshape(B * T, H), "gru.bias_hh_l0": dGH2.sum(0)}
+    grads.update(orc.gcn2_backward(A, p, cache, gl.grad.reshape(B, T, S, F)))
+    return Y, float(loss), grads
+
+
+def kloop_input_problems(shape, roles):
+    """What is wrong with the inputs of a K-loop shape, measured on the oracle alone over the first KLOOP_WINDOWS windows of the
+    case's own draw: a list of sentences."""
+    from oracle import windgnn_oracle as orc
+    from conftest import PARAM_KEYS, max_abs, rel_to_max
+    from test_gpu_instances import _draw
+    S, T, B, H, io, state = shape
+    assert not state and io == "f32"                              # (the K-loop cases are the training route's)
+    d = _draw(S, T, B, H, io, state)
+    n = min(B, KLOOP_WINDOWS)
+    r = dict(A=d["A"], X=d["X"][:n], L=d["L"][:n], p=d["p"])
+    Y64, loss64, g64 = orc.train_step(r["A"].double(), r["X"].double(), r["L"].double(), {k: v.double() for k, v in r["p"].items()})
+    bad = []
+    # the oracle in fp32 against itself in fp64: a draw on which rounding alone costs a tenth of the bar proves nothing
+    Y32, _, g32 = orc.train_step(r["A"], r["X"], r["L"], r["p"])
+    gap = {"Y": rel_to_max(Y32, Y64)}
+    gap.update({k: rel_to_max(g32[k], g64[k]) for k in PARAM_KEYS})
+    bad += ["%s: %s in fp32 is %.1e off the fp64 oracle: pick another seed" % (shape, k, e) for k, e in gap.items() if e > 1e-5]
+    # the restated step is the oracle's, bit for bit
+    Yr, lossr, gr = kloop_step(r)
+    assert torch.equal(Yr, Y64) and lossr == float(loss64) and all(torch.equal(gr[k], g64[k]) for k in PARAM_KEYS), shape
+    # each mistake planted into the keyed product moves Y or a gradient by more than 10 fp32-grade bars
+    for role in sorted(roles):
+        moved = {}
+        for m in KLOOP_MISTAKES:
+            Ym, _, gm = kloop_step(r, (role, m))
+            moved[m] = (max_abs(Ym, Y64), max(rel_to_max(gm[k], g64[k]) for k in PARAM_KEYS))
+        print("%s %s: seed %d, %d windows, max|Y| %.2f, fp32 against fp64 at most %.1e; planted (Y, worst gradient): %s "
+              "(in one-pass bars of 2e-2 / 5e-2: %s)"
+              % (shape, role, ic.param_seed(S, H), n, float(Y64.abs().max()), max(gap.values()),
+                 "  ".join("%.1e %.1e" % v for v in moved.values()),
+                 "  ".join("%.2f %.2f" % (v[0] / F16_Y_BAR, v[1] / F16_G_BAR) for v in moved.values())))
+        bad += ["%s: '%s' planted into %s moves Y by %.1e and no gradient by more than %.1e: pick another seed" % ((shape, m, role) + v)
+                for m, v in moved.items() if not max(v) > 10 * Y_BAR]
+    return bad
+
+
+def test_kloop_inputs_are_well_conditioned_and_can_tell_the_planted_mistakes():
+    """Per distinct K-loop shape, on the oracle alone and on the first 64 windows of the case's own draw (the conditioning is a
+    property of (S, H) and the draw; 37 000 rows in fp64 several times over are not needed to see it): fp32 against fp64 within
+    1e-5 on Y and every gradient; the step restated around _InputProjection equals the oracle's bit for bit; and each of the
+    three K-loop mistakes, planted into the keyed product alone, moves Y or some gradient by more than 10 x 1e-4 (a mistake in
+    dg leaves the forward alone and moves the four conv gradients).  Against the one-pass bars the figures are printed only."""
+    shapes = _kloop_shapes()
+    assert len(shapes) == 53
+    problems = [p for shape, roles in shapes.items() for p in kloop_input_problems(shape, roles)]
+    assert problems == []
+    # the check notices a projection that is not the oracle's: the planted step differs from it
+    S, T, B, H, io, state = next(iter(shapes))
+    from test_gpu_instances import _draw
+    d = _draw(S, T, B, H, io, state)
+    r = dict(A=d["A"], X=d["X"][:4], L=d["L"][:4], p=d["p"])
+    assert not torch.equal(kloop_step(r, ("GI", KLOOP_MISTAKES[2]))[0], kloop_step(r)[0])
