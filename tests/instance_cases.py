@@ -26,6 +26,11 @@ The two NT GEMM families (NT_FAMILIES) have a second case per key past a one-sta
 plan()'s NT launches with their contraction, and the product that carries the key runs seven K stages instead of one;
 tests/test_gpu_instance_kloop.py proves them on the GPU.
 
+gemm_f32_kernel has the same second half: gemm_f32_products() restates plan()'s gemm.hip launches with their contraction,
+GEMM_F32_KLOOP_CASES runs every NT key at seven K steps of 16 columns instead of one and GEMM_F32_FOLD_CASES takes every tile past
+the two-level fold (33 steps in one chunk); tests/test_general_loops_host.py re-derives them, tests/test_gpu_general_loops.py
+proves them on the GPU (next to the CSR layers' item loop: tests/general_cases.py).
+
 The series entry points (wgnn_series_*) have their own half: SERIES_FAMILIES, series_plan() and SERIES_CASES, whose cases are
 (family, key, S, H, rows, T, stride, n, seed, route) with route 'series' (wgnn_series_fwd + wgnn_series_bwd with a signed
 random dY), 'series_mse' (wgnn_series_fwd_loss + wgnn_series_bwd_mse) or 'series_last' (wgnn_series_fwd_last);
@@ -380,6 +385,55 @@ def keyed_product(key, S, T, B, H, math, io="f32", state=False, route="train", r
     launch order among equals (of that role alone where one is given); None where no such NT launch of the step has the key."""
     mine = [p for p in nt_products(S, T, B, H, math, io, state, route) if p[0] == key and role in (None, p[1])]
     return max(mine, key=lambda p: p[4])[1:] if mine else None
+
+
+GEMM_F32_ROLES = ("GI", "rec", "bptt", "dg", "dW_hh", "dW_ih")
+GEMM_F32_NT_ROLES = GEMM_F32_ROLES[:4]
+GEMM_F32_BK = 16                                            # columns of the contraction per K step (gemm.hip: BK)
+GEMM_F32_FOLD = 512 // GEMM_F32_BK                          # steps after which gemm.hip folds acc into tot (since == 512 / BK)
+
+
+def gemm_f32_products(S, T, B, H, math, io="f32", state=False, route="train"):
+    """plan()'s gemm_f32_kernel launches restated with their contraction: (key, role, M, N, K, split, steps) of every such
+    launch of one step, in launch order.  role: 'GI' = g W_ih^T (K = 13 S; the bias is added in the epilogue), 'rec' / 'bptt'
+    the per-step products of the wide-GRU path (K = H / 3 H), 'dg' = dGI W_ih (K = 3 H), 'dW_hh' / 'dW_ih' the two TN products
+    (K = B*T rows, cut by pick_splitk).  steps = the trip count of the kernel's K loop in its first chunk: ceil(K / split) rounded
+    up to 16 columns, over 16 (launch_gemm_f32's kchunk).  Nothing for the fp16-plane modes or where gemm32.hip's products run.
+    plan() stays the authority for names: tests/test_general_loops_host.py holds the keys of the two together."""
+    assert refusal(S, T, B, H, math, io) is None, (S, T, B, H, math, io)
+    if math != "f32":
+        return []
+    gen = H > 128
+    BT, I, G3 = B * T, 13 * S, 3 * H
+    if not gen and g32_rows(BT, S, H):
+        return []
+    out = []
+
+    def prod(role, M, N, K, sk, form):
+        steps = cdiv(min(K, rup(cdiv(K, sk), GEMM_F32_BK)), GEMM_F32_BK)
+        out.append((gemm_f32_name(M, N, sk, form), role, M, N, K, sk, steps))
+
+    prod("GI", BT, G3, I, gemm_f32_nt_splitk(BT, G3, I) if BT < 65536 else 1, "kk")
+    steps = T if state else T - 1
+    if gen:
+        for _ in range(steps):
+            prod("rec", B, G3, H, 1, "kk")
+    if route == "infer":
+        return out
+    if gen:
+        for _ in range(steps):
+            prod("bptt", B, H, G3, 1, "kn")
+    prod("dW_hh", G3, H + 1, BT, pick_splitk(BT, gemm_f32_tiles(G3, H + 1), 1024, 128), "tn,ones" if state else "tn,ones,shift")
+    prod("dW_ih", G3, I + 1, BT, pick_splitk(BT, gemm_f32_tiles(G3, I + 1), 1024, 128), "tn,ones")
+    prod("dg", BT, I, G3, gemm_f32_nt_splitk(BT, I, G3) if BT < 65536 else 1, "kn")
+    return out
+
+
+def gemm_f32_keyed(key, S, T, B, H, math, io="f32", state=False, route="train", role=None):
+    """The product of gemm_f32_products() that carries `key`: (role, M, N, K, split, steps) of the one with the most steps per
+    chunk, the first in launch order among equals (of that role alone where one is given); None where none has the key."""
+    mine = [p for p in gemm_f32_products(S, T, B, H, math, io, state, route) if p[0] == key and role in (None, p[1])]
+    return max(mine, key=lambda p: p[6])[1:] if mine else None
 
 
 H_SCAN = 128                                                # past it no register-resident recurrence runs (gen_gru)
@@ -1635,6 +1689,52 @@ KLOOP_CASES = [
 # (lattice_inputs.fp64_step(f16_operands=True)) on the case's inputs, held by a host test as F16_FIGURES is.  Kept apart from
 # F16_EXCEPTIONS: the keys are the same, the dims are not, and neither list may start applying to the other's cases.
 KLOOP_F16_EXCEPTIONS = {}
+
+# ---- gemm_f32_kernel past one K step ------------------------------------------------------------------------------------------
+# The same question asked of gemm.hip's exact-fp32 products (gemm_f32_products()).  A K step is 16 columns; CASES keeps H = 4
+# where S selects the key and S = 1 where H does, so the keyed product of an NT key contracts over 13 S = 13 or 3 H = 12 columns:
+# ONE partial step -- no commit of step k + 1 into the other LDS stage, no refill of a register stage, and the 128 x 128 tile's
+# one-register-stage pipeline (RS = 1) as little as the others' (RS = 2).  The exact count, over every launch of CASES, EDGE_CASES
+# and KLOOP_CASES (the host test prints it): of the seven NT keys, FOUR never pass one step -- <64,128>[kk], <64,128>[kn],
+# <128,128>[kk], <128,128>[kn]; <64,64>[kk] reaches 43 steps (GI of the <128,128>[kn] case, K = 676) and <64,64>[kn] 36 and
+# <128,64>[kk] 12 as per-step products of the wide-GRU path (K = 3 H = 576, K = H = 192).  By the keyed product of its own CASES
+# entry, six of seven run one step; <128,64>[kk] is keyed through `rec` at 12.  The four TN keys run 3 to 49 steps a chunk.
+# GEMM_F32_KLOOP_CASES gives a second case, same tuple form, to every NT key whose keyed product (gemm_f32_keyed()) runs fewer
+# than GEMM_F32_KLOOP_STEPS steps in one chunk in its CASES entry; dims by rule from that entry:
+#   keyed through GI ([kk]: N = 3 H selects the tile, K = 13 S):  S = 8  -- K = 104: seven steps, the last with 8 live columns;
+#   keyed through dg ([kn]: N = 13 S selects it, K = 3 H):        H = 35 -- K = 105: seven steps, the last with 9 live columns;
+#   T, B and the rest are the entry's own: M, N, the tile and the split (1) do not depend on the dimension that moved.
+# Seven: odd, so the two LDS stages are used an unequal number of times, and every register stage is refilled at least twice
+# (RS = 2: at steps 0 to 3; RS = 1: at steps 0 to 4).  No key leaves the rule; no exact-fp32 layout here is gemm32.hip's (S = 52
+# pads to 704 > 512 columns, H = 129 is the wide-GRU path) and no NT product is split.
+GEMM_F32_KLOOP_STEPS = 7
+GEMM_F32_KLOOP_S, GEMM_F32_KLOOP_H = 8, 35                  # the rule's S (keyed through GI) and H (keyed through dg)
+GEMM_F32_KLOOP_CASES = [
+    ("gemm_f32_kernel", "gemm_f32_kernel<64,64>[kk]", 8, 2, 17, 4, "f32", "f32", False, "train"),
+    ("gemm_f32_kernel", "gemm_f32_kernel<64,64>[kn]", 1, 2, 17, 35, "f32", "f32", False, "train"),
+    ("gemm_f32_kernel", "gemm_f32_kernel<64,128>[kk]", 8, 2, 17, 22, "f32", "f32", False, "train"),
+    ("gemm_f32_kernel", "gemm_f32_kernel<64,128>[kn]", 5, 2, 17, 35, "f32", "f32", False, "train"),
+    ("gemm_f32_kernel", "gemm_f32_kernel<128,128>[kk]", 8, 24, 1537, 129, "f32", "f32", False, "train"),
+    ("gemm_f32_kernel", "gemm_f32_kernel<128,128>[kn]", 52, 3, 8161, 35, "f32", "f32", False, "train"),
+]
+
+# The two-level fold (`since == 32`: after 512 columns acc is added into tot and cleared) needs 33 steps in ONE chunk.  One case
+# per tile whose keyed product -- GI or dg: the role is tabled -- runs at least GEMM_F32_FOLD + 1 steps unsplit (so at least 64
+# tiles) outside gemm32.hip's layouts (S >= 40, or the wide-GRU path):
+#   <64,64>     an existing case does it and is named, not repeated: GI of CASES' <128,128>[kn] entry, K = 676, 43 steps;
+#   <64,128>    (40, 2, 2017, 35):   GI, K = 520: 32 steps, the fold, one step of 8 live columns;
+#   <128,64>    (40, 3, 2411, 192):  GI, K = 520 over 7233 rows x 576 columns (57 x 9 = 513 tiles of 128 x 64; in CASES the key is
+#               carried by the wide-GRU path's per-step product, whose K = H could reach 513 only at N = 1539);
+#   <128,128>   (40, 24, 1537, 129): GI [kk], K = 520;  (52, 3, 8161, 171): dg [kn], K = 513: ONE live column after the fold
+#               (the same step runs <64,64>[kn] past the fold too, as the BPTT product: K = 513).
+# (family, key, S, T, B, H, math, io, state, route, role): the case tuple and the role of the product that folds
+GEMM_F32_FOLD_NAMED = ("gemm_f32_kernel<64,64>[kk]", "gemm_f32_kernel<128,128>[kn]", "GI")    # key, the CASES entry that runs it, role
+GEMM_F32_FOLD_CASES = [
+    ("gemm_f32_kernel", "gemm_f32_kernel<64,128>[kk]", 40, 2, 2017, 35, "f32", "f32", False, "train", "GI"),
+    ("gemm_f32_kernel", "gemm_f32_kernel<128,64>[kk]", 40, 3, 2411, 192, "f32", "f32", False, "train", "GI"),
+    ("gemm_f32_kernel", "gemm_f32_kernel<128,128>[kk]", 40, 24, 1537, 129, "f32", "f32", False, "train", "GI"),
+    ("gemm_f32_kernel", "gemm_f32_kernel<128,128>[kn]", 52, 3, 8161, 171, "f32", "f32", False, "train", "dg"),
+]
 
 # ---- the series entry points -------------------------------------------------------------------------------------------
 # (family, key, S, H, rows, T, stride, n, seed, route); the inputs are tests/test_gpu_series.py's _draw(S, H, rows, T, stride, n,

@@ -234,7 +234,8 @@ def test_the_library_accepts_every_case_and_splits_k_as_the_formulas_do():
     build.build(verbose=False)
     lib = L.load()
     seen = set()
-    for fam, key, S, T, B, H, math, io, state, route in ic.CASES + ic.KLOOP_CASES:
+    for fam, key, S, T, B, H, math, io, state, route in (ic.CASES + ic.KLOOP_CASES + ic.GEMM_F32_KLOOP_CASES
+                                                          + [c[:10] for c in ic.GEMM_F32_FOLD_CASES]):
         dims = (S, T, B, H, math, io, state)
         if dims in seen:
             continue
@@ -812,9 +813,10 @@ class _InputProjection(torch.autograd.Function):
         return dg.reshape(g.shape), dW, db, None
 
 
-def kloop_step(r, plant=None):
+def kloop_step(r, plant=None, projection=None):
     """Y, the loss and the 8 gradients of the oracle's training step restated in fp64 around _InputProjection: the oracle's own
-    graph convolutions, recurrence, BPTT and GCN backward, with GI and (dg, dW_ih, db_ih) taken from the Function."""
+    graph convolutions, recurrence, BPTT and GCN backward, with GI and (dg, dW_ih, db_ih) taken from the Function (`projection`:
+    another Function of the same signature, as tests/test_general_loops_host.py's for gemm.hip's operands)."""
     from oracle import windgnn_oracle as orc
     A, X, L = r["A"].double(), r["X"].double(), r["L"].double()
     p = {k: v.double() for k, v in r["p"].items()}
@@ -823,7 +825,7 @@ def kloop_step(r, plant=None):
     H = Whh.shape[1]
     g, cache = orc.gcn2_forward(A, X, p)
     gl, Wl, bl = (t.detach().clone().requires_grad_(True) for t in (g, p["gru.weight_ih_l0"], p["gru.bias_ih_l0"]))
-    GIa = _InputProjection.apply(gl, Wl, bl, plant)
+    GIa = (projection or _InputProjection).apply(gl, Wl, bl, plant)
     GI = GIa.detach()
     h = torch.zeros(B, H, dtype=torch.float64)
     Y, R, Z, N, GHN = (torch.empty(B, T, H, dtype=torch.float64) for _ in range(5))
