@@ -1,5 +1,5 @@
 """ctypes binding of libwindgnn_hip.so (the C ABI declared in include/windgnn.h, windgnn_optim.h, windgnn_sched.h,
-windgnn_eval.h, windgnn_best.h, windgnn_series.h and windgnn_series_train.h).
+windgnn_eval.h, windgnn_best.h, windgnn_series.h, windgnn_series_train.h and windgnn_series_at.h).
 
 The library is the product: there is no CPU or eager-PyTorch fallback.  If the shared object is
 missing or a call fails this module raises, loudly."""
@@ -201,6 +201,29 @@ EXPORTS_SERIES_TRAIN = {
                                       C.c_size_t, C.c_void_p]),
 }
 
+# include/windgnn_series_at.h: series mode on windows at a table of start rows (an eighth header and table, as above)
+SERIES_AT_VERSION = 1       # WGNN_SERIES_AT_VERSION
+STATUS_WINDOW_START = 16    # WGNN_STATUS_WINDOW_START
+_SD = C.POINTER(SeriesDims)
+EXPORTS_SERIES_AT = {
+    "wgnn_series_at_version": (C.c_int, []),
+    "wgnn_series_at_workspace_bytes": (C.c_size_t, [_SD]),
+    "wgnn_series_at_stash_bytes": (C.c_size_t, [_SD]),
+    "wgnn_series_at_loss_bytes": (C.c_size_t, [_SD]),
+    "wgnn_series_at_status_offset": (C.c_size_t, [_SD]),
+    "wgnn_series_fwd_at": (C.c_int, [_SD, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wgnn_series_fwd_last_at": (C.c_int, [_SD, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_float, C.c_float,
+                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wgnn_series_bwd_at": (C.c_int, [_SD, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.POINTER(Grads), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wgnn_series_fwd_loss_at": (C.c_int, [_SD, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wgnn_series_bwd_mse_at": (C.c_int, [_SD, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,
+                                         C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Grads),
+                                         C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -262,6 +285,16 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    if not hasattr(lib, "wgnn_series_at_version"):
+        raise RuntimeError("windgnn_amd: %s predates include/windgnn_series_at.h (no wgnn_series_at_version): rebuild it "
+                           "with `python -m windgnn_amd.build --force`" % LIB_PATH)
+    for name, (res, args) in EXPORTS_SERIES_AT.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.wgnn_series_at_version() < SERIES_AT_VERSION:
+        raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_series_at_version %d < %d)"
+                           % (lib.wgnn_series_at_version(), SERIES_AT_VERSION))
     if lib.wgnn_series_train_version() < SERIES_TRAIN_VERSION:
         raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_series_train_version %d < %d)"
                            % (lib.wgnn_series_train_version(), SERIES_TRAIN_VERSION))

@@ -955,10 +955,12 @@ int series_plan(const wgnn_dims* df, const wgnn_dims* dr, SeriesPlan* sp) {
 namespace {
 
 // Ls / loss_buf (wgnn_series_fwd_loss, both or neither): the recurrence also reads the label series and leaves the MSE partial
-// pairs and the tag in loss_buf; Y and the stash are the same either way
+// pairs and the tag in loss_buf; Y and the stash are the same either way.  starts (with stride = 0; include/windgnn_series_at.h):
+// window w begins at row starts[w], clamped into [0, rows - T], instead of w * stride -- the recurrence is the only reader
 int series_forward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
                    float* Y, float* last, float wind_min, float wind_max, void* stash, void* workspace, const SeriesPlan& sp,
-                   void* stream, const float* Ls, int64_t ls_rows, float* loss_buf) {
+                   void* stream, const float* Ls, int64_t ls_rows, float* loss_buf, const int* starts) {
+  const int last_start = df->T - dr->T;        // the largest legal start: rows - T
   const Layout Lf = make_layout(df, false, SER_FRONT), Lr = make_layout(dr, false, SER_REC);
   FwdCall cf(workspace, sizeof(float) * sp.ws_front, stream);
   cf.A = A; cf.X = Xs; cf.p = p; cf.stash = stash;
@@ -969,17 +971,19 @@ int series_forward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const f
   const int ld = (int)Lf.Gp;
   if (last)
     return launch_gru_fwd(dr->B, dr->T, dr->H, f.GI, ld, p->w_hh, p->b_hh, last, nullptr, nullptr, nullptr, nullptr, 0, 1,
-                          wind_max - wind_min, wind_min, st, nullptr, nullptr, stride);
+                          wind_max - wind_min, wind_min, st, nullptr, nullptr, stride, 0, starts, last_start);
   float* sr = stash ? (float*)stash + sp.st_front : nullptr;
   return launch_gru_fwd(dr->B, dr->T, dr->H, f.GI, ld, p->w_hh, p->b_hh, Y, sr ? sr + Lr.st_gates : nullptr, Ls, loss_buf,
-                        sr && Lr.g32tn ? sr + Lr.st_hprev : nullptr, Lr.hq, 0, 1.f, 0.f, st, nullptr, nullptr, stride, ls_rows);
+                        sr && Lr.g32tn ? sr + Lr.st_hprev : nullptr, Lr.hq, 0, 1.f, 0.f, st, nullptr, nullptr, stride, ls_rows,
+                        starts, last_start);
 }
 
 // dY, or Ls with the forward's loss_buf (wgnn_series_bwd_mse): BPTT forms dY = (Y - label) 2 grad_scale / (n T H) itself and its
 // workgroup 0 finalises loss[0]; a missing tag sets WGNN_STATUS_NO_LOSS_STATS in the rec half's status block
 int series_backward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
                     const float* Y, const float* dY, const void* stash, const wgnn_grads* g, void* workspace, const SeriesPlan& sp,
-                    void* stream, const float* Ls, int64_t ls_rows, float grad_scale, const float* loss_buf, float* loss) {
+                    void* stream, const float* Ls, int64_t ls_rows, float grad_scale, const float* loss_buf, float* loss,
+                    const int* starts) {
   const Layout Lf = make_layout(df, false, SER_FRONT), Lr = make_layout(dr, false, SER_REC);
   const float* sff = (const float*)stash;
   BwdCall cr((float*)workspace + sp.ws_front, sizeof(float) * sp.ws_rec, stream);
@@ -991,13 +995,15 @@ int series_backward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const 
   // 1. BPTT per window: n is recomputed from GI_s rows w * stride + t; dGI / dGHn (or dGH) come out window-major
   int rc = launch_gru_bwd(dr->B, dr->T, dr->H, p->w_hh, Y, dY, Ls, br.sf + Lr.st_gates, sff + Lf.st_GI, (int)Lf.Gp, br.dGI,
                           (int)Lr.Gp, Lr.dghn ? br.dGH : nullptr, Lr.dghn ? nullptr : br.dGH, loss_buf, (int64_t)Lr.BT * Lr.H,
-                          grad_scale, loss, Ls ? br.status : nullptr, br.st, nullptr, stride, ls_rows);
+                          grad_scale, loss, Ls ? br.status : nullptr, br.st, nullptr, stride, ls_rows, starts,
+                          df->T - dr->T);
   if (rc != WGNN_OK) return rc;
   // 2. dW_hh | db_hh over the n * T window-major rows
   rc = bwd_weights(br, WGNN_ROWS_HH, 0, (int)Lr.G3);
   if (rc != WGNN_OK) return rc;
   // 3. dGI_s[tau] = sum over the windows that cover tau
-  rc = launch_series_fold(br.dGI, dr->B, dr->T, stride, df->T, (int)Lf.G3, (int)Lf.Gp, bf.dGI, bf.st);
+  rc = starts ? launch_series_fold_at(br.dGI, starts, dr->B, dr->T, df->T, (int)Lf.G3, (int)Lf.Gp, bf.dGI, bf.st)
+              : launch_series_fold(br.dGI, dr->B, dr->T, stride, df->T, (int)Lf.G3, (int)Lf.Gp, bf.dGI, bf.st);
   if (rc != WGNN_OK) return rc;
   // 4. + 5. dW_ih | db_ih, dg and the GCN backward over the `rows` hours, each with its reduction
   rc = bwd_weights(bf, WGNN_ROWS_IH, 0, (int)Lf.G3);
@@ -1009,29 +1015,32 @@ int series_backward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const 
 
 int series_fwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
                float* Y, float* last, float wind_min, float wind_max, void* stash, void* workspace, const SeriesPlan& sp,
-               void* stream) {
-  return series_forward(df, dr, stride, A, Xs, p, Y, last, wind_min, wind_max, stash, workspace, sp, stream, nullptr, 0, nullptr);
+               void* stream, const int* starts) {
+  return series_forward(df, dr, stride, A, Xs, p, Y, last, wind_min, wind_max, stash, workspace, sp, stream, nullptr, 0, nullptr,
+                        starts);
 }
 
 int series_bwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
                const float* Y, const float* dY, const void* stash, const wgnn_grads* g, void* workspace, const SeriesPlan& sp,
-               void* stream) {
-  return series_backward(df, dr, stride, A, Xs, p, Y, dY, stash, g, workspace, sp, stream, nullptr, 0, 1.f, nullptr, nullptr);
+               void* stream, const int* starts) {
+  return series_backward(df, dr, stride, A, Xs, p, Y, dY, stash, g, workspace, sp, stream, nullptr, 0, 1.f, nullptr, nullptr,
+                         starts);
 }
 
 size_t series_loss_floats(int n) { return 2 * (size_t)gru_blocks(n) + 4; }   // pairs, tag, 3 spare words (as Layout::st_stats)
 
 int series_fwd_loss(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
                     const float* Ls, int64_t ls_rows, float* Y, void* stash, float* loss_buf, void* workspace,
-                    const SeriesPlan& sp, void* stream) {
-  return series_forward(df, dr, stride, A, Xs, p, Y, nullptr, 0.f, 1.f, stash, workspace, sp, stream, Ls, ls_rows, loss_buf);
+                    const SeriesPlan& sp, void* stream, const int* starts) {
+  return series_forward(df, dr, stride, A, Xs, p, Y, nullptr, 0.f, 1.f, stash, workspace, sp, stream, Ls, ls_rows, loss_buf,
+                        starts);
 }
 
 int series_bwd_mse(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
                    const float* Y, const float* Ls, int64_t ls_rows, float grad_scale, const void* stash, const float* loss_buf,
-                   float* loss, const wgnn_grads* g, void* workspace, const SeriesPlan& sp, void* stream) {
+                   float* loss, const wgnn_grads* g, void* workspace, const SeriesPlan& sp, void* stream, const int* starts) {
   return series_backward(df, dr, stride, A, Xs, p, Y, nullptr, stash, g, workspace, sp, stream, Ls, ls_rows, grad_scale, loss_buf,
-                         loss);
+                         loss, starts);
 }
 
 extern "C" {

@@ -97,6 +97,11 @@ __device__ __forceinline__ BwdState bwd_state(S... s) {
 // BwdState, as an optional trailing argument pack: the instances without it keep their argument list and their code.
 struct SeriesRows { int stride; };
 __device__ __forceinline__ BwdState bwd_state(SeriesRows) { return BwdState{nullptr, nullptr, nullptr}; }
+// The table variant (include/windgnn_series_at.h): window w starts at row clamp(starts[w], 0, last) of the series, last = rows - T,
+// so no value in the table can take a read outside GI_s / Ls.  A second type in the same place: the SeriesRows instances and
+// the instances without a pack keep their code.
+struct SeriesStarts { const int* starts; int last; };
+__device__ __forceinline__ BwdState bwd_state(SeriesStarts) { return BwdState{nullptr, nullptr, nullptr}; }
 
 // ---- internal launchers (defined in the .hip files, used by api.hip) -------------------------
 struct GemmArgs {
@@ -289,7 +294,9 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
                    float* gates, const float* labels, float* stat_part, float* hprev, int hq, int last_only, float y_mul,
                    float y_add, hipStream_t st, const float* h0 = nullptr, float* hn = nullptr,
                    int series_stride = 0 /*> 0: GI is one series [rows][ldgi], window w at rows w * stride + t (no h0)*/,
-                   int64_t ls_rows = 0 /*series with labels: they are one series too, Ls [ls_rows][H], read at the same rows*/);
+                   int64_t ls_rows = 0 /*series with labels: they are one series too, Ls [ls_rows][H], read at the same rows*/,
+                   const int* starts = nullptr /*instead of a stride: window w at rows clamp(starts[w], 0, starts_last) + t*/,
+                   int starts_last = 0);
 //   backward: exactly one of dY / labels; dGI [B*T][ldd] and EITHER dGHn [B*T][gru_hn(H)] (dGH's r and z thirds equal
 //   dGI's) OR the full dGH [B*T][ldd]; stat_part (nullable, with labels): loss[0] is finalised from the forward's partials
 int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
@@ -297,7 +304,8 @@ int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const 
                    int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st,
                    const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given*/,
                    int series_stride = 0 /*> 0: GI is one series, as in launch_gru_fwd (no state)*/,
-                   int64_t ls_rows = 0 /*series with labels: Ls [ls_rows][H], as in launch_gru_fwd*/);
+                   int64_t ls_rows = 0 /*series with labels: Ls [ls_rows][H], as in launch_gru_fwd*/,
+                   const int* starts = nullptr /*instead of a stride, as in launch_gru_fwd*/, int starts_last = 0);
 bool gru_shape_supported(int H);
 size_t gru_gates_floats(int B, int T, int H);
 int gru_blocks(int B);
@@ -333,22 +341,26 @@ struct SeriesPlan {
 int series_plan(const wgnn_dims* front, const wgnn_dims* rec, SeriesPlan* sp);   // check_dims of both + the sizes
 int series_fwd(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs, const wgnn_params* p,
                float* Y, float* last /*one of Y / last*/, float wind_min, float wind_max, void* stash /*nullable*/,
-               void* workspace, const SeriesPlan& sp, void* stream);
+               void* workspace, const SeriesPlan& sp, void* stream, const int* starts = nullptr /*stride = 0: the table*/);
 int series_bwd(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs, const wgnn_params* p,
                const float* Y, const float* dY, const void* stash, const wgnn_grads* g, void* workspace, const SeriesPlan& sp,
-               void* stream);
+               void* stream, const int* starts = nullptr);
 // include/windgnn_series_train.h (series_train.hip validates): the same two sequences with the labels as a series Ls [ls_rows][H]
 // in the recurrences; loss_buf = 2 * gru_blocks(n) partials (sum | max) + the tag word, series_loss_floats(n) floats in all
 size_t series_loss_floats(int n);
 int series_fwd_loss(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs,
                     const wgnn_params* p, const float* Ls, int64_t ls_rows, float* Y, void* stash /*nullable*/, float* loss_buf,
-                    void* workspace, const SeriesPlan& sp, void* stream);
+                    void* workspace, const SeriesPlan& sp, void* stream, const int* starts = nullptr);
 int series_bwd_mse(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs,
                    const wgnn_params* p, const float* Y, const float* Ls, int64_t ls_rows, float grad_scale, const void* stash,
-                   const float* loss_buf, float* loss, const wgnn_grads* g, void* workspace, const SeriesPlan& sp, void* stream);
+                   const float* loss_buf, float* loss, const wgnn_grads* g, void* workspace, const SeriesPlan& sp, void* stream,
+                   const int* starts = nullptr);
 // dGIs [rows][ld] = the sum, in ascending w, of the window-major rows dGI [(w, tau - w * stride)][ld] that cover hour tau;
 // uncovered rows and the columns [G3, ld) are written as zeros (series.hip)
 int launch_series_fold(const float* dGI, int n, int T, int stride, int rows, int G3, int ld, float* dGIs, hipStream_t st);
+// the same with window w at row starts[w] (non-decreasing): the windows covering hour tau are one index range of the table
+int launch_series_fold_at(const float* dGI, const int* starts, int n, int T, int rows, int G3, int ld, float* dGIs,
+                          hipStream_t st);
 
 // one hour of carried-state inference as ONE launch (gru_step.hip): T = 1, dense A with S <= 64, F = 13, H <= 128, B <= WGNN_STEP_MAX_B;
 // exact fp32 VALU arithmetic in every math mode.  Y [B][H] and hn [B][H] nullable (not both).

@@ -50,11 +50,19 @@ __device__ __forceinline__ void lds_row(const float* p, float (&a)[N]) {
   }
 }
 
-// GI rows between the first rows of two consecutive windows: T (window-major GI), or the stride of a SeriesRows
+// GI rows between the first rows of two consecutive windows: T (window-major GI), or the stride of a SeriesRows; 0 for a
+// SeriesStarts (the workgroup's base is the series' base, and a window's first row comes from the table: series_start)
 template <typename... S>
 __device__ __forceinline__ int gi_window_rows(int T, S... s) {
   if constexpr ((std::is_same<S, SeriesRows>::value || ...)) return SeriesRows{s...}.stride;
+  else if constexpr ((std::is_same<S, SeriesStarts>::value || ...)) return 0;
   else return T;
+}
+// SeriesStarts: the first series row of window w (w < B), clamped so that rows [start, start + T) lie inside the series
+template <typename... S>
+__device__ __forceinline__ int series_start(int w, S... s) {
+  const SeriesStarts ss{s...};
+  return min(max(ss.starts[w], 0), ss.last);
 }
 
 // gate stash: grux.hip's layout, [workgroup][t][wave][r | z | n | gh_n][lane] x float4 (the 4 window rows a lane owns):
@@ -65,6 +73,7 @@ __host__ __device__ inline size_t gate_floats(int B, int T, int H) {
 
 // Sr (empty, or one SeriesRows: wgnn_series_fwd): GI is one series and window w reads row w * stride + t of it, and so are the
 // labels (wgnn_series_fwd_loss: Lab = Ls [ls_rows][H], the same row); everything the kernel writes stays window-major.
+// Or one SeriesStarts (wgnn_series_fwd_at): the row is clamp(starts[w], 0, last) + t.
 template <int KS, bool ST = false, typename... Sr>   // k steps of 4 over the hidden index, 4 KS >= H, KS even; ST: the wgnn_fwd_state instance
 __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, const float* __restrict__ GI, int ldgi,
                                                            const float* __restrict__ Whh,
@@ -75,6 +84,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
                                                            const float* __restrict__ h0, float* __restrict__ hn,
                                                            Sr... series) {
   constexpr bool SR = sizeof...(Sr) > 0;
+  constexpr bool SS = (std::is_same<Sr, SeriesStarts>::value || ...);
   // h0 (nullable, wgnn_fwd_state): [B][H] initial state instead of zeros; hn (nullable): h_{T-1} [B][H], unrounded
   if (!ST) { h0 = nullptr; hn = nullptr; }       // (the plain forward's instance compiles exactly as before)
   constexpr int KP = 4 * KS, HS = KP + 4;          // row stride: 16-byte aligned rows
@@ -133,7 +143,8 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
     const int m = 4 * lk + r;
     rowok[r] = jv && b0 + m < B;
     rowt[r] = (b0 + m < B ? m : B - 1 - b0) * T;
-    if constexpr (SR) rowg[r] = (b0 + m < B ? m : B - 1 - b0) * gi_window_rows(T, series...);
+    if constexpr (SS) rowg[r] = series_start(b0 + m < B ? b0 + m : B - 1, series...);
+    else if constexpr (SR) rowg[r] = (b0 + m < B ? m : B - 1 - b0) * gi_window_rows(T, series...);
   }
   float gi[3][4], gin[3][4], lab[4] = {0.f, 0.f, 0.f, 0.f}, labn[4] = {0.f, 0.f, 0.f, 0.f};
   auto load_gi = [&](int t, float (&dst)[3][4], float (&ldst)[4]) {
@@ -250,7 +261,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
 // Outputs for the GEMMs that follow: dGI rows [B*T][ldd] (3H layout, zero K padding) and dGHn = dnt r rows [B*T][hn].
 // St (empty, or one BwdState: wgnn_bwd_state_part): h_{-1} = h0, the carry starts at dh_n, and the step at t = 0 also forms
 // dh_{-1} = dh z + dgh W_hh into dh0.  Or one SeriesRows (wgnn_series_bwd / wgnn_series_bwd_mse): GIn, and Lab if given, are
-// one series each, as in the forward.
+// one series each, as in the forward; or one SeriesStarts (the _at entry points), likewise.
 template <int KS3, typename... St>   // k steps of 4 over the gate-row index, 4 KS3 >= 3H, KS3 even
 __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, const float* __restrict__ Whh,
                                                            const float* __restrict__ Y, const float* __restrict__ dY,
@@ -263,7 +274,8 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
                                                            const float* __restrict__ stat_part, int nstat, float inv_n,
                                                            float coef_lab, float* __restrict__ loss_out,
                                                            unsigned* status, St... state) {
-  constexpr bool SR = (std::is_same<St, SeriesRows>::value || ...);
+  constexpr bool SS = (std::is_same<St, SeriesStarts>::value || ...);
+  constexpr bool SR = (std::is_same<St, SeriesRows>::value || ...) || SS;
   constexpr bool ST = sizeof...(St) > 0 && !SR;
   const BwdState sb = bwd_state(state...);
   constexpr int KP = 4 * KS3, DS = KP + 4;
@@ -331,7 +343,8 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
     const int m = 4 * lk + r;
     rowok[r] = jv && b0 + m < B;
     rowt[r] = (b0 + m < B ? m : B - 1 - b0) * T;
-    if constexpr (SR) rowg[r] = (b0 + m < B ? m : B - 1 - b0) * gi_window_rows(T, state...);
+    if constexpr (SS) rowg[r] = series_start(b0 + m < B ? b0 + m : B - 1, state...);
+    else if constexpr (SR) rowg[r] = (b0 + m < B ? m : B - 1 - b0) * gi_window_rows(T, state...);
   }
   // h0 in registers before the loop: a load under `tc == 0` inside load_step would make the compiler wait for all of
   // the step's prefetches at the join
@@ -468,11 +481,14 @@ int gru_msplit(int H) { return 4 * cdiv_i(2 * H, 4); }   // first GEMM row of th
 
 int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
                    float* gates, const float* labels, float* stat_part, float* hprev, int hq, int last_only, float y_mul,
-                   float y_add, hipStream_t st, const float* h0, float* hn, int series_stride, int64_t ls_rows) {
+                   float y_add, hipStream_t st, const float* h0, float* hn, int series_stride, int64_t ls_rows,
+                   const int* starts, int starts_last) {
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
   if (last_only && (gates || labels || hprev)) return WGNN_ERR_UNSUPPORTED;
   if (series_stride < 0 || (series_stride && (h0 || hn))) return WGNN_ERR_UNSUPPORTED;
-  if (series_stride && labels && ls_rows * H >= (1ll << 31)) return WGNN_ERR_SHAPE;   // 32-bit offsets into Ls
+  if (starts && (series_stride || h0 || hn || starts_last < 0)) return WGNN_ERR_UNSUPPORTED;
+  if ((series_stride || starts) && labels && ls_rows * H >= (1ll << 31)) return WGNN_ERR_SHAPE;   // 32-bit offsets into Ls
+  if (starts && labels && ls_rows < (int64_t)starts_last + T) return WGNN_ERR_SHAPE;   // every clamped window has its label rows
   if (hprev && (hq < H + 1 || hq % 4 != 0)) return WGNN_ERR_SHAPE;
   const int ks = pick_ks(cdiv_i(H, 4), FWD_KS, (int)(sizeof(FWD_KS) / sizeof(int)));
   const double bt = (double)B * T;
@@ -481,6 +497,13 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
                     (gates ? 3.0 * gate_floats(B, T, H) : 0.0);     // three of the buffer's four components are used
 #define FCASE(K)                                                                                                  \
   case K:                                                                                                         \
+    if (starts) {                                                                                                 \
+      PROF_LAUNCH("gru_fwd_kernel<" #K ",starts>", fl, by, st,                                                    \
+                  hipLaunchKernelGGL((gru_fwd_kernel<K, false, SeriesStarts>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, \
+                                     GI, ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq, last_only, y_mul, y_add,         \
+                                     nullptr, nullptr, SeriesStarts{starts, starts_last}));                                       \
+      break;                                                                                                      \
+    }                                                                                                             \
     PROF_LAUNCH("gru_fwd_kernel<" #K ">", fl, by, st,                                                             \
                 if (series_stride) hipLaunchKernelGGL((gru_fwd_kernel<K, false, SeriesRows>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, \
                                                       st, B, T, H, GI, ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq,       \
@@ -506,11 +529,13 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
 int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
                    const float* gates, const float* GI /*the forward's GI rows [B*T][ldgi] (stash)*/, int ldgi, float* dGI, int ldd, float* dGHn, float* dGH, const float* stat_part,
                    int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st, const BwdState* state,
-                   int series_stride, int64_t ls_rows) {
+                   int series_stride, int64_t ls_rows, const int* starts, int starts_last) {
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
   if (state && (!state->h0 || labels)) return WGNN_ERR_UNSUPPORTED;
   if (series_stride < 0 || (series_stride && state)) return WGNN_ERR_UNSUPPORTED;
-  if (series_stride && labels && ls_rows * H >= (1ll << 31)) return WGNN_ERR_SHAPE;   // 32-bit offsets into Ls
+  if (starts && (series_stride || state || starts_last < 0)) return WGNN_ERR_UNSUPPORTED;
+  if ((series_stride || starts) && labels && ls_rows * H >= (1ll << 31)) return WGNN_ERR_SHAPE;   // 32-bit offsets into Ls
+  if (starts && labels && ls_rows < (int64_t)starts_last + T) return WGNN_ERR_SHAPE;
   if ((dY == nullptr) == (labels == nullptr) || ldd < 3 * H || (dGHn == nullptr) == (dGH == nullptr)) return WGNN_ERR_SHAPE;
   if (stat_part && (!labels || !loss)) return WGNN_ERR_NULL;
   if (!GI || ldgi < 3 * H) return WGNN_ERR_NULL;
@@ -522,6 +547,13 @@ int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const 
                                           bt * 4.0 * H;   // + GI's n third
 #define BCASE(K)                                                                                                  \
   case K:                                                                                                         \
+    if (starts) {                                                                                                 \
+      PROF_LAUNCH("gru_bwd_kernel<" #K ",starts>", fl, by, st,                                                    \
+                  hipLaunchKernelGGL((gru_bwd_kernel<K, SeriesStarts>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, Whh, Y, \
+                                     dY, labels, gates, GI, ldgi, dGI, ldd, dGHn, hn, dGH, stat_part, gru_blocks(B), inv_n, coef,    \
+                                     loss, status, SeriesStarts{starts, starts_last}));                                              \
+      break;                                                                                                      \
+    }                                                                                                             \
     PROF_LAUNCH("gru_bwd_kernel<" #K ">", fl, by, st,                                                             \
                 if (series_stride) hipLaunchKernelGGL((gru_bwd_kernel<K, SeriesRows>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, \
                                                       T, H, Whh, Y, dY, labels, gates, GI, ldgi, dGI, ldd, dGHn, hn, dGH, stat_part,  \

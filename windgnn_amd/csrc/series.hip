@@ -1,10 +1,11 @@
-// Series mode (include/windgnn_series.h, include/windgnn_series_train.h): the entry points, their validation, and the fold
-// kernel of the backward.
+// Series mode (include/windgnn_series.h, include/windgnn_series_train.h, include/windgnn_series_at.h): the entry points, their
+// validation, the fold kernels of the backward and the check of a table of window starts.
 // The launches themselves are api.hip's (series_fwd / series_bwd): they run the materialised path's own front end, weight-gradient
 // products and GCN backward on two of its layouts, with gru.hip's recurrences reading GI at series rows.
 #include "common.h"
 #include "../../include/windgnn_series.h"
 #include "../../include/windgnn_series_train.h"
+#include "../../include/windgnn_series_at.h"
 
 #include <cmath>
 
@@ -34,15 +35,69 @@ __global__ void __launch_bounds__(256) series_fold_kernel(const float* __restric
   *(f32x4*)(dGIs + (size_t)tau * ld + c) = acc;
 }
 
+// The fold for windows at a table of starts (include/windgnn_series_at.h).  starts is non-decreasing, so the windows that cover
+// hour tau -- tau - T < starts[w] <= tau -- are the index range [lower_bound(tau - T + 1), upper_bound(tau)): two binary searches,
+// then the terms in ascending w as above.  Duplicated starts make the range longer than T.  The searches stay inside [0, n) for
+// any table; a term whose row tau - starts[w] is not in [0, T) (possible only in a table that series_starts_check_kernel has
+// flagged) is skipped, so no table can take a read outside dGI.
+__global__ void __launch_bounds__(256) series_fold_at_kernel(const float* __restrict__ dGI, const int* __restrict__ starts,
+                                                             int n, int T, int rows, int G3, int ld,
+                                                             float* __restrict__ dGIs) {
+  const int ld4 = ld >> 2;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)rows * ld4) return;
+  const int tau = (int)(i / ld4), c = 4 * (int)(i % ld4);
+  int lo = 0, hi = n;                    // first w with starts[w] > tau - T
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (starts[mid] > tau - T) hi = mid;
+    else lo = mid + 1;
+  }
+  const int w_lo = lo;
+  hi = n;                                // first w >= w_lo with starts[w] > tau
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (starts[mid] > tau) hi = mid;
+    else lo = mid + 1;
+  }
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int w = w_lo; w < lo; ++w) {
+    const int t = tau - starts[w];
+    if ((unsigned)t < (unsigned)T) {
+      const f32x4 v = *(const f32x4*)(dGI + ((size_t)w * T + (size_t)t) * ld + c);
+      acc += v;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if (c + q >= G3) acc[q] = 0.f;
+  *(f32x4*)(dGIs + (size_t)tau * ld + c) = acc;
+}
+
+// One thread per window: a start outside [0, last] or below its predecessor is reported in the status word; nothing else is
+// written.  (The kernels that read the table clamp; this is what tells the caller that they had to.)
+__global__ void __launch_bounds__(256) series_starts_check_kernel(const int* __restrict__ starts, int n, int last,
+                                                                  unsigned* status) {
+  const int w = blockIdx.x * 256 + threadIdx.x;
+  if (w >= n) return;
+  const int s = starts[w];
+  report_status(status, s < 0 || s > last || (w > 0 && s < starts[w - 1]), WGNN_STATUS_WINDOW_START);
+}
+
 struct Plan {
   wgnn_dims front, rec;
   SeriesPlan sp;
 };
 
 // Everything about sd that needs no pointer: the order is shape, scope, then the element-count limits of both layouts
-int plan(const wgnn_series_dims* sd, Plan* pl) {
+// at: the dims of include/windgnn_series_at.h -- stride = 0 means "a table", whose values size nothing
+int plan(const wgnn_series_dims* sd, Plan* pl, bool at = false) {
   if (!sd) return WGNN_ERR_NULL;
-  if (sd->rows < 1 || sd->T < 1 || sd->stride < 1 || sd->n < 1 || sd->S < 1 || sd->H < 1 || sd->F != 13) return WGNN_ERR_SHAPE;
+  if (at) {   // (the fit below then reads T <= rows)
+    if (sd->rows < 1 || sd->T < 1 || sd->stride != 0 || sd->n < 1 || sd->S < 1 || sd->H < 1 || sd->F != 13) return WGNN_ERR_SHAPE;
+  } else {
+    if (sd->rows < 1 || sd->T < 1 || sd->stride < 1 || sd->n < 1 || sd->S < 1 || sd->H < 1 || sd->F != 13) return WGNN_ERR_SHAPE;
+  }
   if ((int64_t)(sd->n - 1) * sd->stride + sd->T > (int64_t)sd->rows) return WGNN_ERR_SHAPE;
   if (sd->math != WGNN_MATH_F32 || sd->io != WGNN_IO_F32 || sd->adj_format != WGNN_ADJ_DENSE || sd->S > 64 ||
       !gru_shape_supported(sd->H))
@@ -66,14 +121,78 @@ bool complete(const wgnn_grads* g) {
   return all8(v);
 }
 
+int launch_starts_check(const wgnn_series_dims* sd, const int* starts, void* workspace, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  PROF_LAUNCH("series_starts_check_kernel", 0.0, 4.0 * sd->n, st,
+              hipLaunchKernelGGL(series_starts_check_kernel, dim3((unsigned)cdiv_i(sd->n, 256)), dim3(256), 0, st, starts, sd->n,
+                                 sd->rows - sd->T, (unsigned*)workspace));
+  WGNN_CHECK_LAUNCH();
+  return WGNN_OK;
+}
+
+// at: the table entry points (starts is then required, and checked on the device ahead of everything else)
 int forward(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, float* Y, float* last,
-            float wind_min, float wind_max, void* stash, void* workspace, size_t workspace_bytes, void* stream) {
+            float wind_min, float wind_max, void* stash, void* workspace, size_t workspace_bytes, void* stream,
+            bool at = false, const int* starts = nullptr) {
   Plan pl;
-  const int rc = plan(sd, &pl);
+  int rc = plan(sd, &pl, at);
   if (rc != WGNN_OK) return rc;
-  if (!A || !Xs || !p || (!Y && !last) || !workspace || !complete(p)) return WGNN_ERR_NULL;
+  if (!A || !Xs || !p || (!Y && !last) || !workspace || !complete(p) || (at && !starts)) return WGNN_ERR_NULL;
   if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
-  return series_fwd(&pl.front, &pl.rec, sd->stride, A, Xs, p, Y, last, wind_min, wind_max, stash, workspace, pl.sp, stream);
+  if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
+  return series_fwd(&pl.front, &pl.rec, sd->stride, A, Xs, p, Y, last, wind_min, wind_max, stash, workspace, pl.sp, stream,
+                    starts);
+}
+
+int backward(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, const float* Y, const float* dY,
+             const void* stash, const wgnn_grads* grads, void* workspace, size_t workspace_bytes, void* stream, bool at = false,
+             const int* starts = nullptr) {
+  Plan pl;
+  int rc = plan(sd, &pl, at);
+  if (rc != WGNN_OK) return rc;
+  if (!A || !Xs || !p || !Y || !dY || !stash || !grads || !workspace || !complete(p) || !complete(grads) || (at && !starts))
+    return WGNN_ERR_NULL;
+  if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
+  if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
+  return series_bwd(&pl.front, &pl.rec, sd->stride, A, Xs, p, Y, dY, stash, grads, workspace, pl.sp, stream, starts);
+}
+
+// the label rows a call needs: up to the last row a window covers -- any row of the series, for a table
+bool labels_fit(const wgnn_series_dims* sd, bool at, int64_t ls_rows) {
+  const int64_t need = at ? (int64_t)sd->rows : (int64_t)(sd->n - 1) * sd->stride + sd->T;
+  return ls_rows >= need && ls_rows * sd->H < (1ll << 31);
+}
+
+int forward_loss(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, const float* Ls,
+                 int64_t ls_rows, float* Y, void* stash, void* loss_buf, void* workspace, size_t workspace_bytes, void* stream,
+                 bool at = false, const int* starts = nullptr) {
+  if (sd && !Y) return WGNN_ERR_NULL;      // before the dims, as in wgnn_series_fwd
+  Plan pl;
+  int rc = plan(sd, &pl, at);
+  if (rc != WGNN_OK) return rc;
+  if (!A || !Xs || !p || !Ls || !loss_buf || !workspace || !complete(p) || (at && !starts)) return WGNN_ERR_NULL;
+  if (!labels_fit(sd, at, ls_rows)) return WGNN_ERR_SHAPE;
+  if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
+  if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
+  return series_fwd_loss(&pl.front, &pl.rec, sd->stride, A, Xs, p, Ls, ls_rows, Y, stash, (float*)loss_buf, workspace, pl.sp,
+                         stream, starts);
+}
+
+int backward_mse(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, const float* Y,
+                 const float* Ls, int64_t ls_rows, float grad_scale, const void* stash, const void* loss_buf, float* loss,
+                 const wgnn_grads* grads, void* workspace, size_t workspace_bytes, void* stream, bool at = false,
+                 const int* starts = nullptr) {
+  Plan pl;
+  int rc = plan(sd, &pl, at);
+  if (rc != WGNN_OK) return rc;
+  if (!A || !Xs || !p || !Y || !Ls || !stash || !loss_buf || !loss || !grads || !workspace || !complete(p) || !complete(grads) ||
+      (at && !starts))
+    return WGNN_ERR_NULL;
+  if (!labels_fit(sd, at, ls_rows) || !std::isfinite(grad_scale) || !(grad_scale > 0.f)) return WGNN_ERR_SHAPE;
+  if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
+  if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
+  return series_bwd_mse(&pl.front, &pl.rec, sd->stride, A, Xs, p, Y, Ls, ls_rows, grad_scale, stash, (const float*)loss_buf,
+                        loss, grads, workspace, pl.sp, stream, starts);
 }
 
 }  // namespace
@@ -84,6 +203,18 @@ int launch_series_fold(const float* dGI, int n, int T, int stride, int rows, int
   const int terms = cdiv_i(T, stride);
   PROF_LAUNCH("series_fold_kernel", (double)items * 4 * terms, 4.0 * items * 4 * (terms + 1), st,
               hipLaunchKernelGGL(series_fold_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, dGI, n, T, stride,
+                                 rows, G3, ld, dGIs));
+  WGNN_CHECK_LAUNCH();
+  return WGNN_OK;
+}
+
+int launch_series_fold_at(const float* dGI, const int* starts, int n, int T, int rows, int G3, int ld, float* dGIs,
+                          hipStream_t st) {
+  if (ld % 4 != 0 || G3 > ld || !starts) return WGNN_ERR_SHAPE;
+  const size_t items = (size_t)rows * (ld / 4);
+  const double terms = (double)n * T / rows;      // mean coverage of an hour
+  PROF_LAUNCH("series_fold_at_kernel", (double)items * 4 * terms, 4.0 * items * 4 * (terms + 1), st,
+              hipLaunchKernelGGL(series_fold_at_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, dGI, starts, n, T,
                                  rows, G3, ld, dGIs));
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;
@@ -118,12 +249,7 @@ int wgnn_series_fwd_last(const wgnn_series_dims* sd, const float* A, const float
 int wgnn_series_bwd(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, const float* Y,
                     const float* dY, const void* stash, const wgnn_grads* grads, void* workspace, size_t workspace_bytes,
                     void* stream) {
-  Plan pl;
-  const int rc = plan(sd, &pl);
-  if (rc != WGNN_OK) return rc;
-  if (!A || !Xs || !p || !Y || !dY || !stash || !grads || !workspace || !complete(p) || !complete(grads)) return WGNN_ERR_NULL;
-  if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
-  return series_bwd(&pl.front, &pl.rec, sd->stride, A, Xs, p, Y, dY, stash, grads, workspace, pl.sp, stream);
+  return backward(sd, A, Xs, p, Y, dY, stash, grads, workspace, workspace_bytes, stream);
 }
 
 // ---- include/windgnn_series_train.h ----
@@ -137,36 +263,74 @@ size_t wgnn_series_loss_bytes(const wgnn_series_dims* sd) {
 int wgnn_series_fwd_loss(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, const float* Ls,
                          int64_t ls_rows, float* Y, void* stash, void* loss_buf, void* workspace, size_t workspace_bytes,
                          void* stream) {
-  if (sd && !Y) return WGNN_ERR_NULL;      // before the dims, as in wgnn_series_fwd
-  Plan pl;
-  const int rc = plan(sd, &pl);
-  if (rc != WGNN_OK) return rc;
-  if (!A || !Xs || !p || !Ls || !loss_buf || !workspace || !complete(p)) return WGNN_ERR_NULL;
-  if (ls_rows < (int64_t)(sd->n - 1) * sd->stride + sd->T || ls_rows * sd->H >= (1ll << 31)) return WGNN_ERR_SHAPE;
-  if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
-  return series_fwd_loss(&pl.front, &pl.rec, sd->stride, A, Xs, p, Ls, ls_rows, Y, stash, (float*)loss_buf, workspace, pl.sp,
-                         stream);
+  return forward_loss(sd, A, Xs, p, Ls, ls_rows, Y, stash, loss_buf, workspace, workspace_bytes, stream);
 }
 
 int wgnn_series_bwd_mse(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, const float* Y,
                         const float* Ls, int64_t ls_rows, float grad_scale, const void* stash, const void* loss_buf, float* loss,
                         const wgnn_grads* grads, void* workspace, size_t workspace_bytes, void* stream) {
-  Plan pl;
-  const int rc = plan(sd, &pl);
-  if (rc != WGNN_OK) return rc;
-  if (!A || !Xs || !p || !Y || !Ls || !stash || !loss_buf || !loss || !grads || !workspace || !complete(p) || !complete(grads))
-    return WGNN_ERR_NULL;
-  if (ls_rows < (int64_t)(sd->n - 1) * sd->stride + sd->T || ls_rows * sd->H >= (1ll << 31) || !std::isfinite(grad_scale) ||
-      !(grad_scale > 0.f))
-    return WGNN_ERR_SHAPE;
-  if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
-  return series_bwd_mse(&pl.front, &pl.rec, sd->stride, A, Xs, p, Y, Ls, ls_rows, grad_scale, stash, (const float*)loss_buf,
-                        loss, grads, workspace, pl.sp, stream);
+  return backward_mse(sd, A, Xs, p, Y, Ls, ls_rows, grad_scale, stash, loss_buf, loss, grads, workspace, workspace_bytes, stream);
 }
 
 size_t wgnn_series_status_offset(const wgnn_series_dims* sd) {
   Plan pl;
   return plan(sd, &pl) == WGNN_OK ? sizeof(float) * pl.sp.ws_front : 0;
+}
+
+// ---- include/windgnn_series_at.h ----
+int wgnn_series_at_version(void) { return WGNN_SERIES_AT_VERSION; }
+
+size_t wgnn_series_at_workspace_bytes(const wgnn_series_dims* sd) {
+  Plan pl;
+  return plan(sd, &pl, true) == WGNN_OK ? sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec) : 0;
+}
+
+size_t wgnn_series_at_stash_bytes(const wgnn_series_dims* sd) {
+  Plan pl;
+  return plan(sd, &pl, true) == WGNN_OK ? sizeof(float) * (pl.sp.st_front + pl.sp.st_rec) : 0;
+}
+
+size_t wgnn_series_at_loss_bytes(const wgnn_series_dims* sd) {
+  Plan pl;
+  return plan(sd, &pl, true) == WGNN_OK ? sizeof(float) * series_loss_floats(sd->n) : 0;
+}
+
+size_t wgnn_series_at_status_offset(const wgnn_series_dims* sd) {
+  Plan pl;
+  return plan(sd, &pl, true) == WGNN_OK ? sizeof(float) * pl.sp.ws_front : 0;
+}
+
+int wgnn_series_fwd_at(const wgnn_series_dims* sd, const float* A, const float* Xs, const int32_t* starts, const wgnn_params* p,
+                       float* Y, void* stash, void* workspace, size_t workspace_bytes, void* stream) {
+  if (sd && !Y) return WGNN_ERR_NULL;
+  return forward(sd, A, Xs, p, Y, nullptr, 0.f, 1.f, stash, workspace, workspace_bytes, stream, true, starts);
+}
+
+int wgnn_series_fwd_last_at(const wgnn_series_dims* sd, const float* A, const float* Xs, const int32_t* starts,
+                            const wgnn_params* p, float wind_min, float wind_max, float* last, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  if (sd && !last) return WGNN_ERR_NULL;
+  return forward(sd, A, Xs, p, nullptr, last, wind_min, wind_max, nullptr, workspace, workspace_bytes, stream, true, starts);
+}
+
+int wgnn_series_bwd_at(const wgnn_series_dims* sd, const float* A, const float* Xs, const int32_t* starts, const wgnn_params* p,
+                       const float* Y, const float* dY, const void* stash, const wgnn_grads* grads, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  return backward(sd, A, Xs, p, Y, dY, stash, grads, workspace, workspace_bytes, stream, true, starts);
+}
+
+int wgnn_series_fwd_loss_at(const wgnn_series_dims* sd, const float* A, const float* Xs, const int32_t* starts,
+                            const wgnn_params* p, const float* Ls, int64_t ls_rows, float* Y, void* stash, void* loss_buf,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  return forward_loss(sd, A, Xs, p, Ls, ls_rows, Y, stash, loss_buf, workspace, workspace_bytes, stream, true, starts);
+}
+
+int wgnn_series_bwd_mse_at(const wgnn_series_dims* sd, const float* A, const float* Xs, const int32_t* starts,
+                           const wgnn_params* p, const float* Y, const float* Ls, int64_t ls_rows, float grad_scale,
+                           const void* stash, const void* loss_buf, float* loss, const wgnn_grads* grads, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  return backward_mse(sd, A, Xs, p, Y, Ls, ls_rows, grad_scale, stash, loss_buf, loss, grads, workspace, workspace_bytes, stream,
+                      true, starts);
 }
 
 }  // extern "C"

@@ -133,7 +133,10 @@ def _workspace(d, device, refused=None):
     """(workspace, bytes to pass) of the dims struct `d` (wgnn_dims or wgnn_series_dims) on `device`: one size query of the
     library per call, then this stream's shared buffer, grown if need be.  The library sizes nothing (0) for dims it refuses:
     with `refused` (the call, for the message) that is raised here with its reason; without, the entry point reports it."""
-    ws_bytes = getattr(_lib.load(), _WORKSPACE_BYTES[type(d)])(C.byref(d))
+    query = _WORKSPACE_BYTES[type(d)]
+    if isinstance(d, _lib.SeriesDims) and d.stride == 0:       # a table of starts: include/windgnn_series_at.h
+        query = "wgnn_series_at_workspace_bytes"
+    ws_bytes = getattr(_lib.load(), query)(C.byref(d))
     if ws_bytes == 0 and refused is not None:
         _lib.check(-5 if d.F == 13 else -2, refused)
     return _Workspace.get(device, ws_bytes), ws_bytes
@@ -163,7 +166,10 @@ _STATUS_TEXT = {1: "a graph-convolution pre-activation left fp16's range (|x| > 
                 2: "a GRU weight or bias lies outside fp16's range",
                 4: "a gradient came out inf / NaN",
                 8: "wgnn_bwd_mse_part(part | 8) ran on a stash whose last forward was not wgnn_fwd_loss: the loss is NaN "
-                   "and the gradients are not to be used"}
+                   "and the gradients are not to be used",
+                16: "a table of window starts (series mode, starts=) holds an entry outside [0, rows - seq_len] or is not "
+                    "non-decreasing: the results of that call are not to be used"}
+_STATUS_FP16_BITS = 1 | 2      # the reports that come from fp16's range: only they get the advice about the math modes
 
 
 def check_range_status(device=None) -> None:
@@ -177,10 +183,10 @@ def check_range_status(device=None) -> None:
         if word:
             buf[:4].zero_()
             what = "; ".join(t for b, t in _STATUS_TEXT.items() if word & b)
-            raise RuntimeError("windgnn_amd: %s (status %d: %s). The f16x3 / f16 math modes hold activations and "
-                               "weights as fp16 planes: normalise the inputs (the reference min-max-normalises "
-                               "every feature to [0, 1]) or use math='f32'."
-                               % (_lib.load().wgnn_strerror(-7).decode(), word, what))
+            advice = (" The f16x3 / f16 math modes hold activations and weights as fp16 planes: normalise the inputs (the "
+                      "reference min-max-normalises every feature to [0, 1]) or use math='f32'."
+                      if word & _STATUS_FP16_BITS else "")
+            raise RuntimeError("windgnn_amd: %s (status %d: %s).%s" % (_lib.load().wgnn_strerror(-7).decode(), word, what, advice))
 
 
 def _forward_setup(A, X, params: Sequence[torch.Tensor], math, labels=None, h0=None, h_n=None, B=None):

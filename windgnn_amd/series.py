@@ -5,12 +5,16 @@ Window w = 0 .. n-1 covers rows w*stride .. w*stride + T - 1 of `series` [rows, 
 those of GCN_GRU.forward on the materialised windows (make_windows(starts=...)).  What depends on the hour alone -- both graph
 convolutions and the GRU's input projection -- runs once per hour instead of once per window and hour.
 
+With `starts` (include/windgnn_series_at.h) the windows begin at a table of rows instead of w*stride: a series with outages
+(segment_starts), a hold-out at window level, a shuffled mini-batch.  The front end still runs on every row of the series passed.
+
 Exact fp32 with a dense adjacency (S <= 64) and H <= 128 only; everything else raises and names the materialised path."""
 from __future__ import annotations
 
 import ctypes as C
 from typing import List, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -42,8 +46,100 @@ def series_coverage(rows: int, seq_len: int, stride: int, n: int) -> List[Tuple[
     return out
 
 
-def _series_setup(A, series, seq_len: int, stride: int, params: Sequence[torch.Tensor], math: int, n_windows=None):
-    """Everything a series call checks and sizes before it launches: (adjacency, dims, workspace, workspace bytes)."""
+def segment_starts(segments, seq_len: int, stride: int = 1, horizon: int = 0) -> List[int]:
+    """The ascending starts of every window of seq_len rows that, together with `horizon` further label hours, lies inside ONE
+    of `segments`, a list of (first_row, n_rows) clean stretches of a series: per segment first_row, first_row + stride, ...
+    while start + seq_len + horizon <= first_row + n_rows.  A segment shorter than seq_len + horizon gives none; segments that
+    overlap give the windows of each (duplicates included).  Plain Python, no device."""
+    if seq_len < 1 or stride < 1 or horizon < 0:
+        raise ValueError("segment_starts: seq_len and stride must be >= 1 and horizon >= 0, got %r, %r and %r"
+                         % (seq_len, stride, horizon))
+    out = []
+    for first, count in segments:
+        first, count = int(first), int(count)
+        if first < 0 or count < 0:
+            raise ValueError("segment_starts: a segment is (first_row >= 0, n_rows >= 0), got (%d, %d)" % (first, count))
+        out.extend(range(first, first + count - seq_len - horizon + 1, stride))
+    return sorted(out)
+
+
+def starts_coverage(starts, seq_len: int, rows: int) -> np.ndarray:
+    """[rows, 2] int64: per series row tau the half-open index range [lo, hi) of the windows of the NON-DECREASING table
+    `starts` that cover it -- tau - seq_len < starts[w] <= tau -- as the fold kernel of the backward finds it (two binary
+    searches); lo == hi: no window covers the row and its gate gradient is zero.  numpy, no device."""
+    st = np.asarray(starts, dtype=np.int64).reshape(-1)
+    if seq_len < 1 or rows < seq_len or (st.size and (np.any(np.diff(st) < 0) or st[0] < 0 or st[-1] > rows - seq_len)):
+        raise ValueError("starts_coverage: starts must be non-decreasing within [0, rows - seq_len = %d]" % (rows - seq_len))
+    tau = np.arange(rows, dtype=np.int64)
+    return np.stack([np.searchsorted(st, tau - seq_len, side="right"), np.searchsorted(st, tau, side="right")], axis=1)
+
+
+def _starts_table(starts, rows: int, seq_len: int, device, who: str, ordered: bool):
+    """`starts` as the int32 device table the _at entry points take.  A list / numpy array / CPU tensor is checked here, before
+    the upload (integer dtype, one dimension, every entry in [0, rows - seq_len], and non-decreasing where `ordered`):
+    ValueError.  A device tensor is taken as it is -- its values are checked by the kernel (WGNN_STATUS_WINDOW_START, raised
+    by check_range_status) so that no call synchronises."""
+    if rows < seq_len:
+        raise RuntimeError("windgnn_amd: no window of %d rows fits into a series of %d rows" % (seq_len, rows))
+    if isinstance(starts, torch.Tensor) and starts.device.type != "cpu":
+        if starts.dtype not in (torch.int32, torch.int64) or starts.dim() != 1:
+            raise ValueError("%s: starts must be a 1-D int32 / int64 tensor, got %s %s" % (who, starts.dtype, tuple(starts.shape)))
+        if starts.device != device:
+            raise ValueError("%s: starts is on %s, the series on %s" % (who, starts.device, device))
+        return starts.to(torch.int32).contiguous()
+    host = starts.numpy() if isinstance(starts, torch.Tensor) else np.asarray(starts)
+    if host.size == 0:
+        host = host.astype(np.int64)
+    if host.dtype.kind not in "iu" or host.ndim != 1:
+        raise ValueError("%s: starts must be a 1-D sequence of integers, got dtype %s, shape %s" % (who, host.dtype, host.shape))
+    host = host.astype(np.int64)
+    bad = np.nonzero((host < 0) | (host > rows - seq_len))[0]
+    if bad.size:
+        raise ValueError("%s: starts[%d] = %d, but a window of %d rows in a series of %d rows starts at 0 .. %d"
+                         % (who, bad[0], host[bad[0]], seq_len, rows, rows - seq_len))
+    if ordered and np.any(np.diff(host) < 0):
+        w = int(np.nonzero(np.diff(host) < 0)[0][0]) + 1
+        raise ValueError("%s: starts must be non-decreasing here, but starts[%d] = %d < starts[%d] = %d (GCN_GRU.forward_series "
+                         "and TrainStep.step_series take any order)" % (who, w, host[w], w - 1, host[w - 1]))
+    return torch.from_numpy(host.astype(np.int32)).to(device)
+
+
+def sorted_starts(starts, rows: int, seq_len: int, device, who: str):
+    """(table, inverse): `starts` in any order as the sorted int32 device table, and the index tensor that takes rows of the
+    sorted call's Y back into the caller's order (None: the order was the caller's already).  A host table is sorted on the host;
+    a device table on the device, without a synchronisation."""
+    if isinstance(starts, torch.Tensor) and starts.device.type != "cpu":
+        table = _starts_table(starts, rows, seq_len, device, who, ordered=False)
+        table, order = torch.sort(table, stable=True)
+        inverse = torch.empty_like(order)
+        inverse[order] = torch.arange(order.numel(), device=device)
+        return table, inverse
+    table = _starts_table(starts, rows, seq_len, "cpu", who, ordered=False)
+    table, order = torch.sort(table, stable=True)
+    if torch.equal(order, torch.arange(order.numel())):
+        return table.to(device), None
+    inverse = torch.empty_like(order)
+    inverse[order] = torch.arange(order.numel())
+    return table.to(device), inverse.to(device)
+
+
+def _no_stride_with_starts(who: str, stride, starts, n_windows=None) -> None:
+    if starts is not None and stride not in (None, 0):
+        raise ValueError("%s: pass stride= or starts=, not both (got stride=%r with a table of starts)" % (who, stride))
+    if starts is not None and n_windows is not None:
+        raise ValueError("%s: n_windows= belongs to stride=; with starts= the table's length is the window count" % who)
+
+
+def _fn(lib, name: str, sd):
+    """The entry point `name` of the family sd belongs to: wgnn_series_<name>, or its _at form for a table (stride = 0)."""
+    if sd.stride != 0:
+        return getattr(lib, "wgnn_series_" + name)
+    return getattr(lib, ("wgnn_series_at_%s" if name.endswith("_bytes") else "wgnn_series_%s_at") % name)
+
+
+def _series_setup(A, series, seq_len: int, stride: int, params: Sequence[torch.Tensor], math: int, n_windows=None, starts=None):
+    """Everything a series call checks and sizes before it launches: (adjacency, dims, workspace, workspace bytes); with
+    `starts` also the int32 device table (dims.stride = 0, dims.n = its length), as a fifth result."""
     if hasattr(A, "blob"):
         raise RuntimeError("windgnn_amd: series mode takes a dense adjacency (S <= 64), not a CsrAdjacency: " + _MATERIALISED)
     if math != _lib.MATH_F32:
@@ -55,6 +151,18 @@ def _series_setup(A, series, seq_len: int, stride: int, params: Sequence[torch.T
     if series.dim() != 3:
         raise RuntimeError("windgnn_amd: series must be [rows, S, 13], got %s" % (tuple(series.shape),))
     rows, S, F = series.shape
+    if starts is not None:
+        _no_stride_with_starts("windgnn_amd series mode", stride, starts, n_windows)
+        table = _starts_table(starts, rows, seq_len, series.device, "windgnn_amd series mode", ordered=True)
+        if table.numel() < 1:
+            raise RuntimeError("windgnn_amd: the table of starts is empty: a series call needs at least one window")
+        A, fmt, nnz = _adj(A, S)
+        H = params[5].shape[1]
+        sd = _lib.SeriesDims(rows, seq_len, 0, table.numel(), S, F, H, math, fmt, nnz, _lib.IO_F32)
+        ws, ws_bytes = _workspace(sd, series.device,
+                                  refused="wgnn_series_at_workspace_bytes(rows=%d,T=%d,n=%d,S=%d,F=%d,H=%d) [%s]"
+                                  % (rows, seq_len, table.numel(), S, F, H, _MATERIALISED))
+        return A, sd, ws, ws_bytes, table
     fit = n_series_windows(rows, seq_len, stride)
     if fit < 1:
         raise RuntimeError("windgnn_amd: no window of %d rows fits into a series of %d rows" % (seq_len, rows))
@@ -71,34 +179,57 @@ def _series_setup(A, series, seq_len: int, stride: int, params: Sequence[torch.T
     return A, sd, ws, ws_bytes
 
 
-def series_forward_raw(A, series, seq_len, stride, params, math=_lib.MATH_F32, want_stash=True, n_windows=None):
-    """Y [n, T, H], stash, dims = wgnn_series_fwd(...).  n_windows: the first that many windows (default: all that fit)."""
+def _table_arg(sd, starts=None):
+    """The `starts` argument of an _at entry point as a tuple to splice in after Xs (empty for the strided family)."""
+    if sd.stride != 0:
+        if starts is not None:
+            raise ValueError("windgnn_amd: these dims have stride %d: they take no table of starts" % sd.stride)
+        return ()
+    if (starts is None or starts.dtype != torch.int32 or starts.dim() != 1 or starts.numel() != sd.n
+            or not starts.is_contiguous()):
+        raise ValueError("windgnn_amd: dims with stride = 0 take starts=, the contiguous int32 device table of n = %d entries "
+                         "the forward was given" % sd.n)
+    if not starts.is_cuda:
+        raise RuntimeError("windgnn_amd runs on an MI355X (HIP) only: the table of starts is a %s tensor" % starts.device)
+    return (_ptr(starts),)
+
+
+def series_forward_raw(A, series, seq_len, stride, params, math=_lib.MATH_F32, want_stash=True, n_windows=None, starts=None):
+    """Y [n, T, H], stash, dims = wgnn_series_fwd(...).  n_windows: the first that many windows (default: all that fit).
+    starts (with stride None): a NON-DECREASING table of window starts -- wgnn_series_fwd_at; a fourth result is then the int32
+    device table to hand to series_backward_raw."""
     lib = _lib.load()
-    A, sd, ws, ws_bytes = _series_setup(A, series, seq_len, stride, params, math, n_windows)
-    stash = (torch.empty(lib.wgnn_series_stash_bytes(C.byref(sd)), dtype=torch.uint8, device=series.device)
+    A, sd, ws, ws_bytes, *table = _series_setup(A, series, seq_len, stride, params, math, n_windows, starts)
+    stash = (torch.empty(_fn(lib, "stash_bytes", sd)(C.byref(sd)), dtype=torch.uint8, device=series.device)
              if want_stash else None)
     Y = torch.empty(sd.n, sd.T, sd.H, dtype=torch.float32, device=series.device)
     ps = _params_struct(_lib.Params, params)
-    rc = lib.wgnn_series_fwd(C.byref(sd), _ptr(A), _ptr(series), C.byref(ps), _ptr(Y), _stash_ptr(stash), _ptr(ws), ws_bytes,
-                             _stream())
-    _lib.check(rc, "wgnn_series_fwd")
-    return Y, stash, sd
+    at = _table_arg(sd, *table)
+    rc = _fn(lib, "fwd", sd)(C.byref(sd), _ptr(A), _ptr(series), *at, C.byref(ps), _ptr(Y), _stash_ptr(stash), _ptr(ws),
+                             ws_bytes, _stream())
+    _lib.check(rc, "wgnn_series_fwd_at" if at else "wgnn_series_fwd")
+    return (Y, stash, sd, *table)
 
 
-def series_backward_raw(sd, A, series, params, Y, dY, stash, grads: Sequence[torch.Tensor]) -> None:
-    """wgnn_series_bwd: the 8 gradients of sum(Y * dY), summed over all windows, into `grads` (overwritten)."""
+def series_backward_raw(sd, A, series, params, Y, dY, stash, grads: Sequence[torch.Tensor], starts=None) -> None:
+    """wgnn_series_bwd: the 8 gradients of sum(Y * dY), summed over all windows, into `grads` (overwritten).  starts: the
+    forward's table (dims with stride = 0: wgnn_series_bwd_at)."""
     lib = _lib.load()
     _require_contiguous(series=series, Y=Y, dY=dY, adj_matrix=A, grads=grads, params=params)
+    at = _table_arg(sd, starts)
     ws, ws_bytes = _workspace(sd, series.device)
     ps = _params_struct(_lib.Params, params)
     gs = _params_struct(_lib.Grads, grads)
-    rc = lib.wgnn_series_bwd(C.byref(sd), _ptr(A), _ptr(series), C.byref(ps), _ptr(Y), _ptr(dY), _stash_ptr(stash), C.byref(gs),
-                             _ptr(ws), ws_bytes, _stream())
-    _lib.check(rc, "wgnn_series_bwd")
+    rc = _fn(lib, "bwd", sd)(C.byref(sd), _ptr(A), _ptr(series), *at, C.byref(ps), _ptr(Y), _ptr(dY), _stash_ptr(stash),
+                             C.byref(gs), _ptr(ws), ws_bytes, _stream())
+    _lib.check(rc, "wgnn_series_bwd_at" if at else "wgnn_series_bwd")
 
 
 def _check_label_series(Ls, sd) -> None:
     """Ls as series_labels returns it: contiguous [rows, H] fp32 on the GPU with a row for every hour a window covers."""
+    if sd.stride == 0 and (Ls.dim() != 2 or Ls.shape[1] != sd.H or Ls.shape[0] < sd.rows):
+        raise RuntimeError("windgnn_amd: with a table of starts the label series Ls must be [rows >= the series' %d, H = %d] (a "
+                           "window may start at any row up to rows - seq_len), got %s" % (sd.rows, sd.H, tuple(Ls.shape)))
     need = (sd.n - 1) * sd.stride + sd.T
     if Ls.dim() != 2 or Ls.shape[1] != sd.H or Ls.shape[0] < need:
         raise RuntimeError("windgnn_amd: the label series Ls must be [rows >= (n - 1) * stride + seq_len = %d, H = %d] (what "
@@ -108,57 +239,63 @@ def _check_label_series(Ls, sd) -> None:
     _require_contiguous(Ls=Ls)
 
 
-def series_forward_loss_raw(A, series, Ls, seq_len, stride, params, math=_lib.MATH_F32, n_windows=None, prepared=None):
+def series_forward_loss_raw(A, series, Ls, seq_len, stride, params, math=_lib.MATH_F32, n_windows=None, prepared=None,
+                            starts=None):
     """Y [n, T, H], stash, loss_buf, dims = wgnn_series_fwd_loss(...): series_forward_raw with the MSE statistics of (Y - labels)
     left in loss_buf for series_backward_mse_raw.  Ls [rows - 3, H]: the label SERIES (series_labels' first result); window w,
-    step t reads its row w * stride + t."""
+    step t reads its row w * stride + t.  starts (with stride None): a NON-DECREASING table, the row is starts[w] + t, Ls needs
+    the series' rows, and a fifth result is the int32 device table (wgnn_series_fwd_loss_at)."""
     lib = _lib.load()
-    A, sd, ws, ws_bytes = _series_setup(A, series, seq_len, stride, params, math, n_windows)
+    A, sd, ws, ws_bytes, *table = _series_setup(A, series, seq_len, stride, params, math, n_windows, starts)
     _check_label_series(Ls, sd)
-    stash = torch.empty(lib.wgnn_series_stash_bytes(C.byref(sd)), dtype=torch.uint8, device=series.device)
-    loss_buf = torch.empty(lib.wgnn_series_loss_bytes(C.byref(sd)) // 4, dtype=torch.float32, device=series.device)
+    stash = torch.empty(_fn(lib, "stash_bytes", sd)(C.byref(sd)), dtype=torch.uint8, device=series.device)
+    loss_buf = torch.empty(_fn(lib, "loss_bytes", sd)(C.byref(sd)) // 4, dtype=torch.float32, device=series.device)
     Y = torch.empty(sd.n, sd.T, sd.H, dtype=torch.float32, device=series.device)
     ps = _params_struct(_lib.Params, params, prepared)
-    rc = lib.wgnn_series_fwd_loss(C.byref(sd), _ptr(A), _ptr(series), C.byref(ps), _ptr(Ls), Ls.shape[0], _ptr(Y),
+    at = _table_arg(sd, *table)
+    rc = _fn(lib, "fwd_loss", sd)(C.byref(sd), _ptr(A), _ptr(series), *at, C.byref(ps), _ptr(Ls), Ls.shape[0], _ptr(Y),
                                   _stash_ptr(stash), _ptr(loss_buf), _ptr(ws), ws_bytes, _stream())
-    _lib.check(rc, "wgnn_series_fwd_loss")
-    return Y, stash, loss_buf, sd
+    _lib.check(rc, "wgnn_series_fwd_loss_at" if at else "wgnn_series_fwd_loss")
+    return (Y, stash, loss_buf, sd, *table)
 
 
 def series_backward_mse_raw(sd, A, series, params, Y, Ls, stash, loss_buf, grads: Sequence[torch.Tensor], loss: torch.Tensor,
-                            grad_scale: float = 1.0, prepared=None) -> None:
+                            grad_scale: float = 1.0, prepared=None, starts=None) -> None:
     """wgnn_series_bwd_mse: the 8 gradients of grad_scale * mean((Y - labels)^2) into `grads` (overwritten, final) and the
     unweighted mean into `loss` (a 0-dim fp32 device tensor), without a dY tensor.  Y, stash, loss_buf: as
-    series_forward_loss_raw returned them for the same inputs."""
+    series_forward_loss_raw returned them for the same inputs (starts: its table, for dims with stride = 0)."""
     lib = _lib.load()
     _check_label_series(Ls, sd)
     _require_gpu(loss, loss_buf)
     _require_contiguous(series=series, Y=Y, adj_matrix=A, loss_buf=loss_buf, grads=grads, params=params)
-    if loss_buf.numel() * 4 < lib.wgnn_series_loss_bytes(C.byref(sd)):
-        raise RuntimeError("windgnn_amd: loss_buf holds %d bytes, wgnn_series_loss_bytes says %d"
-                           % (loss_buf.numel() * 4, lib.wgnn_series_loss_bytes(C.byref(sd))))
+    at = _table_arg(sd, starts)
+    need = _fn(lib, "loss_bytes", sd)(C.byref(sd))
+    if loss_buf.numel() * 4 < need:
+        raise RuntimeError("windgnn_amd: loss_buf holds %d bytes, wgnn_series_loss_bytes says %d" % (loss_buf.numel() * 4, need))
     ws, ws_bytes = _workspace(sd, series.device)
     ps = _params_struct(_lib.Params, params, prepared)
     gs = _params_struct(_lib.Grads, grads)
-    rc = lib.wgnn_series_bwd_mse(C.byref(sd), _ptr(A), _ptr(series), C.byref(ps), _ptr(Y), _ptr(Ls), Ls.shape[0],
-                                 float(grad_scale), _stash_ptr(stash), _ptr(loss_buf), _ptr(loss), C.byref(gs), _ptr(ws), ws_bytes,
-                                 _stream())
-    _lib.check(rc, "wgnn_series_bwd_mse")
+    rc = _fn(lib, "bwd_mse", sd)(C.byref(sd), _ptr(A), _ptr(series), *at, C.byref(ps), _ptr(Y), _ptr(Ls), Ls.shape[0],
+                                 float(grad_scale), _stash_ptr(stash), _ptr(loss_buf), _ptr(loss), C.byref(gs), _ptr(ws),
+                                 ws_bytes, _stream())
+    _lib.check(rc, "wgnn_series_bwd_mse_at" if at else "wgnn_series_bwd_mse")
 
 
 class SeriesFunction(torch.autograd.Function):
     """Y [n, T, H] = GCN_GRU on every window of the series.  Gradients flow to the 8 parameters only, as in GCNGRUFunction."""
 
     @staticmethod
-    def forward(ctx, A, series, seq_len, stride, n_windows, math, *params):
+    def forward(ctx, A, series, seq_len, stride, n_windows, starts, math, *params):
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[0]:
             raise RuntimeError("windgnn_amd: series mode gives gradients for the 8 parameters only; a series / adj_matrix "
                                "with requires_grad=True is not supported (detach it)")
         series = series.contiguous()
         params = tuple(p.contiguous() for p in params)
-        need = any(ctx.needs_input_grad[6:])
-        Y, stash, sd = series_forward_raw(A, series, seq_len, stride, params, math, want_stash=need, n_windows=n_windows)
+        need = any(ctx.needs_input_grad[7:])
+        Y, stash, sd, *table = series_forward_raw(A, series, seq_len, stride, params, math, want_stash=need, n_windows=n_windows,
+                                                  starts=starts)
         ctx.sd = sd
+        ctx.table = table[0] if table else None      # (not a saved tensor: an index table, no gradient, never modified)
         ctx.save_for_backward(_adj(A)[0], series, Y, stash, *params)
         return Y
 
@@ -168,14 +305,17 @@ class SeriesFunction(torch.autograd.Function):
         if stash is None:
             raise RuntimeError("windgnn_amd: backward called but the forward ran without a stash")
         grads = _flat_grads(params, series.device)
-        series_backward_raw(ctx.sd, A, series, params, Y, dY.float().contiguous(), stash, grads)
-        return (None, None, None, None, None, None, *grads)
+        series_backward_raw(ctx.sd, A, series, params, Y, dY.float().contiguous(), stash, grads, starts=ctx.table)
+        return (None, None, None, None, None, None, None, *grads)
 
 
-def gcn_gru_series(A, series, seq_len: int, stride: int, params, math=_lib.MATH_F32, n_windows=None):
+def gcn_gru_series(A, series, seq_len: int, stride, params, math=_lib.MATH_F32, n_windows=None, starts=None):
     """Y [n, seq_len, H] for the first n = n_windows (default: all n_series_windows(rows, seq_len, stride)) windows of series
-    [rows, S, 13]."""
-    return SeriesFunction.apply(A, series, int(seq_len), int(stride), n_windows, math, *params)
+    [rows, S, 13]; or, with stride None and `starts` (NON-DECREASING; GCN_GRU.forward_series sorts), for the windows at those
+    rows."""
+    _no_stride_with_starts("gcn_gru_series", stride, starts, n_windows)
+    return SeriesFunction.apply(A, series, int(seq_len), None if starts is not None else int(stride), n_windows, starts, math,
+                                *params)
 
 
 def _require_fused(model, who: str) -> None:
@@ -186,21 +326,30 @@ def _require_fused(model, who: str) -> None:
 
 
 def forward_last_series(model, adj_matrix, series: torch.Tensor, seq_len: int, wind_min: float, wind_max: float,
-                        stride: int = 1, n_windows=None) -> torch.Tensor:
+                        stride: int = None, n_windows=None, starts=None) -> torch.Tensor:
     """The rolling backtest: [n, 3S] de-normalised forecasts, one per window, each from its own zero-state seq_len-hour
     window (wgnn_series_fwd_last; no Y is written).  The rows are what forward_last gives on the materialised windows and feed
-    evaluate.eval_accum as they are."""
+    evaluate.eval_accum as they are.  stride defaults to 1.  starts (instead of stride / n_windows): the windows at that table
+    of rows, in any order; row i of the result belongs to starts[i]."""
     lib = _lib.load()
     _require_fused(model, "forward_last_series")
+    _no_stride_with_starts("forward_last_series", stride, starts, n_windows)
     params = [p.detach().contiguous() for p in model.hot_path_parameters()]
     series = series.contiguous()
-    A, sd, ws, ws_bytes = _series_setup(adj_matrix, series, int(seq_len), int(stride), params, model.math, n_windows)
+    inverse = None
+    if starts is not None:
+        if series.dim() != 3:
+            raise RuntimeError("windgnn_amd: series must be [rows, S, 13], got %s" % (tuple(series.shape),))
+        starts, inverse = sorted_starts(starts, series.shape[0], int(seq_len), series.device, "forward_last_series")
+    A, sd, ws, ws_bytes, *table = _series_setup(adj_matrix, series, int(seq_len), None if starts is not None else
+                                                int(1 if stride is None else stride), params, model.math, n_windows, starts)
     out = torch.empty(sd.n, sd.H, dtype=torch.float32, device=series.device)
     ps = _params_struct(_lib.Params, params)
-    rc = lib.wgnn_series_fwd_last(C.byref(sd), _ptr(A), _ptr(series), C.byref(ps), float(wind_min), float(wind_max), _ptr(out),
-                                  _ptr(ws), ws_bytes, _stream())
-    _lib.check(rc, "wgnn_series_fwd_last")
-    return out
+    at = _table_arg(sd, *table)
+    rc = _fn(lib, "fwd_last", sd)(C.byref(sd), _ptr(A), _ptr(series), *at, C.byref(ps), float(wind_min), float(wind_max),
+                                  _ptr(out), _ptr(ws), ws_bytes, _stream())
+    _lib.check(rc, "wgnn_series_fwd_last_at" if at else "wgnn_series_fwd_last")
+    return out if inverse is None else out.index_select(0, inverse)
 
 
 def series_labels(feat: torch.Tensor, seq_len: int, stride: int = 1, n_windows: int = None):

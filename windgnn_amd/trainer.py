@@ -79,7 +79,8 @@ from .functional import (PARAM_ORDER, _forward_setup, _require_gpu, best_bytes, 
                          gcn_gru_backward_mse_raw, gcn_gru_forward_raw, gcn_gru_state_backward_raw, gcn_gru_state_forward_raw,
                          keep_best_args, keep_best_launch, mse_loss_grad, prepared_weights, refresh_prepared, rows_align)
 from .modules import GCN_GRU
-from .series import n_series_windows, series_backward_mse_raw, series_forward_loss_raw
+from .series import (_no_stride_with_starts, n_series_windows, series_backward_mse_raw, series_forward_loss_raw,
+                     sorted_starts)
 
 AUTO_GRAD_BLOCKS = 8                # grad_blocks="auto": row blocks per GRU weight ...
 AUTO_BLOCK_BYTES = 64 << 20         # ... from a gradient bucket of this size (smaller ones are latency-bound: one bucket)
@@ -591,16 +592,32 @@ class TrainStep:
             raise ValueError("windgnn_amd: TrainStep.step_series: seq_len and stride must be >= 1, got %r and %r"
                              % (seq_len, stride))
 
-    def _series_forward(self, A, series, Ls, seq_len, stride, n):
+    def _series_forward(self, A, series, Ls, seq_len, stride, n, starts=None):
         """The W_ih images, then wgnn_series_fwd_loss: (Y, stash, loss_buf, sd, d); d = the B-independent dims of the
-        tail, as in _empty_shard_step."""
+        tail, as in _empty_shard_step.  starts: the sorted device table instead of (stride, n) -- wgnn_series_fwd_loss_at."""
         _require_gpu(series, Ls, *self.p_views)      # before the images: nothing is launched on host memory
         S, H = series.shape[1], self.p_views[5].shape[1]
         d = _lib.Dims(1, seq_len, S, 13, H, _lib.MATH_F32, _lib.ADJ_DENSE, 0, _lib.IO_F32)
         self._ensure_images(lambda: d)
+        if starts is not None:
+            Y, stash, loss_buf, sd, _ = series_forward_loss_raw(A, series, Ls, seq_len, None, self.p_views, _lib.MATH_F32,
+                                                                prepared=self._prepared, starts=starts)
+            return Y, stash, loss_buf, sd, d
         Y, stash, loss_buf, sd = series_forward_loss_raw(A, series, Ls, seq_len, stride, self.p_views, _lib.MATH_F32,
                                                          n_windows=n, prepared=self._prepared)
         return Y, stash, loss_buf, sd, d
+
+    def _series_table(self, series, Ls, seq_len, stride, n_windows, starts):
+        """starts= of step_series / forward_backward_series: (sorted device table, inverse or None, n) with the label series
+        checked -- a window may start at any row, so Ls needs a row for every row of the series."""
+        _no_stride_with_starts("windgnn_amd: TrainStep.step_series", stride, starts, n_windows)
+        table, inverse = sorted_starts(starts, series.shape[0], seq_len, series.device, "windgnn_amd: TrainStep.step_series")
+        H = self.p_views[5].shape[1]
+        if table.numel() > 0 and (Ls.dim() != 2 or Ls.shape[1] != H or Ls.shape[0] < series.shape[0]):
+            raise RuntimeError("windgnn_amd: TrainStep.step_series: with starts= the label series Ls must be [rows >= the "
+                               "series' %d, H = %d] (series_labels(feat, ...)[0] of a feat 3 rows longer than the series), got %s"
+                               % (series.shape[0], H, tuple(Ls.shape)))
+        return table, inverse, table.numel()
 
     def _series_count(self, series, Ls, seq_len, stride, n_windows):
         """The window count of this call, with n_windows and Ls checked against it."""
@@ -617,43 +634,58 @@ class TrainStep:
                                "for TrainStep.step on materialised windows), got %s" % (need, H, tuple(Ls.shape)))
         return n
 
-    def forward_backward_series(self, A, series, Ls, seq_len, stride=1, n_windows=None):
+    def forward_backward_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, starts=None):
         """forward_backward on the first n_windows sliding windows of `series` [rows, S, 13] with the label series Ls
         [>= (n - 1) * stride + seq_len, H]: returns (loss, Y [n, seq_len, H]); the gradients land in the flat bucket, final (no
-        optimiser step).  `loss` is a view of the bucket's header word."""
-        seq_len, stride = int(seq_len), int(stride)
-        self._series_refusals(A, series, seq_len, stride)
+        optimiser step).  `loss` is a view of the bucket's header word.  starts: as in step_series."""
+        seq_len, table, inverse = int(seq_len), None, None
+        self._series_refusals(A, series, seq_len, 1 if stride is None else int(stride))
         series, Ls = series.contiguous(), Ls.contiguous()
-        n = self._series_count(series, Ls, seq_len, stride, n_windows)
+        if starts is not None:
+            table, inverse, n = self._series_table(series, Ls, seq_len, stride, n_windows, starts)
+        else:
+            stride = 1 if stride is None else int(stride)
+            n = self._series_count(series, Ls, seq_len, stride, n_windows)
         if n == 0:
             raise RuntimeError("windgnn_amd: TrainStep.forward_backward_series needs at least one window (a series of %d rows, "
                                "seq_len %d, n_windows %r)" % (series.shape[0], seq_len, n_windows))
-        Y, stash, loss_buf, sd, _ = self._series_forward(A, series, Ls, seq_len, stride, n)
+        at = {} if table is None else {"starts": table}     # (the strided call is the call it has always been)
+        Y, stash, loss_buf, sd, _ = self._series_forward(A, series, Ls, seq_len, stride, n, table)
         series_backward_mse_raw(sd, A, series, self.p_views, Y, Ls, stash, loss_buf, self.g_views, self._loss, 1.0,
-                                prepared=self._prepared)
-        return self._loss, Y
+                                prepared=self._prepared, **at)
+        return self._loss, (Y if inverse is None else Y.index_select(0, inverse))
 
-    def step_series(self, A, series, Ls, seq_len, stride=1, n_windows=None, n_global=None):
+    def step_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, n_global=None, starts=None):
         """One optimiser step on the first `n_windows` (default: all that fit) sliding windows of this rank's `series`
         [rows, S, 13]: window w covers rows w * stride .. w * stride + seq_len - 1 and starts from h = 0, as step() on the
         materialised windows would.  Ls [>= (n - 1) * stride + seq_len, H]: the label SERIES (series_labels(feat, seq_len,
         stride, n_windows)[0]), read at the rows the windows cover; no window-major labels and no dY exist.  `n_global`: as in
         step().  Returns (loss, Y [n, seq_len, H]); the loss is the same 0-dim VIEW of the bucket's header word.  Under a
         process group every rank passes its own sub-series (the caller's slicing: consecutive ranks' rows overlap by
-        seq_len - stride); a rank with no window takes the empty-shard step."""
-        seq_len, stride = int(seq_len), int(stride)
-        self._series_refusals(A, series, seq_len, stride)
+        seq_len - stride); a rank with no window takes the empty-shard step.  stride defaults to 1.
+        starts (instead of stride / n_windows): the step runs on exactly the windows that begin at these rows of `series` -- a list
+        or tensor in any order, duplicates allowed (series.segment_starts for a series with outages, a hold-out, one block of a
+        shuffled epoch).  The loss and the gradients are over the listed windows, the window count is the table's length (an
+        empty table: the empty-shard step), Y comes back in the table's order, and Ls needs a row for every row of `series`.
+        The graph convolutions and the input projection still run on every row of `series`."""
+        seq_len, table, inverse = int(seq_len), None, None
+        self._series_refusals(A, series, seq_len, 1 if stride is None else int(stride))
         series, Ls = series.contiguous(), Ls.contiguous()
-        n = self._series_count(series, Ls, seq_len, stride, n_windows)
+        if starts is not None:
+            table, inverse, n = self._series_table(series, Ls, seq_len, stride, n_windows, starts)
+        else:
+            stride = 1 if stride is None else int(stride)
+            n = self._series_count(series, Ls, seq_len, stride, n_windows)
         if n == 0:
             return self._empty_shard_step(A, series.new_empty((0, seq_len) + tuple(series.shape[1:])), n_global)
         gs = self.exchange.shard_weight(n, n_global) if self.collective else 1.0
-        Y, stash, loss_buf, sd, d = self._series_forward(A, series, Ls, seq_len, stride, n)
+        at = {} if table is None else {"starts": table}     # (the strided call is the call it has always been)
+        Y, stash, loss_buf, sd, d = self._series_forward(A, series, Ls, seq_len, stride, n, table)
         series_backward_mse_raw(sd, A, series, self.p_views, Y, Ls, stash, loss_buf, self.g_views, self._loss, gs,
-                                prepared=self._prepared)
+                                prepared=self._prepared, **at)
         self._run_schedule(d, _FINAL, gs)       # the bucket is final: (the all-reduce,) Adam and the W_ih images
         self._end_step()
-        return self._loss, Y
+        return self._loss, (Y if inverse is None else Y.index_select(0, inverse))
 
     def _forward(self, A, X, L):
         # the first call sizes and builds the images from the dims of this batch (they depend on S, H, math only)
