@@ -197,7 +197,10 @@ const char* wgnn_strerror(int status);
 /* The two GRU weight-gradient products of the fp16-plane modes (register-resident recurrence, H <= 127): 1 (default) ONE
  * launch in which every workgroup runs one work item of dW_ih and then one of dW_hh; 0 one launch per product.  A schedule
  * choice like WGNN_OPT_FUSED_FWD: both forms run the same tiles over the same K chunks into the same partial sums (the
- * split-K factors belong to the workspace layout, not to this option), so the results are bit-identical. */
+ * split-K factors belong to the workspace layout, not to this option), so the results are bit-identical.  With 1, the
+ * stateless step of the split-fp16 modes with fp32 I/O also forms the dW_hh product's h rows from Y itself, and its forward
+ * leaves the fp16 Y planes of the stash unwritten: keep the value unchanged between a forward and the backward that uses
+ * its stash. */
 #define WGNN_OPT_TN_MERGED 6
 #define WGNN_OPT_COUNT 7
 int wgnn_set_option(int key, int value);

@@ -23,7 +23,7 @@ STEP_MAX_B = 256            # wgnn_fwd_state: T == 1 calls up to this batch (den
 STATUS_BYTES = 256          # WGNN_STATUS_BYTES: status block at the start of every workspace
 OPT_FUSED_FWD = 0           # WGNN_OPT_FUSED_FWD (wgnn_set_option): 0 never / 1 stash-less forwards / 2 every supported forward
 OPT_BIG_GEMM = 4            # WGNN_OPT_BIG_GEMM: 1 (default) the 256 x 256-tile kernel for large NT plane products / 0 off (keys 1, 2, 3, 5 are retired)
-OPT_TN_MERGED = 6           # WGNN_OPT_TN_MERGED: 1 (default) one launch for both GRU weight-gradient GEMMs / 0 one each; same bits
+OPT_TN_MERGED = 6           # WGNN_OPT_TN_MERGED: 1 (default) one launch for both GRU weight-gradient GEMMs (dW_hh reads h from fp32 Y, no Y planes) / 0 one each; same bits; not to be changed between a forward and its backward
 
 
 class Dims(C.Structure):

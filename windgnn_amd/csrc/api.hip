@@ -533,8 +533,9 @@ int fwd_recurrence(const Fwd& f) {
       return launch_grux_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, lo ? (void*)c.hn : f.Y, nullptr, nullptr,
                              f.full, f.status, nullptr, nullptr, d->io, lo, 1.f, 0.f, f.st, c.h0, lo ? nullptr : c.hn);
     }
-    rc = launch_grux_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, f.Y, f.gates, f.sf ? f.sf + L.st_yp : nullptr,
-                         f.full, f.status, labels, stats, d->io, 0, 1.f, 0.f, f.st, c.h0, c.hn, c.sst ? L.plane_rows : 0);
+    rc = launch_grux_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, f.Y, f.gates,   // (no Y planes for a dW_hh from Y)
+                         f.sf && !hh_from_y(d, L.tn_merge, c.sst) ? f.sf + L.st_yp : nullptr, f.full, f.status, labels, stats,
+                         d->io, 0, 1.f, 0.f, f.st, c.h0, c.hn, c.sst ? L.plane_rows : 0);
   } else if (L.rec32) {       // exact fp32, W_hh in registers
     if (c.last)
       return launch_gru_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, c.last, nullptr, nullptr, nullptr, nullptr, 0,
@@ -737,8 +738,7 @@ int bwd_weights(const Bwd& b, int prods, int r0, int rows) {
     const _Float16* dGIh = (const _Float16*)b.dGI + r0;
     const _Float16* dGHh = (const _Float16*)b.dGH + r0;
     const _Float16* gh = (const _Float16*)b.gact;
-    const _Float16* yph = (const _Float16*)(b.sf + L.st_yp);
-    const _Float16* ypl = yph + L.plane_rows * L.Hp;
+    const _Float16 *yph = (const _Float16*)(b.sf + L.st_yp), *ypl = yph + L.plane_rows * L.Hp;
     const size_t PG = L.BT * L.Gp;
     // Hprev row (b,t) = Y-plane row (b,t-1); row B*T stands in at t = 0, or in the state stash row B*T + b, window b's own
     // [h0 | 1].  Register-resident recurrence: dGH = [dGI_r | dGI_z | dGHn], the A operand takes GEMM rows < msplit from the
@@ -769,7 +769,7 @@ int bwd_weights(const Bwd& b, int prods, int r0, int rows) {
     // WGNN_OPT_TN_MERGED: both products as one launch whose work items are exactly the workgroups of the two launches
     // (same tiles, same K chunks, same partial regions: bit-identical)
     if (prods == (WGNN_ROWS_IH | WGNN_ROWS_HH) && L.tn_merge && opt(WGNN_OPT_TN_MERGED) && pgemm_tn2_covers(ih, hh)) {
-      rc = launch_pgemm_tn2(ih, hh, (int)L.BT, b.st);
+      rc = launch_pgemm_tn2(ih, tn_b_from_y(hh, hh_from_y(d, L.tn_merge, sst) ? b.Y : nullptr, (int)L.H), (int)L.BT, b.st);
     } else {
       if (prods & WGNN_ROWS_HH) {
         rc = one(hh);
@@ -933,6 +933,21 @@ int check_rows(const wgnn_dims* d, const Layout& L, int which, int row0, int row
 }  // namespace
 
 int opt_big_gemm() { return opt(WGNN_OPT_BIG_GEMM); }
+
+// Whether the dW_hh product of this step takes h from the caller's fp32 Y (TnProd::By) instead of the stash's fp16 Y planes,
+// which the forward recurrence then does not write: their region of the stash stays untouched, the layout and
+// wgnn_stash_bytes are as they were.  Both sides of a step ask here, so WGNN_OPT_TN_MERGED must not change between a forward
+// and its backward.  In scope: the merged weight-gradient launch (tn_merge: the register-resident recurrence of the fp16-plane
+// family) in the split-fp16 modes with fp32 I/O -- 16-bit Y is rounded on the wire, not the value the planes split -- and
+// the stateless step: the carried-state entries (sst) keep their per-window [h0 | 1] plane rows.  Series mode and
+// wgnn_bwd_rows run one product per launch and do not ask; every layout with tn_merge passes pgemm_tn2_covers (two-source A,
+// H <= 127: one N block of at most four tiles), so a step that asked takes the merged launch.  WGNN_OPT_TN_MERGED = 0 (two
+// launches) is the plane form, bit for bit the same; the environment variable WGNN_TN_YFP32 = 0, read once, keeps the planes
+// under the merged launch too (the alternated runs of profiles/tn_yfp32_ab.txt).
+bool hh_from_y(const wgnn_dims* d, bool tn_merge, bool sst) {
+  static const int from_env = env_int("WGNN_TN_YFP32", 1, 0, 1);
+  return tn_merge && three_pass(d) && d->io == WGNN_IO_F32 && !sst && from_env && opt(WGNN_OPT_TN_MERGED);
+}
 
 // ---- series mode (series.hip validates and sizes; the launches live here, next to the layouts and the parts they reuse) ----
 // Workspace: [front | rec], each a workspace of its layout with a status block of its own; stash: [front | rec] likewise.

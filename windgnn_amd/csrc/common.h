@@ -207,6 +207,8 @@ int launch_pgemm_nt256(const void* Aimg_hi, const void* Aimg_lo, int M, int k0, 
 size_t pgemm_nt256_aimg_bytes(int M, int N, int Kp, int planes);
 int launch_pgemm_repack_a(const void* Ahi, const void* Alo, int lda, int M, int Kp, void* img, hipStream_t st);
 int opt_big_gemm();   // WGNN_OPT_BIG_GEMM: 0 off, 1 on (needs the caller's A-image scratch)
+// api.hip: the dW_hh product of this step reads h from the caller's fp32 Y, the forward recurrence writes no Y planes
+bool hh_from_y(const wgnn_dims* d, bool tn_merge, bool sst);
 // ---- The image of a B operand (weights: W_ih | b_ih, W_ih^T, W_hh | b_hh), written by split_weight2_kernel / finish.hip and
 // staged by the NT plane GEMMs and the fused front end: one fp16 plane of B[Np][Kp] is STAGE-major (a 32-deep K step of all
 // Np rows is contiguous) and, since round 5, FRAGMENT-major inside a stage: the 16 rows x 32 k of one MFMA B fragment are 1 KB
@@ -248,8 +250,12 @@ struct TnProd {
   bool x3;
   const void *A2hi, *A2lo; int lda2, msplit;
   bool b_stream, per_window;
+  // dW_hh of the stateless fp32-I/O step in the merged launch only: the B rows [Hprev | 1] are formed from the caller's fp32 Y
+  // [K][ldb] (row k = Y row k - 1, zeros at k % shift_T == 0, 1.0 in column ldb) and split in the GEMM; Bhi / Blo unread
+  const float* By;
 };
 bool pgemm_tn2_covers(const TnProd& ih, const TnProd& hh);
+TnProd tn_b_from_y(TnProd hh, const float* Y, int H);   // hh with its B rows formed from fp32 Y [K][H] (TnProd::By); Y = NULL: hh itself
 int launch_pgemm_tn2(const TnProd& ih, const TnProd& hh, int K, hipStream_t st);
 // general shapes (general.hip): CSR adjacency (blob layout: see include/windgnn.h) and any hidden width
 size_t gcn_csr_bwd_partial_floats();

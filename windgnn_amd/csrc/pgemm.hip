@@ -1,6 +1,8 @@
 // Plane GEMMs: split-fp16 ("f16x3") MFMA GEMMs whose operands already live in HBM as fp16 hi/lo
 // planes written by their producers (gcnx_fwd -> g, grux_bwd -> dGI/dGH, grux_fwd -> Y planes,
-// split_weight -> W_ih).  No conversion work is left in the GEMMs: staging is a pure 16-byte copy.
+// split_weight -> W_ih).  No conversion work is left in the GEMMs: staging is a pure 16-byte copy.  (One exception: dW_hh of the
+// stateless fp32-I/O step stages the caller's fp32 Y and splits its B fragments in registers, pgemm_tn_tile<.., YB>: the Y
+// planes then need not exist.)
 //
 //   NT  C[M][N] (fp32) = A[M][Kp] . B[N][Kp]^T          GI = g W_ih^T (+b_ih via the ones column),
 //                                                       dg = dGI W_ih
@@ -38,6 +40,24 @@ __device__ __forceinline__ int sw16_off(int row, int c) { return row * 64 + ((c 
 
 __device__ __forceinline__ f32x4 mfma_q(h8 a, h8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+
+// hi = fp16(x), lo = fp16(x - hi), two values at a time: the two-instruction split of grux.hip / gcnx_dev.h (v_cvt_pk_f16_f32,
+// then v_fma_mix_f32 reading hi out of the packed register; the conversions stay compiler-visible for the MFMA hazards)
+__device__ __forceinline__ unsigned cvt2(float x0, float x1) {
+  typedef float f2v __attribute__((ext_vector_type(2)));
+  typedef _Float16 h2v __attribute__((ext_vector_type(2)));
+  const f2v xv = {x0, x1};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(xv, h2v));
+}
+__device__ __forceinline__ void split2(float x0, float x1, unsigned& hi, unsigned& lo) {
+  float t0, t1;
+  hi = cvt2(x0, x1);
+  asm("v_fma_mix_f32 %0, %2, -1.0, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mix_f32 %1, %2, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
+      : "=&v"(t0), "=&v"(t1)
+      : "v"(hi), "v"(x0), "v"(x1));
+  lo = cvt2(t0, t1);
 }
 
 // Slots of the A ring and the kernel's dynamic LDS.  A third A slot (an A stage then has two compute phases to arrive) pays
@@ -358,20 +378,22 @@ __device__ __forceinline__ int tn_g(int stride32, int r) {   // stride32 = row b
 // own prefetch (staging + MFMAs in sequence, T = 7: 99 us); without it the prefetch runs under the MFMAs (78 us).  The
 // synchronisation the stages need is the explicit vmcnt(0) + s_barrier at the top of the loop.  Check after a compiler
 // change: the K loop of the assembly has that wait and the one of the partial last stage, and no third.
-template <int T, bool X3, bool A2, bool ALO, bool PW = false>
+template <int T, bool X3, bool A2, bool ALO, bool PW = false, bool YB = false>
 __device__ __forceinline__ void pgemm_tn_tile(const _Float16* __restrict__ Ahi, const _Float16* __restrict__ Alo, int lda,
                                               const _Float16* __restrict__ Bhi, const _Float16* __restrict__ Blo, int ldb,
                                               int shift_T, int K, int kchunk, float* __restrict__ partial, int Mout,
                                               int Nout, int nNb, const _Float16* __restrict__ A2hi,
                                               const _Float16* __restrict__ A2lo, int lda2, int msplit, int b_stream,
-                                              const int z, const int tile, const int ntile) {
+                                              const int z, const int tile, const int ntile,
+                                              const float* __restrict__ By = nullptr) {
+  static_assert(!YB || (X3 && !PW), "the fp32 B source: split modes, the stateless step");
   constexpr int BM = TN_BM, BN = 32 * T;
   constexpr int ARB = BM * 2, BRB = BN * 2;                         // row bytes
   constexpr int A_PL = 32 * ARB, B_PL = 32 * BRB, STAGE = 2 * A_PL + 2 * B_PL;
   constexpr int PL = X3 ? 2 : 1;                                   // B planes moved: hi (+ lo)
   constexpr int PLA = (X3 && ALO) ? 2 : 1;                         // A planes moved
   constexpr int AP = A_PL / 1024, BP = B_PL / 1024;                // 1 KB pieces per plane
-  constexpr int NPIECE = PLA * AP + PL * BP, NIT = (NPIECE + TN_WAVES - 1) / TN_WAVES;
+  constexpr int NPIECE = PLA * AP + (YB ? 2 : PL) * BP, NIT = (NPIECE + TN_WAVES - 1) / TN_WAVES;
   constexpr int ACH = ARB / 16, BCH = BRB / 16;                    // 16-byte chunks per row
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -388,6 +410,17 @@ __device__ __forceinline__ void pgemm_tn_tile(const _Float16* __restrict__ Ahi, 
 #pragma unroll
     for (int j = 0; j < T; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  // YB: the stage's 32 B rows are ONE block of 32 ldb floats of By (row k of the operand is row k - 1 of By, so the block
+  // starts one row early), copied as it lies, 16 bytes per lane, from the 16-byte boundary at or below its first float into
+  // the two planes' room (128 ldb + 12 <= 4096 T bytes, as ldb < 32 T).  kbeg and the stage step are multiples of 32 rows, so
+  // the block sits the same y_d4 bytes past its boundary in every stage of the chunk.  Granules wholly outside By (row -1 of
+  // chunk 0, the round-up past the last row) are re-aimed at By's first / last granule: no access leaves the aligned 16 bytes
+  // that hold a float of By, and no fragment uses what they bring (t = 0 rows and rows >= kend are formed, not read)
+  const uintptr_t y_s0 = YB ? (uintptr_t)By + ((ptrdiff_t)kbeg - 1) * ldb * 4 : 0;
+  const int y_d4 = (int)(y_s0 & 15);
+  const uintptr_t y_stage = y_s0 - y_d4;
+  const uintptr_t y_lo = (uintptr_t)By & ~(uintptr_t)15, y_hi = ((uintptr_t)By + (size_t)K * ldb * 4 - 4) & ~(uintptr_t)15;
+  const int y_bytes = y_d4 + 128 * ldb;
   // ---- staging map: piece p = wave + 8*it; lane-linear chunk q of a plane's stage image is (row q / CH,
   // position q % CH) and receives source chunk position ^ 2 g(row)
   const _Float16* base[NIT];
@@ -413,6 +446,14 @@ __device__ __forceinline__ void pgemm_tn_tile(const _Float16* __restrict__ Ahi, 
         pcol[it] = col - msplit < lda2 ? col - msplit : 0;
       }
       dst[it] = plane * A_PL + (pp % AP) * 1024;
+    } else if (YB) {
+      const int q2 = pp - PLA * AP;
+      on[it] = on[it] && q2 * 1024 < y_bytes;                         // wave-uniform
+      base[it] = Bhi;
+      ld[it] = 0;
+      prow[it] = 0;
+      pcol[it] = q2 * 1024 + lane * 16;                               // byte offset from the stage's boundary
+      dst[it] = 2 * A_PL + q2 * 1024;
     } else {
       const int q2 = pp - PLA * AP;
       const int plane = q2 / BP, q = 64 * (q2 % BP) + lane;
@@ -431,6 +472,13 @@ __device__ __forceinline__ void pgemm_tn_tile(const _Float16* __restrict__ Ahi, 
 #pragma unroll
     for (int it = 0; it < NIT; ++it)
       if (on[it]) {
+        if (YB && isb[it]) {
+          uintptr_t a = y_stage + (size_t)(k0 - kbeg) * ldb * 4 + pcol[it];
+          a = a < y_lo ? y_lo : (a > y_hi ? y_hi : a);
+          if (b_stream) __builtin_amdgcn_global_load_lds((glb_void*)a, (lds_void*)(st + dst[it]), 16, 0, 2);
+          else __builtin_amdgcn_global_load_lds((glb_void*)a, (lds_void*)(st + dst[it]), 16, 0, 0);
+          continue;
+        }
         int k = min(k0 + prow[it], kend - 1);                      // rows past the chunk: zeroed in LDS below
         if (isb[it] && shift_T > 0) k = (k % shift_T) != 0 ? k - 1 : (PW ? K + k / shift_T : K);   // row K = the stored t = 0 row
         // b_stream: the B operand is an old, read-once tensor (the g plane, the Hprev planes): non-temporal, so that it does
@@ -465,7 +513,43 @@ __device__ __forceinline__ void pgemm_tn_tile(const _Float16* __restrict__ Ahi, 
     r[4] = w1[0]; r[5] = w1[1]; r[6] = w1[2]; r[7] = w1[3];
     return r;
   };
-  auto compute = [&](const char* cur) {
+  // YB fragments: lane 16x + n of block j holds column 16 (T wn + j) + n of the stage rows the transpose reads give it
+  // (slot e: row 4x + e, from e = 4 on 16 rows further down), read K-strided from the fp32 block and split here as
+  // grux_fwd_kernel split h_t for the planes -- hi = fp16(h), lo = fp16(h - hi): the planes' bits.  Formed, not read:
+  // rows with t = 0 (h0 = 0) and rows >= kend are 0 (bit e of the stage's `keep` word), column ldb is 1, columns past it 0
+  int y_off[8];
+  bool y_col[T], y_edge[T];
+  float y_pad[T];
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    y_off[e] = 2 * A_PL + y_d4 + 4 * ((4 * x + (e & 3) + 16 * (e >> 2)) * ldb + 16 * T * wn + (lane & 15));
+#pragma unroll
+  for (int j = 0; j < T; ++j) {
+    const int c = 16 * (T * wn + j) + (lane & 15);
+    y_col[j] = c < ldb;
+    y_pad[j] = c == ldb ? 1.f : 0.f;
+    y_edge[j] = 16 * (T * wn + j) + 16 > ldb;                         // wave-uniform
+  }
+  auto yfrag = [&](const char* cur, int j, const unsigned (&m)[8], h8& bh, h8& bl) {
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = __builtin_bit_cast(float, *(const unsigned*)(cur + y_off[e] + 64 * j) & m[e]);
+    if (y_edge[j]) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = y_col[j] ? v[e] : y_pad[j];
+    }
+    u32x4 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      unsigned h, l;
+      split2(v[2 * e], v[2 * e + 1], h, l);
+      hi[e] = h;
+      lo[e] = l;
+    }
+    bh = __builtin_bit_cast(h8, hi);
+    bl = __builtin_bit_cast(h8, lo);
+  };
+  auto compute = [&](const char* cur, unsigned keep) {
     h8 ah[5], al[5];
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
@@ -473,11 +557,19 @@ __device__ __forceinline__ void pgemm_tn_tile(const _Float16* __restrict__ Ahi, 
       al[i] = ah[i];
       if (X3 && ALO) al[i] = trread(cur + A_PL + a_off[i], ARB);
     }
+    unsigned ym[8];
+    if (YB) {
+      const unsigned sh = keep >> (4 * x);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) ym[e] = 0u - ((sh >> ((e & 3) + 16 * (e >> 2))) & 1u);
+    }
 #pragma unroll
     for (int j = 0; j < T; ++j) {
-      const h8 bh = trread(cur + b_off[j], BRB);
+      h8 bh, ybl;
+      if (YB) yfrag(cur, j, ym, bh, ybl);
+      else bh = trread(cur + b_off[j], BRB);
       if (X3) {
-        const h8 bl = trread(cur + B_PL + b_off[j], BRB);
+        const h8 bl = YB ? ybl : trread(cur + B_PL + b_off[j], BRB);
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
           if (ALO) acc[i][j] = mfma_q(al[i], bh, acc[i][j]);
@@ -489,6 +581,8 @@ __device__ __forceinline__ void pgemm_tn_tile(const _Float16* __restrict__ Ahi, 
     }
   };
 
+  int y_rem = YB ? kbeg % shift_T : 0;                              // (kbeg + 32 kt) % shift_T
+  const int y_step = YB ? 32 % shift_T : 0;
   if (nk > 0) dma_stage(smem, kbeg);
   for (int kt = 0; kt < nk; ++kt) {
     char* cur = smem + (kt & 1) * STAGE;
@@ -504,7 +598,15 @@ __device__ __forceinline__ void pgemm_tn_tile(const _Float16* __restrict__ Ahi, 
       }
       __syncthreads();
     }
-    compute(cur);
+    unsigned keep = 0u;
+    if (YB) {                          // (all of it wave-uniform)
+      unsigned t0 = 0u;
+      for (int r = y_rem ? shift_T - y_rem : 0; r < 32; r += shift_T) t0 |= 1u << r;
+      keep = ~t0 & (rows >= 32 ? ~0u : (1u << rows) - 1u);
+      y_rem += y_step;
+      if (y_rem >= shift_T) y_rem -= shift_T;
+    }
+    compute(cur, keep);
   }
 
   // Partials are stored in the accumulators' own layout, [z][tile][wave][i][j][lane][4]: every store is a
@@ -545,12 +647,16 @@ __global__ void __launch_bounds__(64 * TN_WAVES) pgemm_tn_kernel(const _Float16*
 // 168 instances (every (I, H) this path accepts can occur), none with scratch, all at 2 waves per SIMD.
 // MODE 0: three passes both (f16x3); 1: dGI / dGHn are ONE fp16 plane -- dW_ih one pass, dW_hh two (f16x3g at large B*T);
 // 2: one pass both (f16).
+// YB (dW_hh of the stateless fp32-I/O step, MODE 0 / 1): the B rows come from the caller's fp32 Y (hh.By, pitch hh.ldb
+// floats) and are split in the fragment former of pgemm_tn_tile -- the planes' bits, so the partials are the same bits again
+// (28 x 2 more instances).
 struct TnRole {
   const _Float16 *Ahi, *Alo, *Bhi, *Blo, *A2hi, *A2lo;
+  const float* By;
   float* partial;
   int lda, ldb, lda2, shift_T, K, kchunk, Mout, Nout, nNb, msplit, b_stream, splitk, ntile;
 };
-template <int TI, int TH, int MODE, bool PW>
+template <int TI, int TH, int MODE, bool PW, bool YB = false>
 __global__ void __launch_bounds__(64 * TN_WAVES) pgemm_tn2_kernel(const TnRole ih, const TnRole hh) {
   const int item = (int)blockIdx.x;                                 // (both conditions are workgroup-uniform)
   if (item < ih.splitk * ih.ntile)
@@ -559,9 +665,10 @@ __global__ void __launch_bounds__(64 * TN_WAVES) pgemm_tn2_kernel(const TnRole i
                                                      ih.b_stream, item % ih.splitk, item / ih.splitk, ih.ntile);
   __syncthreads();                                                  // the last stage of the first item has been read
   if (item < hh.splitk * hh.ntile)
-    pgemm_tn_tile<TH, MODE != 2, true, MODE != 1, PW>(hh.Ahi, hh.Alo, hh.lda, hh.Bhi, hh.Blo, hh.ldb, hh.shift_T, hh.K, hh.kchunk,
-                                                      hh.partial, hh.Mout, hh.Nout, hh.nNb, hh.A2hi, hh.A2lo, hh.lda2, hh.msplit,
-                                                      hh.b_stream, item % hh.splitk, item / hh.splitk, hh.ntile);
+    pgemm_tn_tile<TH, MODE != 2, true, MODE != 1, PW, YB>(hh.Ahi, hh.Alo, hh.lda, hh.Bhi, hh.Blo, hh.ldb, hh.shift_T, hh.K,
+                                                          hh.kchunk, hh.partial, hh.Mout, hh.Nout, hh.nNb, hh.A2hi, hh.A2lo,
+                                                          hh.lda2, hh.msplit, hh.b_stream, item % hh.splitk, item / hh.splitk,
+                                                          hh.ntile, hh.By);
 }
 
 // Planes of O[Rp][Cp] (O[r][c] = transpose ? W[c][r] : W[r][c]; optional extra column `bias_col`
@@ -877,7 +984,7 @@ int launch_tn2_t(const TnProd& pi, const TnProd& ph, int K, int mode, int nNi, i
     TnRole r;
     const bool alo = p.Alo != nullptr;             // single-plane A operand: the lo pointers are never read
     r.Ahi = (const _Float16*)p.Ahi; r.Alo = (const _Float16*)(alo ? p.Alo : p.Ahi);
-    r.Bhi = (const _Float16*)p.Bhi; r.Blo = (const _Float16*)p.Blo;
+    r.Bhi = (const _Float16*)p.Bhi; r.Blo = (const _Float16*)p.Blo; r.By = p.By;
     r.A2hi = (const _Float16*)p.A2hi; r.A2lo = (const _Float16*)(alo ? p.A2lo : p.A2hi);
     r.partial = p.partial;
     r.lda = p.lda; r.ldb = p.ldb; r.lda2 = p.lda2; r.shift_T = p.shift_T; r.K = K;
@@ -890,28 +997,30 @@ int launch_tn2_t(const TnProd& pi, const TnProd& ph, int K, int mode, int nNi, i
   constexpr int TMAX = TI > TH ? TI : TH;
   const size_t smem = 2 * (size_t)(2 * 32 * 2 * (TN_BM + 32 * TMAX));
   auto bytes = [K](const TnProd& p) {
-    return ((p.x3 && p.Alo) ? 4.0 : 2.0) * (double)K * p.Mout + (p.x3 ? 4.0 : 2.0) * (double)K * p.Nout +
-           4.0 * (double)p.splitk * p.Mout * p.Nout;
+    return ((p.x3 && p.Alo) ? 4.0 : 2.0) * (double)K * p.Mout +
+           (p.By ? 4.0 * (double)K * p.ldb : (p.x3 ? 4.0 : 2.0) * (double)K * p.Nout) + 4.0 * (double)p.splitk * p.Mout * p.Nout;
   };
   const double fl = 2.0 * K * ((double)pi.Mout * pi.Nout + (double)ph.Mout * ph.Nout), by = bytes(pi) + bytes(ph);
   static const std::string base = "pgemm_tn_kernel<" + std::to_string(TI) + "+" + std::to_string(TH);
   static const std::string names[3] = {base + ">", base + ",x2>", base + ",f16>"};
   const int ni = ri.splitk * ri.ntile, nh = rh.splitk * rh.ntile;
   const dim3 grid(ni > nh ? ni : nh), block(64 * TN_WAVES);
-#define TN2_GO(MODE, PWV)                                                                                        \
+#define TN2_GO(MODE, PWV, YBV)                                                                                   \
   do {                                                                                                           \
     static std::atomic<unsigned long long> done_{0};                                                             \
-    if (ensure_dyn_smem((const void*)pgemm_tn2_kernel<TI, TH, MODE, PWV>, smem, done_) != WGNN_OK) return WGNN_ERR_HIP; \
+    if (ensure_dyn_smem((const void*)pgemm_tn2_kernel<TI, TH, MODE, PWV, YBV>, smem, done_) != WGNN_OK) return WGNN_ERR_HIP; \
     PROF_LAUNCH(names[MODE].c_str(), fl, by, st,                                                                 \
-                hipLaunchKernelGGL((pgemm_tn2_kernel<TI, TH, MODE, PWV>), grid, block, smem, st, ri, rh));       \
+                hipLaunchKernelGGL((pgemm_tn2_kernel<TI, TH, MODE, PWV, YBV>), grid, block, smem, st, ri, rh));  \
   } while (0)
-  switch (2 * mode + (ph.per_window ? 1 : 0)) {
-    case 0: TN2_GO(0, false); break;
-    case 1: TN2_GO(0, true); break;
-    case 2: TN2_GO(1, false); break;
-    case 3: TN2_GO(1, true); break;
-    case 4: TN2_GO(2, false); break;
-    case 5: TN2_GO(2, true); break;
+  switch (2 * mode + (ph.per_window ? 1 : 0) + (ph.By ? 6 : 0)) {
+    case 0: TN2_GO(0, false, false); break;
+    case 1: TN2_GO(0, true, false); break;
+    case 2: TN2_GO(1, false, false); break;
+    case 3: TN2_GO(1, true, false); break;
+    case 4: TN2_GO(2, false, false); break;
+    case 5: TN2_GO(2, true, false); break;
+    case 6: TN2_GO(0, false, true); break;
+    case 8: TN2_GO(1, false, true); break;
     default: return WGNN_ERR_UNSUPPORTED;
   }
 #undef TN2_GO
@@ -925,13 +1034,21 @@ int launch_tn2_t(const TnProd& pi, const TnProd& ph, int K, int mode, int nNi, i
 bool pgemm_tn2_covers(const TnProd& ih, const TnProd& hh) {
   int nNb, T;
   tn_shape(hh.Nout, nNb, T);
-  return tn2_mode(ih, hh) >= 0 && !ih.A2hi && ih.shift_T == 0 && !ih.per_window && hh.A2hi && T <= 4 && ih.splitk >= 1 &&
-         hh.splitk >= 1;
+  // (fp32 B rows: the three- and two-pass dW_hh of the stateless step, one N block, rows that leave room for the ones column)
+  if (hh.By && (tn2_mode(ih, hh) > 1 || hh.per_window || hh.shift_T < 1 || nNb != 1 || hh.ldb + 1 != hh.Nout)) return false;
+  return tn2_mode(ih, hh) >= 0 && !ih.By && !ih.A2hi && ih.shift_T == 0 && !ih.per_window && hh.A2hi && T <= 4 &&
+         ih.splitk >= 1 && hh.splitk >= 1;
+}
+
+TnProd tn_b_from_y(TnProd hh, const float* Y, int H) {
+  if (Y) { hh.By = Y; hh.ldb = H; hh.Bhi = hh.Blo = nullptr; }
+  return hh;
 }
 
 int launch_pgemm_tn2(const TnProd& ih, const TnProd& hh, int K, hipStream_t st) {
   if (!pgemm_tn2_covers(ih, hh)) return WGNN_ERR_UNSUPPORTED;
-  if (ih.lda % 8 != 0 || ih.ldb % 8 != 0 || hh.lda % 8 != 0 || hh.ldb % 8 != 0 || K < 1) return WGNN_ERR_SHAPE;
+  if (ih.lda % 8 != 0 || ih.ldb % 8 != 0 || hh.lda % 8 != 0 || (!hh.By && hh.ldb % 8 != 0) || K < 1) return WGNN_ERR_SHAPE;
+  if (hh.By && ((uintptr_t)hh.By & 3)) return WGNN_ERR_SHAPE;
   if (hh.per_window && hh.shift_T < 1) return WGNN_ERR_SHAPE;
   if (hh.lda2 % 8 != 0 || hh.msplit % 8 != 0 || hh.msplit > hh.lda) return WGNN_ERR_SHAPE;
   int nNi, TI, nNh, TH;

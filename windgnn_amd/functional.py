@@ -218,13 +218,19 @@ def _forward_setup(A, X, params: Sequence[torch.Tensor], math, labels=None, h0=N
 
 
 def gcn_gru_forward_raw(A, X, params: Sequence[torch.Tensor], math=_lib.MATH_F32, want_stash=True, labels=None,
-                        prepared=None):
+                        prepared=None, stash=None):
     """Y[B,T,H], stash = wgnn_fwd(...).  X is [B,T,S,F].  labels [B,T,H]: wgnn_fwd_loss (the MSE statistics of
-    (Y - labels) are left in the stash for gcn_gru_backward_mse_raw(..., part | 8))."""
+    (Y - labels) are left in the stash for gcn_gru_backward_mse_raw(..., part | 8)).  stash: a caller's buffer of
+    wgnn_stash_bytes bytes (uint8, on X's device) instead of a new one."""
     lib = _lib.load()
     A, d, ws, ws_bytes = _forward_setup(A, X, params, math, labels=labels)
     B, T, H = d.B, d.T, d.H
-    stash = torch.empty(lib.wgnn_stash_bytes(C.byref(d)), dtype=torch.uint8, device=X.device) if want_stash else None
+    if stash is not None:
+        if not want_stash or stash.dtype != torch.uint8 or stash.device != X.device or stash.numel() < lib.wgnn_stash_bytes(C.byref(d)):
+            raise RuntimeError("windgnn_amd: stash must be a uint8 buffer of wgnn_stash_bytes = %d bytes on %s"
+                               % (lib.wgnn_stash_bytes(C.byref(d)), X.device))
+    elif want_stash:
+        stash = torch.empty(lib.wgnn_stash_bytes(C.byref(d)), dtype=torch.uint8, device=X.device)
     Y = torch.empty(B, T, H, dtype=X.dtype, device=X.device)
     ps = _params_struct(_lib.Params, params, prepared)
     if labels is not None:
