@@ -37,10 +37,10 @@ def _base(name):
 
 
 @functools.lru_cache(maxsize=3)
-def _reference(S, T, B, H, sparse, shift, io, state):
+def _reference(S, T, B, H, sparse, shift, io, state, seed=0):
     """The lattice draw of a shape (labels rounded to the I/O type; X is exact in it) and the fp64 reference's step on it."""
     from oracle import windgnn_oracle as orc
-    d = li.draw(S, T, B, H, sparse, shift)
+    d = li.draw(S, T, B, H, sparse, shift, seed) if seed else li.draw(S, T, B, H, sparse, shift)
     X, L = d.X.to(IODT[io]), d.L.to(IODT[io])
     assert torch.equal(X.float(), d.X)
     if not state:
@@ -67,14 +67,15 @@ def _bars(cid, S, T, B, H, math, io, state, route):
     return b
 
 
-def _step(S, T, B, H, math, io, state, route, sparse, shift):
-    """One step of this call form on the GPU: the names it launched and its errors against the reference."""
+def _step(S, T, B, H, math, io, state, route, sparse, shift, seed=0):
+    """One step of this call form on the GPU: the names it launched and its errors against the reference (seed: the draw's, for
+    tests/test_gpu_gcn_loops.py's tabled shapes)."""
     from windgnn_amd import _lib
     from windgnn_amd.functional import (check_range_status, gcn_gru_backward_mse_raw, gcn_gru_forward_raw,
                                         gcn_gru_state_backward_raw, gcn_gru_state_forward_raw)
     from windgnn_amd.graph import CsrAdjacency
     dev = _dev()
-    r = _reference(S, T, B, H, sparse, shift, io, state)
+    r = _reference(S, T, B, H, sparse, shift, io, state, seed) if seed else _reference(S, T, B, H, sparse, shift, io, state)
     A = CsrAdjacency.from_dense(r["A"]).to(dev) if sparse else r["A"].to(dev)
     X = r["X"].to(dev)
     ps = [r["p"][k].to(dev).contiguous() for k in PARAM_KEYS]
