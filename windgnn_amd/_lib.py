@@ -224,6 +224,21 @@ EXPORTS_SERIES_AT = {
                                          C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
+# include/windgnn_series_masked.h: series training / evaluation through missing labels, NaN = no label (a ninth header and table)
+SERIES_MASKED_VERSION = 1   # WGNN_SERIES_MASKED_VERSION
+STATUS_NO_LABELS = 32       # WGNN_STATUS_NO_LABELS
+EXPORTS_SERIES_MASKED = {
+    "wgnn_series_masked_version": (C.c_int, []),
+    "wgnn_series_masked_loss_bytes": (C.c_size_t, [_SD]),
+    "wgnn_series_fwd_loss_masked": (C.c_int, [_SD, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_int64,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wgnn_series_bwd_mse_masked": (C.c_int, [_SD, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,
+                                             C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Grads),
+                                             C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wgnn_eval_accum_series": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -292,6 +307,16 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    if not hasattr(lib, "wgnn_series_masked_version"):
+        raise RuntimeError("windgnn_amd: %s predates include/windgnn_series_masked.h (no wgnn_series_masked_version): rebuild it "
+                           "with `python -m windgnn_amd.build --force`" % LIB_PATH)
+    for name, (res, args) in EXPORTS_SERIES_MASKED.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.wgnn_series_masked_version() < SERIES_MASKED_VERSION:
+        raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_series_masked_version %d < %d)"
+                           % (lib.wgnn_series_masked_version(), SERIES_MASKED_VERSION))
     if lib.wgnn_series_at_version() < SERIES_AT_VERSION:
         raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_series_at_version %d < %d)"
                            % (lib.wgnn_series_at_version(), SERIES_AT_VERSION))

@@ -102,6 +102,11 @@ __device__ __forceinline__ BwdState bwd_state(SeriesRows) { return BwdState{null
 // the instances without a pack keep their code.
 struct SeriesStarts { const int* starts; int last; };
 __device__ __forceinline__ BwdState bwd_state(SeriesStarts) { return BwdState{nullptr, nullptr, nullptr}; }
+// Missing labels (include/windgnn_series_masked.h): a tag BEHIND a SeriesRows / SeriesStarts in the same pack -- a NaN in Ls is
+// "no label".  New instances only: every pack without the tag keeps its code.
+struct MaskedLabels {};
+__device__ __forceinline__ BwdState bwd_state(SeriesRows, MaskedLabels) { return BwdState{nullptr, nullptr, nullptr}; }
+__device__ __forceinline__ BwdState bwd_state(SeriesStarts, MaskedLabels) { return BwdState{nullptr, nullptr, nullptr}; }
 
 // ---- internal launchers (defined in the .hip files, used by api.hip) -------------------------
 struct GemmArgs {
@@ -162,6 +167,14 @@ int launch_grux_bwd(int B, int T, int H, const float* Whh, const void* Y, const 
                     int write_lo /*0: dGI / dGHn as one fp16 plane (x3 only)*/, hipStream_t st,
                     const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given, no labels*/);
 #define WGNN_STATS_TAG 20261004.0f   // float word behind the MSE partial pairs: "wgnn_fwd_loss wrote these"
+#define WGNN_STATS_TAG_MASKED 20261019.0f   // the same word from wgnn_series_fwd_loss_masked: sums over the labels that exist
+// the masked loss_buf: [nb sums | nb maxima | tag | 3 spare words | nb uint32 label counts], nb = gru_blocks(n)
+__host__ __device__ __forceinline__ unsigned* masked_counts(float* stat_part, int nb) {
+  return (unsigned*)(stat_part + 2 * (size_t)nb + 4);
+}
+__host__ __device__ __forceinline__ const unsigned* masked_counts(const float* stat_part, int nb) {
+  return (const unsigned*)(stat_part + 2 * (size_t)nb + 4);
+}
 
 
 int launch_gcn_partial_reduce(const float* partial, int nblk, float* dW1, float* db1, float* dW2, float* db2,
@@ -302,7 +315,7 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
                    int series_stride = 0 /*> 0: GI is one series [rows][ldgi], window w at rows w * stride + t (no h0)*/,
                    int64_t ls_rows = 0 /*series with labels: they are one series too, Ls [ls_rows][H], read at the same rows*/,
                    const int* starts = nullptr /*instead of a stride: window w at rows clamp(starts[w], 0, starts_last) + t*/,
-                   int starts_last = 0);
+                   int starts_last = 0, bool masked = false /*series with labels: NaN = no label, counts behind stat_part*/);
 //   backward: exactly one of dY / labels; dGI [B*T][ldd] and EITHER dGHn [B*T][gru_hn(H)] (dGH's r and z thirds equal
 //   dGI's) OR the full dGH [B*T][ldd]; stat_part (nullable, with labels): loss[0] is finalised from the forward's partials
 int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
@@ -311,7 +324,8 @@ int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const 
                    const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given*/,
                    int series_stride = 0 /*> 0: GI is one series, as in launch_gru_fwd (no state)*/,
                    int64_t ls_rows = 0 /*series with labels: Ls [ls_rows][H], as in launch_gru_fwd*/,
-                   const int* starts = nullptr /*instead of a stride, as in launch_gru_fwd*/, int starts_last = 0);
+                   const int* starts = nullptr /*instead of a stride, as in launch_gru_fwd*/, int starts_last = 0,
+                   bool masked = false /*as in launch_gru_fwd: n_loss is then the forward's count, summed in the kernel*/);
 bool gru_shape_supported(int H);
 size_t gru_gates_floats(int B, int T, int H);
 int gru_blocks(int B);
@@ -354,13 +368,14 @@ int series_bwd(const wgnn_dims* front, const wgnn_dims* rec, int stride, const f
 // include/windgnn_series_train.h (series_train.hip validates): the same two sequences with the labels as a series Ls [ls_rows][H]
 // in the recurrences; loss_buf = 2 * gru_blocks(n) partials (sum | max) + the tag word, series_loss_floats(n) floats in all
 size_t series_loss_floats(int n);
+size_t series_masked_loss_floats(int n);   // + gru_blocks(n) label counts (include/windgnn_series_masked.h)
 int series_fwd_loss(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs,
                     const wgnn_params* p, const float* Ls, int64_t ls_rows, float* Y, void* stash /*nullable*/, float* loss_buf,
-                    void* workspace, const SeriesPlan& sp, void* stream, const int* starts = nullptr);
+                    void* workspace, const SeriesPlan& sp, void* stream, const int* starts = nullptr, bool masked = false);
 int series_bwd_mse(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs,
                    const wgnn_params* p, const float* Y, const float* Ls, int64_t ls_rows, float grad_scale, const void* stash,
                    const float* loss_buf, float* loss, const wgnn_grads* g, void* workspace, const SeriesPlan& sp, void* stream,
-                   const int* starts = nullptr);
+                   const int* starts = nullptr, bool masked = false);
 // dGIs [rows][ld] = the sum, in ascending w, of the window-major rows dGI [(w, tau - w * stride)][ld] that cover hour tau;
 // uncovered rows and the columns [G3, ld) are written as zeros (series.hip)
 int launch_series_fold(const float* dGI, int n, int T, int stride, int rows, int G3, int ld, float* dGIs, hipStream_t st);

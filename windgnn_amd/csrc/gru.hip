@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "../../include/windgnn_series_masked.h"
 
 namespace {
 
@@ -52,16 +53,18 @@ __device__ __forceinline__ void lds_row(const float* p, float (&a)[N]) {
 
 // GI rows between the first rows of two consecutive windows: T (window-major GI), or the stride of a SeriesRows; 0 for a
 // SeriesStarts (the workgroup's base is the series' base, and a window's first row comes from the table: series_start)
+template <typename A, typename... R>
+__device__ __forceinline__ A first_of(A a, R...) { return a; }   // the row mapping of a pack (a MaskedLabels tag may follow it)
 template <typename... S>
 __device__ __forceinline__ int gi_window_rows(int T, S... s) {
-  if constexpr ((std::is_same<S, SeriesRows>::value || ...)) return SeriesRows{s...}.stride;
+  if constexpr ((std::is_same<S, SeriesRows>::value || ...)) return first_of(s...).stride;
   else if constexpr ((std::is_same<S, SeriesStarts>::value || ...)) return 0;
   else return T;
 }
 // SeriesStarts: the first series row of window w (w < B), clamped so that rows [start, start + T) lie inside the series
 template <typename... S>
 __device__ __forceinline__ int series_start(int w, S... s) {
-  const SeriesStarts ss{s...};
+  const SeriesStarts ss = first_of(s...);
   return min(max(ss.starts[w], 0), ss.last);
 }
 
@@ -74,6 +77,8 @@ __host__ __device__ inline size_t gate_floats(int B, int T, int H) {
 // Sr (empty, or one SeriesRows: wgnn_series_fwd): GI is one series and window w reads row w * stride + t of it, and so are the
 // labels (wgnn_series_fwd_loss: Lab = Ls [ls_rows][H], the same row); everything the kernel writes stays window-major.
 // Or one SeriesStarts (wgnn_series_fwd_at): the row is clamp(starts[w], 0, last) + t.
+// A MaskedLabels behind either (wgnn_series_fwd_loss_masked): a NaN label is no label -- it adds nothing to the sum and the
+// maximum, and the workgroup leaves the integer count of its labels behind the statistics (common.h: masked_counts).
 template <int KS, bool ST = false, typename... Sr>   // k steps of 4 over the hidden index, 4 KS >= H, KS even; ST: the wgnn_fwd_state instance
 __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, const float* __restrict__ GI, int ldgi,
                                                            const float* __restrict__ Whh,
@@ -85,6 +90,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
                                                            Sr... series) {
   constexpr bool SR = sizeof...(Sr) > 0;
   constexpr bool SS = (std::is_same<Sr, SeriesStarts>::value || ...);
+  constexpr bool MK = (std::is_same<Sr, MaskedLabels>::value || ...);
   // h0 (nullable, wgnn_fwd_state): [B][H] initial state instead of zeros; hn (nullable): h_{T-1} [B][H], unrounded
   if (!ST) { h0 = nullptr; hn = nullptr; }       // (the plain forward's instance compiles exactly as before)
   constexpr int KP = 4 * KS, HS = KP + 4;          // row stride: 16-byte aligned rows
@@ -102,7 +108,8 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
   const int jc = jv ? j : H - 1;
   const int b0 = blockIdx.x * MB;
   // tag behind the MSE partial pairs: set by wgnn_fwd_loss, cleared by a plain forward on the same stash
-  if (stat_part && blockIdx.x == 0 && threadIdx.x == 0) stat_part[2 * gridDim.x] = Lab ? WGNN_STATS_TAG : 0.f;
+  if (stat_part && blockIdx.x == 0 && threadIdx.x == 0)
+    stat_part[2 * gridDim.x] = Lab ? (MK ? WGNN_STATS_TAG_MASKED : WGNN_STATS_TAG) : 0.f;
   if (hprev) {
     // [Hprev | 1 | 0..] rows: the constant tail of every row (b, t) and the whole row (b, 0) (h_{-1} = 0); the body of
     // row (b, t + 1) is written with h_t below
@@ -165,6 +172,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
     for (int r = 0; r < 4; ++r) hold[r] = rowok[r] ? h0[(size_t)(b0 + 4 * lk + r) * H + j] : 0.f;
   }
   float ssum = 0.f, smax = 0.f;
+  unsigned cnt = 0;       // MK: labels seen by this thread (at most 4 T)
   __syncthreads();
 
   for (int t = 0; t < T; ++t) {
@@ -202,7 +210,13 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
           else if (t == T - 1) Y[(size_t)(b0 + 4 * lk + r) * H + j] = hnew[r] * y_mul + y_add;
           if (hn && t == T - 1) hn[(size_t)(b0 + 4 * lk + r) * H + j] = hnew[r];
           if (Hpw && t + 1 < T) Hpw[(rowt[r] + t + 1) * hq + j] = hnew[r];
-          if (Lab) {
+          if constexpr (MK) {
+            const bool has = lab[r] == lab[r];               // a NaN is no label; the select keeps NaN * 0 out of the sum
+            const float dl = has ? hnew[r] - lab[r] : 0.f;
+            ssum = fmaf(dl, dl, ssum);
+            smax = fmaxf(smax, fabsf(dl));
+            cnt += has ? 1u : 0u;
+          } else if (Lab) {
             const float dl = hnew[r] - lab[r];
             ssum = fmaf(dl, dl, ssum);
             smax = fmaxf(smax, fabsf(dl));
@@ -251,6 +265,19 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
       stat_part[blockIdx.x] = s;
       stat_part[gridDim.x + blockIdx.x] = m;
     }
+    if constexpr (MK) {   // the exact count: integer adds, any order
+      __shared__ unsigned redc[NTHREADS / 64];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+      if (lane == 0) redc[wave] = cnt;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        unsigned c = 0;
+#pragma unroll
+        for (int w = 0; w < NTHREADS / 64; ++w) c += redc[w];
+        masked_counts(stat_part, gridDim.x)[blockIdx.x] = c;
+      }
+    }
   }
 }
 
@@ -261,7 +288,10 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
 // Outputs for the GEMMs that follow: dGI rows [B*T][ldd] (3H layout, zero K padding) and dGHn = dnt r rows [B*T][hn].
 // St (empty, or one BwdState: wgnn_bwd_state_part): h_{-1} = h0, the carry starts at dh_n, and the step at t = 0 also forms
 // dh_{-1} = dh z + dgh W_hh into dh0.  Or one SeriesRows (wgnn_series_bwd / wgnn_series_bwd_mse): GIn, and Lab if given, are
-// one series each, as in the forward; or one SeriesStarts (the _at entry points), likewise.
+// one series each, as in the forward; or one SeriesStarts (the _at entry points), likewise.  A MaskedLabels behind either
+// (wgnn_series_bwd_mse_masked): dY = 2 grad_scale (Y - label) / m where the label is not NaN and +0 elsewhere, m = the sum of the
+// forward's per-workgroup counts, which EVERY workgroup adds up itself before its loop (integers: no order to fix, no launch
+// between forward and backward); coef_lab carries grad_scale, inv_n is unused; m = 0: loss NaN, dY = 0, WGNN_STATUS_NO_LABELS.
 template <int KS3, typename... St>   // k steps of 4 over the gate-row index, 4 KS3 >= 3H, KS3 even
 __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, const float* __restrict__ Whh,
                                                            const float* __restrict__ Y, const float* __restrict__ dY,
@@ -277,6 +307,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
   constexpr bool SS = (std::is_same<St, SeriesStarts>::value || ...);
   constexpr bool SR = (std::is_same<St, SeriesRows>::value || ...) || SS;
   constexpr bool ST = sizeof...(St) > 0 && !SR;
+  constexpr bool MK = (std::is_same<St, MaskedLabels>::value || ...);
   const BwdState sb = bwd_state(state...);
   constexpr int KP = 4 * KS3, DS = KP + 4;
   __shared__ __attribute__((aligned(16))) float dbuf[2 * MB * DS];   // dgh rows [dar | daz | dnr | 0..], by step parity
@@ -290,6 +321,25 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
   const int jc = jv ? j : H - 1;
   const int b0 = blockIdx.x * MB;
   const int G3 = 3 * H;
+  if constexpr (MK) {
+    __shared__ unsigned long long cred[NTHREADS / 64];
+    const unsigned* counts = masked_counts(stat_part, nstat);
+    unsigned long long c = 0;
+    for (int i = threadIdx.x; i < nstat; i += NTHREADS) c += counts[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (lane == 0) cred[wave] = c;
+    __syncthreads();
+    c = 0;
+#pragma unroll
+    for (int w = 0; w < NTHREADS / 64; ++w) c += cred[w];
+    const bool counted = stat_part[2 * nstat] == WGNN_STATS_TAG_MASKED;   // else: not this forward's buffer, no count to trust
+    if (!counted) c = 0;
+    // the two factors as launch_gru_bwd forms them on the host from n_loss (IEEE division)
+    inv_n = c ? 1.0f / (float)c : __builtin_nanf("");       // m = 0: loss[0] = NaN whatever the partial sums hold
+    coef_lab = c ? 2.0f * coef_lab / (float)c : 0.f;
+    if (counted && c == 0 && blockIdx.x == 0 && threadIdx.x == 0 && status) atomicOr(status, WGNN_STATUS_NO_LABELS);
+  }
   if (stat_part && blockIdx.x == 0) {   // loss = (sum of the forward's per-workgroup partial sums) / n, fixed order
     __shared__ float sred[NTHREADS / 64];
     float a = 0.f;
@@ -302,7 +352,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
       a = 0.f;
 #pragma unroll
       for (int w = 0; w < NTHREADS / 64; ++w) a += sred[w];
-      const bool tagged = stat_part[2 * nstat] == WGNN_STATS_TAG;
+      const bool tagged = stat_part[2 * nstat] == (MK ? WGNN_STATS_TAG_MASKED : WGNN_STATS_TAG);
       loss_out[0] = tagged ? a * inv_n : __builtin_nanf("");     // no statistics of these labels in the stash: loud
       if (!tagged && status) atomicOr(status, WGNN_STATUS_NO_LOSS_STATS);
     }
@@ -395,7 +445,9 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int m = 4 * lk + r;
-        const float dyv = Lab ? (ycur[r] - cur.dy[r]) * coef_lab : cur.dy[r];
+        float dyv;
+        if constexpr (MK) dyv = cur.dy[r] == cur.dy[r] ? (ycur[r] - cur.dy[r]) * coef_lab : 0.f;   // no label: exactly +0
+        else dyv = Lab ? (ycur[r] - cur.dy[r]) * coef_lab : cur.dy[r];
         const float dh = rowok[r] ? dyv + dhn[r] : 0.f;
         const float rg = cur.r[r], zg = cur.z[r];
         const float ng = tanh_fast(__builtin_fmaf(rg, cur.ghn[r], cur.n[r]));   // the forward's n, bit for bit
@@ -482,8 +534,9 @@ int gru_msplit(int H) { return 4 * cdiv_i(2 * H, 4); }   // first GEMM row of th
 int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
                    float* gates, const float* labels, float* stat_part, float* hprev, int hq, int last_only, float y_mul,
                    float y_add, hipStream_t st, const float* h0, float* hn, int series_stride, int64_t ls_rows,
-                   const int* starts, int starts_last) {
+                   const int* starts, int starts_last, bool masked) {
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
+  if (masked && (!(series_stride || starts) || !labels || !stat_part || last_only)) return WGNN_ERR_UNSUPPORTED;
   if (last_only && (gates || labels || hprev)) return WGNN_ERR_UNSUPPORTED;
   if (series_stride < 0 || (series_stride && (h0 || hn))) return WGNN_ERR_UNSUPPORTED;
   if (starts && (series_stride || h0 || hn || starts_last < 0)) return WGNN_ERR_UNSUPPORTED;
@@ -495,8 +548,18 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
   const double fl = bt * 2.0 * 3 * H * H;
   const double by = bt * 4.0 * (3 * H + (last_only ? 0 : H) + (labels ? H : 0) + (hprev ? hq : 0)) +
                     (gates ? 3.0 * gate_floats(B, T, H) : 0.0);     // three of the buffer's four components are used
+#define FMASKED(K, NAME, MAP, ...)                                                                                \
+  PROF_LAUNCH("gru_fwd_kernel<" #K NAME ">", fl, by, st,                                                          \
+              hipLaunchKernelGGL((gru_fwd_kernel<K, false, MAP, MaskedLabels>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, \
+                                 H, GI, ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq, last_only, y_mul, y_add, nullptr,  \
+                                 nullptr, MAP{__VA_ARGS__}, MaskedLabels{}))
 #define FCASE(K)                                                                                                  \
   case K:                                                                                                         \
+    if (masked) {                                                                                                 \
+      if (starts) FMASKED(K, ",starts,masked", SeriesStarts, starts, starts_last);                                \
+      else FMASKED(K, ",masked", SeriesRows, series_stride);                                                      \
+      break;                                                                                                      \
+    }                                                                                                             \
     if (starts) {                                                                                                 \
       PROF_LAUNCH("gru_fwd_kernel<" #K ",starts>", fl, by, st,                                                    \
                   hipLaunchKernelGGL((gru_fwd_kernel<K, false, SeriesStarts>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, \
@@ -520,6 +583,7 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
     default: return WGNN_ERR_UNSUPPORTED;
   }
 #undef FCASE
+#undef FMASKED
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;
 }
@@ -529,8 +593,9 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
 int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
                    const float* gates, const float* GI /*the forward's GI rows [B*T][ldgi] (stash)*/, int ldgi, float* dGI, int ldd, float* dGHn, float* dGH, const float* stat_part,
                    int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st, const BwdState* state,
-                   int series_stride, int64_t ls_rows, const int* starts, int starts_last) {
+                   int series_stride, int64_t ls_rows, const int* starts, int starts_last, bool masked) {
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
+  if (masked && (!(series_stride || starts) || !labels || !stat_part || state)) return WGNN_ERR_UNSUPPORTED;
   if (state && (!state->h0 || labels)) return WGNN_ERR_UNSUPPORTED;
   if (series_stride < 0 || (series_stride && state)) return WGNN_ERR_UNSUPPORTED;
   if (starts && (series_stride || state || starts_last < 0)) return WGNN_ERR_UNSUPPORTED;
@@ -545,8 +610,19 @@ int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const 
   const double bt = (double)B * T;
   const double fl = bt * 2.0 * 3 * H * H, by = bt * 4.0 * (H + H + 3 * H + (dGH ? 3 * H : H)) + 3.0 * gate_floats(B, T, H) +
                                           bt * 4.0 * H;   // + GI's n third
+  // masked: the kernel forms both factors from the forward's count; coef_lab carries grad_scale there
+#define BMASKED(K, NAME, MAP, ...)                                                                                \
+  PROF_LAUNCH("gru_bwd_kernel<" #K NAME ">", fl, by, st,                                                          \
+              hipLaunchKernelGGL((gru_bwd_kernel<K, MAP, MaskedLabels>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, Whh, \
+                                 Y, dY, labels, gates, GI, ldgi, dGI, ldd, dGHn, hn, dGH, stat_part, gru_blocks(B), 0.f,          \
+                                 grad_scale, loss, status, MAP{__VA_ARGS__}, MaskedLabels{}))
 #define BCASE(K)                                                                                                  \
   case K:                                                                                                         \
+    if (masked) {                                                                                                 \
+      if (starts) BMASKED(K, ",starts,masked", SeriesStarts, starts, starts_last);                                \
+      else BMASKED(K, ",masked", SeriesRows, series_stride);                                                      \
+      break;                                                                                                      \
+    }                                                                                                             \
     if (starts) {                                                                                                 \
       PROF_LAUNCH("gru_bwd_kernel<" #K ",starts>", fl, by, st,                                                    \
                   hipLaunchKernelGGL((gru_bwd_kernel<K, SeriesStarts>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, Whh, Y, \
@@ -570,6 +646,7 @@ int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const 
     default: return WGNN_ERR_UNSUPPORTED;
   }
 #undef BCASE
+#undef BMASKED
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;
 }

@@ -6,6 +6,7 @@
 #include "../../include/windgnn_series.h"
 #include "../../include/windgnn_series_train.h"
 #include "../../include/windgnn_series_at.h"
+#include "../../include/windgnn_series_masked.h"
 
 #include <cmath>
 
@@ -165,26 +166,28 @@ bool labels_fit(const wgnn_series_dims* sd, bool at, int64_t ls_rows) {
 
 int forward_loss(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, const float* Ls,
                  int64_t ls_rows, float* Y, void* stash, void* loss_buf, void* workspace, size_t workspace_bytes, void* stream,
-                 bool at = false, const int* starts = nullptr) {
+                 bool at = false, const int* starts = nullptr, bool masked = false) {
   if (sd && !Y) return WGNN_ERR_NULL;      // before the dims, as in wgnn_series_fwd
   Plan pl;
   int rc = plan(sd, &pl, at);
   if (rc != WGNN_OK) return rc;
+  if (masked && !at && starts) return WGNN_ERR_SHAPE;      // a table with a stride (windgnn_series_masked.h)
   if (!A || !Xs || !p || !Ls || !loss_buf || !workspace || !complete(p) || (at && !starts)) return WGNN_ERR_NULL;
   if (!labels_fit(sd, at, ls_rows)) return WGNN_ERR_SHAPE;
   if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
   if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
   return series_fwd_loss(&pl.front, &pl.rec, sd->stride, A, Xs, p, Ls, ls_rows, Y, stash, (float*)loss_buf, workspace, pl.sp,
-                         stream, starts);
+                         stream, starts, masked);
 }
 
 int backward_mse(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, const float* Y,
                  const float* Ls, int64_t ls_rows, float grad_scale, const void* stash, const void* loss_buf, float* loss,
                  const wgnn_grads* grads, void* workspace, size_t workspace_bytes, void* stream, bool at = false,
-                 const int* starts = nullptr) {
+                 const int* starts = nullptr, bool masked = false) {
   Plan pl;
   int rc = plan(sd, &pl, at);
   if (rc != WGNN_OK) return rc;
+  if (masked && !at && starts) return WGNN_ERR_SHAPE;
   if (!A || !Xs || !p || !Y || !Ls || !stash || !loss_buf || !loss || !grads || !workspace || !complete(p) || !complete(grads) ||
       (at && !starts))
     return WGNN_ERR_NULL;
@@ -192,7 +195,7 @@ int backward_mse(const wgnn_series_dims* sd, const float* A, const float* Xs, co
   if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
   if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
   return series_bwd_mse(&pl.front, &pl.rec, sd->stride, A, Xs, p, Y, Ls, ls_rows, grad_scale, stash, (const float*)loss_buf,
-                        loss, grads, workspace, pl.sp, stream, starts);
+                        loss, grads, workspace, pl.sp, stream, starts, masked);
 }
 
 }  // namespace
@@ -331,6 +334,29 @@ int wgnn_series_bwd_mse_at(const wgnn_series_dims* sd, const float* A, const flo
                            size_t workspace_bytes, void* stream) {
   return backward_mse(sd, A, Xs, p, Y, Ls, ls_rows, grad_scale, stash, loss_buf, loss, grads, workspace, workspace_bytes, stream,
                       true, starts);
+}
+
+// ---- include/windgnn_series_masked.h (wgnn_eval_accum_series: eval.hip) ----
+int wgnn_series_masked_version(void) { return WGNN_SERIES_MASKED_VERSION; }
+
+size_t wgnn_series_masked_loss_bytes(const wgnn_series_dims* sd) {
+  Plan pl;
+  return plan(sd, &pl, sd && sd->stride == 0) == WGNN_OK ? sizeof(float) * series_masked_loss_floats(sd->n) : 0;
+}
+
+int wgnn_series_fwd_loss_masked(const wgnn_series_dims* sd, const float* A, const float* Xs, const int32_t* starts,
+                                const wgnn_params* p, const float* Ls, int64_t ls_rows, float* Y, void* stash, void* loss_buf,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  return forward_loss(sd, A, Xs, p, Ls, ls_rows, Y, stash, loss_buf, workspace, workspace_bytes, stream, sd && sd->stride == 0,
+                      starts, true);
+}
+
+int wgnn_series_bwd_mse_masked(const wgnn_series_dims* sd, const float* A, const float* Xs, const int32_t* starts,
+                               const wgnn_params* p, const float* Y, const float* Ls, int64_t ls_rows, float grad_scale,
+                               const void* stash, const void* loss_buf, float* loss, const wgnn_grads* grads, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  return backward_mse(sd, A, Xs, p, Y, Ls, ls_rows, grad_scale, stash, loss_buf, loss, grads, workspace, workspace_bytes, stream,
+                      sd && sd->stride == 0, starts, true);
 }
 
 }  // extern "C"

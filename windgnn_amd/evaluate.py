@@ -66,6 +66,41 @@ def eval_accum(pred: torch.Tensor, labels: torch.Tensor, wind_min: float, wind_m
                                    _stream()), "wgnn_eval_accum")
 
 
+def eval_accum_series(pred: torch.Tensor, Ls: torch.Tensor, seq_len: int, wind_min: float, wind_max: float, acc: torch.Tensor,
+                      stride: Optional[int] = 1, starts: Optional[torch.Tensor] = None, skip_missing: bool = False,
+                      abs_err: Optional[torch.Tensor] = None) -> None:
+    """wgnn_eval_accum_series: eval_accum with the truth of window b read at row b*stride + seq_len - 1 of the label SERIES
+    Ls [ls_rows, H] (series.series_labels' first result) -- or, with `starts` (a contiguous int32 device tensor [B] in pred's
+    order, stride None), at row starts[b] + seq_len - 1.  No [B, T, H] label tensor exists.  skip_missing: a NaN truth adds
+    nothing to its column, whose count (header row n) is not incremented; abs_err gets NaN there."""
+    lib = _lib.load()
+    _require_gpu(pred, Ls)
+    _require_contiguous(pred=pred, Ls=Ls, abs_err=abs_err, starts=starts)
+    if pred.dim() != 2 or Ls.dim() != 2 or Ls.shape[1] != pred.shape[1]:
+        raise RuntimeError("windgnn_amd: eval_accum_series wants pred [B,H] and Ls [ls_rows,H], got %s and %s"
+                           % (tuple(pred.shape), tuple(Ls.shape)))
+    B, H = pred.shape
+    if starts is not None:
+        if stride not in (None, 0):
+            raise ValueError("eval_accum_series: pass stride= or starts=, not both (got stride=%r with a table of starts)" % (stride,))
+        if not starts.is_cuda:
+            raise RuntimeError("windgnn_amd runs on an MI355X (HIP) only: the table of starts is a %s tensor" % starts.device)
+        if starts.dtype != torch.int32 or tuple(starts.shape) != (B,):
+            raise ValueError("eval_accum_series: starts must be an int32 tensor of B = %d entries, got %s %s"
+                             % (B, starts.dtype, tuple(starts.shape)))
+        stride = 0
+    elif stride is None or int(stride) < 1:
+        raise ValueError("eval_accum_series: stride must be >= 1 without a table of starts, got %r" % (stride,))
+    if abs_err is not None:
+        _require_gpu(abs_err)
+        if tuple(abs_err.shape) != (B, H):
+            raise RuntimeError("windgnn_amd: abs_err must be [%d,%d], got %s" % (B, H, tuple(abs_err.shape)))
+    ap = _acc_ptr(acc, H, eval_bytes(H))
+    _lib.check(lib.wgnn_eval_accum_series(_ptr(pred), _ptr(Ls), Ls.shape[0], _ptr(starts), int(stride), B, int(seq_len), H,
+                                          float(wind_min), float(wind_max), 1 if skip_missing else 0, ap, _ptr(abs_err),
+                                          _stream()), "wgnn_eval_accum_series")
+
+
 def eval_stats(acc: torch.Tensor, H: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """wgnn_eval_stats: [H,4] fp32 (RMSE, MAE, accuracy mean, accuracy std per column) from the header of `acc` -- an
     accumulator, or any fp64 tensor that starts with 5*H header doubles (a merged copy)."""
@@ -94,7 +129,9 @@ def stats_frames(stats, stations):
 
 class EvalResult(NamedTuple):
     stats: torch.Tensor            # [3,S,4] fp32: horizon, station, (RMSE, MAE, accuracy mean, accuracy std)
-    count: torch.Tensor            # 0-dim int64: windows accumulated (over all ranks with a process group)
+    count: torch.Tensor            # 0-dim int64: windows accumulated (over all ranks with a process group).  Counts are kept PER
+                                   # COLUMN (header[0]); this is column 0's.  The columns differ only after update_series(...,
+                                   # skip_missing=True), where a NaN truth is not counted: read header[0] there
     mse_normalised: torch.Tensor   # [3] fp64: Σe² / (n S (wind_max - wind_min)²) per horizon, the training loss's units
     header: torch.Tensor           # [5,H] fp64: the sums the figures came from (merged over the ranks)
 
@@ -130,6 +167,34 @@ class Evaluator:
         p2 = pred.reshape(-1, self.H)                    # (a view: forward_last's tensor is contiguous)
         err = torch.empty_like(p2) if self.keep_errors else None
         eval_accum(p2, labels.contiguous(), self.wind_min, self.wind_max, self._acc(), err)
+        if err is not None:
+            self._errors.append(err)
+        return pred
+
+    def update_series(self, series: torch.Tensor, Ls: torch.Tensor, seq_len: int, stride: Optional[int] = None, n_windows=None,
+                      starts=None, skip_missing: bool = False) -> torch.Tensor:
+        """The rolling backtest on ONE series: series.forward_last_series(model, adj, series, seq_len, ...) followed by
+        wgnn_eval_accum_series against the label series Ls [ls_rows, 3S] (series.series_labels' first result: the truth of a
+        window that starts at row s is row s + seq_len - 1).  Returns the [n, 3S] forecasts in the caller's order (starts= in any
+        order, duplicates allowed; otherwise stride, default 1, and n_windows).  No [n, T, 3S] label tensor is built and nothing
+        synchronises with the host.  skip_missing=True: a NaN in Ls is "no truth here" -- that station and horizon is left out of
+        this window's sums and of its column's count, so the counts differ per column (compute().header[0]; compute().count is
+        column 0's); a column that never saw a truth has count 0 and NaN figures."""
+        from .series import _no_stride_with_starts, _starts_table, forward_last_series
+        _no_stride_with_starts("Evaluator.update_series", stride, starts, n_windows)
+        seq_len = int(seq_len)
+        pred = forward_last_series(self.model, self.adj, series, seq_len, self.wind_min, self.wind_max, stride, n_windows, starts)
+        table = None
+        if starts is not None:      # in the caller's order, as the rows of pred are (the kernel only looks the table up)
+            table = _starts_table(starts, series.shape[0], seq_len, series.device, "Evaluator.update_series", ordered=False)
+        step = None if starts is not None else int(1 if stride is None else stride)
+        need = series.shape[0] if starts is not None else (pred.shape[0] - 1) * step + seq_len
+        if Ls.dim() != 2 or Ls.shape[1] != self.H or Ls.shape[0] < need:
+            raise RuntimeError("windgnn_amd: Evaluator.update_series: the label series Ls must be [rows >= %d, H = %d], got %s"
+                               % (need, self.H, tuple(Ls.shape)))
+        err = torch.empty_like(pred) if self.keep_errors else None
+        eval_accum_series(pred, Ls.contiguous(), seq_len, self.wind_min, self.wind_max, self._acc(), step, table, skip_missing,
+                          err)
         if err is not None:
             self._errors.append(err)
         return pred

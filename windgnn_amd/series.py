@@ -239,16 +239,33 @@ def _check_label_series(Ls, sd) -> None:
     _require_contiguous(Ls=Ls)
 
 
+def _masked_table(at):
+    """The `starts` argument of a masked entry point (include/windgnn_series_masked.h): one pair serves both row mappings, so
+    the strided form passes NULL where the table goes."""
+    return at if at else (None,)
+
+
 def series_forward_loss_raw(A, series, Ls, seq_len, stride, params, math=_lib.MATH_F32, n_windows=None, prepared=None,
-                            starts=None):
+                            starts=None, missing_labels=False):
     """Y [n, T, H], stash, loss_buf, dims = wgnn_series_fwd_loss(...): series_forward_raw with the MSE statistics of (Y - labels)
     left in loss_buf for series_backward_mse_raw.  Ls [rows - 3, H]: the label SERIES (series_labels' first result); window w,
     step t reads its row w * stride + t.  starts (with stride None): a NON-DECREASING table, the row is starts[w] + t, Ls needs
-    the series' rows, and a fifth result is the int32 device table (wgnn_series_fwd_loss_at)."""
+    the series' rows, and a fifth result is the int32 device table (wgnn_series_fwd_loss_at).
+    missing_labels=True (wgnn_series_fwd_loss_masked, either row mapping): a NaN in Ls is "no label" and enters neither the sum nor
+    the count; loss_buf then has wgnn_series_masked_loss_bytes and goes to series_backward_mse_raw(..., missing_labels=True)."""
     lib = _lib.load()
     A, sd, ws, ws_bytes, *table = _series_setup(A, series, seq_len, stride, params, math, n_windows, starts)
     _check_label_series(Ls, sd)
     stash = torch.empty(_fn(lib, "stash_bytes", sd)(C.byref(sd)), dtype=torch.uint8, device=series.device)
+    if missing_labels:
+        loss_buf = torch.empty(lib.wgnn_series_masked_loss_bytes(C.byref(sd)) // 4, dtype=torch.float32, device=series.device)
+        Y = torch.empty(sd.n, sd.T, sd.H, dtype=torch.float32, device=series.device)
+        ps = _params_struct(_lib.Params, params, prepared)
+        rc = lib.wgnn_series_fwd_loss_masked(C.byref(sd), _ptr(A), _ptr(series), *_masked_table(_table_arg(sd, *table)),
+                                             C.byref(ps), _ptr(Ls), Ls.shape[0], _ptr(Y), _stash_ptr(stash), _ptr(loss_buf),
+                                             _ptr(ws), ws_bytes, _stream())
+        _lib.check(rc, "wgnn_series_fwd_loss_masked")
+        return (Y, stash, loss_buf, sd, *table)
     loss_buf = torch.empty(_fn(lib, "loss_bytes", sd)(C.byref(sd)) // 4, dtype=torch.float32, device=series.device)
     Y = torch.empty(sd.n, sd.T, sd.H, dtype=torch.float32, device=series.device)
     ps = _params_struct(_lib.Params, params, prepared)
@@ -260,21 +277,30 @@ def series_forward_loss_raw(A, series, Ls, seq_len, stride, params, math=_lib.MA
 
 
 def series_backward_mse_raw(sd, A, series, params, Y, Ls, stash, loss_buf, grads: Sequence[torch.Tensor], loss: torch.Tensor,
-                            grad_scale: float = 1.0, prepared=None, starts=None) -> None:
+                            grad_scale: float = 1.0, prepared=None, starts=None, missing_labels=False) -> None:
     """wgnn_series_bwd_mse: the 8 gradients of grad_scale * mean((Y - labels)^2) into `grads` (overwritten, final) and the
     unweighted mean into `loss` (a 0-dim fp32 device tensor), without a dY tensor.  Y, stash, loss_buf: as
-    series_forward_loss_raw returned them for the same inputs (starts: its table, for dims with stride = 0)."""
+    series_forward_loss_raw returned them for the same inputs (starts: its table, for dims with stride = 0).
+    missing_labels=True (wgnn_series_bwd_mse_masked; the forward's flag): the mean and the gradients are over the labels that are
+    not NaN; with none at all the loss is NaN and the gradients are zero."""
     lib = _lib.load()
     _check_label_series(Ls, sd)
     _require_gpu(loss, loss_buf)
     _require_contiguous(series=series, Y=Y, adj_matrix=A, loss_buf=loss_buf, grads=grads, params=params)
     at = _table_arg(sd, starts)
-    need = _fn(lib, "loss_bytes", sd)(C.byref(sd))
+    need = (lib.wgnn_series_masked_loss_bytes if missing_labels else _fn(lib, "loss_bytes", sd))(C.byref(sd))
     if loss_buf.numel() * 4 < need:
-        raise RuntimeError("windgnn_amd: loss_buf holds %d bytes, wgnn_series_loss_bytes says %d" % (loss_buf.numel() * 4, need))
+        raise RuntimeError("windgnn_amd: loss_buf holds %d bytes, wgnn_series_%sloss_bytes says %d"
+                           % (loss_buf.numel() * 4, "masked_" if missing_labels else "", need))
     ws, ws_bytes = _workspace(sd, series.device)
     ps = _params_struct(_lib.Params, params, prepared)
     gs = _params_struct(_lib.Grads, grads)
+    if missing_labels:
+        rc = lib.wgnn_series_bwd_mse_masked(C.byref(sd), _ptr(A), _ptr(series), *_masked_table(at), C.byref(ps), _ptr(Y),
+                                            _ptr(Ls), Ls.shape[0], float(grad_scale), _stash_ptr(stash), _ptr(loss_buf),
+                                            _ptr(loss), C.byref(gs), _ptr(ws), ws_bytes, _stream())
+        _lib.check(rc, "wgnn_series_bwd_mse_masked")
+        return
     rc = _fn(lib, "bwd_mse", sd)(C.byref(sd), _ptr(A), _ptr(series), *at, C.byref(ps), _ptr(Y), _ptr(Ls), Ls.shape[0],
                                  float(grad_scale), _stash_ptr(stash), _ptr(loss_buf), _ptr(loss), C.byref(gs), _ptr(ws),
                                  ws_bytes, _stream())

@@ -565,12 +565,16 @@ class TrainStep:
                                  prepared=self._prepared)
         return loss, Y
 
-    def _series_refusals(self, A, series, seq_len, stride):
+    def _series_refusals(self, A, series, seq_len, stride, missing_labels=False):
         """What step_series / forward_backward_series refuse, each before any launch and with the alternative."""
         windows = ("materialise the windows and labels (windgnn_amd.data.make_windows(feat, seq_len, starts=...)) and call "
                    "TrainStep.step(A, X, L) on them")
         why = None
-        if self.carry_state:
+        if missing_labels and self.collective:
+            why = ("missing_labels=True under a process group: the mean is over the labels that exist, so the ranks' label counts "
+                   "would have to be exchanged before the backward, which is out of scope; train on one device, or drop the "
+                   "windows that touch a gap (series.segment_starts) and pass missing_labels=False")
+        elif self.carry_state:
             why = ("carry_state=True: every window of series mode starts from h = 0; for truncated BPTT over consecutive chunks "
                    + windows)
         elif self.plan is not None:
@@ -592,7 +596,7 @@ class TrainStep:
             raise ValueError("windgnn_amd: TrainStep.step_series: seq_len and stride must be >= 1, got %r and %r"
                              % (seq_len, stride))
 
-    def _series_forward(self, A, series, Ls, seq_len, stride, n, starts=None):
+    def _series_forward(self, A, series, Ls, seq_len, stride, n, starts=None, **masked):
         """The W_ih images, then wgnn_series_fwd_loss: (Y, stash, loss_buf, sd, d); d = the B-independent dims of the
         tail, as in _empty_shard_step.  starts: the sorted device table instead of (stride, n) -- wgnn_series_fwd_loss_at."""
         _require_gpu(series, Ls, *self.p_views)      # before the images: nothing is launched on host memory
@@ -601,10 +605,10 @@ class TrainStep:
         self._ensure_images(lambda: d)
         if starts is not None:
             Y, stash, loss_buf, sd, _ = series_forward_loss_raw(A, series, Ls, seq_len, None, self.p_views, _lib.MATH_F32,
-                                                                prepared=self._prepared, starts=starts)
+                                                                prepared=self._prepared, starts=starts, **masked)
             return Y, stash, loss_buf, sd, d
         Y, stash, loss_buf, sd = series_forward_loss_raw(A, series, Ls, seq_len, stride, self.p_views, _lib.MATH_F32,
-                                                         n_windows=n, prepared=self._prepared)
+                                                         n_windows=n, prepared=self._prepared, **masked)
         return Y, stash, loss_buf, sd, d
 
     def _series_table(self, series, Ls, seq_len, stride, n_windows, starts):
@@ -634,12 +638,12 @@ class TrainStep:
                                "for TrainStep.step on materialised windows), got %s" % (need, H, tuple(Ls.shape)))
         return n
 
-    def forward_backward_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, starts=None):
+    def forward_backward_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, starts=None, missing_labels=False):
         """forward_backward on the first n_windows sliding windows of `series` [rows, S, 13] with the label series Ls
         [>= (n - 1) * stride + seq_len, H]: returns (loss, Y [n, seq_len, H]); the gradients land in the flat bucket, final (no
-        optimiser step).  `loss` is a view of the bucket's header word.  starts: as in step_series."""
+        optimiser step).  `loss` is a view of the bucket's header word.  starts, missing_labels: as in step_series."""
         seq_len, table, inverse = int(seq_len), None, None
-        self._series_refusals(A, series, seq_len, 1 if stride is None else int(stride))
+        self._series_refusals(A, series, seq_len, 1 if stride is None else int(stride), missing_labels)
         series, Ls = series.contiguous(), Ls.contiguous()
         if starts is not None:
             table, inverse, n = self._series_table(series, Ls, seq_len, stride, n_windows, starts)
@@ -650,12 +654,14 @@ class TrainStep:
             raise RuntimeError("windgnn_amd: TrainStep.forward_backward_series needs at least one window (a series of %d rows, "
                                "seq_len %d, n_windows %r)" % (series.shape[0], seq_len, n_windows))
         at = {} if table is None else {"starts": table}     # (the strided call is the call it has always been)
-        Y, stash, loss_buf, sd, _ = self._series_forward(A, series, Ls, seq_len, stride, n, table)
+        masked = {"missing_labels": True} if missing_labels else {}     # (and so is the call without the flag)
+        Y, stash, loss_buf, sd, _ = self._series_forward(A, series, Ls, seq_len, stride, n, table, **masked)
         series_backward_mse_raw(sd, A, series, self.p_views, Y, Ls, stash, loss_buf, self.g_views, self._loss, 1.0,
-                                prepared=self._prepared, **at)
+                                prepared=self._prepared, **at, **masked)
         return self._loss, (Y if inverse is None else Y.index_select(0, inverse))
 
-    def step_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, n_global=None, starts=None):
+    def step_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, n_global=None, starts=None,
+                    missing_labels=False):
         """One optimiser step on the first `n_windows` (default: all that fit) sliding windows of this rank's `series`
         [rows, S, 13]: window w covers rows w * stride .. w * stride + seq_len - 1 and starts from h = 0, as step() on the
         materialised windows would.  Ls [>= (n - 1) * stride + seq_len, H]: the label SERIES (series_labels(feat, seq_len,
@@ -667,9 +673,12 @@ class TrainStep:
         or tensor in any order, duplicates allowed (series.segment_starts for a series with outages, a hold-out, one block of a
         shuffled epoch).  The loss and the gradients are over the listed windows, the window count is the table's length (an
         empty table: the empty-shard step), Y comes back in the table's order, and Ls needs a row for every row of `series`.
-        The graph convolutions and the input projection still run on every row of `series`."""
+        The graph convolutions and the input projection still run on every row of `series`.
+        missing_labels=True (include/windgnn_series_masked.h): a NaN in Ls means "no label" -- it adds nothing to the loss or to
+        any gradient, and the mean is over the labels that exist (build `series` from the filled table, Ls from the unfilled
+        one).  With no label at all the loss is NaN and the gradients are zero.  Refused under a process group."""
         seq_len, table, inverse = int(seq_len), None, None
-        self._series_refusals(A, series, seq_len, 1 if stride is None else int(stride))
+        self._series_refusals(A, series, seq_len, 1 if stride is None else int(stride), missing_labels)
         series, Ls = series.contiguous(), Ls.contiguous()
         if starts is not None:
             table, inverse, n = self._series_table(series, Ls, seq_len, stride, n_windows, starts)
@@ -680,9 +689,10 @@ class TrainStep:
             return self._empty_shard_step(A, series.new_empty((0, seq_len) + tuple(series.shape[1:])), n_global)
         gs = self.exchange.shard_weight(n, n_global) if self.collective else 1.0
         at = {} if table is None else {"starts": table}     # (the strided call is the call it has always been)
-        Y, stash, loss_buf, sd, d = self._series_forward(A, series, Ls, seq_len, stride, n, table)
+        masked = {"missing_labels": True} if missing_labels else {}     # (and so is the call without the flag)
+        Y, stash, loss_buf, sd, d = self._series_forward(A, series, Ls, seq_len, stride, n, table, **masked)
         series_backward_mse_raw(sd, A, series, self.p_views, Y, Ls, stash, loss_buf, self.g_views, self._loss, gs,
-                                prepared=self._prepared, **at)
+                                prepared=self._prepared, **at, **masked)
         self._run_schedule(d, _FINAL, gs)       # the bucket is final: (the all-reduce,) Adam and the W_ih images
         self._end_step()
         return self._loss, (Y if inverse is None else Y.index_select(0, inverse))
