@@ -31,6 +31,11 @@ GEMM_F32_KLOOP_CASES runs every NT key at seven K steps of 16 columns instead of
 the two-level fold (33 steps in one chunk); tests/test_general_loops_host.py re-derives them, tests/test_gpu_general_loops.py
 proves them on the GPU (next to the CSR layers' item loop: tests/general_cases.py).
 
+The three TN weight-gradient GEMM families (TN_FAMILIES) have theirs: tn_products() restates plan()'s TN launches with their
+contraction over the B*T rows (split-K chunks walked in stages of 32 rows), and TN_KLOOP_CASES runs every key at seven stages a
+chunk instead of two or three, both B sources of the merged launch included; tests/test_tn_kloop_host.py re-derives them,
+tests/test_gpu_tn_kloop.py proves them on the GPU.
+
 The series entry points (wgnn_series_*) have their own half: SERIES_FAMILIES, series_plan() and SERIES_CASES, whose cases are
 (family, key, S, H, rows, T, stride, n, seed, route) with route 'series' (wgnn_series_fwd + wgnn_series_bwd with a signed
 random dY), 'series_mse' (wgnn_series_fwd_loss + wgnn_series_bwd_mse) or 'series_last' (wgnn_series_fwd_last);
@@ -434,6 +439,106 @@ def gemm_f32_keyed(key, S, T, B, H, math, io="f32", state=False, route="train", 
     chunk, the first in launch order among equals (of that role alone where one is given); None where none has the key."""
     mine = [p for p in gemm_f32_products(S, T, B, H, math, io, state, route) if p[0] == key and role in (None, p[1])]
     return max(mine, key=lambda p: p[6])[1:] if mine else None
+
+
+TN_FAMILIES = ("pgemm_tn_kernel", "pgemm_tn2_kernel", "gemm32_tn_kernel")
+TN_ROLES = ("dW_ih", "dW_hh")
+TN_BK = 32                                                  # rows of the contraction per K stage (pgemm.hip: nk = (kend - kbeg + 31) / 32; gemm32.hip: T_BK)
+TN_BM = 320                                                 # output rows per workgroup tile (common.h TN_BM, gemm32.hip T_BM)
+
+
+def pgemm_tn_tiles(Mout, Nout):
+    """pgemm.hip pgemm_tn_tiles: output tiles per K chunk."""
+    return cdiv(Mout, TN_BM) * pgemm_tn_shape(Nout)[0]
+
+
+def gemm32_tn_tiles(Mo, No):
+    """gemm32.hip gemm32_tn_tiles."""
+    return cdiv(Mo, TN_BM) * gemm32_tn_shape(No)[0]
+
+
+def tn_m_hh(H, x3f, dghn):
+    """api.hip make_layout, L.m_hh: GEMM rows of the dW_hh product -- [dGI_r | dGI_z | pad to msplit | dGHn] where the BPTT
+    kernel stores the n third of dGH alone (grux.hip / gru.hip: msplit and hn in units of 8 halfs / 4 floats), else 3 H."""
+    if not dghn:
+        return 3 * H
+    return 8 * cdiv(2 * H, 8) + 8 * cdiv(H, 8) if x3f else 4 * cdiv(2 * H, 4) + H
+
+
+def tn_kchunk(K, sk):
+    """pgemm.hip launch_tn_t / launch_tn2_t, gemm32.hip launch_tn_t: rows per split-K chunk, whole stages of 32."""
+    return cdiv(cdiv(K, sk), TN_BK) * TN_BK
+
+
+def tn_hh_from_y(math, io, state, route):
+    """api.hip hh_from_y under pgemm_tn2_covers, at the library's defaults: the merged launch of the split modes' stateless
+    fp32-I/O step forms dW_hh's [Hprev | 1] rows from the caller's fp32 Y (the caller knows the launch is the merged one)."""
+    return math in ("f16x3", "f16x3g") and io == "f32" and not state and route != "unmerged"
+
+
+def tn_products(S, T, B, H, math, io="f32", state=False, route="train"):
+    """plan()'s launches of the three TN families restated with their contraction, in launch order: one dict per product --
+    a merged launch '<TI+TH..>' gives two, role dW_ih then dW_hh, under the same key.
+      key, role in TN_ROLES; Mout, Nout, tiles (per K chunk); rows = B*T, the contraction;
+      sk, kchunk (rows per chunk) and stages = kchunk / 32, the trip count of the K loop in a full chunk;
+      chunks = the non-empty ones (the splitter rounds kchunk up, so the last of the sk may start past the rows),
+      last_stages / tail = stages of the last non-empty chunk and live rows of its final stage (32: not partial);
+      shift_T = T where B row k is row k - 1 of the h rows and the stored start row where k % T == 0 (0: rows as they lie),
+      per_window = the start row is window k / T's own [h0 | 1];
+      source = where the B operand lies: 'planes' (fp16 hi / lo planes), 'Y' (the merged launch's fp32 Y form) or 'rows'
+      (gemm32.hip's fp32 operand rows: g with its ones column, the [Hprev | 1] rows the forward recurrence wrote).
+    Nothing for gemm.hip's exact-fp32 products (gemm_f32_products() has those) or the inference route.
+    plan() stays the authority for names: tests/test_tn_kloop_host.py holds the keys of the two together, and sk / kchunk to
+    wgnn_tn_split."""
+    assert refusal(S, T, B, H, math, io) is None, (S, T, B, H, math, io)
+    if route == "infer":
+        return []
+    x3f, full = math != "f32", math in ("f16x3", "f16x3g")
+    gen = H > 127 if x3f else H > 128
+    BT, I, G3 = B * T, 13 * S, 3 * H
+    out = []
+
+    def prod(key, role, Mout, Nout, tiles, shift_T, pw, source):
+        sk = pick_splitk(BT, tiles, 256, 64)
+        kchunk = tn_kchunk(BT, sk)
+        chunks = cdiv(BT, kchunk)
+        last = BT - (chunks - 1) * kchunk
+        out.append(dict(key=key, role=role, Mout=Mout, Nout=Nout, tiles=tiles, rows=BT, sk=sk, kchunk=kchunk,
+                        stages=kchunk // TN_BK, chunks=chunks, last_stages=cdiv(last, TN_BK), tail=last - (cdiv(last, TN_BK) - 1) * TN_BK,
+                        shift_T=shift_T, per_window=pw, source=source))
+
+    if not x3f:
+        if gen or not g32_rows(BT, S, H):
+            return out
+        dghn = B > 768                                      # rec32 && g32tn
+        m_hh = tn_m_hh(H, False, dghn)
+        prod(f32_dw_hh(H, BT, True, dghn, state), "dW_hh", m_hh, H + 1, gemm32_tn_tiles(m_hh, H + 1), 0, False, "rows")
+        prod(f32_dw_ih(S, H, BT, True), "dW_ih", G3, I + 1, gemm32_tn_tiles(G3, I + 1), 0, False, "rows")
+        return out
+    dgi1 = math == "f16x3g" and not gen and BT >= 4096
+    gen2p = math == "f16x3g" and gen and BT >= 3072
+    dghn = not gen
+    _, ti = pgemm_tn_shape(I + 1)
+    _, th = pgemm_tn_shape(H + 1)
+    hh_sfx = "" if (full and not (dgi1 if dghn else gen2p)) else (",x2" if full else ",f16")
+    ih_sfx = "" if (full and not (dgi1 or gen2p)) else ",f16"
+    m_hh = tn_m_hh(H, True, dghn)
+    hh = (m_hh, H + 1, pgemm_tn_tiles(m_hh, H + 1), T, bool(state))
+    ih = (G3, I + 1, pgemm_tn_tiles(G3, I + 1), 0, False)
+    if dghn and route != "unmerged":                        # tn_merge, WGNN_OPT_TN_MERGED, pgemm_tn2_covers
+        key = "pgemm_tn_kernel<%d+%d%s>|pw=%d" % (ti, th, hh_sfx, state)
+        prod(key, "dW_ih", *ih, "planes")
+        prod(key, "dW_hh", *hh, "Y" if tn_hh_from_y(math, io, state, route) else "planes")
+    else:
+        prod("pgemm_tn_kernel<%d%s>|a2=%d|pw=%d" % (th, hh_sfx, dghn, state), "dW_hh", *hh, "planes")
+        prod("pgemm_tn_kernel<%d%s>|a2=0|pw=0" % (ti, ih_sfx), "dW_ih", *ih, "planes")
+    return out
+
+
+def tn_carried(key, S, T, B, H, math, io="f32", state=False, route="train"):
+    """The products of tn_products() launched under `key`: one for a plain key, both roles for a merged '<TI+TH..>' key; where
+    a step launches a plain key twice (the same tile count for both products), both."""
+    return [p for p in tn_products(S, T, B, H, math, io, state, route) if p["key"] == key]
 
 
 H_SCAN = 128                                                # past it no register-resident recurrence runs (gen_gru)
@@ -1735,6 +1840,193 @@ GEMM_F32_FOLD_CASES = [
     ("gemm_f32_kernel", "gemm_f32_kernel<128,128>[kk]", 40, 24, 1537, 129, "f32", "f32", False, "train", "GI"),
     ("gemm_f32_kernel", "gemm_f32_kernel<128,128>[kn]", 52, 3, 8161, 171, "f32", "f32", False, "train", "dg"),
 ]
+
+# ---- the K-loop half of the three TN families -----------------------------------------------------------------------------
+# The weight-gradient products contract over the B*T rows, cut into split-K chunks of `kchunk` rows that are walked in stages of
+# 32 rows through a two-slot LDS ring (tn_products()).  The splitter aims at 64 to 96 rows a chunk until sk reaches 256 / tiles,
+# so at the smallest dims that select a key a chunk is two or three stages (CASES: 34 rows, sk = 1, kchunk = 64; the 4098-row
+# keys sk = 64, kchunk = 96) and over every table above no launch of about 100 keys passes three (the exact count:
+# tests/test_tn_kloop_host.py).  TN_KLOOP_CASES gives a second case, same tuple form, to the keys of TN_FAMILIES that CASES
+# claims, walked in CASES order; a key gets one unless an earlier case of THIS table already launches it with every product it
+# carries -- one role for a plain key, both for a merged '<TI+TH..>' key -- at seven stages (tn_seven()).  Dims by rule:
+#   S, H, math, io, state and route are the CASES entry's own;
+#   T = 3: 32 % 3 = 2, so the Y form's y_rem moves and wraps inside a chunk and the window-start mask meets every stage offset;
+#   B = the smallest for which every carried product has kchunk >= 224 (TN_KLOOP_STAGES stages), B*T is no multiple of 32 (the
+#       final stage is partial), the last non-empty chunk of every carried product has at least two stages (the partial stage
+#       is zeroed in a slot that held an earlier one) and plan() still selects the key.
+# One tile a chunk (sk = 256) gives B = 16 385: 49 155 rows, 220 chunks, the last of 99 rows -- four stages, three live rows in
+# the fourth; two tiles (sk = 128: dW_hh of H = 128 ... 192) B = 8193; six (H = 224: sk = 40) B = 2561, 7683 rows.
+# Seven: as KLOOP_STAGES -- odd, and each of the two slots is rewritten after it was read at least twice.
+# Plane-form twins: every merged pw=0 key of the split modes forms dW_hh's B rows from fp32 Y at fp32 I/O (tn_hh_from_y());
+# each has a second entry with bf16 I/O, which keeps the fp16 planes, so that both B sources of the same instantiation reach
+# seven stages (tn_products()' `source`).  The rule skips three keys -- pgemm_tn_kernel<1>|a2=1|pw=0, <1,f16>|a2=1|pw=0 and
+# gemm32_tn_kernel<1>|a2=1: the case of the <1>..|a2=0 key before each launches them at seven stages -- and no key leaves it:
+# 105 keys and 14 twins, 119 cases on 39 distinct (S, T, B, H, io, state).  tests/test_tn_kloop_host.py re-derives every
+# entry and qualifies the inputs on the oracle alone, tests/test_gpu_tn_kloop.py runs them.
+#
+# ONE deviation, TN_KLOOP_B_MOVED: the carried-state cases of six (S, H) run the first B ABOVE the rule's whose draw
+# qualifies, because the rule's own draw does not -- a defect of the inputs, not of a kernel.  The carried-state step
+# back-propagates a signed random dY, so every gradient is a sum of B*T (x S) cancelling terms, and two things that average
+# out of the MSE step's coherent sums (no stateless case is touched) show at full size:
+#   ReLU ties.  ONE term is ~1e-3 of a conv gradient's max.  A pre-activation of the fp64 reference within half an fp32 ulp of
+#     zero (relative to the magnitudes of its 13 terms) has no sign to fp32 accuracy, and where a kernel -- or the reference itself
+#     in fp32 -- lands on the other side the two differ by that whole term.  With 0.6 to 9.6 million pre-activations a case:
+#     (8, 64)   B = 16 385: layer-2 element 1 665 318 is 1.6e-8 of its terms from zero (z = -2.8e-8).  Measured on the MI355X:
+#               pgemm_tn_kernel<4+3>|pw=1 (f16x3) conv1.weight 9.41e-4, conv1.bias 8.70e-4, conv2.weight 1.18e-3, conv2.bias 6.75e-4
+#               against the bar of 1e-4, every GRU gradient <= 4.9e-7; flipping that ONE mask element in the fp64 reference
+#               moves the four by 9.29e-4, 8.58e-4, 1.17e-3, 6.74e-4.  (<4+3,x2>|pw=1: 1.25e-3 against 1e-3, the same element.)
+#     (13, 32)  B = 16 385: the reference's own fp32 evaluation is 1.5e-4 / 1.6e-4 off its fp64 one on conv1.weight / conv1.bias
+#     (5, 96), (10, 4), (15, 64)   elements at 5.2e-8, 1.4e-8 and 5.9e-9 whose flip costs 2.2e-3, 2.5e-4 and 1.7e-4 of max (the
+#               MI355X happened to land on the reference's side of all three: <= 6.2e-5 measured)
+#   f16x3g's single plane.  From 4096 rows that mode rounds dGI / dGHn to ONE fp16 plane and forms dW_ih as hi(dGI)^T hi(g):
+#     2^-11 of each element, which the imported bar of such a case allows for (1e-3).  The fp64 step with those operands
+#     rounded reproduces the MI355X's figures to two digits and depends on the draw: at (10, 4) it moves gru.weight_ih_l0 by
+#     5.5e-4, 1.09e-3, 3.1e-4, 1.5e-3 and 2.4e-4 of max at B = 16 385 ... 16 389 (measured at 16 385 / 16 386: 5.61e-4 /
+#     1.10e-3 -- above the bar with no kernel at fault), at (1, 96) conv2.weight by 5.1e-4, at (13, 32) and B = 16 386 conv1.bias
+#     by 5.7e-4.  A draw qualifies where that rounding alone stays within half the bar.
+# The moved B keeps every condition of the rule (49 158 ... 49 173 rows: tails of 6 to 21 live rows instead of 3); the host test
+# shows that every B from the rule's up to the tabled one fails the qualification -- fp32 against fp64, the tie check or the
+# single-plane check -- and that the tabled one passes.
+TN_KLOOP_STAGES = 7
+TN_KLOOP_T = 3
+TN_KLOOP_TWIN_IO = "bf16"
+TN_KLOOP_B_MOVED = {(1, 96): 16386, (5, 96): 16389, (8, 64): 16386, (10, 4): 16387, (13, 32): 16391, (15, 64): 16388}    # (S, H) of a carried-state case -> B
+
+
+def tn_seven(p):
+    """A product of tn_products() is taken to seven stages: full chunks of at least TN_KLOOP_STAGES stages, a partial final
+    stage, and a last non-empty chunk of at least two stages."""
+    return p["kchunk"] >= TN_KLOOP_STAGES * TN_BK and p["rows"] % TN_BK != 0 and p["last_stages"] >= 2
+
+
+TN_KLOOP_CASES = [
+    # ---- pgemm_tn_kernel
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<1>|a2=0|pw=0", 1, 3, 16385, 4, "f16x3", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<1,f16>|a2=0|pw=0", 1, 3, 16385, 4, "f16", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<2>|a2=0|pw=0", 3, 3, 16385, 4, "f16x3", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<2,f16>|a2=0|pw=0", 3, 3, 16385, 4, "f16", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<3>|a2=0|pw=0", 5, 3, 16385, 4, "f16x3", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<3,f16>|a2=0|pw=0", 5, 3, 16385, 4, "f16", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<4>|a2=0|pw=0", 8, 3, 16385, 4, "f16x3", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<4>|a2=0|pw=1", 1, 3, 2561, 224, "f16x3", "f32", True, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<4,x2>|a2=0|pw=0", 1, 3, 2561, 224, "f16x3g", "f32", False, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<4,x2>|a2=0|pw=1", 1, 3, 2561, 224, "f16x3g", "f32", True, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<4,f16>|a2=0|pw=0", 8, 3, 16385, 4, "f16", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<4,f16>|a2=0|pw=1", 1, 3, 2561, 224, "f16", "f32", True, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<5>|a2=0|pw=0", 10, 3, 16385, 4, "f16x3", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<5>|a2=0|pw=1", 1, 3, 8193, 128, "f16x3", "f32", True, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<5,x2>|a2=0|pw=0", 1, 3, 8193, 128, "f16x3g", "f32", False, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<5,x2>|a2=0|pw=1", 1, 3, 8193, 128, "f16x3g", "f32", True, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<5,f16>|a2=0|pw=0", 10, 3, 16385, 4, "f16", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<5,f16>|a2=0|pw=1", 1, 3, 8193, 128, "f16", "f32", True, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<6>|a2=0|pw=0", 13, 3, 16385, 4, "f16x3", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<6>|a2=0|pw=1", 1, 3, 8193, 160, "f16x3", "f32", True, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<6,x2>|a2=0|pw=0", 1, 3, 8193, 160, "f16x3g", "f32", False, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<6,x2>|a2=0|pw=1", 1, 3, 8193, 160, "f16x3g", "f32", True, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<6,f16>|a2=0|pw=0", 13, 3, 16385, 4, "f16", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<6,f16>|a2=0|pw=1", 1, 3, 8193, 160, "f16", "f32", True, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<7>|a2=0|pw=0", 15, 3, 16385, 4, "f16x3", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<7>|a2=0|pw=1", 1, 3, 8193, 192, "f16x3", "f32", True, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<7,x2>|a2=0|pw=0", 1, 3, 8193, 192, "f16x3g", "f32", False, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<7,x2>|a2=0|pw=1", 1, 3, 8193, 192, "f16x3g", "f32", True, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<7,f16>|a2=0|pw=0", 15, 3, 16385, 4, "f16", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<7,f16>|a2=0|pw=1", 1, 3, 8193, 192, "f16", "f32", True, "train"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<1>|a2=1|pw=1", 1, 3, 16385, 4, "f16x3", "f32", True, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<1,x2>|a2=1|pw=0", 1, 3, 16385, 4, "f16x3g", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<1,x2>|a2=1|pw=1", 1, 3, 16385, 4, "f16x3g", "f32", True, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<1,f16>|a2=1|pw=1", 1, 3, 16385, 4, "f16", "f32", True, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<2>|a2=1|pw=0", 1, 3, 16385, 32, "f16x3", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<2>|a2=1|pw=1", 1, 3, 16385, 32, "f16x3", "f32", True, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<2,x2>|a2=1|pw=0", 1, 3, 16385, 32, "f16x3g", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<2,x2>|a2=1|pw=1", 1, 3, 16385, 32, "f16x3g", "f32", True, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<2,f16>|a2=1|pw=0", 1, 3, 16385, 32, "f16", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<2,f16>|a2=1|pw=1", 1, 3, 16385, 32, "f16", "f32", True, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<3>|a2=1|pw=0", 1, 3, 16385, 64, "f16x3", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<3>|a2=1|pw=1", 1, 3, 16385, 64, "f16x3", "f32", True, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<3,x2>|a2=1|pw=0", 1, 3, 16385, 64, "f16x3g", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<3,x2>|a2=1|pw=1", 1, 3, 16385, 64, "f16x3g", "f32", True, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<3,f16>|a2=1|pw=0", 1, 3, 16385, 64, "f16", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<3,f16>|a2=1|pw=1", 1, 3, 16385, 64, "f16", "f32", True, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<4>|a2=1|pw=0", 1, 3, 16385, 96, "f16x3", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<4>|a2=1|pw=1", 1, 3, 16386, 96, "f16x3", "f32", True, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<4,x2>|a2=1|pw=0", 1, 3, 16385, 96, "f16x3g", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<4,x2>|a2=1|pw=1", 1, 3, 16386, 96, "f16x3g", "f32", True, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<4,f16>|a2=1|pw=0", 1, 3, 16385, 96, "f16", "f32", False, "unmerged"),
+    ("pgemm_tn_kernel", "pgemm_tn_kernel<4,f16>|a2=1|pw=1", 1, 3, 16386, 96, "f16", "f32", True, "unmerged"),
+    # ---- pgemm_tn2_kernel (the bf16 entries: the plane-form twins)
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<1+2>|pw=0", 1, 3, 16385, 32, "f16x3", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<1+2>|pw=0", 1, 3, 16385, 32, "f16x3", "bf16", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<1+2>|pw=1", 1, 3, 16385, 32, "f16x3", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<1+2,x2>|pw=0", 1, 3, 16385, 32, "f16x3g", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<1+2,x2>|pw=0", 1, 3, 16385, 32, "f16x3g", "bf16", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<1+2,x2>|pw=1", 1, 3, 16385, 32, "f16x3g", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<1+2,f16>|pw=0", 1, 3, 16385, 32, "f16", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<1+2,f16>|pw=1", 1, 3, 16385, 32, "f16", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<2+1>|pw=0", 3, 3, 16385, 4, "f16x3", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<2+1>|pw=0", 3, 3, 16385, 4, "f16x3", "bf16", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<2+1>|pw=1", 3, 3, 16385, 4, "f16x3", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<2+1,x2>|pw=0", 3, 3, 16385, 4, "f16x3g", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<2+1,x2>|pw=0", 3, 3, 16385, 4, "f16x3g", "bf16", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<2+1,x2>|pw=1", 3, 3, 16385, 4, "f16x3g", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<2+1,f16>|pw=0", 3, 3, 16385, 4, "f16", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<2+1,f16>|pw=1", 3, 3, 16385, 4, "f16", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<3+4>|pw=0", 5, 3, 16385, 96, "f16x3", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<3+4>|pw=0", 5, 3, 16385, 96, "f16x3", "bf16", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<3+4>|pw=1", 5, 3, 16389, 96, "f16x3", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<3+4,x2>|pw=0", 5, 3, 16385, 96, "f16x3g", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<3+4,x2>|pw=0", 5, 3, 16385, 96, "f16x3g", "bf16", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<3+4,x2>|pw=1", 5, 3, 16389, 96, "f16x3g", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<3+4,f16>|pw=0", 5, 3, 16385, 96, "f16", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<3+4,f16>|pw=1", 5, 3, 16389, 96, "f16", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<4+3>|pw=0", 8, 3, 16385, 64, "f16x3", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<4+3>|pw=0", 8, 3, 16385, 64, "f16x3", "bf16", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<4+3>|pw=1", 8, 3, 16386, 64, "f16x3", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<4+3,x2>|pw=0", 8, 3, 16385, 64, "f16x3g", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<4+3,x2>|pw=0", 8, 3, 16385, 64, "f16x3g", "bf16", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<4+3,x2>|pw=1", 8, 3, 16386, 64, "f16x3g", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<4+3,f16>|pw=0", 8, 3, 16385, 64, "f16", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<4+3,f16>|pw=1", 8, 3, 16386, 64, "f16", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<5+1>|pw=0", 10, 3, 16385, 4, "f16x3", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<5+1>|pw=0", 10, 3, 16385, 4, "f16x3", "bf16", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<5+1>|pw=1", 10, 3, 16387, 4, "f16x3", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<5+1,x2>|pw=0", 10, 3, 16385, 4, "f16x3g", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<5+1,x2>|pw=0", 10, 3, 16385, 4, "f16x3g", "bf16", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<5+1,x2>|pw=1", 10, 3, 16387, 4, "f16x3g", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<5+1,f16>|pw=0", 10, 3, 16385, 4, "f16", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<5+1,f16>|pw=1", 10, 3, 16387, 4, "f16", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<6+2>|pw=0", 13, 3, 16385, 32, "f16x3", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<6+2>|pw=0", 13, 3, 16385, 32, "f16x3", "bf16", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<6+2>|pw=1", 13, 3, 16391, 32, "f16x3", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<6+2,x2>|pw=0", 13, 3, 16385, 32, "f16x3g", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<6+2,x2>|pw=0", 13, 3, 16385, 32, "f16x3g", "bf16", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<6+2,x2>|pw=1", 13, 3, 16391, 32, "f16x3g", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<6+2,f16>|pw=0", 13, 3, 16385, 32, "f16", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<6+2,f16>|pw=1", 13, 3, 16391, 32, "f16", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<7+3>|pw=0", 15, 3, 16385, 64, "f16x3", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<7+3>|pw=0", 15, 3, 16385, 64, "f16x3", "bf16", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<7+3>|pw=1", 15, 3, 16388, 64, "f16x3", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<7+3,x2>|pw=0", 15, 3, 16385, 64, "f16x3g", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<7+3,x2>|pw=0", 15, 3, 16385, 64, "f16x3g", "bf16", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<7+3,x2>|pw=1", 15, 3, 16388, 64, "f16x3g", "f32", True, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<7+3,f16>|pw=0", 15, 3, 16385, 64, "f16", "f32", False, "train"),
+    ("pgemm_tn2_kernel", "pgemm_tn_kernel<7+3,f16>|pw=1", 15, 3, 16388, 64, "f16", "f32", True, "train"),
+    # ---- gemm32_tn_kernel
+    ("gemm32_tn_kernel", "gemm32_tn_kernel<1>|a2=0", 1, 3, 16385, 4, "f32", "f32", False, "train"),
+    ("gemm32_tn_kernel", "gemm32_tn_kernel<2>|a2=0", 3, 3, 16385, 4, "f32", "f32", False, "train"),
+    ("gemm32_tn_kernel", "gemm32_tn_kernel<2>|a2=1", 1, 3, 16385, 32, "f32", "f32", False, "train"),
+    ("gemm32_tn_kernel", "gemm32_tn_kernel<3>|a2=0", 5, 3, 16385, 4, "f32", "f32", False, "train"),
+    ("gemm32_tn_kernel", "gemm32_tn_kernel<3>|a2=1", 1, 3, 16385, 64, "f32", "f32", False, "train"),
+    ("gemm32_tn_kernel", "gemm32_tn_kernel<4>|a2=0", 8, 3, 16385, 4, "f32", "f32", False, "train"),
+    ("gemm32_tn_kernel", "gemm32_tn_kernel<4>|a2=1", 1, 3, 16385, 96, "f32", "f32", False, "train"),
+    ("gemm32_tn_kernel", "gemm32_tn_kernel<5>|a2=0", 10, 3, 16385, 4, "f32", "f32", False, "train"),
+    ("gemm32_tn_kernel", "gemm32_tn_kernel<5>|a2=1", 1, 3, 8193, 128, "f32", "f32", False, "train"),
+    ("gemm32_tn_kernel", "gemm32_tn_kernel<6>|a2=0", 13, 3, 16385, 4, "f32", "f32", False, "train"),
+    ("gemm32_tn_kernel", "gemm32_tn_kernel<7>|a2=0", 15, 3, 16385, 4, "f32", "f32", False, "train"),
+]
+
+# One-pass fp16 cases of TN_KLOOP_CASES above the imported bars, (key, tensor) -> bar: none (as KLOOP_F16_EXCEPTIONS; kept apart
+# for the same reason)
+TN_KLOOP_F16_EXCEPTIONS = {}
 
 # ---- the series entry points -------------------------------------------------------------------------------------------
 # (family, key, S, H, rows, T, stride, n, seed, route); the inputs are tests/test_gpu_series.py's _draw(S, H, rows, T, stride, n,

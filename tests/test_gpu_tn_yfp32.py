@@ -7,8 +7,13 @@ Shapes (S, T, B, H) and what each can break:
   (3, 2, 1, 5)       a one-row Hprev, H far from a multiple of 8
   (3, 5, 3, 5)       t = 0 rows inside a stage, at rows 0, 5 and 10
   (7, 12, 4, 20)     48 rows: a stage boundary falls mid-window, with an odd shift
-  (34, 24, 17, 102)  408 rows: more than one 384-row K chunk with a ragged tail, at the bench's H
+  (34, 24, 17, 102)  408 rows: five K chunks of 96 rows (wgnn_tn_split: sk = 6), the last a ragged 24, at the bench's H
   (7, 3, 11, 101)    33 rows: odd H, so the stage blocks start on 4-byte boundaries only; one row past a stage
+  (3, 3, 16491, 5)   49 473 rows: 221 chunks of seven stages (sk = 256, kchunk = 224), the last with a one-row tail; T = 3, so
+                     y_rem moves by 32 % 3 = 2 a stage and wraps inside a chunk, and both ring slots are rewritten after a read
+  (3, 24, 2062, 101) 49 488 rows: seven stages again, a 16-row tail; odd H (4-byte stage boundaries, y_d4 realigned) and
+                     y_step = 32 % 24 = 8
+The last two hold the Y form to the plane form bit for bit past three stages (tests/instance_cases.py tn_products()).
 f16x3g runs the same kernels as f16x3 at these sizes: its single-plane dGI, and with it the two-pass dW_hh, starts at
 B*T = 4096, where tests/test_gpu_tn_merged.py (34, 24, 176, 102) compares the merged launch -- the Y form -- with the plane
 form's two launches bit for bit.
@@ -25,7 +30,7 @@ from test_gpu_parity import G_TOL, IO_ROUND, Y_TOL
 pytestmark = pytest.mark.gpu
 
 MATH = {"f16x3": 1, "f16x3g": 3}
-SHAPES = [(3, 2, 1, 5), (3, 5, 3, 5), (7, 12, 4, 20), (34, 24, 17, 102), (7, 3, 11, 101)]
+SHAPES = [(3, 2, 1, 5), (3, 5, 3, 5), (7, 12, 4, 20), (34, 24, 17, 102), (7, 3, 11, 101), (3, 3, 16491, 5), (3, 24, 2062, 101)]
 FILL = 0x5A                                        # what a stash holds before the forward: no kernel writes this byte pattern
 
 
