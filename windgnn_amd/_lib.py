@@ -239,6 +239,28 @@ EXPORTS_SERIES_MASKED = {
                                          C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# include/windgnn_series_lossfn.h: series training on a loss spec -- MSE / L1 / Huber, from a warm-up step on (a tenth header and table)
+SERIES_LOSSFN_VERSION = 1   # WGNN_SERIES_LOSSFN_VERSION
+LOSS_MSE, LOSS_L1, LOSS_HUBER = 0, 1, 2
+LOSS_KINDS = {"mse": LOSS_MSE, "l1": LOSS_L1, "huber": LOSS_HUBER}
+
+
+class LossFn(C.Structure):
+    """wgnn_lossfn"""
+    _fields_ = [("kind", C.c_int32), ("delta", C.c_float), ("t_from", C.c_int32), ("masked", C.c_int32)]
+
+
+EXPORTS_SERIES_LOSSFN = {
+    "wgnn_series_lossfn_version": (C.c_int, []),
+    "wgnn_series_lossfn_bytes": (C.c_size_t, [_SD]),
+    "wgnn_series_fwd_lossfn": (C.c_int, [_SD, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_int64,
+                                         C.POINTER(LossFn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.c_void_p]),
+    "wgnn_series_bwd_lossfn": (C.c_int, [_SD, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p,
+                                         C.c_int64, C.c_float, C.POINTER(LossFn), C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(Grads), C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -317,6 +339,16 @@ def load() -> C.CDLL:
     if lib.wgnn_series_masked_version() < SERIES_MASKED_VERSION:
         raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_series_masked_version %d < %d)"
                            % (lib.wgnn_series_masked_version(), SERIES_MASKED_VERSION))
+    if not hasattr(lib, "wgnn_series_lossfn_version"):
+        raise RuntimeError("windgnn_amd: %s predates include/windgnn_series_lossfn.h (no wgnn_series_lossfn_version): rebuild it "
+                           "with `python -m windgnn_amd.build --force`" % LIB_PATH)
+    for name, (res, args) in EXPORTS_SERIES_LOSSFN.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.wgnn_series_lossfn_version() < SERIES_LOSSFN_VERSION:
+        raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_series_lossfn_version %d < %d)"
+                           % (lib.wgnn_series_lossfn_version(), SERIES_LOSSFN_VERSION))
     if lib.wgnn_series_at_version() < SERIES_AT_VERSION:
         raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_series_at_version %d < %d)"
                            % (lib.wgnn_series_at_version(), SERIES_AT_VERSION))

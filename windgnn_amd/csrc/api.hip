@@ -974,7 +974,8 @@ namespace {
 // window w begins at row starts[w], clamped into [0, rows - T], instead of w * stride -- the recurrence is the only reader
 int series_forward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
                    float* Y, float* last, float wind_min, float wind_max, void* stash, void* workspace, const SeriesPlan& sp,
-                   void* stream, const float* Ls, int64_t ls_rows, float* loss_buf, const int* starts, bool masked = false) {
+                   void* stream, const float* Ls, int64_t ls_rows, float* loss_buf, const int* starts, bool masked = false,
+                   const LossFn* lossfn = nullptr) {
   const int last_start = df->T - dr->T;        // the largest legal start: rows - T
   const Layout Lf = make_layout(df, false, SER_FRONT), Lr = make_layout(dr, false, SER_REC);
   FwdCall cf(workspace, sizeof(float) * sp.ws_front, stream);
@@ -990,7 +991,7 @@ int series_forward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const f
   float* sr = stash ? (float*)stash + sp.st_front : nullptr;
   return launch_gru_fwd(dr->B, dr->T, dr->H, f.GI, ld, p->w_hh, p->b_hh, Y, sr ? sr + Lr.st_gates : nullptr, Ls, loss_buf,
                         sr && Lr.g32tn ? sr + Lr.st_hprev : nullptr, Lr.hq, 0, 1.f, 0.f, st, nullptr, nullptr, stride, ls_rows,
-                        starts, last_start, masked);
+                        starts, last_start, masked, lossfn);
 }
 
 // dY, or Ls with the forward's loss_buf (wgnn_series_bwd_mse): BPTT forms dY = (Y - label) 2 grad_scale / (n T H) itself and its
@@ -998,7 +999,7 @@ int series_forward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const f
 int series_backward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
                     const float* Y, const float* dY, const void* stash, const wgnn_grads* g, void* workspace, const SeriesPlan& sp,
                     void* stream, const float* Ls, int64_t ls_rows, float grad_scale, const float* loss_buf, float* loss,
-                    const int* starts, bool masked = false) {
+                    const int* starts, bool masked = false, const LossFn* lossfn = nullptr) {
   const Layout Lf = make_layout(df, false, SER_FRONT), Lr = make_layout(dr, false, SER_REC);
   const float* sff = (const float*)stash;
   BwdCall cr((float*)workspace + sp.ws_front, sizeof(float) * sp.ws_rec, stream);
@@ -1011,7 +1012,7 @@ int series_backward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const 
   int rc = launch_gru_bwd(dr->B, dr->T, dr->H, p->w_hh, Y, dY, Ls, br.sf + Lr.st_gates, sff + Lf.st_GI, (int)Lf.Gp, br.dGI,
                           (int)Lr.Gp, Lr.dghn ? br.dGH : nullptr, Lr.dghn ? nullptr : br.dGH, loss_buf, (int64_t)Lr.BT * Lr.H,
                           grad_scale, loss, Ls ? br.status : nullptr, br.st, nullptr, stride, ls_rows, starts,
-                          df->T - dr->T, masked);
+                          df->T - dr->T, masked, lossfn);
   if (rc != WGNN_OK) return rc;
   // 2. dW_hh | db_hh over the n * T window-major rows
   rc = bwd_weights(br, WGNN_ROWS_HH, 0, (int)Lr.G3);
@@ -1047,17 +1048,17 @@ size_t series_masked_loss_floats(int n) { return series_loss_floats(n) + (size_t
 
 int series_fwd_loss(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
                     const float* Ls, int64_t ls_rows, float* Y, void* stash, float* loss_buf, void* workspace,
-                    const SeriesPlan& sp, void* stream, const int* starts, bool masked) {
+                    const SeriesPlan& sp, void* stream, const int* starts, bool masked, const LossFn* lossfn) {
   return series_forward(df, dr, stride, A, Xs, p, Y, nullptr, 0.f, 1.f, stash, workspace, sp, stream, Ls, ls_rows, loss_buf,
-                        starts, masked);
+                        starts, masked, lossfn);
 }
 
 int series_bwd_mse(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
                    const float* Y, const float* Ls, int64_t ls_rows, float grad_scale, const void* stash, const float* loss_buf,
                    float* loss, const wgnn_grads* g, void* workspace, const SeriesPlan& sp, void* stream, const int* starts,
-                   bool masked) {
+                   bool masked, const LossFn* lossfn) {
   return series_backward(df, dr, stride, A, Xs, p, Y, nullptr, stash, g, workspace, sp, stream, Ls, ls_rows, grad_scale, loss_buf,
-                         loss, starts, masked);
+                         loss, starts, masked, lossfn);
 }
 
 extern "C" {

@@ -107,6 +107,16 @@ __device__ __forceinline__ BwdState bwd_state(SeriesStarts) { return BwdState{nu
 struct MaskedLabels {};
 __device__ __forceinline__ BwdState bwd_state(SeriesRows, MaskedLabels) { return BwdState{nullptr, nullptr, nullptr}; }
 __device__ __forceinline__ BwdState bwd_state(SeriesStarts, MaskedLabels) { return BwdState{nullptr, nullptr, nullptr}; }
+// A loss spec (include/windgnn_series_lossfn.h: wgnn_lossfn's fields) in the same place BEHIND the row mapping: the loss kind,
+// Huber's delta, the first step that counts and whether a NaN label is "no label".  Kernel arguments, so wave-uniform: the
+// kernels branch on them as scalars, one instance per K and row mapping.  New instances only, as above.
+struct LossFn { int kind; float delta; int t_from; int masked; };
+static inline bool lossfn_valid(const LossFn& f, int T) {   // delta counts for Huber (kind 2) alone
+  return f.kind >= 0 && f.kind <= 2 && (f.masked == 0 || f.masked == 1) && f.t_from >= 0 && f.t_from < T &&
+         (f.kind != 2 || (f.delta > 0.f && f.delta < __builtin_inff()));
+}
+__device__ __forceinline__ BwdState bwd_state(SeriesRows, LossFn) { return BwdState{nullptr, nullptr, nullptr}; }
+__device__ __forceinline__ BwdState bwd_state(SeriesStarts, LossFn) { return BwdState{nullptr, nullptr, nullptr}; }
 
 // ---- internal launchers (defined in the .hip files, used by api.hip) -------------------------
 struct GemmArgs {
@@ -168,6 +178,9 @@ int launch_grux_bwd(int B, int T, int H, const float* Whh, const void* Y, const 
                     const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given, no labels*/);
 #define WGNN_STATS_TAG 20261004.0f   // float word behind the MSE partial pairs: "wgnn_fwd_loss wrote these"
 #define WGNN_STATS_TAG_MASKED 20261019.0f   // the same word from wgnn_series_fwd_loss_masked: sums over the labels that exist
+// a third value from wgnn_series_fwd_lossfn (fp32 spacing is 2 up here: 20261019 IS 20261020), which also fills the three spare
+// words behind it with its spec as integers: kind | masked << 8, the bits of delta (0 unless Huber), t_from
+#define WGNN_STATS_TAG_LOSSFN 20261030.0f
 // the masked loss_buf: [nb sums | nb maxima | tag | 3 spare words | nb uint32 label counts], nb = gru_blocks(n)
 __host__ __device__ __forceinline__ unsigned* masked_counts(float* stat_part, int nb) {
   return (unsigned*)(stat_part + 2 * (size_t)nb + 4);
@@ -315,7 +328,8 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
                    int series_stride = 0 /*> 0: GI is one series [rows][ldgi], window w at rows w * stride + t (no h0)*/,
                    int64_t ls_rows = 0 /*series with labels: they are one series too, Ls [ls_rows][H], read at the same rows*/,
                    const int* starts = nullptr /*instead of a stride: window w at rows clamp(starts[w], 0, starts_last) + t*/,
-                   int starts_last = 0, bool masked = false /*series with labels: NaN = no label, counts behind stat_part*/);
+                   int starts_last = 0, bool masked = false /*series with labels: NaN = no label, counts behind stat_part*/,
+                   const LossFn* lossfn = nullptr /*series with labels: the spec's statistics, counts, tag and spare words*/);
 //   backward: exactly one of dY / labels; dGI [B*T][ldd] and EITHER dGHn [B*T][gru_hn(H)] (dGH's r and z thirds equal
 //   dGI's) OR the full dGH [B*T][ldd]; stat_part (nullable, with labels): loss[0] is finalised from the forward's partials
 int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
@@ -325,7 +339,8 @@ int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const 
                    int series_stride = 0 /*> 0: GI is one series, as in launch_gru_fwd (no state)*/,
                    int64_t ls_rows = 0 /*series with labels: Ls [ls_rows][H], as in launch_gru_fwd*/,
                    const int* starts = nullptr /*instead of a stride, as in launch_gru_fwd*/, int starts_last = 0,
-                   bool masked = false /*as in launch_gru_fwd: n_loss is then the forward's count, summed in the kernel*/);
+                   bool masked = false /*as in launch_gru_fwd: n_loss is then the forward's count, summed in the kernel*/,
+                   const LossFn* lossfn = nullptr /*as in launch_gru_fwd: n_loss is then B (T - t_from) H, or the count*/);
 bool gru_shape_supported(int H);
 size_t gru_gates_floats(int B, int T, int H);
 int gru_blocks(int B);
@@ -371,11 +386,12 @@ size_t series_loss_floats(int n);
 size_t series_masked_loss_floats(int n);   // + gru_blocks(n) label counts (include/windgnn_series_masked.h)
 int series_fwd_loss(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs,
                     const wgnn_params* p, const float* Ls, int64_t ls_rows, float* Y, void* stash /*nullable*/, float* loss_buf,
-                    void* workspace, const SeriesPlan& sp, void* stream, const int* starts = nullptr, bool masked = false);
+                    void* workspace, const SeriesPlan& sp, void* stream, const int* starts = nullptr, bool masked = false,
+                    const LossFn* lossfn = nullptr /*include/windgnn_series_lossfn.h*/);
 int series_bwd_mse(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs,
                    const wgnn_params* p, const float* Y, const float* Ls, int64_t ls_rows, float grad_scale, const void* stash,
                    const float* loss_buf, float* loss, const wgnn_grads* g, void* workspace, const SeriesPlan& sp, void* stream,
-                   const int* starts = nullptr, bool masked = false);
+                   const int* starts = nullptr, bool masked = false, const LossFn* lossfn = nullptr);
 // dGIs [rows][ld] = the sum, in ascending w, of the window-major rows dGI [(w, tau - w * stride)][ld] that cover hour tau;
 // uncovered rows and the columns [G3, ld) are written as zeros (series.hip)
 int launch_series_fold(const float* dGI, int n, int T, int stride, int rows, int G3, int ld, float* dGIs, hipStream_t st);

@@ -67,6 +67,43 @@ __device__ __forceinline__ int series_start(int w, S... s) {
   const SeriesStarts ss = first_of(s...);
   return min(max(ss.starts[w], 0), ss.last);
 }
+__device__ __forceinline__ LossFn lossfn_of(SeriesRows, LossFn f) { return f; }     // the loss spec of a pack that has one
+__device__ __forceinline__ LossFn lossfn_of(SeriesStarts, LossFn f) { return f; }
+// the first spare word behind the tag (common.h: WGNN_STATS_TAG_LOSSFN); the second holds delta's bits for Huber and 0 otherwise
+__device__ __forceinline__ unsigned lossfn_word(LossFn f) { return (unsigned)f.kind | (unsigned)f.masked << 8; }
+__device__ __forceinline__ unsigned lossfn_delta(LossFn f) { return f.kind == 2 ? __float_as_uint(f.delta) : 0u; }
+// The three kinds without a branch in the recurrences' steps.  With d = h - label and a = |d|, the forward adds
+//   fmaf(a > thr ? lin : q d,  a > thr ? a - off : d,  sum):   MSE  thr = inf:  fmaf(d, d, sum), the other instances' chain
+//                                                              L1   thr = -1:   sum + a        Huber  thr = delta:  both arms
+// and BPTT takes rho'(d) = a > gthr ? copysign(lin, d) : d (MSE: d, the 2 is in the factor; L1: gthr = 0, so sign(0) = 0;
+// Huber: the clamp).  A NaN fails both comparisons and stays a NaN.
+struct LossArms { float thr, q, lin, off, gthr; };
+__device__ __forceinline__ LossArms loss_arms(LossFn f) {
+  if (f.kind == 1) return LossArms{-1.f, 1.f, 1.f, 0.f, 0.f};
+  if (f.kind == 2) return LossArms{f.delta, 0.5f, f.delta, 0.5f * f.delta, f.delta};
+  return LossArms{__builtin_inff(), 1.f, 1.f, 0.f, __builtin_inff()};
+}
+// did wgnn_series_fwd_lossfn write this buffer, with this spec?
+__device__ __forceinline__ bool lossfn_paired(const float* stat_part, int nb, LossFn f) {
+  const unsigned* w = (const unsigned*)(stat_part + 2 * (size_t)nb + 1);
+  return stat_part[2 * (size_t)nb] == WGNN_STATS_TAG_LOSSFN && w[0] == lossfn_word(f) && w[1] == lossfn_delta(f) &&
+         w[2] == (unsigned)f.t_from;
+}
+
+// unsigned long long c = the sum of a forward's n per-workgroup label counts, formed by every thread of a BPTT workgroup
+// (integers: any order; uses the kernel's `lane` and `wave`).  read (workgroup-uniform) = false: nothing is loaded, c = 0.
+// A macro, not a function: both users expand the text the masked instances were compiled from, so their code stays as it was.
+#define BLOCK_COUNT_SUM(c, counts, n, read)                                       \
+  __shared__ unsigned long long cred[NTHREADS / 64];                              \
+  const unsigned* cnts = (counts);                                                \
+  unsigned long long c = 0;                                                       \
+  if (read)                                                                       \
+    for (int i = threadIdx.x; i < (n); i += NTHREADS) c += cnts[i];               \
+  _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);   \
+  if (lane == 0) cred[wave] = c;                                                  \
+  __syncthreads();                                                                \
+  c = 0;                                                                          \
+  _Pragma("unroll") for (int w = 0; w < NTHREADS / 64; ++w) c += cred[w]
 
 // gate stash: grux.hip's layout, [workgroup][t][wave][r | z | n | gh_n][lane] x float4 (the 4 window rows a lane owns):
 // one 16-byte access per lane and component, 1 KB per wave-instruction
@@ -79,6 +116,8 @@ __host__ __device__ inline size_t gate_floats(int B, int T, int H) {
 // Or one SeriesStarts (wgnn_series_fwd_at): the row is clamp(starts[w], 0, last) + t.
 // A MaskedLabels behind either (wgnn_series_fwd_loss_masked): a NaN label is no label -- it adds nothing to the sum and the
 // maximum, and the workgroup leaves the integer count of its labels behind the statistics (common.h: masked_counts).
+// Or a LossFn behind either (wgnn_series_fwd_lossfn): the sum is of rho(h - label) for the spec's kind over the steps
+// t >= t_from (and, with masked, the labels that are not NaN); the counts, a third tag and the spec go behind the statistics.
 template <int KS, bool ST = false, typename... Sr>   // k steps of 4 over the hidden index, 4 KS >= H, KS even; ST: the wgnn_fwd_state instance
 __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, const float* __restrict__ GI, int ldgi,
                                                            const float* __restrict__ Whh,
@@ -91,6 +130,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
   constexpr bool SR = sizeof...(Sr) > 0;
   constexpr bool SS = (std::is_same<Sr, SeriesStarts>::value || ...);
   constexpr bool MK = (std::is_same<Sr, MaskedLabels>::value || ...);
+  constexpr bool LF = (std::is_same<Sr, LossFn>::value || ...);
   // h0 (nullable, wgnn_fwd_state): [B][H] initial state instead of zeros; hn (nullable): h_{T-1} [B][H], unrounded
   if (!ST) { h0 = nullptr; hn = nullptr; }       // (the plain forward's instance compiles exactly as before)
   constexpr int KP = 4 * KS, HS = KP + 4;          // row stride: 16-byte aligned rows
@@ -108,6 +148,16 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
   const int jc = jv ? j : H - 1;
   const int b0 = blockIdx.x * MB;
   // tag behind the MSE partial pairs: set by wgnn_fwd_loss, cleared by a plain forward on the same stash
+  if constexpr (LF) {   // a third tag, and the spec in the three spare words: the backward must come with the same one
+    if (stat_part && blockIdx.x == 0 && threadIdx.x == 0) {
+      const LossFn fn = lossfn_of(series...);
+      stat_part[2 * gridDim.x] = Lab ? WGNN_STATS_TAG_LOSSFN : 0.f;
+      unsigned* w = (unsigned*)(stat_part + 2 * gridDim.x + 1);
+      w[0] = lossfn_word(fn);
+      w[1] = lossfn_delta(fn);
+      w[2] = (unsigned)fn.t_from;
+    }
+  } else
   if (stat_part && blockIdx.x == 0 && threadIdx.x == 0)
     stat_part[2 * gridDim.x] = Lab ? (MK ? WGNN_STATS_TAG_MASKED : WGNN_STATS_TAG) : 0.f;
   if (hprev) {
@@ -172,7 +222,13 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
     for (int r = 0; r < 4; ++r) hold[r] = rowok[r] ? h0[(size_t)(b0 + 4 * lk + r) * H + j] : 0.f;
   }
   float ssum = 0.f, smax = 0.f;
-  unsigned cnt = 0;       // MK: labels seen by this thread (at most 4 T)
+  unsigned cnt = 0;       // MK, LF: labels seen by this thread (at most 4 T)
+  LossFn fn{};            // LF: the spec and its arms, scalars
+  LossArms arms{};
+  if constexpr (LF) {
+    fn = lossfn_of(series...);
+    arms = loss_arms(fn);
+  }
   __syncthreads();
 
   for (int t = 0; t < T; ++t) {
@@ -210,7 +266,17 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
           else if (t == T - 1) Y[(size_t)(b0 + 4 * lk + r) * H + j] = hnew[r] * y_mul + y_add;
           if (hn && t == T - 1) hn[(size_t)(b0 + 4 * lk + r) * H + j] = hnew[r];
           if (Hpw && t + 1 < T) Hpw[(rowt[r] + t + 1) * hq + j] = hnew[r];
-          if constexpr (MK) {
+          if constexpr (LF) {
+            // rho as ONE fmaf(a, b, ssum) for every kind, operands picked by selects (LossArms above the loop): no branch
+            // inside the step.  A warm-up step (t < t_from) and a missing label are selected away together, as below.
+            const bool has = t >= fn.t_from && (!fn.masked || lab[r] == lab[r]);
+            const float dl = has ? hnew[r] - lab[r] : 0.f;
+            const float ad = fabsf(dl);
+            const bool lin = ad > arms.thr;                  // (a NaN takes the quadratic arm and stays one)
+            ssum = fmaf(lin ? arms.lin : arms.q * dl, lin ? ad - arms.off : dl, ssum);
+            smax = fmaxf(smax, ad);
+            cnt += has ? 1u : 0u;
+          } else if constexpr (MK) {
             const bool has = lab[r] == lab[r];               // a NaN is no label; the select keeps NaN * 0 out of the sum
             const float dl = has ? hnew[r] - lab[r] : 0.f;
             ssum = fmaf(dl, dl, ssum);
@@ -265,7 +331,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
       stat_part[blockIdx.x] = s;
       stat_part[gridDim.x + blockIdx.x] = m;
     }
-    if constexpr (MK) {   // the exact count: integer adds, any order
+    if constexpr (MK || LF) {   // the exact count: integer adds, any order
       __shared__ unsigned redc[NTHREADS / 64];
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
@@ -292,6 +358,9 @@ __global__ void __launch_bounds__(NTHREADS) gru_fwd_kernel(int B, int T, int H, 
 // (wgnn_series_bwd_mse_masked): dY = 2 grad_scale (Y - label) / m where the label is not NaN and +0 elsewhere, m = the sum of the
 // forward's per-workgroup counts, which EVERY workgroup adds up itself before its loop (integers: no order to fix, no launch
 // between forward and backward); coef_lab carries grad_scale, inv_n is unused; m = 0: loss NaN, dY = 0, WGNN_STATUS_NO_LABELS.
+// Or a LossFn behind either (wgnn_series_bwd_lossfn): dY = coef_lab rho'(Y - label) on the steps t >= t_from (and, with
+// masked, where the label is not NaN), +0 elsewhere; every step still runs.  Without masked inv_n and coef_lab come from the
+// host (m = B (T - t_from) H), with it from the counts as above.  stat_part must be this spec's forward's: else loss NaN, dY = 0.
 template <int KS3, typename... St>   // k steps of 4 over the gate-row index, 4 KS3 >= 3H, KS3 even
 __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, const float* __restrict__ Whh,
                                                            const float* __restrict__ Y, const float* __restrict__ dY,
@@ -308,6 +377,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
   constexpr bool SR = (std::is_same<St, SeriesRows>::value || ...) || SS;
   constexpr bool ST = sizeof...(St) > 0 && !SR;
   constexpr bool MK = (std::is_same<St, MaskedLabels>::value || ...);
+  constexpr bool LF = (std::is_same<St, LossFn>::value || ...);
   const BwdState sb = bwd_state(state...);
   constexpr int KP = 4 * KS3, DS = KP + 4;
   __shared__ __attribute__((aligned(16))) float dbuf[2 * MB * DS];   // dgh rows [dar | daz | dnr | 0..], by step parity
@@ -322,23 +392,30 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
   const int b0 = blockIdx.x * MB;
   const int G3 = 3 * H;
   if constexpr (MK) {
-    __shared__ unsigned long long cred[NTHREADS / 64];
-    const unsigned* counts = masked_counts(stat_part, nstat);
-    unsigned long long c = 0;
-    for (int i = threadIdx.x; i < nstat; i += NTHREADS) c += counts[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if (lane == 0) cred[wave] = c;
-    __syncthreads();
-    c = 0;
-#pragma unroll
-    for (int w = 0; w < NTHREADS / 64; ++w) c += cred[w];
+    BLOCK_COUNT_SUM(c, masked_counts(stat_part, nstat), nstat, true);
     const bool counted = stat_part[2 * nstat] == WGNN_STATS_TAG_MASKED;   // else: not this forward's buffer, no count to trust
     if (!counted) c = 0;
     // the two factors as launch_gru_bwd forms them on the host from n_loss (IEEE division)
     inv_n = c ? 1.0f / (float)c : __builtin_nanf("");       // m = 0: loss[0] = NaN whatever the partial sums hold
     coef_lab = c ? 2.0f * coef_lab / (float)c : 0.f;
     if (counted && c == 0 && blockIdx.x == 0 && threadIdx.x == 0 && status) atomicOr(status, WGNN_STATUS_NO_LABELS);
+  }
+  bool paired = false;    // LF: this spec's forward wrote stat_part
+  LossFn fn{};            // LF: the spec and its arms, scalars
+  LossArms arms{};
+  if constexpr (LF) {
+    fn = lossfn_of(state...);
+    arms = loss_arms(fn);
+    paired = lossfn_paired(stat_part, nstat, fn);
+    if (fn.masked) {      // (uniform) m from the forward's counts, as above; coef_lab carries grad_scale
+      // (a buffer this forward did not write may be wgnn_series_fwd_loss's shorter one: its counts are not even read)
+      BLOCK_COUNT_SUM(c, masked_counts(stat_part, nstat), nstat, paired);
+      inv_n = c ? 1.0f / (float)c : __builtin_nanf("");
+      coef_lab = c ? (fn.kind == 0 ? 2.0f * coef_lab / (float)c : coef_lab / (float)c) : 0.f;
+      if (paired && c == 0 && blockIdx.x == 0 && threadIdx.x == 0 && status) atomicOr(status, WGNN_STATUS_NO_LABELS);
+    } else if (!paired) {
+      coef_lab = 0.f;     // another forward's statistics: dY = 0, and the loss below is NaN
+    }
   }
   if (stat_part && blockIdx.x == 0) {   // loss = (sum of the forward's per-workgroup partial sums) / n, fixed order
     __shared__ float sred[NTHREADS / 64];
@@ -352,7 +429,7 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
       a = 0.f;
 #pragma unroll
       for (int w = 0; w < NTHREADS / 64; ++w) a += sred[w];
-      const bool tagged = stat_part[2 * nstat] == (MK ? WGNN_STATS_TAG_MASKED : WGNN_STATS_TAG);
+      const bool tagged = LF ? paired : stat_part[2 * nstat] == (MK ? WGNN_STATS_TAG_MASKED : WGNN_STATS_TAG);
       loss_out[0] = tagged ? a * inv_n : __builtin_nanf("");     // no statistics of these labels in the stash: loud
       if (!tagged && status) atomicOr(status, WGNN_STATUS_NO_LOSS_STATS);
     }
@@ -446,7 +523,12 @@ __global__ void __launch_bounds__(NTHREADS) gru_bwd_kernel(int B, int T, int H, 
       for (int r = 0; r < 4; ++r) {
         const int m = 4 * lk + r;
         float dyv;
-        if constexpr (MK) dyv = cur.dy[r] == cur.dy[r] ? (ycur[r] - cur.dy[r]) * coef_lab : 0.f;   // no label: exactly +0
+        if constexpr (LF) {
+          const bool on = paired && t >= fn.t_from && (!fn.masked || cur.dy[r] == cur.dy[r]);
+          const float rr = ycur[r] - cur.dy[r];
+          const float g = fabsf(rr) > arms.gthr ? copysignf(arms.lin, rr) : rr;   // rho' without a branch (LossArms)
+          dyv = on ? g * coef_lab : 0.f;                       // outside M: exactly +0, whatever the label holds
+        } else if constexpr (MK) dyv = cur.dy[r] == cur.dy[r] ? (ycur[r] - cur.dy[r]) * coef_lab : 0.f;   // no label: exactly +0
         else dyv = Lab ? (ycur[r] - cur.dy[r]) * coef_lab : cur.dy[r];
         const float dh = rowok[r] ? dyv + dhn[r] : 0.f;
         const float rg = cur.r[r], zg = cur.z[r];
@@ -534,9 +616,11 @@ int gru_msplit(int H) { return 4 * cdiv_i(2 * H, 4); }   // first GEMM row of th
 int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
                    float* gates, const float* labels, float* stat_part, float* hprev, int hq, int last_only, float y_mul,
                    float y_add, hipStream_t st, const float* h0, float* hn, int series_stride, int64_t ls_rows,
-                   const int* starts, int starts_last, bool masked) {
+                   const int* starts, int starts_last, bool masked, const LossFn* lossfn) {
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
   if (masked && (!(series_stride || starts) || !labels || !stat_part || last_only)) return WGNN_ERR_UNSUPPORTED;
+  if (lossfn && (!(series_stride || starts) || !labels || !stat_part || last_only || masked)) return WGNN_ERR_UNSUPPORTED;
+  if (lossfn && !lossfn_valid(*lossfn, T)) return WGNN_ERR_SHAPE;
   if (last_only && (gates || labels || hprev)) return WGNN_ERR_UNSUPPORTED;
   if (series_stride < 0 || (series_stride && (h0 || hn))) return WGNN_ERR_UNSUPPORTED;
   if (starts && (series_stride || h0 || hn || starts_last < 0)) return WGNN_ERR_UNSUPPORTED;
@@ -553,8 +637,18 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
               hipLaunchKernelGGL((gru_fwd_kernel<K, false, MAP, MaskedLabels>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, \
                                  H, GI, ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq, last_only, y_mul, y_add, nullptr,  \
                                  nullptr, MAP{__VA_ARGS__}, MaskedLabels{}))
+#define FLOSSFN(K, NAME, MAP, ...)                                                                                \
+  PROF_LAUNCH("gru_fwd_kernel<" #K NAME ">", fl, by, st,                                                          \
+              hipLaunchKernelGGL((gru_fwd_kernel<K, false, MAP, LossFn>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, GI, \
+                                 ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq, last_only, y_mul, y_add, nullptr,         \
+                                 nullptr, MAP{__VA_ARGS__}, *lossfn))
 #define FCASE(K)                                                                                                  \
   case K:                                                                                                         \
+    if (lossfn) {                                                                                                 \
+      if (starts) FLOSSFN(K, ",starts,lossfn", SeriesStarts, starts, starts_last);                                \
+      else FLOSSFN(K, ",lossfn", SeriesRows, series_stride);                                                      \
+      break;                                                                                                      \
+    }                                                                                                             \
     if (masked) {                                                                                                 \
       if (starts) FMASKED(K, ",starts,masked", SeriesStarts, starts, starts_last);                                \
       else FMASKED(K, ",masked", SeriesRows, series_stride);                                                      \
@@ -583,6 +677,7 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
     default: return WGNN_ERR_UNSUPPORTED;
   }
 #undef FCASE
+#undef FLOSSFN
 #undef FMASKED
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;
@@ -593,9 +688,11 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
 int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
                    const float* gates, const float* GI /*the forward's GI rows [B*T][ldgi] (stash)*/, int ldgi, float* dGI, int ldd, float* dGHn, float* dGH, const float* stat_part,
                    int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st, const BwdState* state,
-                   int series_stride, int64_t ls_rows, const int* starts, int starts_last, bool masked) {
+                   int series_stride, int64_t ls_rows, const int* starts, int starts_last, bool masked, const LossFn* lossfn) {
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
   if (masked && (!(series_stride || starts) || !labels || !stat_part || state)) return WGNN_ERR_UNSUPPORTED;
+  if (lossfn && (!(series_stride || starts) || !labels || !stat_part || state || masked)) return WGNN_ERR_UNSUPPORTED;
+  if (lossfn && !lossfn_valid(*lossfn, T)) return WGNN_ERR_SHAPE;
   if (state && (!state->h0 || labels)) return WGNN_ERR_UNSUPPORTED;
   if (series_stride < 0 || (series_stride && state)) return WGNN_ERR_UNSUPPORTED;
   if (starts && (series_stride || state || starts_last < 0)) return WGNN_ERR_UNSUPPORTED;
@@ -610,6 +707,16 @@ int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const 
   const double bt = (double)B * T;
   const double fl = bt * 2.0 * 3 * H * H, by = bt * 4.0 * (H + H + 3 * H + (dGH ? 3 * H : H)) + 3.0 * gate_floats(B, T, H) +
                                           bt * 4.0 * H;   // + GI's n third
+  // a loss spec without missing labels: m = B (T - t_from) H, and no factor 2 but for the mean square; with them, as masked
+  const int64_t fn_m = lossfn ? (int64_t)B * (T - lossfn->t_from) * H : 1;
+  const float fn_inv = lossfn && !lossfn->masked ? 1.0f / (float)fn_m : 0.f;
+  const float fn_coef = !lossfn || lossfn->masked ? grad_scale
+                        : (lossfn->kind == 0 ? 2.0f * grad_scale / (float)fn_m : grad_scale / (float)fn_m);
+#define BLOSSFN(K, NAME, MAP, ...)                                                                                \
+  PROF_LAUNCH("gru_bwd_kernel<" #K NAME ">", fl, by, st,                                                          \
+              hipLaunchKernelGGL((gru_bwd_kernel<K, MAP, LossFn>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY, \
+                                 labels, gates, GI, ldgi, dGI, ldd, dGHn, hn, dGH, stat_part, gru_blocks(B), fn_inv, fn_coef, loss, \
+                                 status, MAP{__VA_ARGS__}, *lossfn))
   // masked: the kernel forms both factors from the forward's count; coef_lab carries grad_scale there
 #define BMASKED(K, NAME, MAP, ...)                                                                                \
   PROF_LAUNCH("gru_bwd_kernel<" #K NAME ">", fl, by, st,                                                          \
@@ -618,6 +725,11 @@ int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const 
                                  grad_scale, loss, status, MAP{__VA_ARGS__}, MaskedLabels{}))
 #define BCASE(K)                                                                                                  \
   case K:                                                                                                         \
+    if (lossfn) {                                                                                                 \
+      if (starts) BLOSSFN(K, ",starts,lossfn", SeriesStarts, starts, starts_last);                                \
+      else BLOSSFN(K, ",lossfn", SeriesRows, series_stride);                                                      \
+      break;                                                                                                      \
+    }                                                                                                             \
     if (masked) {                                                                                                 \
       if (starts) BMASKED(K, ",starts,masked", SeriesStarts, starts, starts_last);                                \
       else BMASKED(K, ",masked", SeriesRows, series_stride);                                                      \
@@ -646,6 +758,7 @@ int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const 
     default: return WGNN_ERR_UNSUPPORTED;
   }
 #undef BCASE
+#undef BLOSSFN
 #undef BMASKED
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;

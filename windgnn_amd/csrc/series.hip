@@ -7,6 +7,7 @@
 #include "../../include/windgnn_series_train.h"
 #include "../../include/windgnn_series_at.h"
 #include "../../include/windgnn_series_masked.h"
+#include "../../include/windgnn_series_lossfn.h"
 
 #include <cmath>
 
@@ -164,38 +165,50 @@ bool labels_fit(const wgnn_series_dims* sd, bool at, int64_t ls_rows) {
   return ls_rows >= need && ls_rows * sd->H < (1ll << 31);
 }
 
+// include/windgnn_series_lossfn.h: the caller's spec as the kernels' argument, or why not
+int loss_spec(const wgnn_series_dims* sd, const wgnn_lossfn* fn, LossFn* out) {
+  if (!fn) return WGNN_ERR_NULL;
+  *out = LossFn{fn->kind, fn->kind == WGNN_LOSS_HUBER ? fn->delta : 0.f, fn->t_from, fn->masked};
+  return lossfn_valid(*out, sd->T) ? WGNN_OK : WGNN_ERR_SHAPE;
+}
+
 int forward_loss(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, const float* Ls,
                  int64_t ls_rows, float* Y, void* stash, void* loss_buf, void* workspace, size_t workspace_bytes, void* stream,
-                 bool at = false, const int* starts = nullptr, bool masked = false) {
+                 bool at = false, const int* starts = nullptr, bool masked = false, bool lossfn = false,
+                 const wgnn_lossfn* fn = nullptr) {
   if (sd && !Y) return WGNN_ERR_NULL;      // before the dims, as in wgnn_series_fwd
   Plan pl;
   int rc = plan(sd, &pl, at);
   if (rc != WGNN_OK) return rc;
-  if (masked && !at && starts) return WGNN_ERR_SHAPE;      // a table with a stride (windgnn_series_masked.h)
+  if ((masked || lossfn) && !at && starts) return WGNN_ERR_SHAPE;      // a table with a stride (windgnn_series_masked.h)
   if (!A || !Xs || !p || !Ls || !loss_buf || !workspace || !complete(p) || (at && !starts)) return WGNN_ERR_NULL;
   if (!labels_fit(sd, at, ls_rows)) return WGNN_ERR_SHAPE;
   if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
+  LossFn spec{};
+  if (lossfn && (rc = loss_spec(sd, fn, &spec)) != WGNN_OK) return rc;      // last of the host checks, ahead of any launch
   if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
   return series_fwd_loss(&pl.front, &pl.rec, sd->stride, A, Xs, p, Ls, ls_rows, Y, stash, (float*)loss_buf, workspace, pl.sp,
-                         stream, starts, masked);
+                         stream, starts, masked, lossfn ? &spec : nullptr);
 }
 
 int backward_mse(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, const float* Y,
                  const float* Ls, int64_t ls_rows, float grad_scale, const void* stash, const void* loss_buf, float* loss,
                  const wgnn_grads* grads, void* workspace, size_t workspace_bytes, void* stream, bool at = false,
-                 const int* starts = nullptr, bool masked = false) {
+                 const int* starts = nullptr, bool masked = false, bool lossfn = false, const wgnn_lossfn* fn = nullptr) {
   Plan pl;
   int rc = plan(sd, &pl, at);
   if (rc != WGNN_OK) return rc;
-  if (masked && !at && starts) return WGNN_ERR_SHAPE;
+  if ((masked || lossfn) && !at && starts) return WGNN_ERR_SHAPE;
   if (!A || !Xs || !p || !Y || !Ls || !stash || !loss_buf || !loss || !grads || !workspace || !complete(p) || !complete(grads) ||
       (at && !starts))
     return WGNN_ERR_NULL;
   if (!labels_fit(sd, at, ls_rows) || !std::isfinite(grad_scale) || !(grad_scale > 0.f)) return WGNN_ERR_SHAPE;
   if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
+  LossFn spec{};
+  if (lossfn && (rc = loss_spec(sd, fn, &spec)) != WGNN_OK) return rc;
   if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
   return series_bwd_mse(&pl.front, &pl.rec, sd->stride, A, Xs, p, Y, Ls, ls_rows, grad_scale, stash, (const float*)loss_buf,
-                        loss, grads, workspace, pl.sp, stream, starts, masked);
+                        loss, grads, workspace, pl.sp, stream, starts, masked, lossfn ? &spec : nullptr);
 }
 
 }  // namespace
@@ -357,6 +370,26 @@ int wgnn_series_bwd_mse_masked(const wgnn_series_dims* sd, const float* A, const
                                size_t workspace_bytes, void* stream) {
   return backward_mse(sd, A, Xs, p, Y, Ls, ls_rows, grad_scale, stash, loss_buf, loss, grads, workspace, workspace_bytes, stream,
                       sd && sd->stride == 0, starts, true);
+}
+
+// ---- include/windgnn_series_lossfn.h ----
+int wgnn_series_lossfn_version(void) { return WGNN_SERIES_LOSSFN_VERSION; }
+
+size_t wgnn_series_lossfn_bytes(const wgnn_series_dims* sd) { return wgnn_series_masked_loss_bytes(sd); }
+
+int wgnn_series_fwd_lossfn(const wgnn_series_dims* sd, const float* A, const float* Xs, const int32_t* starts,
+                           const wgnn_params* p, const float* Ls, int64_t ls_rows, const wgnn_lossfn* fn, float* Y, void* stash,
+                           void* loss_buf, void* workspace, size_t workspace_bytes, void* stream) {
+  return forward_loss(sd, A, Xs, p, Ls, ls_rows, Y, stash, loss_buf, workspace, workspace_bytes, stream, sd && sd->stride == 0,
+                      starts, false, true, fn);
+}
+
+int wgnn_series_bwd_lossfn(const wgnn_series_dims* sd, const float* A, const float* Xs, const int32_t* starts,
+                           const wgnn_params* p, const float* Y, const float* Ls, int64_t ls_rows, float grad_scale,
+                           const wgnn_lossfn* fn, const void* stash, const void* loss_buf, float* loss, const wgnn_grads* grads,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  return backward_mse(sd, A, Xs, p, Y, Ls, ls_rows, grad_scale, stash, loss_buf, loss, grads, workspace, workspace_bytes, stream,
+                      sd && sd->stride == 0, starts, false, true, fn);
 }
 
 }  // extern "C"

@@ -245,18 +245,52 @@ def _masked_table(at):
     return at if at else (None,)
 
 
+def loss_spec(loss, huber_delta, loss_from, seq_len, missing_labels=False, who="windgnn_amd series mode"):
+    """The wgnn_lossfn of loss= / huber_delta= / loss_from= (include/windgnn_series_lossfn.h), or None for the defaults ("mse"
+    from step 0), which are the entry points that need no spec.  Everything the library would refuse is refused here first, by
+    the argument's name."""
+    import math as _math
+    if loss not in _lib.LOSS_KINDS:
+        raise ValueError("%s: loss=%r: the series recurrences form 'mse', 'l1' or 'huber'; any other loss works on "
+                         "GCN_GRU.forward_series' output through autograd" % (who, loss))
+    t_from = int(loss_from)
+    if t_from != loss_from or not 0 <= t_from < int(seq_len):
+        raise ValueError("%s: loss_from=%r must be a step of the window, an integer in [0, seq_len = %d): 0 counts every step, "
+                         "seq_len - 1 the last alone" % (who, loss_from, int(seq_len)))
+    delta = float(huber_delta)
+    if loss == "huber" and not (_math.isfinite(delta) and delta > 0.0):
+        raise ValueError("%s: huber_delta=%r must be finite and > 0 (nn.HuberLoss's delta); loss='l1' is the limit of a small "
+                         "one and loss='mse' twice that of a large one" % (who, huber_delta))
+    if loss == "mse" and t_from == 0:
+        return None
+    return _lib.LossFn(_lib.LOSS_KINDS[loss], delta if loss == "huber" else 0.0, t_from, 1 if missing_labels else 0)
+
+
 def series_forward_loss_raw(A, series, Ls, seq_len, stride, params, math=_lib.MATH_F32, n_windows=None, prepared=None,
-                            starts=None, missing_labels=False):
+                            starts=None, missing_labels=False, loss="mse", huber_delta=1.0, loss_from=0):
     """Y [n, T, H], stash, loss_buf, dims = wgnn_series_fwd_loss(...): series_forward_raw with the MSE statistics of (Y - labels)
     left in loss_buf for series_backward_mse_raw.  Ls [rows - 3, H]: the label SERIES (series_labels' first result); window w,
     step t reads its row w * stride + t.  starts (with stride None): a NON-DECREASING table, the row is starts[w] + t, Ls needs
     the series' rows, and a fifth result is the int32 device table (wgnn_series_fwd_loss_at).
     missing_labels=True (wgnn_series_fwd_loss_masked, either row mapping): a NaN in Ls is "no label" and enters neither the sum nor
-    the count; loss_buf then has wgnn_series_masked_loss_bytes and goes to series_backward_mse_raw(..., missing_labels=True)."""
+    the count; loss_buf then has wgnn_series_masked_loss_bytes and goes to series_backward_mse_raw(..., missing_labels=True).
+    loss="mse" | "l1" | "huber" (with huber_delta), loss_from=t: the statistics of that loss over the steps t .. seq_len - 1 of
+    every window (wgnn_series_fwd_lossfn, either row mapping, with or without missing_labels); the backward takes the same
+    keywords.  The defaults are the calls above."""
     lib = _lib.load()
+    spec = loss_spec(loss, huber_delta, loss_from, seq_len, missing_labels)
     A, sd, ws, ws_bytes, *table = _series_setup(A, series, seq_len, stride, params, math, n_windows, starts)
     _check_label_series(Ls, sd)
     stash = torch.empty(_fn(lib, "stash_bytes", sd)(C.byref(sd)), dtype=torch.uint8, device=series.device)
+    if spec is not None:
+        loss_buf = torch.empty(lib.wgnn_series_lossfn_bytes(C.byref(sd)) // 4, dtype=torch.float32, device=series.device)
+        Y = torch.empty(sd.n, sd.T, sd.H, dtype=torch.float32, device=series.device)
+        ps = _params_struct(_lib.Params, params, prepared)
+        rc = lib.wgnn_series_fwd_lossfn(C.byref(sd), _ptr(A), _ptr(series), *_masked_table(_table_arg(sd, *table)), C.byref(ps),
+                                        _ptr(Ls), Ls.shape[0], C.byref(spec), _ptr(Y), _stash_ptr(stash), _ptr(loss_buf),
+                                        _ptr(ws), ws_bytes, _stream())
+        _lib.check(rc, "wgnn_series_fwd_lossfn")
+        return (Y, stash, loss_buf, sd, *table)
     if missing_labels:
         loss_buf = torch.empty(lib.wgnn_series_masked_loss_bytes(C.byref(sd)) // 4, dtype=torch.float32, device=series.device)
         Y = torch.empty(sd.n, sd.T, sd.H, dtype=torch.float32, device=series.device)
@@ -277,24 +311,35 @@ def series_forward_loss_raw(A, series, Ls, seq_len, stride, params, math=_lib.MA
 
 
 def series_backward_mse_raw(sd, A, series, params, Y, Ls, stash, loss_buf, grads: Sequence[torch.Tensor], loss: torch.Tensor,
-                            grad_scale: float = 1.0, prepared=None, starts=None, missing_labels=False) -> None:
+                            grad_scale: float = 1.0, prepared=None, starts=None, missing_labels=False, loss_kind="mse",
+                            huber_delta=1.0, loss_from=0) -> None:
     """wgnn_series_bwd_mse: the 8 gradients of grad_scale * mean((Y - labels)^2) into `grads` (overwritten, final) and the
     unweighted mean into `loss` (a 0-dim fp32 device tensor), without a dY tensor.  Y, stash, loss_buf: as
     series_forward_loss_raw returned them for the same inputs (starts: its table, for dims with stride = 0).
     missing_labels=True (wgnn_series_bwd_mse_masked; the forward's flag): the mean and the gradients are over the labels that are
-    not NaN; with none at all the loss is NaN and the gradients are zero."""
+    not NaN; with none at all the loss is NaN and the gradients are zero.
+    loss_kind (the forward's loss=; `loss` is the output tensor here), huber_delta, loss_from: the forward's (wgnn_series_bwd_lossfn): the gradients of grad_scale * that loss over the steps
+    loss_from .. seq_len - 1 and its unweighted value; other values than the forward's give a NaN loss and zero gradients."""
     lib = _lib.load()
+    spec = loss_spec(loss_kind, huber_delta, loss_from, sd.T, missing_labels)
     _check_label_series(Ls, sd)
     _require_gpu(loss, loss_buf)
     _require_contiguous(series=series, Y=Y, adj_matrix=A, loss_buf=loss_buf, grads=grads, params=params)
     at = _table_arg(sd, starts)
-    need = (lib.wgnn_series_masked_loss_bytes if missing_labels else _fn(lib, "loss_bytes", sd))(C.byref(sd))
+    counted = missing_labels or spec is not None
+    need = (lib.wgnn_series_masked_loss_bytes if counted else _fn(lib, "loss_bytes", sd))(C.byref(sd))
     if loss_buf.numel() * 4 < need:
         raise RuntimeError("windgnn_amd: loss_buf holds %d bytes, wgnn_series_%sloss_bytes says %d"
-                           % (loss_buf.numel() * 4, "masked_" if missing_labels else "", need))
+                           % (loss_buf.numel() * 4, "masked_" if counted else "", need))
     ws, ws_bytes = _workspace(sd, series.device)
     ps = _params_struct(_lib.Params, params, prepared)
     gs = _params_struct(_lib.Grads, grads)
+    if spec is not None:
+        rc = lib.wgnn_series_bwd_lossfn(C.byref(sd), _ptr(A), _ptr(series), *_masked_table(at), C.byref(ps), _ptr(Y), _ptr(Ls),
+                                        Ls.shape[0], float(grad_scale), C.byref(spec), _stash_ptr(stash), _ptr(loss_buf),
+                                        _ptr(loss), C.byref(gs), _ptr(ws), ws_bytes, _stream())
+        _lib.check(rc, "wgnn_series_bwd_lossfn")
+        return
     if missing_labels:
         rc = lib.wgnn_series_bwd_mse_masked(C.byref(sd), _ptr(A), _ptr(series), *_masked_table(at), C.byref(ps), _ptr(Y),
                                             _ptr(Ls), Ls.shape[0], float(grad_scale), _stash_ptr(stash), _ptr(loss_buf),

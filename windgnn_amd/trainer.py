@@ -79,7 +79,7 @@ from .functional import (PARAM_ORDER, _forward_setup, _require_gpu, best_bytes, 
                          gcn_gru_backward_mse_raw, gcn_gru_forward_raw, gcn_gru_state_backward_raw, gcn_gru_state_forward_raw,
                          keep_best_args, keep_best_launch, mse_loss_grad, prepared_weights, refresh_prepared, rows_align)
 from .modules import GCN_GRU
-from .series import (_no_stride_with_starts, n_series_windows, series_backward_mse_raw, series_forward_loss_raw,
+from .series import (_no_stride_with_starts, loss_spec, n_series_windows, series_backward_mse_raw, series_forward_loss_raw,
                      sorted_starts)
 
 AUTO_GRAD_BLOCKS = 8                # grad_blocks="auto": row blocks per GRU weight ...
@@ -638,12 +638,24 @@ class TrainStep:
                                "for TrainStep.step on materialised windows), got %s" % (need, H, tuple(Ls.shape)))
         return n
 
-    def forward_backward_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, starts=None, missing_labels=False):
+    def _series_loss(self, who, seq_len, missing_labels, loss, huber_delta, loss_from):
+        """loss= / huber_delta= / loss_from= of step_series / forward_backward_series, refused here by name before any launch:
+        the keywords for (series_forward_loss_raw, series_backward_mse_raw) -- none at the defaults, which are the calls the
+        two methods have always made."""
+        if loss_spec(loss, huber_delta, loss_from, seq_len, missing_labels, "windgnn_amd: TrainStep." + who) is None:
+            return {}, {}
+        rest = {"huber_delta": float(huber_delta), "loss_from": int(loss_from)}
+        return dict(rest, loss=loss), dict(rest, loss_kind=loss)
+
+    def forward_backward_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, starts=None, missing_labels=False,
+                                loss="mse", huber_delta=1.0, loss_from=0):
         """forward_backward on the first n_windows sliding windows of `series` [rows, S, 13] with the label series Ls
         [>= (n - 1) * stride + seq_len, H]: returns (loss, Y [n, seq_len, H]); the gradients land in the flat bucket, final (no
-        optimiser step).  `loss` is a view of the bucket's header word.  starts, missing_labels: as in step_series."""
+        optimiser step).  `loss` is a view of the bucket's header word.  starts, missing_labels, loss, huber_delta, loss_from:
+        as in step_series."""
         seq_len, table, inverse = int(seq_len), None, None
         self._series_refusals(A, series, seq_len, 1 if stride is None else int(stride), missing_labels)
+        fn_f, fn_b = self._series_loss("forward_backward_series", seq_len, missing_labels, loss, huber_delta, loss_from)
         series, Ls = series.contiguous(), Ls.contiguous()
         if starts is not None:
             table, inverse, n = self._series_table(series, Ls, seq_len, stride, n_windows, starts)
@@ -655,13 +667,13 @@ class TrainStep:
                                "seq_len %d, n_windows %r)" % (series.shape[0], seq_len, n_windows))
         at = {} if table is None else {"starts": table}     # (the strided call is the call it has always been)
         masked = {"missing_labels": True} if missing_labels else {}     # (and so is the call without the flag)
-        Y, stash, loss_buf, sd, _ = self._series_forward(A, series, Ls, seq_len, stride, n, table, **masked)
+        Y, stash, loss_buf, sd, _ = self._series_forward(A, series, Ls, seq_len, stride, n, table, **masked, **fn_f)
         series_backward_mse_raw(sd, A, series, self.p_views, Y, Ls, stash, loss_buf, self.g_views, self._loss, 1.0,
-                                prepared=self._prepared, **at, **masked)
+                                prepared=self._prepared, **at, **masked, **fn_b)
         return self._loss, (Y if inverse is None else Y.index_select(0, inverse))
 
     def step_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, n_global=None, starts=None,
-                    missing_labels=False):
+                    missing_labels=False, loss="mse", huber_delta=1.0, loss_from=0):
         """One optimiser step on the first `n_windows` (default: all that fit) sliding windows of this rank's `series`
         [rows, S, 13]: window w covers rows w * stride .. w * stride + seq_len - 1 and starts from h = 0, as step() on the
         materialised windows would.  Ls [>= (n - 1) * stride + seq_len, H]: the label SERIES (series_labels(feat, seq_len,
@@ -676,9 +688,15 @@ class TrainStep:
         The graph convolutions and the input projection still run on every row of `series`.
         missing_labels=True (include/windgnn_series_masked.h): a NaN in Ls means "no label" -- it adds nothing to the loss or to
         any gradient, and the mean is over the labels that exist (build `series` from the filled table, Ls from the unfilled
-        one).  With no label at all the loss is NaN and the gradients are zero.  Refused under a process group."""
+        one).  With no label at all the loss is NaN and the gradients are zero.  Refused under a process group.
+        loss="mse" | "l1" | "huber" (include/windgnn_series_lossfn.h): the mean over the counted entries of (Y - L)^2, |Y - L| or
+        nn.HuberLoss(delta=huber_delta); loss_from=t counts steps t .. seq_len - 1 of every window alone (seq_len - 1: the last
+        step, what the reference evaluates), while the gradient still flows back through the warm-up steps.  Both work with
+        missing_labels, and under a process group without it (every window counts the same number of entries on every rank).
+        The returned loss, keep_best, max_grad_norm and checkpoints see that loss; with the defaults the step is the one it was."""
         seq_len, table, inverse = int(seq_len), None, None
         self._series_refusals(A, series, seq_len, 1 if stride is None else int(stride), missing_labels)
+        fn_f, fn_b = self._series_loss("step_series", seq_len, missing_labels, loss, huber_delta, loss_from)
         series, Ls = series.contiguous(), Ls.contiguous()
         if starts is not None:
             table, inverse, n = self._series_table(series, Ls, seq_len, stride, n_windows, starts)
@@ -690,9 +708,9 @@ class TrainStep:
         gs = self.exchange.shard_weight(n, n_global) if self.collective else 1.0
         at = {} if table is None else {"starts": table}     # (the strided call is the call it has always been)
         masked = {"missing_labels": True} if missing_labels else {}     # (and so is the call without the flag)
-        Y, stash, loss_buf, sd, d = self._series_forward(A, series, Ls, seq_len, stride, n, table, **masked)
+        Y, stash, loss_buf, sd, d = self._series_forward(A, series, Ls, seq_len, stride, n, table, **masked, **fn_f)
         series_backward_mse_raw(sd, A, series, self.p_views, Y, Ls, stash, loss_buf, self.g_views, self._loss, gs,
-                                prepared=self._prepared, **at, **masked)
+                                prepared=self._prepared, **at, **masked, **fn_b)
         self._run_schedule(d, _FINAL, gs)       # the bucket is final: (the all-reduce,) Adam and the W_ih images
         self._end_step()
         return self._loss, (Y if inverse is None else Y.index_select(0, inverse))
