@@ -1,5 +1,6 @@
 """ctypes binding of libwindgnn_hip.so (the C ABI declared in include/windgnn.h, windgnn_optim.h, windgnn_sched.h,
-windgnn_eval.h, windgnn_best.h, windgnn_series.h, windgnn_series_train.h and windgnn_series_at.h).
+windgnn_eval.h, windgnn_best.h, windgnn_series.h, windgnn_series_train.h, windgnn_series_at.h, windgnn_series_masked.h,
+windgnn_series_lossfn.h and windgnn_series_val.h).
 
 The library is the product: there is no CPU or eager-PyTorch fallback.  If the shared object is
 missing or a call fails this module raises, loudly."""
@@ -261,6 +262,24 @@ EXPORTS_SERIES_LOSSFN = {
                                          C.POINTER(Grads), C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
+# include/windgnn_series_val.h: the held-out loss of a spec, forward-only, accumulated on the device (an eleventh header and table)
+SERIES_VAL_VERSION = 1      # WGNN_SERIES_VAL_VERSION
+STATUS_NO_LOSS_STATS = 8    # WGNN_STATUS_NO_LOSS_STATS
+# the public words of the record: name -> (byte offset, torch dtype name); `count` is a uint64 read as int64
+VAL_WORDS = {"sum": (0, "float64"), "count": (8, "int64"), "mean": (16, "float64"), "max_abs": (24, "float32"),
+             "loss": (28, "float32"), "calls": (32, "int64"), "passes": (40, "int64"), "stale": (48, "int64")}
+EXPORTS_SERIES_VAL = {
+    "wgnn_series_val_version": (C.c_int, []),
+    "wgnn_val_bytes": (C.c_size_t, []),
+    "wgnn_val_init": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "wgnn_val_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "wgnn_series_val_workspace_bytes": (C.c_size_t, [_SD]),
+    "wgnn_series_val": (C.c_int, [_SD, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_int64,
+                                  C.POINTER(LossFn), C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_size_t, C.c_void_p]),
+    "wgnn_val_close": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -349,6 +368,16 @@ def load() -> C.CDLL:
     if lib.wgnn_series_lossfn_version() < SERIES_LOSSFN_VERSION:
         raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_series_lossfn_version %d < %d)"
                            % (lib.wgnn_series_lossfn_version(), SERIES_LOSSFN_VERSION))
+    if not hasattr(lib, "wgnn_series_val_version"):
+        raise RuntimeError("windgnn_amd: %s predates include/windgnn_series_val.h (no wgnn_series_val_version): rebuild it "
+                           "with `python -m windgnn_amd.build --force`" % LIB_PATH)
+    for name, (res, args) in EXPORTS_SERIES_VAL.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.wgnn_series_val_version() < SERIES_VAL_VERSION:
+        raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_series_val_version %d < %d)"
+                           % (lib.wgnn_series_val_version(), SERIES_VAL_VERSION))
     if lib.wgnn_series_at_version() < SERIES_AT_VERSION:
         raise RuntimeError("windgnn_amd: libwindgnn_hip.so is too old (wgnn_series_at_version %d < %d)"
                            % (lib.wgnn_series_at_version(), SERIES_AT_VERSION))

@@ -18,7 +18,8 @@ HEADERS = ["common.h", "gcnx_dev.h", os.path.join("..", "..", "include", "windgn
            os.path.join("..", "..", "include", "windgnn_series_train.h"),
            os.path.join("..", "..", "include", "windgnn_series_at.h"),
            os.path.join("..", "..", "include", "windgnn_series_masked.h"),
-           os.path.join("..", "..", "include", "windgnn_series_lossfn.h")]
+           os.path.join("..", "..", "include", "windgnn_series_lossfn.h"),
+           os.path.join("..", "..", "include", "windgnn_series_val.h")]
 # -amdgpu-mfma-vgpr-form: MFMA accumulators live in VGPRs, so no v_accvgpr_read per value in the VALU-bound
 # GCN/GRU kernels (gcnx_bwd -8 %).  Safe only because every first read of an MFMA result is a compiler-visible
 # instruction (see split2 in gcnx.hip).

@@ -959,6 +959,7 @@ int series_plan(const wgnn_dims* df, const wgnn_dims* dr, SeriesPlan* sp) {
   if ((int64_t)Lf.BT * (int64_t)Lf.Gp >= (1ll << 31)) return WGNN_ERR_SHAPE;   // 32-bit row offsets into GI_s (gru.hip)
   sp->ws_front = Lf.fwd_floats > Lf.bwd_floats ? Lf.fwd_floats : Lf.bwd_floats;
   sp->ws_rec = Lr.fwd_floats > Lr.bwd_floats ? Lr.fwd_floats : Lr.bwd_floats;
+  sp->ws_front_fwd = Lf.fwd_floats;
   sp->st_front = Lf.stash_floats;
   sp->st_rec = Lr.stash_floats;
   sp->st_g = Lf.BT * Lf.Ip; sp->st_GI = Lf.BT * Lf.Gp;
@@ -1059,6 +1060,20 @@ int series_bwd_mse(const wgnn_dims* df, const wgnn_dims* dr, int stride, const f
                    bool masked, const LossFn* lossfn) {
   return series_backward(df, dr, stride, A, Xs, p, Y, nullptr, stash, g, workspace, sp, stream, Ls, ls_rows, grad_scale, loss_buf,
                          loss, starts, masked, lossfn);
+}
+
+int series_val_fwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
+                   const float* Ls, int64_t ls_rows, float* last, float wind_min, float wind_max, float* loss_buf,
+                   void* workspace, const SeriesPlan& sp, void* stream, const int* starts, const LossFn* lossfn) {
+  const Layout Lf = make_layout(df, false, SER_FRONT);
+  FwdCall cf(workspace, sizeof(float) * sp.ws_front_fwd, stream);
+  cf.A = A; cf.X = Xs; cf.p = p;
+  const Fwd f{df, cf, Lf};
+  int rc = fwd_front(f);                 // g_s and GI_s in the workspace: nothing is kept
+  if (rc != WGNN_OK) return rc;
+  return launch_gru_fwd(dr->B, dr->T, dr->H, f.GI, (int)Lf.Gp, p->w_hh, p->b_hh, last, nullptr, Ls, loss_buf, nullptr, 0, 1,
+                        wind_max - wind_min, wind_min, (hipStream_t)stream, nullptr, nullptr, stride, ls_rows, starts,
+                        df->T - dr->T, false, lossfn);
 }
 
 extern "C" {

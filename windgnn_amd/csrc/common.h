@@ -321,7 +321,7 @@ int launch_gcn1_bwd(int ntiles, int S, const float* A, const float* X, const flo
 // exact-fp32 recurrences with register-resident W_hh (gru.hip), H <= 128
 //   forward: gates (nullable) = gru_gates_floats() floats of stash in the kernels' own layout; labels + stat_part (nullable):
 //   2 * gru_blocks(B) MSE partials + a tag word; hprev (nullable): [B*T][hq] rows [h_{t-1} | 1 | 0..] for the dW_hh GEMM;
-//   last_only: Y is [B][H] and receives only h_{T-1} * y_mul + y_add
+//   last_only: Y is [B][H] and receives only h_{T-1} * y_mul + y_add (no gates, no hprev; labels with a lossfn alone)
 int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
                    float* gates, const float* labels, float* stat_part, float* hprev, int hq, int last_only, float y_mul,
                    float y_add, hipStream_t st, const float* h0 = nullptr, float* hn = nullptr,
@@ -370,6 +370,7 @@ static inline size_t ser_front(int series, size_t n) { return series == SER_REC 
 static inline size_t ser_rec(int series, size_t n) { return series == SER_FRONT ? 0 : n; }    // a region of the window-major half
 struct SeriesPlan {
   size_t ws_front, ws_rec;     // the two sub-workspaces, front first
+  size_t ws_front_fwd;         // the front workspace of a forward alone (include/windgnn_series_val.h: no backward follows)
   size_t st_front, st_rec;     // the two sub-stashes, front first
   size_t st_g, st_GI, st_gates, st_hprev;   // what the stash holds, unpadded: g_s, GI_s | gate records, [Hprev | 1] rows
 };
@@ -392,6 +393,11 @@ int series_bwd_mse(const wgnn_dims* front, const wgnn_dims* rec, int stride, con
                    const wgnn_params* p, const float* Y, const float* Ls, int64_t ls_rows, float grad_scale, const void* stash,
                    const float* loss_buf, float* loss, const wgnn_grads* g, void* workspace, const SeriesPlan& sp, void* stream,
                    const int* starts = nullptr, bool masked = false, const LossFn* lossfn = nullptr);
+// include/windgnn_series_val.h: the front end without a stash, then the spec's recurrence with last_only = 1 and neither gate
+// records nor [Hprev | 1] rows: `last` [n][H] and the statistics in loss_buf are all it writes (workspace: ws_front_fwd floats)
+int series_val_fwd(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs,
+                   const wgnn_params* p, const float* Ls, int64_t ls_rows, float* last, float wind_min, float wind_max,
+                   float* loss_buf, void* workspace, const SeriesPlan& sp, void* stream, const int* starts, const LossFn* lossfn);
 // dGIs [rows][ld] = the sum, in ascending w, of the window-major rows dGI [(w, tau - w * stride)][ld] that cover hour tau;
 // uncovered rows and the columns [G3, ld) are written as zeros (series.hip)
 int launch_series_fold(const float* dGI, int n, int T, int stride, int rows, int G3, int ld, float* dGIs, hipStream_t st);

@@ -619,9 +619,10 @@ int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* 
                    const int* starts, int starts_last, bool masked, const LossFn* lossfn) {
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
   if (masked && (!(series_stride || starts) || !labels || !stat_part || last_only)) return WGNN_ERR_UNSUPPORTED;
-  if (lossfn && (!(series_stride || starts) || !labels || !stat_part || last_only || masked)) return WGNN_ERR_UNSUPPORTED;
+  if (lossfn && (!(series_stride || starts) || !labels || !stat_part || masked)) return WGNN_ERR_UNSUPPORTED;
   if (lossfn && !lossfn_valid(*lossfn, T)) return WGNN_ERR_SHAPE;
-  if (last_only && (gates || labels || hprev)) return WGNN_ERR_UNSUPPORTED;
+  // last_only with labels: a spec alone (include/windgnn_series_val.h: the statistics of a forward that keeps nothing else)
+  if (last_only && (gates || hprev || (labels && !lossfn))) return WGNN_ERR_UNSUPPORTED;
   if (series_stride < 0 || (series_stride && (h0 || hn))) return WGNN_ERR_UNSUPPORTED;
   if (starts && (series_stride || h0 || hn || starts_last < 0)) return WGNN_ERR_UNSUPPORTED;
   if ((series_stride || starts) && labels && ls_rows * H >= (1ll << 31)) return WGNN_ERR_SHAPE;   // 32-bit offsets into Ls

@@ -1,5 +1,6 @@
 // Series mode (include/windgnn_series.h, include/windgnn_series_train.h, include/windgnn_series_at.h): the entry points, their
-// validation, the fold kernels of the backward and the check of a table of window starts.
+// validation, the fold kernels of the backward, the check of a table of window starts, and the kernels of the forward-only
+// validation pass (include/windgnn_series_val.h): its finish and the three single-thread launches on its record.
 // The launches themselves are api.hip's (series_fwd / series_bwd): they run the materialised path's own front end, weight-gradient
 // products and GCN backward on two of its layouts, with gru.hip's recurrences reading GI at series rows.
 #include "common.h"
@@ -8,8 +9,10 @@
 #include "../../include/windgnn_series_at.h"
 #include "../../include/windgnn_series_masked.h"
 #include "../../include/windgnn_series_lossfn.h"
+#include "../../include/windgnn_series_val.h"
 
 #include <cmath>
+#include <stddef.h>
 
 namespace {
 
@@ -84,6 +87,123 @@ __global__ void __launch_bounds__(256) series_starts_check_kernel(const int* __r
   if (w >= n) return;
   const int s = starts[w];
   report_status(status, s < 0 || s > last || (w > 0 && s < starts[w - 1]), WGNN_STATUS_WINDOW_START);
+}
+
+// ---- validation (include/windgnn_series_val.h) ----
+constexpr size_t VAL_BYTES = 256;
+constexpr int VAL_THREADS = 512;         // the BPTT workgroup: the loss below is summed in its order
+
+struct ValRecord {                       // the public words of include/windgnn_series_val.h
+  double sum;
+  unsigned long long count;
+  double mean;
+  float max_abs, loss;
+  int64_t calls, passes, stale;
+};
+static_assert(sizeof(ValRecord) <= VAL_BYTES && offsetof(ValRecord, loss) == 28 && offsetof(ValRecord, stale) == 48, "public layout");
+
+__device__ __forceinline__ void val_open(ValRecord* rec) {
+  rec->sum = 0.0;
+  rec->count = 0ull;
+  rec->mean = __builtin_nan("");
+  rec->max_abs = 0.f;
+  rec->loss = __builtin_nanf("");
+  rec->calls = 0;
+}
+
+__global__ void __launch_bounds__(64) val_init_kernel(unsigned long long* __restrict__ rec) {
+  const int i = threadIdx.x;
+  if (i < (int)(VAL_BYTES / 8)) rec[i] = 0ull;      // every byte, then the words that are not zero (the same thread order)
+  __syncthreads();
+  if (i == 0) val_open((ValRecord*)rec);
+}
+
+__global__ void __launch_bounds__(64) val_begin_kernel(ValRecord* __restrict__ rec) {
+  if (threadIdx.x == 0) val_open(rec);
+}
+
+__global__ void __launch_bounds__(64) val_close_kernel(ValRecord* __restrict__ rec, const int32_t* __restrict__ improved) {
+  if (threadIdx.x != 0) return;
+  rec->passes += 1;
+  if (improved) rec->stale = improved[0] ? 0 : rec->stale + 1;
+}
+
+// The loss of a forward-only pass from the statistics gru_fwd_kernel<.., LossFn> left in stat_part
+// [nstat sums | nstat maxima | tag | 3 spec words | nstat counts]: ONE workgroup.  loss_out[0] restates the loss block of
+// gru_bwd_kernel -- per-thread strided sum, xor tree over the lanes, the 8 waves ascending, times 1.0f / (float)m -- so that it
+// comes out with the bits the training pair writes.  m is the sum of the counts for both values of fn.masked (the forward
+// always writes them; with masked = 0 it is n (T - t_from) H, what the host forms for BPTT).  Statistics that are not this
+// spec's forward's: NaN and WGNN_STATUS_NO_LOSS_STATS; m = 0: NaN and WGNN_STATUS_NO_LABELS.  For the record one thread adds
+// the partial sums in ascending order in fp64 and the maxima, takes the counts' sum, and rewrites the public words.
+__global__ void __launch_bounds__(VAL_THREADS) series_val_finish_kernel(const float* __restrict__ stat_part, int nstat, LossFn fn,
+                                                                        float* __restrict__ loss_out, ValRecord* __restrict__ rec,
+                                                                        unsigned* status) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned* w = (const unsigned*)(stat_part + 2 * (size_t)nstat + 1);
+  const bool paired = stat_part[2 * (size_t)nstat] == WGNN_STATS_TAG_LOSSFN && w[0] == ((unsigned)fn.kind | (unsigned)fn.masked << 8) &&
+                      w[1] == (fn.kind == 2 ? __float_as_uint(fn.delta) : 0u) && w[2] == (unsigned)fn.t_from;
+  __shared__ unsigned long long cred[VAL_THREADS / 64];
+  __shared__ float sred[VAL_THREADS / 64];
+  const unsigned* cnts = masked_counts(stat_part, nstat);
+  unsigned long long c = 0;
+  float a = 0.f;
+  if (paired)     // (another forward's buffer may be the shorter one: its counts are not even read)
+    for (int i = threadIdx.x; i < nstat; i += VAL_THREADS) c += cnts[i];
+  for (int i = threadIdx.x; i < nstat; i += VAL_THREADS) a += stat_part[i];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    c += __shfl_xor(c, o, 64);
+    a += __shfl_xor(a, o, 64);
+  }
+  if (lane == 0) {
+    cred[wave] = c;
+    sred[wave] = a;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    c = 0;
+    a = 0.f;
+#pragma unroll
+    for (int v = 0; v < VAL_THREADS / 64; ++v) {
+      c += cred[v];
+      a += sred[v];
+    }
+    const float inv_n = c ? 1.0f / (float)c : __builtin_nanf("");
+    if (loss_out) loss_out[0] = paired ? a * inv_n : __builtin_nanf("");
+    if (status && !paired) atomicOr(status, WGNN_STATUS_NO_LOSS_STATS);
+    if (status && paired && c == 0) atomicOr(status, WGNN_STATUS_NO_LABELS);
+  }
+  if (!rec) return;      // (uniform)
+  // The record: onto the running sum term by term, so that calls cut at workgroup boundaries add the same terms in the same
+  // order as one call.  The workgroup stages VAL_THREADS sums and maxima at a time in LDS; thread 0 alone adds them, ascending.
+  __shared__ float ssum[VAL_THREADS], smax[VAL_THREADS];
+  double sum = paired ? rec->sum : __builtin_nan("");
+  float mx = rec->max_abs;
+  for (int base = 0; base < nstat; base += VAL_THREADS) {
+    const int i = base + (int)threadIdx.x;
+    if (i < nstat) {
+      ssum[threadIdx.x] = stat_part[i];
+      smax[threadIdx.x] = stat_part[nstat + i];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int m = min(VAL_THREADS, nstat - base);
+      for (int k = 0; k < m; ++k) {
+        sum += (double)ssum[k];
+        mx = fmaxf(mx, smax[k]);
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const unsigned long long count = rec->count + c;
+  const double mean = count ? sum / (double)count : __builtin_nan("");
+  rec->sum = sum;
+  rec->count = count;
+  rec->mean = mean;
+  rec->max_abs = mx;
+  rec->loss = (float)mean;
+  rec->calls += 1;
 }
 
 struct Plan {
@@ -209,6 +329,47 @@ int backward_mse(const wgnn_series_dims* sd, const float* A, const float* Xs, co
   if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
   return series_bwd_mse(&pl.front, &pl.rec, sd->stride, A, Xs, p, Y, Ls, ls_rows, grad_scale, stash, (const float*)loss_buf,
                         loss, grads, workspace, pl.sp, stream, starts, masked, lossfn ? &spec : nullptr);
+}
+
+// include/windgnn_series_val.h: floats of the workspace -- [front end, forward alone | loss_buf | last rows]
+struct ValLayout { size_t loss_buf, last, total; };
+ValLayout val_layout(const wgnn_series_dims* sd, const Plan& pl) {
+  ValLayout v;
+  v.loss_buf = pl.sp.ws_front_fwd;
+  v.last = v.loss_buf + align_up(series_masked_loss_floats(sd->n), 64);
+  v.total = v.last + align_up((size_t)sd->n * sd->H, 64);
+  return v;
+}
+
+int validate(const wgnn_series_dims* sd, const float* A, const float* Xs, const int* starts, const wgnn_params* p,
+             const float* Ls, int64_t ls_rows, const wgnn_lossfn* fn, float wind_min, float wind_max, float* last, float* loss,
+             void* val, void* workspace, size_t workspace_bytes, void* stream) {
+  if (sd && !loss && !val) return WGNN_ERR_NULL;      // nothing to report: before the dims, as Y in wgnn_series_fwd_lossfn
+  const bool at = sd && sd->stride == 0;
+  Plan pl;
+  int rc = plan(sd, &pl, at);
+  if (rc != WGNN_OK) return rc;
+  if (!at && starts) return WGNN_ERR_SHAPE;           // a table with a stride
+  if (!A || !Xs || !p || !Ls || !workspace || !complete(p) || (at && !starts)) return WGNN_ERR_NULL;
+  if (val && (uintptr_t)val % VAL_BYTES != 0) return WGNN_ERR_SHAPE;
+  if (!labels_fit(sd, at, ls_rows)) return WGNN_ERR_SHAPE;
+  const ValLayout vl = val_layout(sd, pl);
+  if (workspace_bytes < sizeof(float) * vl.total) return WGNN_ERR_WORKSPACE;
+  LossFn spec{};
+  if ((rc = loss_spec(sd, fn, &spec)) != WGNN_OK) return rc;      // last of the host checks, ahead of any launch
+  if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
+  float* ws = (float*)workspace;
+  float* loss_buf = ws + vl.loss_buf;
+  rc = series_val_fwd(&pl.front, &pl.rec, sd->stride, A, Xs, p, Ls, ls_rows, last ? last : ws + vl.last, wind_min, wind_max,
+                      loss_buf, workspace, pl.sp, stream, starts, &spec);
+  if (rc != WGNN_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = gru_blocks(sd->n);
+  PROF_LAUNCH("series_val_finish_kernel", 3.0 * nb, 12.0 * nb, st,
+              hipLaunchKernelGGL(series_val_finish_kernel, dim3(1), dim3(VAL_THREADS), 0, st, loss_buf, nb, spec, loss,
+                                 (ValRecord*)val, (unsigned*)workspace));
+  WGNN_CHECK_LAUNCH();
+  return WGNN_OK;
 }
 
 }  // namespace
@@ -390,6 +551,50 @@ int wgnn_series_bwd_lossfn(const wgnn_series_dims* sd, const float* A, const flo
                            void* workspace, size_t workspace_bytes, void* stream) {
   return backward_mse(sd, A, Xs, p, Y, Ls, ls_rows, grad_scale, stash, loss_buf, loss, grads, workspace, workspace_bytes, stream,
                       sd && sd->stride == 0, starts, false, true, fn);
+}
+
+// ---- include/windgnn_series_val.h ----
+int wgnn_series_val_version(void) { return WGNN_SERIES_VAL_VERSION; }
+
+size_t wgnn_val_bytes(void) { return VAL_BYTES; }
+
+int wgnn_val_init(void* val, void* stream) {
+  if (!val) return WGNN_ERR_NULL;
+  hipStream_t st = (hipStream_t)stream;
+  PROF_LAUNCH("val_init_kernel", 0.0, (double)VAL_BYTES, st,
+              hipLaunchKernelGGL(val_init_kernel, dim3(1), dim3(64), 0, st, (unsigned long long*)val));
+  WGNN_CHECK_LAUNCH();
+  return WGNN_OK;
+}
+
+int wgnn_val_begin(void* val, void* stream) {
+  if (!val) return WGNN_ERR_NULL;
+  hipStream_t st = (hipStream_t)stream;
+  PROF_LAUNCH("val_begin_kernel", 0.0, 40.0, st,
+              hipLaunchKernelGGL(val_begin_kernel, dim3(1), dim3(64), 0, st, (ValRecord*)val));
+  WGNN_CHECK_LAUNCH();
+  return WGNN_OK;
+}
+
+size_t wgnn_series_val_workspace_bytes(const wgnn_series_dims* sd) {
+  Plan pl;
+  return plan(sd, &pl, sd && sd->stride == 0) == WGNN_OK ? sizeof(float) * val_layout(sd, pl).total : 0;
+}
+
+int wgnn_series_val(const wgnn_series_dims* sd, const float* A, const float* Xs, const int32_t* starts, const wgnn_params* p,
+                    const float* Ls, int64_t ls_rows, const wgnn_lossfn* fn, float wind_min, float wind_max, float* last,
+                    float* loss, void* val, void* workspace, size_t workspace_bytes, void* stream) {
+  return validate(sd, A, Xs, starts, p, Ls, ls_rows, fn, wind_min, wind_max, last, loss, val, workspace, workspace_bytes, stream);
+}
+
+int wgnn_val_close(void* val, const void* best, void* stream) {
+  if (!val) return WGNN_ERR_NULL;
+  hipStream_t st = (hipStream_t)stream;
+  PROF_LAUNCH("val_close_kernel", 0.0, 24.0, st,
+              hipLaunchKernelGGL(val_close_kernel, dim3(1), dim3(64), 0, st, (ValRecord*)val,
+                                 best ? (const int32_t*)((const char*)best + 32) : nullptr));
+  WGNN_CHECK_LAUNCH();
+  return WGNN_OK;
 }
 
 }  // extern "C"

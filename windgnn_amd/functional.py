@@ -129,13 +129,15 @@ class _Workspace:
 _WORKSPACE_BYTES = {_lib.Dims: "wgnn_workspace_bytes", _lib.SeriesDims: "wgnn_series_workspace_bytes"}
 
 
-def _workspace(d, device, refused=None):
+def _workspace(d, device, refused=None, query=None):
     """(workspace, bytes to pass) of the dims struct `d` (wgnn_dims or wgnn_series_dims) on `device`: one size query of the
     library per call, then this stream's shared buffer, grown if need be.  The library sizes nothing (0) for dims it refuses:
-    with `refused` (the call, for the message) that is raised here with its reason; without, the entry point reports it."""
-    query = _WORKSPACE_BYTES[type(d)]
-    if isinstance(d, _lib.SeriesDims) and d.stride == 0:       # a table of starts: include/windgnn_series_at.h
-        query = "wgnn_series_at_workspace_bytes"
+    with `refused` (the call, for the message) that is raised here with its reason; without, the entry point reports it.
+    query: another size query of the same dims (wgnn_series_val_workspace_bytes, which serves both row mappings)."""
+    if query is None:
+        query = _WORKSPACE_BYTES[type(d)]
+        if isinstance(d, _lib.SeriesDims) and d.stride == 0:       # a table of starts: include/windgnn_series_at.h
+            query = "wgnn_series_at_workspace_bytes"
     ws_bytes = getattr(_lib.load(), query)(C.byref(d))
     if ws_bytes == 0 and refused is not None:
         _lib.check(-5 if d.F == 13 else -2, refused)
@@ -168,7 +170,9 @@ _STATUS_TEXT = {1: "a graph-convolution pre-activation left fp16's range (|x| > 
                 8: "wgnn_bwd_mse_part(part | 8) ran on a stash whose last forward was not wgnn_fwd_loss: the loss is NaN "
                    "and the gradients are not to be used",
                 16: "a table of window starts (series mode, starts=) holds an entry outside [0, rows - seq_len] or is not "
-                    "non-decreasing: the results of that call are not to be used"}
+                    "non-decreasing: the results of that call are not to be used",
+                32: "a validation call (wgnn_series_val, missing_labels=True) found no label at all on its windows: its loss is "
+                    "NaN"}
 _STATUS_FP16_BITS = 1 | 2      # the reports that come from fp16's range: only they get the advice about the math modes
 
 
@@ -456,6 +460,54 @@ def keep_best(d, loss: torch.Tensor, params, best_params, step: int, record: tor
     """wgnn_keep_best: the reference's rule (src/main.py:83-86) on the device -- if float64(loss) < record.best_loss, the 8
     tensors `params` are copied into `best_params` and best_loss / best_step = loss / `step`; no host synchronisation."""
     keep_best_launch(keep_best_args(d, loss, params, best_params, record), step)
+
+
+def val_bytes() -> int:
+    """wgnn_val_bytes(): bytes of the record of a validation pass (include/windgnn_series_val.h)."""
+    return int(_lib.load().wgnn_val_bytes())
+
+
+def val_word(record: torch.Tensor, name: str) -> torch.Tensor:
+    """A 0-dim VIEW of one public word of a validation record (uint8 [val_bytes()]): _lib.VAL_WORDS names them."""
+    off, dtype = _lib.VAL_WORDS[name]
+    dtype = getattr(torch, dtype)
+    return record[off:off + torch.empty((), dtype=dtype).element_size()].view(dtype)[0]
+
+
+def _val_ptr(record):
+    if not record.is_cuda:
+        raise RuntimeError("windgnn_amd runs on an MI355X (HIP) only: the validation record is on %s. There is no CPU fallback."
+                           % record.device)
+    _require_contiguous(val=record)
+    _require_scratch_aligned(val=record)
+    if record.dtype != torch.uint8 or record.numel() < val_bytes():
+        raise RuntimeError("windgnn_amd: the validation record must be a uint8 tensor of wgnn_val_bytes() = %d bytes, got %s %s"
+                           % (val_bytes(), record.dtype, tuple(record.shape)))
+    return _ptr(record)
+
+
+def val_init(record: torch.Tensor) -> None:
+    """wgnn_val_init: every byte of `record` (it may be dirty) written; sums, counts, passes and stale 0, mean and loss NaN."""
+    _lib.check(_lib.load().wgnn_val_init(_val_ptr(record), _stream()), "wgnn_val_init")
+
+
+def val_buffer(device) -> torch.Tensor:
+    """A fresh, initialised validation record on `device` (uint8 [val_bytes()]); val_word reads its public words."""
+    record = torch.empty(val_bytes(), dtype=torch.uint8, device=device)
+    val_init(record)
+    return record
+
+
+def val_begin(record: torch.Tensor) -> None:
+    """wgnn_val_begin: opens a pass (sum, count, mean, max_abs, loss and calls reset; passes and stale kept)."""
+    _lib.check(_lib.load().wgnn_val_begin(_val_ptr(record), _stream()), "wgnn_val_begin")
+
+
+def val_close(record: torch.Tensor, best: torch.Tensor = None) -> None:
+    """wgnn_val_close: passes += 1 and, with the best record that wgnn_keep_best has just decided on from this record's loss
+    word, stale = 0 if it won, else stale + 1."""
+    _lib.check(_lib.load().wgnn_val_close(_val_ptr(record), _record_ptr(best) if best is not None else C.c_void_p(0), _stream()),
+               "wgnn_val_close")
 
 
 def rows_align(d) -> int:

@@ -137,9 +137,11 @@ def _fn(lib, name: str, sd):
     return getattr(lib, ("wgnn_series_at_%s" if name.endswith("_bytes") else "wgnn_series_%s_at") % name)
 
 
-def _series_setup(A, series, seq_len: int, stride: int, params: Sequence[torch.Tensor], math: int, n_windows=None, starts=None):
+def _series_setup(A, series, seq_len: int, stride: int, params: Sequence[torch.Tensor], math: int, n_windows=None, starts=None,
+                  ws_query=None):
     """Everything a series call checks and sizes before it launches: (adjacency, dims, workspace, workspace bytes); with
-    `starts` also the int32 device table (dims.stride = 0, dims.n = its length), as a fifth result."""
+    `starts` also the int32 device table (dims.stride = 0, dims.n = its length), as a fifth result.  ws_query: the size query
+    of an entry point with a workspace of its own (series_val_raw)."""
     if hasattr(A, "blob"):
         raise RuntimeError("windgnn_amd: series mode takes a dense adjacency (S <= 64), not a CsrAdjacency: " + _MATERIALISED)
     if math != _lib.MATH_F32:
@@ -161,7 +163,7 @@ def _series_setup(A, series, seq_len: int, stride: int, params: Sequence[torch.T
         sd = _lib.SeriesDims(rows, seq_len, 0, table.numel(), S, F, H, math, fmt, nnz, _lib.IO_F32)
         ws, ws_bytes = _workspace(sd, series.device,
                                   refused="wgnn_series_at_workspace_bytes(rows=%d,T=%d,n=%d,S=%d,F=%d,H=%d) [%s]"
-                                  % (rows, seq_len, table.numel(), S, F, H, _MATERIALISED))
+                                  % (rows, seq_len, table.numel(), S, F, H, _MATERIALISED), query=ws_query)
         return A, sd, ws, ws_bytes, table
     fit = n_series_windows(rows, seq_len, stride)
     if fit < 1:
@@ -175,7 +177,7 @@ def _series_setup(A, series, seq_len: int, stride: int, params: Sequence[torch.T
     sd = _lib.SeriesDims(rows, seq_len, stride, n, S, F, H, math, fmt, nnz, _lib.IO_F32)
     ws, ws_bytes = _workspace(sd, series.device,
                               refused="wgnn_series_workspace_bytes(rows=%d,T=%d,stride=%d,n=%d,S=%d,F=%d,H=%d) [%s]"
-                              % (rows, seq_len, stride, n, S, F, H, _MATERIALISED))
+                              % (rows, seq_len, stride, n, S, F, H, _MATERIALISED), query=ws_query)
     return A, sd, ws, ws_bytes
 
 
@@ -350,6 +352,48 @@ def series_backward_mse_raw(sd, A, series, params, Y, Ls, stash, loss_buf, grads
                                  float(grad_scale), _stash_ptr(stash), _ptr(loss_buf), _ptr(loss), C.byref(gs), _ptr(ws),
                                  ws_bytes, _stream())
     _lib.check(rc, "wgnn_series_bwd_mse_at" if at else "wgnn_series_bwd_mse")
+
+
+def val_spec(loss, huber_delta, loss_from, seq_len, missing_labels=False, who="windgnn_amd series mode"):
+    """The wgnn_lossfn of a validation pass: loss_spec's checks and refusals, but always a spec -- wgnn_series_val has no entry
+    point without one, so the defaults are {MSE, 0, step 0, masked}."""
+    spec = loss_spec(loss, huber_delta, loss_from, seq_len, missing_labels, who)
+    return spec if spec is not None else _lib.LossFn(_lib.LOSS_MSE, 0.0, 0, 1 if missing_labels else 0)
+
+
+def series_val_raw(A, series, params, Ls, seq_len, stride=None, n_windows=None, math=_lib.MATH_F32, prepared=None, loss="mse",
+                   huber_delta=1.0, loss_from=0, missing_labels=False, starts=None, last=None, out_loss=None, val=None,
+                   wind_min=0.0, wind_max=1.0):
+    """wgnn_series_val (include/windgnn_series_val.h): the loss of the spec loss= / huber_delta= / loss_from= / missing_labels= on
+    the windows of `series` (stride / n_windows, or a NON-DECREASING table starts=), forward-only: no Y, no stash, no backward.
+    last [n, H] (optional): Y[:, -1] * (wind_max - wind_min) + wind_min, as forward_last_series gives it; out_loss (a 0-dim or
+    1-element fp32 device tensor, optional): the bits series_forward_loss_raw + series_backward_mse_raw would leave in their
+    loss; val (functional.val_buffer, optional): the record this call's sums are added to.  At least one of out_loss / val.
+    Returns (dims, table or None)."""
+    from .functional import _val_ptr
+    lib = _lib.load()
+    spec = val_spec(loss, huber_delta, loss_from, seq_len, missing_labels)
+    if out_loss is None and val is None:
+        raise ValueError("windgnn_amd: series_val_raw needs out_loss= or val= (or both): there is nothing else to report the loss in")
+    stride = None if starts is not None else (1 if stride is None else int(stride))
+    A, sd, ws, ws_bytes, *table = _series_setup(A, series, seq_len, stride, params, math, n_windows, starts,
+                                                ws_query="wgnn_series_val_workspace_bytes")
+    _check_label_series(Ls, sd)
+    if last is not None:
+        _require_gpu(last)
+        _require_contiguous(last=last)
+        if tuple(last.shape) != (sd.n, sd.H):
+            raise RuntimeError("windgnn_amd: series_val_raw: last must be [n = %d, H = %d], got %s" % (sd.n, sd.H, tuple(last.shape)))
+    if out_loss is not None:
+        _require_gpu(out_loss)
+        if out_loss.numel() != 1:
+            raise RuntimeError("windgnn_amd: series_val_raw: out_loss must hold one float, got %s" % (tuple(out_loss.shape),))
+    ps = _params_struct(_lib.Params, params, prepared)
+    rc = lib.wgnn_series_val(C.byref(sd), _ptr(A), _ptr(series), *_masked_table(_table_arg(sd, *table)), C.byref(ps), _ptr(Ls),
+                             Ls.shape[0], C.byref(spec), float(wind_min), float(wind_max), _ptr(last), _ptr(out_loss),
+                             _val_ptr(val) if val is not None else C.c_void_p(0), _ptr(ws), ws_bytes, _stream())
+    _lib.check(rc, "wgnn_series_val")
+    return sd, (table[0] if table else None)
 
 
 class SeriesFunction(torch.autograd.Function):

@@ -65,7 +65,13 @@ series Ls (series.series_labels' first result), which the recurrence kernels rea
 the MSE partial sums in a small buffer, wgnn_series_bwd_mse forms dY inside BPTT, finalises the loss into the bucket's header
 word and leaves FINAL gradients in the bucket (series mode does not defer its partial sums), so the schedule runs on _FINAL:
 its tail is one wgnn_finish(0, adam) that only steps Adam and refreshes the W_ih images.  With a process group the one
-all-reduce sits between the backward and that tail.  Exact fp32, a dense adjacency, the one-bucket schedules; the rest is refused with the alternative."""
+all-reduce sits between the backward and that tail.  Exact fp32, a dense adjacency, the one-bucket schedules; the rest is refused with the alternative.
+
+Validation (validate_series; include/windgnn_series_val.h): the loss of step_series' spec on windows the model is not training
+on, forward-only (wgnn_series_val: no Y, no stash, no backward) and accumulated over calls in a device record.  With
+TrainStep(keep_best=..., best_on="validation") no training step decides on the best model; a closed validation pass does --
+wgnn_keep_best on the record's loss word, then wgnn_val_close, which keeps the patience counter `val_stale`.  Nothing is
+exchanged under a process group: every rank validates the same tables and takes the same decision.  No host read anywhere."""
 from __future__ import annotations
 
 import collections
@@ -77,10 +83,11 @@ from .distributed import HEADER, LOSS_SLOT, BucketExchange, grad_block_plan
 from .functional import (PARAM_ORDER, _forward_setup, _require_gpu, best_bytes, best_init, best_word, bwd_rows, check_range_status,
                          clip_buffer, clip_bytes, finish_clipped, finish_norm, finish_rows, finish_step,
                          gcn_gru_backward_mse_raw, gcn_gru_forward_raw, gcn_gru_state_backward_raw, gcn_gru_state_forward_raw,
-                         keep_best_args, keep_best_launch, mse_loss_grad, prepared_weights, refresh_prepared, rows_align)
+                         keep_best_args, keep_best_launch, mse_loss_grad, prepared_weights, refresh_prepared, rows_align,
+                         val_begin, val_buffer, val_close, val_init, val_word)
 from .modules import GCN_GRU
-from .series import (_no_stride_with_starts, loss_spec, n_series_windows, series_backward_mse_raw, series_forward_loss_raw,
-                     sorted_starts)
+from .series import (_no_stride_with_starts, _starts_table, loss_spec, n_series_windows, series_backward_mse_raw,
+                     series_forward_loss_raw, series_val_raw, sorted_starts, val_spec)
 
 AUTO_GRAD_BLOCKS = 8                # grad_blocks="auto": row blocks per GRU weight ...
 AUTO_BLOCK_BYTES = 64 << 20         # ... from a gradient bucket of this size (smaller ones are latency-bound: one bucket)
@@ -127,7 +134,8 @@ _FINAL = _Final()
 class TrainStep:
     def __init__(self, model: GCN_GRU, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  process_group=None, check_every: int = 100, overlap_collectives: bool = False, direct_rccl=None,
-                 rccl_loader=None, carry_state: bool = False, grad_blocks=None, max_grad_norm=None, keep_best=None):
+                 rccl_loader=None, carry_state: bool = False, grad_blocks=None, max_grad_norm=None, keep_best=None,
+                 best_on: str = "train"):
         """carry_state: truncated BPTT over consecutive chunks -- each step starts the recurrence from the h_n of the previous
         step (detached; zeros on the first step and after reset_state()), so a model trained on chunks of a long series
         learns the carried-state regime StreamingForecaster(window=None) serves.  The batch size must stay the same
@@ -149,7 +157,10 @@ class TrainStep:
         the step with the smallest loss so far (threshold +inf: the first finite loss wins); a float = keep them only once
         the loss falls below it (0.03 is the reference's initial best_loss, src/main.py:60).  As in the reference the loss
         of the forward BEFORE the update decides and the parameters AFTER the optimiser step are kept (module docstring).
-        Every schedule takes it, the empty-shard step included."""
+        Every schedule takes it, the empty-shard step included.
+
+        best_on (with keep_best): "train" = the rule above, launch for launch; "validation" = no step decides -- a CLOSED
+        validation pass does (validate_series): its held-out loss is compared, and the parameters at that moment are kept."""
         if not getattr(model, "fused", True):
             raise RuntimeError("windgnn_amd: TrainStep drives the fused hot path, i.e. the reference model's own widths "
                                "(input_dim = hidden_dim = 13, src/main.py:41); a GCN_GRU of other widths trains through "
@@ -186,6 +197,14 @@ class TrainStep:
             if keep_best != keep_best:
                 raise ValueError("windgnn_amd: keep_best must be None, True or a loss threshold, got NaN")
         self.keep_best = keep_best
+        if best_on not in ("train", "validation"):
+            raise ValueError("windgnn_amd: TrainStep(best_on=%r): 'train' (the loss of every step decides) or 'validation' (the "
+                             "loss of every closed validate_series pass does)" % (best_on,))
+        if best_on == "validation" and keep_best is None:
+            raise ValueError("windgnn_amd: TrainStep(best_on='validation') needs keep_best (True, or a loss threshold): without it "
+                             "there is no record and no snapshot for a validation pass to decide on")
+        self.best_on = best_on
+        self._val, self._val_open, self._val_best_call = None, False, None     # the validation record: made by the first pass
         self._clip = None               # wgnn_finish_norm's buffer: sized at the first clipped step (wgnn_clip_bytes needs its dims)
         # gradient bucket with a 4-float header (16-byte aligned bucket): header[3] = the step's loss, so that the loss
         # rides in the conv-gradient all-reduce (the conv gradients are the first 364 floats of the bucket).  The blocked
@@ -329,7 +348,7 @@ class TrainStep:
             best_word(self._best, name).copy_(torch.as_tensor(value).reshape(()))
 
     def _keep_best(self):
-        if self._best_call is not None:
+        if self._best_call is not None and self.best_on == "train":      # ("validation": a closed pass decides, not a step)
             keep_best_launch(self._best_call, self.steps)
 
     def _best_word(self, name):
@@ -375,7 +394,8 @@ class TrainStep:
         "optimizer": torch.optim.Adam(model.parameters(), lr, betas, eps).state_dict()'s layout (state[i] = {step, exp_avg,
         exp_avg_sq} for i in 0..7, one param group; hot_path_parameters() is in model.parameters() order);
         "steps"; "best": None or the record's public words plus the snapshot under the reference's keys; "carry": the
-        carried [B, H] state or None.  The parameters are model.state_dict()'s."""
+        carried [B, H] state or None; and, only once validate_series has run, "val": the public words of the validation record
+        (the last closed pass, `passes`, `stale`; an open pass raises).  The parameters are model.state_dict()'s."""
         opt = torch.optim.Adam(self.params, lr=self.lr, betas=tuple(self.betas), eps=self.eps).state_dict()
         opt["state"] = {i: {"step": torch.tensor(float(self.steps)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
                         for i, (m, v) in enumerate(zip(self.m_views, self.v_views))}
@@ -383,12 +403,19 @@ class TrainStep:
         if self._best is not None:
             best = {name: best_word(self._best, name).clone() for name in _lib.BEST_WORDS}
             best.update((k, v.clone()) for k, v in zip(PARAM_ORDER, self._best_views))
-        return {"optimizer": opt, "steps": self.steps, "best": best, "carry": self.state}
+        out = {"optimizer": opt, "steps": self.steps, "best": best, "carry": self.state}
+        if self._val is not None:       # "val": only once validate_series has made a record (else the four keys above)
+            if self._val_open:
+                raise RuntimeError("windgnn_amd: TrainStep.state_dict(): a validation pass is open (validate_series(..., more=True)); "
+                                   "passes are not checkpointed mid-way: close it with a call with more=False first")
+            out["val"] = {name: val_word(self._val, name).clone() for name in _lib.VAL_WORDS}
+        return out
 
     def load_state_dict(self, sd):
         """Takes state_dict()'s output or a bare torch.optim.Adam state dict (all eight `step` values must agree; an empty
         `state` is step 0).  Moments are written into the existing flat buffers, lr / betas / eps restored, and from the full
-        form the best record + snapshot and the carried state.  Load the parameters with model.load_state_dict."""
+        form the best record + snapshot, the carried state and, when the checkpoint has one, the validation record ("val":
+        val_passes, val_stale and the last closed pass).  Load the parameters with model.load_state_dict."""
         full = "param_groups" not in sd
         opt = sd["optimizer"] if full else sd
         groups = opt["param_groups"]
@@ -433,6 +460,11 @@ class TrainStep:
                 if tuple(best[key].shape) != tuple(view.shape):
                     raise ValueError("windgnn_amd: TrainStep.load_state_dict: best %s is %s, expected %s"
                                      % (key, tuple(best[key].shape), tuple(view.shape)))
+        val = sd.get("val") if full else None
+        if val is not None:
+            missing = [k for k in _lib.VAL_WORDS if k not in val]
+            if missing:
+                raise ValueError("windgnn_amd: TrainStep.load_state_dict: the validation record lacks %s" % ", ".join(missing))
         if carry is not None:
             H = self.p_views[5].shape[1]
             if not self.carry_state:
@@ -457,6 +489,14 @@ class TrainStep:
                 self._reset_best(float(best["best_loss"]), {name: best[name] for name in _lib.BEST_WORDS})
                 for key, view in zip(PARAM_ORDER, self._best_views):
                     view.copy_(best[key])
+        if full and val is not None:
+            if self._val is None:
+                self._val = val_buffer(self.device)
+            else:
+                val_init(self._val)
+            for name in _lib.VAL_WORDS:
+                val_word(self._val, name).copy_(torch.as_tensor(val[name]).reshape(()))
+            self._val_open = False
         if full and self.carry_state:
             if carry is None:
                 self._has_state = False
@@ -611,29 +651,29 @@ class TrainStep:
                                                          n_windows=n, prepared=self._prepared, **masked)
         return Y, stash, loss_buf, sd, d
 
-    def _series_table(self, series, Ls, seq_len, stride, n_windows, starts):
+    def _series_table(self, series, Ls, seq_len, stride, n_windows, starts, who="step_series"):
         """starts= of step_series / forward_backward_series: (sorted device table, inverse or None, n) with the label series
         checked -- a window may start at any row, so Ls needs a row for every row of the series."""
-        _no_stride_with_starts("windgnn_amd: TrainStep.step_series", stride, starts, n_windows)
-        table, inverse = sorted_starts(starts, series.shape[0], seq_len, series.device, "windgnn_amd: TrainStep.step_series")
+        _no_stride_with_starts("windgnn_amd: TrainStep." + who, stride, starts, n_windows)
+        table, inverse = sorted_starts(starts, series.shape[0], seq_len, series.device, "windgnn_amd: TrainStep." + who)
         H = self.p_views[5].shape[1]
         if table.numel() > 0 and (Ls.dim() != 2 or Ls.shape[1] != H or Ls.shape[0] < series.shape[0]):
-            raise RuntimeError("windgnn_amd: TrainStep.step_series: with starts= the label series Ls must be [rows >= the "
+            raise RuntimeError("windgnn_amd: TrainStep." + who + ": with starts= the label series Ls must be [rows >= the "
                                "series' %d, H = %d] (series_labels(feat, ...)[0] of a feat 3 rows longer than the series), got %s"
                                % (series.shape[0], H, tuple(Ls.shape)))
         return table, inverse, table.numel()
 
-    def _series_count(self, series, Ls, seq_len, stride, n_windows):
+    def _series_count(self, series, Ls, seq_len, stride, n_windows, who="step_series"):
         """The window count of this call, with n_windows and Ls checked against it."""
         fit = n_series_windows(series.shape[0], seq_len, stride)
         n = fit if n_windows is None else int(n_windows)
         if n < 0 or n > fit:
-            raise RuntimeError("windgnn_amd: TrainStep.step_series: n_windows = %d, but a series of %d rows holds %d windows of "
+            raise RuntimeError("windgnn_amd: TrainStep." + who + ": n_windows = %d, but a series of %d rows holds %d windows of "
                                "%d rows at stride %d" % (n, series.shape[0], fit, seq_len, stride))
         need = (n - 1) * stride + seq_len
         H = self.p_views[5].shape[1]
         if n > 0 and (Ls.dim() != 2 or Ls.shape[1] != H or Ls.shape[0] < need):
-            raise RuntimeError("windgnn_amd: TrainStep.step_series: the label series Ls must be [rows >= (n - 1) * stride + "
+            raise RuntimeError("windgnn_amd: TrainStep." + who + ": the label series Ls must be [rows >= (n - 1) * stride + "
                                "seq_len = %d, H = %d] (series_labels(feat, seq_len, stride, n_windows)[0]; its window view L is "
                                "for TrainStep.step on materialised windows), got %s" % (need, H, tuple(Ls.shape)))
         return n
@@ -714,6 +754,137 @@ class TrainStep:
         self._run_schedule(d, _FINAL, gs)       # the bucket is final: (the all-reduce,) Adam and the W_ih images
         self._end_step()
         return self._loss, (Y if inverse is None else Y.index_select(0, inverse))
+
+    def validate_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, starts=None, missing_labels=False,
+                        loss="mse", huber_delta=1.0, loss_from=0, more=False, evaluator=None):
+        """The loss of step_series' spec on windows the model is NOT training on (include/windgnn_series_val.h): the model's
+        current parameters, forward-only -- no Y, no stash, no backward -- and no change to the optimiser, the gradient bucket or
+        `steps`.  A, series, Ls, seq_len, stride / n_windows or starts (any order, duplicates allowed; series.segment_starts gives
+        a hold-out at window level), missing_labels, loss, huber_delta, loss_from: as in step_series.  A pass accumulates over
+        calls: more=True leaves it open for the next table or segment of the hold-out, more=False (the default) closes it.  The
+        return value is the pass's mean loss so far, a 0-dim fp32 VIEW of the device record (`val_loss`), overwritten by the
+        next call.  Closing: with TrainStep(keep_best=..., best_on="validation") wgnn_keep_best runs on that loss word with the
+        current parameters and step = `steps` (best_loss / best_step / best_state_dict() then speak of validation passes), then
+        wgnn_val_close counts the pass in `val_passes` and keeps `val_stale`, the closed passes since the last one that won --
+        the reference's `if patience > 10: break` is `int(tr.val_stale) > 10`, one host read per epoch.  With best_on="train"
+        a pass touches neither the best record nor val_stale.
+        evaluator=ev (evaluate.Evaluator): the same forward's last rows, de-normalised with ev's wind_min / wind_max, go to ev's
+        accumulator as ev.update_series would put them there (skip_missing = missing_labels): the loss the model is trained on
+        and the reference's RMSE / MAE / accuracy from one forward.
+        Nothing synchronises with the host.  Under a process group nothing is exchanged: every rank must validate the SAME tables;
+        each then gets the same bits and takes the same decision.  A hold-out sharded over the ranks is out of scope.
+        Exact fp32, a dense adjacency, S <= 64, H <= 128: the rest is refused as step_series refuses it, before any launch."""
+        seq_len, table, inverse = int(seq_len), None, None
+        self._validate_refusals(A, series, seq_len, 1 if stride is None else int(stride))
+        val_spec(loss, huber_delta, loss_from, seq_len, missing_labels, "windgnn_amd: TrainStep.validate_series")
+        if evaluator is not None and (getattr(evaluator, "H", None) != self.p_views[5].shape[1]):
+            raise ValueError("windgnn_amd: TrainStep.validate_series: evaluator= must be an evaluate.Evaluator of this model's %d "
+                             "outputs, got %r" % (self.p_views[5].shape[1], evaluator))
+        series, Ls = series.contiguous(), Ls.contiguous()
+        if starts is not None:
+            table, inverse, n = self._series_table(series, Ls, seq_len, stride, n_windows, starts, "validate_series")
+        else:
+            stride = 1 if stride is None else int(stride)
+            n = self._series_count(series, Ls, seq_len, stride, n_windows, "validate_series")
+        if n == 0:
+            raise RuntimeError("windgnn_amd: TrainStep.validate_series needs at least one window (a series of %d rows, seq_len %d, "
+                               "n_windows %r, starts %s)" % (series.shape[0], seq_len, n_windows,
+                                                             "empty" if starts is not None else None))
+        _require_gpu(series, Ls, *self.p_views)      # before the images and the record: nothing is launched on host memory
+        S, H = series.shape[1], self.p_views[5].shape[1]
+        self._ensure_images(lambda: _lib.Dims(1, seq_len, S, 13, H, _lib.MATH_F32, _lib.ADJ_DENSE, 0, _lib.IO_F32))
+        if self._val is None:
+            self._val = val_buffer(self.device)
+        if not self._val_open:
+            val_begin(self._val)
+            self._val_open = True
+        last = torch.empty(n, H, dtype=torch.float32, device=series.device) if evaluator is not None else None
+        wmin, wmax = (evaluator.wind_min, evaluator.wind_max) if evaluator is not None else (0.0, 1.0)
+        series_val_raw(A, series, self.p_views, Ls, seq_len, stride=None if table is not None else stride,
+                       n_windows=None if table is not None else n, prepared=self._prepared, loss=loss, huber_delta=huber_delta,
+                       loss_from=loss_from, missing_labels=missing_labels, starts=table, last=last, val=self._val,
+                       wind_min=wmin, wind_max=wmax)
+        if evaluator is not None:
+            self._feed_evaluator(evaluator, last, inverse, series, Ls, seq_len, stride, starts, missing_labels)
+        if not more:
+            self._close_validation()
+        return val_word(self._val, "loss")
+
+    def _validate_refusals(self, A, series, seq_len, stride):
+        """What validate_series refuses, each before any launch and with the alternative: step_series' scope without what
+        belongs to the optimiser's schedule (a pass takes no step, so carry_state, grad_blocks and overlap_collectives do not
+        enter) and without the process-group refusal of missing labels (nothing is exchanged: every rank counts its own)."""
+        windows = ("materialise the windows and labels (windgnn_amd.data.make_windows(feat, seq_len, starts=...)), run "
+                   "GCN_GRU.forward on them under torch.no_grad() and form the loss with torch")
+        why = None
+        if self.model.math != _lib.MATH_F32:
+            why = "math != 'f32': series mode is exact fp32 only; build the model with math='f32', or " + windows
+        elif hasattr(A, "blob"):
+            why = "a CsrAdjacency: series mode takes a dense adjacency (S <= 64); pass the dense matrix, or " + windows
+        elif not getattr(self.model, "fused", False):
+            why = "a model of other widths than the reference's 13 / 13: " + windows
+        if why is not None:
+            raise RuntimeError("windgnn_amd: TrainStep.validate_series with " + why)
+        if series.dim() != 3 or series.shape[2] != 13:
+            raise RuntimeError("windgnn_amd: TrainStep.validate_series: series must be [rows, S, 13], got %s" % (tuple(series.shape),))
+        if int(seq_len) < 1 or int(stride) < 1:
+            raise ValueError("windgnn_amd: TrainStep.validate_series: seq_len and stride must be >= 1, got %r and %r"
+                             % (seq_len, stride))
+
+    def _feed_evaluator(self, ev, last, inverse, series, Ls, seq_len, stride, starts, missing_labels):
+        """The pass's last rows into ev's accumulator, in the caller's order against the caller's table, as
+        Evaluator.update_series does it (the accumulator adds in row order: the same order gives the same bits)."""
+        from .evaluate import eval_accum_series
+        pred = last if inverse is None else last.index_select(0, inverse)
+        table = None
+        if starts is not None:
+            table = _starts_table(starts, series.shape[0], seq_len, series.device, "windgnn_amd: TrainStep.validate_series",
+                                  ordered=False)
+        err = torch.empty_like(pred) if ev.keep_errors else None
+        eval_accum_series(pred, Ls, seq_len, ev.wind_min, ev.wind_max, ev._acc(), None if starts is not None else stride, table,
+                          bool(missing_labels), err)
+        if err is not None:
+            ev._errors.append(err)
+
+    def _close_validation(self):
+        """The end of a pass: with best_on="validation" wgnn_keep_best on the record's loss word (the current parameters,
+        step = `steps`), then wgnn_val_close, which reads the decision that call has just published."""
+        decides = self.best_on == "validation"
+        if decides:
+            if self._val_best_call is None:      # (the record and the views never move: marshalled once)
+                self._val_best_call = keep_best_args(self._best_dims, val_word(self._val, "loss"), self.p_views, self._best_views,
+                                                     self._best)
+            keep_best_launch(self._val_best_call, self.steps)
+        val_close(self._val, self._best if decides else None)
+        self._val_open = False
+
+    def _val_word(self, name, word):
+        if self._val is None:
+            raise RuntimeError("windgnn_amd: TrainStep.%s is kept by validate_series (include/windgnn_series_val.h); no "
+                               "validation call has run on this TrainStep yet" % name)
+        return val_word(self._val, word)
+
+    @property
+    def val_loss(self):
+        """The mean held-out loss of the open pass so far, or of the last closed one (NaN before its first call and when it
+        counted no label): a 0-dim fp32 VIEW of the device record, overwritten by the next validate_series call."""
+        return self._val_word("val_loss", "loss")
+
+    @property
+    def val_count(self):
+        """The entries that pass counted (windows x steps from loss_from on x outputs, less the missing labels): 0-dim int64 VIEW."""
+        return self._val_word("val_count", "count")
+
+    @property
+    def val_passes(self):
+        """Closed validation passes: a 0-dim int64 VIEW of the device record."""
+        return self._val_word("val_passes", "passes")
+
+    @property
+    def val_stale(self):
+        """Closed passes since the last one whose loss won under best_on="validation" (0 right after a win): a 0-dim int64 VIEW;
+        `int(tr.val_stale) > 10` is the reference's patience test, one host read per epoch."""
+        return self._val_word("val_stale", "stale")
 
     def _forward(self, A, X, L):
         # the first call sizes and builds the images from the dims of this batch (they depend on S, H, math only)
