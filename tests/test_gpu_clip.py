@@ -436,9 +436,11 @@ def _clip_flow(r):
                                r.ptr("stash"), C.byref(gs), *r.ws, part), "wgnn_bwd_mse_part(%d)" % part)
     max_norm = C.c_float(0.5 * _fp64_norm(r.c.go.values()))
     r.ok(lib.wgnn_finish_norm(d, C.byref(gs), 6, max_norm, r.ptr("clip"), *r.ws), "wgnn_finish_norm(6)")
-    r.heads = [r.a["clip"].host()[:8].clone()]
+    side = r.tstream is not None                     # on a side stream nothing is read back between the calls
+    r.heads = [] if side else [r.a["clip"].host()[:8].clone()]
     r.ok(lib.wgnn_finish_norm(d, C.byref(gs), 0, max_norm, r.ptr("clip"), *r.ws), "wgnn_finish_norm(0)")
-    r.heads.append(r.a["clip"].host()[:8].clone())
+    if not side:
+        r.heads.append(r.a["clip"].host()[:8].clone())
     ad = r.adam()
     r.ok(lib.wgnn_finish_clipped(d, C.byref(ps), C.byref(gs), C.byref(ad), r.ptr("clip"), *r.ws), "wgnn_finish_clipped")
     outs = ["Y", "loss"] + ["g." + k for k in PARAM_KEYS] + [pre + k for pre in ("p.", "m.", "v.") for k in PARAM_KEYS]

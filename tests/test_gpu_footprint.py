@@ -121,9 +121,13 @@ def _fit(src, n):
 class Run:
     """All buffers of one case under one fill, each of its exact ABI length, and the calls on them."""
 
-    def __init__(self, c, fill, state=False, dirty=None, off=0, seed=0, extra=()):
+    def __init__(self, c, fill, state=False, dirty=None, off=0, seed=0, extra=(), stream=None):
+        """stream: None (the null stream; every call is followed by a synchronise and a look at the status word) or a
+        torch.cuda.Stream: every call and every fill in between is enqueued there, nothing synchronises, and the status word
+        is read once, by final_status(), after the caller's own synchronise (tests/test_gpu_streams.py)."""
         L = self.L = _lib()
         lib = self.lib = L.load()
+        self.tstream = stream
         self.c, self.fill, self.state = c, fill, state
         es = 4 if c.iodt == torch.float32 else 2
         self.d = L.Dims(c.B, c.T, c.S, F, c.H, MATH[c.math], 1 if c.k else 0, c.nnz, IO[c.iodt])
@@ -170,7 +174,7 @@ class Run:
             for nm in ("prepared", "prepared2"):
                 add(nm, torch.uint8, (self.prep_bytes,), _fit(dirty["prepared"], self.prep_bytes) if "prepared" in dirty else None)
         a.commit()
-        self.stream = C.c_void_p(0)
+        self.stream = C.c_void_p(stream.cuda_stream if stream is not None else 0)
         self.ws = (C.c_void_p(a["ws"].ptr), C.c_size_t(self.ws_bytes), self.stream)
 
     # ---- argument helpers
@@ -200,14 +204,25 @@ class Run:
     def ok(self, rc, what):
         """(c): the call succeeded and, once it has run, the status word is still 0."""
         assert rc == 0, (self.c.id, self.fill, what, rc, self.lib.wgnn_strerror(rc).decode())
+        if self.tstream is not None:
+            return
         torch.cuda.synchronize()
         word = int(self.a["ws"].bytes()[:4].view(torch.int32).item())
         assert word == 0, (self.c.id, self.fill, what, "status word %d" % word)
 
     def repoison_ws(self):
         """Between a forward and its backward the workspace is not live state: everything but the status block is poisoned."""
+        if self.tstream is not None:                    # stream-ordered, and the status block keeps what the calls left in it
+            ws = self.a["ws"]
+            with torch.cuda.stream(self.tstream):
+                self.a.mem[ws.start + STATUS:ws.start + ws.nbytes].copy_(self.a.pristine[ws.start + STATUS:ws.start + ws.nbytes])
+            return
         torch.cuda.synchronize()
         self.a["ws"].poison()
+
+    def final_status(self):
+        """The status word, for a run on a side stream: read once, after the caller has synchronised."""
+        return int(self.a["ws"].bytes()[:4].view(torch.int32).item())
 
     def tensor(self, name, res=None):
         dtype, shape = self.meta[name]

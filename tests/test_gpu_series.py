@@ -243,9 +243,10 @@ def _fit(src, n):
     return src.repeat((n + src.numel() - 1) // src.numel())[:n].contiguous()
 
 
-def _arena_run(c, fill, dirty=None):
+def _arena_run(c, fill, dirty=None, gate=None):
     """wgnn_series_fwd, wgnn_series_bwd (on a re-poisoned workspace) and wgnn_series_fwd_last on buffers of exactly their ABI
-    lengths.  Returns (outputs on the CPU, the final stash and workspace bytes)."""
+    lengths.  Returns (outputs on the CPU, the final stash and workspace bytes).  gate (tests/stream_cases.py): the calls go
+    to its side stream, nothing synchronises in between, and guards and status word are looked at once, at the end."""
     from windgnn_amd import _lib as L
     lib = L.load()
     sd = L.SeriesDims(c.rows, c.T, c.stride, c.n, c.S, F, c.H, 0, 0, 0, 0)
@@ -275,22 +276,31 @@ def _arena_run(c, fill, dirty=None):
         setattr(ps, field, a["p." + k].ptr)
         setattr(gs, field, a["g." + k].ptr)
     outs = ["Y", "last"] + ["g." + k for k in PARAM_KEYS]
+    st = gate.handle if gate is not None else None
+    if gate is not None:
+        gate.begin(a)
 
     def after(what):
+        if gate is not None:
+            return
         torch.cuda.synchronize()
         assert a.check() == {}, (what, fill, a.check())
         assert int(a["ws"].view(torch.int32)[0]) == 0, (what, "status word")
 
-    assert lib.wgnn_series_fwd(C.byref(sd), P("A"), P("Xs"), C.byref(ps), P("Y"), P("stash"), P("ws"), ws_bytes, None) == 0
+    assert lib.wgnn_series_fwd(C.byref(sd), P("A"), P("Xs"), C.byref(ps), P("Y"), P("stash"), P("ws"), ws_bytes, st) == 0
     after("wgnn_series_fwd")
-    if "ws" not in dirty:
+    if gate is not None:
+        gate.repoison(a["ws"], STATUS)
+    elif "ws" not in dirty:
         a["ws"].poison()                                   # the workspace carries nothing from the forward to the backward
     assert lib.wgnn_series_bwd(C.byref(sd), P("A"), P("Xs"), C.byref(ps), P("Y"), P("dY"), P("stash"), C.byref(gs), P("ws"),
-                               ws_bytes, None) == 0
+                               ws_bytes, st) == 0
     after("wgnn_series_bwd")
     assert lib.wgnn_series_fwd_last(C.byref(sd), P("A"), P("Xs"), C.byref(ps), WIND_MIN, WIND_MAX, P("last"), P("ws"), ws_bytes,
-                                    None) == 0
+                                    st) == 0
     after("wgnn_series_fwd_last")
+    if gate is not None:
+        gate.close(a)
     if fill != "zero" and not dirty:
         for name in outs:
             assert a[name].unwritten(4) == 0, (name, fill, a[name].unwritten(4))

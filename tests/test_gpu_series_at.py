@@ -27,12 +27,15 @@ WINDOW_START = 16                      # WGNN_STATUS_WINDOW_START
 ROUTES = ("last", "series", "mse")     # wgnn_series_fwd_last_at | _fwd_at + _bwd_at | _fwd_loss_at + _bwd_mse_at
 
 
-def _arena_step(r, fill="nan", dirty=None, table=None, status=0, routes=ROUTES):
+def _arena_step(r, fill="nan", dirty=None, table=None, status=0, routes=ROUTES, gate=None):
     """The five table entry points on the reference r inside an arena.  table: the int32 table to pass (default: r's own);
     status: the bits every call must leave in the status word (it is zeroed again after each).  Returns (outputs as host bytes
-    per route, launched names, final scratch bytes)."""
+    per route, launched names, final scratch bytes).  gate (tests/stream_cases.py): the calls go to its side stream, nothing
+    is read or synchronised in between (so "series" and "mse", which share Y and the gradients, do not go together), no kernel
+    names are collected, and guards and status word are looked at once, at the end."""
     from windgnn_amd import _lib as L
     lib = L.load()
+    assert gate is None or not ("series" in routes and "mse" in routes)
     n, T, H, rows = r.n, r.T, r.H, r.rows
     sd = L.SeriesDims(rows, T, 0, n, r.S, F, H, 0, 0, 0, 0)
     ws_bytes, st_bytes = lib.wgnn_series_at_workspace_bytes(C.byref(sd)), lib.wgnn_series_at_stash_bytes(C.byref(sd))
@@ -65,8 +68,14 @@ def _arena_step(r, fill="nan", dirty=None, table=None, status=0, routes=ROUTES):
         setattr(ps, field, a["p." + k].ptr)
         setattr(gs, field, a["g." + k].ptr)
     word = a["ws"].view(torch.int32)
+    st = gate.handle if gate is not None else None
+    if gate is not None:
+        gate.begin(a, ints=("starts",))
 
     def after(what):
+        if gate is not None:
+            gate.repoison(a["ws"], STATUS)
+            return
         torch.cuda.synchronize()
         assert a.check() == {}, (what, fill, a.check())
         assert int(word[0]) == status, (what, "status word", int(word[0]))
@@ -75,29 +84,39 @@ def _arena_step(r, fill="nan", dirty=None, table=None, status=0, routes=ROUTES):
             a["ws"].poison()                               # the workspace carries nothing from one call to the next
 
     def call(name, *args):
-        assert getattr(lib, name)(C.byref(sd), P("A"), P("Xs"), P("starts"), C.byref(ps), *args, P("ws"), ws_bytes, None) == 0, name
+        assert getattr(lib, name)(C.byref(sd), P("A"), P("Xs"), P("starts"), C.byref(ps), *args, P("ws"), ws_bytes, st) == 0, name
         after(name)
+
+    def read(names):
+        return (lambda: {name: a[name].host() for name in names}) if gate is not None else {name: a[name].host() for name in names}
 
     grads = ["g." + k for k in PARAM_KEYS]
     out = {}
-    L.profile_enable(True)
+    if gate is None:
+        L.profile_enable(True)
     try:
         if "last" in routes:
             call("wgnn_series_fwd_last_at", WIND_MIN, WIND_MAX, P("last"))
-            out["last"] = {"last": a["last"].host()}
+            out["last"] = read(["last"])
         if "series" in routes:
             call("wgnn_series_fwd_at", P("Y"), P("stash"))
             call("wgnn_series_bwd_at", P("Y"), P("dY"), P("stash"), C.byref(gs))
-            out["series"] = {name: a[name].host() for name in ["Y"] + grads}
+            out["series"] = read(["Y"] + grads)
         if "mse" in routes:
-            for name in ["Y"] + grads:
-                a[name].poison()
+            if gate is None:
+                for name in ["Y"] + grads:
+                    a[name].poison()
             call("wgnn_series_fwd_loss_at", P("Ls"), rows, P("Y"), P("stash"), P("loss_buf"))
             call("wgnn_series_bwd_mse_at", P("Y"), P("Ls"), rows, 1.0, P("stash"), P("loss_buf"), P("loss"), C.byref(gs))
-            out["mse"] = {name: a[name].host() for name in ["Y", "loss"] + grads}
-        names = tuple(rec["name"] for rec in L.profile_read())
+            out["mse"] = read(["Y", "loss"] + grads)
+        names = tuple(rec["name"] for rec in L.profile_read()) if gate is None else ()
     finally:
-        L.profile_enable(False)
+        if gate is None:
+            L.profile_enable(False)
+    if gate is not None:
+        gate.close(a)
+        out = {route: get() for route, get in out.items()}
+        return out, names, {k: a[k].host() for k in ("stash", "ws", "loss_buf")}
     if fill != "zero" and not dirty and not status:
         for name in ["Y", "last", "loss"] + grads:
             assert a[name].unwritten(4) == 0, (name, fill, a[name].unwritten(4))

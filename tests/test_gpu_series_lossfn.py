@@ -47,12 +47,15 @@ def _spec(q, **over):
     return (d["kind"], d["delta"], d["t_from"], d["masked"])
 
 
-def _arena_step(q, fwd="lossfn", bwd=None, fill="nan", dirty=None, status=0, grad_scale=1.0, Ls=None, short_buf=False):
+def _arena_step(q, fwd="lossfn", bwd=None, fill="nan", dirty=None, status=0, grad_scale=1.0, Ls=None, short_buf=False,
+                gate=None):
     """One forward + backward pair on the reference q inside an arena, the workspace re-poisoned in between.  fwd / bwd: "plain"
     (wgnn_series_fwd_loss / _bwd_mse or their _at forms), "masked" (the masked pair), "lossfn" (the new pair on q's own spec), or
     a spec tuple (the new pair on that spec); bwd defaults to fwd.  status: the bits the backward must leave in the window-major
     half's status block.  short_buf: loss_buf has the unmasked forward's own, shorter length whatever the backward is.
-    Returns (outputs as host bytes, launched names, final scratch bytes)."""
+    Returns (outputs as host bytes, launched names, final scratch bytes).  gate (tests/stream_cases.py): the calls go to its
+    side stream, nothing synchronises in between, no kernel names are collected, and guards and both status words are looked
+    at once, at the end."""
     from windgnn_amd import _lib as L
     lib = L.load()
     bwd = fwd if bwd is None else bwd
@@ -93,7 +96,11 @@ def _arena_step(q, fwd="lossfn", bwd=None, fill="nan", dirty=None, status=0, gra
     table = (P("starts"),) if q.stride is None else (None,)
     strided = () if q.stride is not None else table              # the unmasked strided entry points take no table argument
 
+    st = gate.handle if gate is not None else None
+
     def after(what, want=0):
+        if gate is not None:
+            return
         torch.cuda.synchronize()
         assert a.check() == {}, (what, fill, a.check())
         assert int(word[0]) == 0, (what, "status word", int(word[0]))
@@ -101,7 +108,7 @@ def _arena_step(q, fwd="lossfn", bwd=None, fill="nan", dirty=None, status=0, gra
 
     def forward(how):
         head = (C.byref(sd), P("A"), P("Xs"))
-        tail = (P("Y"), P("stash"), P("loss_buf"), P("ws"), ws_bytes, None)
+        tail = (P("Y"), P("stash"), P("loss_buf"), P("ws"), ws_bytes, st)
         if how == "plain":
             fn = lib.wgnn_series_fwd_loss_at if q.stride is None else lib.wgnn_series_fwd_loss
             return fn(*head, *strided, C.byref(ps), P("Ls"), ls_rows, *tail)
@@ -113,7 +120,7 @@ def _arena_step(q, fwd="lossfn", bwd=None, fill="nan", dirty=None, status=0, gra
     def backward(how):
         head = (C.byref(sd), P("A"), P("Xs"))
         mid = (C.byref(ps), P("Y"), P("Ls"), ls_rows, grad_scale)
-        tail = (P("stash"), P("loss_buf"), P("loss"), C.byref(gs), P("ws"), ws_bytes, None)
+        tail = (P("stash"), P("loss_buf"), P("loss"), C.byref(gs), P("ws"), ws_bytes, st)
         if how == "plain":
             fn = lib.wgnn_series_bwd_mse_at if q.stride is None else lib.wgnn_series_bwd_mse
             return fn(*head, *strided, *mid, *tail)
@@ -123,20 +130,29 @@ def _arena_step(q, fwd="lossfn", bwd=None, fill="nan", dirty=None, status=0, gra
         return lib.wgnn_series_bwd_lossfn(*head, *table, *mid, C.byref(spec), *tail)
 
     word[off // 4] = 0                                       # kernels only OR into the block: the caller zeroes it
-    L.profile_enable(True)
+    if gate is not None:
+        assert fill == "zero" and not dirty and not status       # (re-poisoning with zeros is what clears the second status block)
+        gate.begin(a, ints=("starts",))
+    else:
+        L.profile_enable(True)
     try:
         rc = forward(fwd)
         assert rc == 0, rc
         after("forward %r" % (fwd,))
-        if "ws" not in dirty:
+        if gate is not None:
+            gate.repoison(a["ws"], STATUS)
+        elif "ws" not in dirty:
             a["ws"].poison()                                 # the workspace carries nothing from the forward to the backward
             word[off // 4] = 0
         rc = backward(bwd)
         assert rc == 0, rc
         after("backward %r" % (bwd,), status)
-        names = tuple(rec["name"] for rec in L.profile_read())
+        names = tuple(rec["name"] for rec in L.profile_read()) if gate is None else ()
     finally:
-        L.profile_enable(False)
+        if gate is None:
+            L.profile_enable(False)
+    if gate is not None:
+        gate.close(a, words=(0, off))
     outs = ["Y", "loss"] + GRADS
     if fill != "zero" and not dirty:
         spare = 0 if fwd not in ("plain", "masked") else 3       # the new forward writes its spec into the three spare words

@@ -321,9 +321,9 @@ def test_checkpoint_round_trip_continues_bit_identically():
 
 
 # ---- footprint: both entry points inside guarded arenas -------------------------------------------------------------------
-def _arena_run(c, t, fill, dirty=None):
+def _arena_run(c, t, fill, dirty=None, gate=None):
     """wgnn_series_fwd_loss and wgnn_series_bwd_mse (on a re-poisoned workspace) on buffers of exactly their ABI lengths.
-    Returns (outputs on the CPU, the final stash / workspace / loss_buf bytes)."""
+    Returns (outputs on the CPU, the final stash / workspace / loss_buf bytes).  gate: as in test_gpu_series._arena_run."""
     from windgnn_amd import _lib as L
     lib = L.load()
     sd = L.SeriesDims(c.rows, c.T, c.stride, c.n, c.S, F, c.H, 0, 0, 0, 0)
@@ -356,20 +356,29 @@ def _arena_run(c, t, fill, dirty=None):
         setattr(ps, field, a["p." + k].ptr)
         setattr(gs, field, a["g." + k].ptr)
     outs = ["Y", "loss"] + ["g." + k for k in PARAM_KEYS]
+    st = gate.handle if gate is not None else None
+    if gate is not None:
+        gate.begin(a)
 
     def after(what):
+        if gate is not None:
+            return
         torch.cuda.synchronize()
         assert a.check() == {}, (what, fill, a.check())
         assert int(a["ws"].view(torch.int32)[0]) == 0, (what, "status word")
 
     assert lib.wgnn_series_fwd_loss(C.byref(sd), P("A"), P("Xs"), C.byref(ps), P("Ls"), t.need, P("Y"), P("stash"),
-                                    P("loss_buf"), P("ws"), ws_bytes, None) == 0
+                                    P("loss_buf"), P("ws"), ws_bytes, st) == 0
     after("wgnn_series_fwd_loss")
-    if "ws" not in dirty:
+    if gate is not None:
+        gate.repoison(a["ws"], STATUS)
+    elif "ws" not in dirty:
         a["ws"].poison()                                   # the workspace carries nothing from the forward to the backward
     assert lib.wgnn_series_bwd_mse(C.byref(sd), P("A"), P("Xs"), C.byref(ps), P("Y"), P("Ls"), t.need, 1.0, P("stash"),
-                                   P("loss_buf"), P("loss"), C.byref(gs), P("ws"), ws_bytes, None) == 0
+                                   P("loss_buf"), P("loss"), C.byref(gs), P("ws"), ws_bytes, st) == 0
     after("wgnn_series_bwd_mse")
+    if gate is not None:
+        gate.close(a)
     if fill != "zero" and not dirty:
         for name in outs:
             assert a[name].unwritten(4) == 0, (name, fill, a[name].unwritten(4))

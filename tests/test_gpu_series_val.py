@@ -52,11 +52,13 @@ def _words(rec):
 
 
 def _val_run(q, fill="nan", dirty=None, spec=None, Ls=None, starts=None, cuts=None, passes=1, null=(), status=0,
-             wind=(WIND_MIN, WIND_MAX)):
+             wind=(WIND_MIN, WIND_MAX), gate=None):
     """wgnn_val_init on a dirty record, then `passes` passes of wgnn_val_begin + wgnn_series_val + wgnn_val_close(NULL) on the
     reference q inside an arena.  starts: another table than q's (table mapping); cuts: window indices at which the table is cut
     into several calls of one pass (table mapping; each call gets exactly its own workspace_bytes); null: outputs passed as NULL
-    ("last", "loss", "val").  Returns (outputs as host tensors, the record's words after each pass, launched names, scratch)."""
+    ("last", "loss", "val").  Returns (outputs as host tensors, the record's words after each pass, launched names, scratch).
+    gate (tests/stream_cases.py): the calls go to its side stream, nothing synchronises between the passes (the record's words
+    are those after the last one only), and no kernel names are collected."""
     from windgnn_amd import _lib as L
     lib = L.load()
     table = q.starts if starts is None else starts
@@ -99,24 +101,33 @@ def _val_run(q, fill="nan", dirty=None, spec=None, Ls=None, starts=None, cuts=No
     def P(name, off=0):
         return None if name in null else C.c_void_p(a[name].ptr + off)
     records = []
-    L.profile_enable(True)
+    st = gate.handle if gate is not None else None
+    if gate is not None:
+        gate.begin(a, ints=("starts",))
+    else:
+        L.profile_enable(True)
     try:
         with_val = "val" not in null
-        assert not with_val or lib.wgnn_val_init(P("val"), None) == 0
+        assert not with_val or lib.wgnn_val_init(P("val"), st) == 0
         for _ in range(passes):
-            assert not with_val or lib.wgnn_val_begin(P("val"), None) == 0
+            assert not with_val or lib.wgnn_val_begin(P("val"), st) == 0
             for i, (lo, hi) in enumerate(calls):
                 sd = dims(hi - lo)
                 rc = lib.wgnn_series_val(C.byref(sd), P("A"), P("Xs"), P("starts", 4 * lo) if q.stride is None else None,
                                          C.byref(ps), P("Ls"), ls_rows, C.byref(fn), wind[0], wind[1], P("last", 4 * lo * H),
-                                         P("loss", 4 * i), P("val"), P("ws"), need[i], None)
+                                         P("loss", 4 * i), P("val"), P("ws"), need[i], st)
                 assert rc == 0, rc
-            assert not with_val or lib.wgnn_val_close(P("val"), None, None) == 0
-            torch.cuda.synchronize()
-            records.append(_words(a["val"].host()))
-        names = tuple(rec["name"] for rec in L.profile_read())
+            assert not with_val or lib.wgnn_val_close(P("val"), None, st) == 0
+            if gate is None:
+                torch.cuda.synchronize()
+                records.append(_words(a["val"].host()))
+        names = tuple(rec["name"] for rec in L.profile_read()) if gate is None else ()
     finally:
-        L.profile_enable(False)
+        if gate is None:
+            L.profile_enable(False)
+    if gate is not None:
+        gate.end()
+        records.append(_words(a["val"].host()))
     assert a.check() == {}, (fill, a.check())
     assert int(word[0]) == status, ("status word", int(word[0]), status)
     if fill != "zero" and "ws" not in dirty:

@@ -15,7 +15,8 @@ LABEL_FEATURE = 11     # reference column 13 ("Wind Speed 10 m Avg.") minus the 
 def make_windows(feat: torch.Tensor, seq_len: int, starts: Optional[Sequence[int]] = None, n_windows: Optional[int] = None):
     """feat [Ttot, S, 13] on the GPU -> (X [B,seq,S,13], L [B,seq,3S]) as src/step4_sequence_preparer.py:7-21.
     Default: the reference's non-overlapping windows i*seq_len; pass `starts` (e.g. a permutation, :23-26)
-    to choose them."""
+    to choose them.  Stream-ordered on the current stream like every other call: the table of starts is uploaded from pinned
+    host memory, so the host does not wait for work already queued there (a pageable upload would)."""
     lib = _lib.load()
     _require_gpu(feat)
     feat = feat.contiguous()
@@ -28,7 +29,7 @@ def make_windows(feat: torch.Tensor, seq_len: int, starts: Optional[Sequence[int
     else:
         B = len(starts)
         host = (C.c_int32 * B)(*[int(s) for s in starts])
-        dev = torch.tensor(list(starts), dtype=torch.int32, device=feat.device)
+        dev = torch.tensor(list(starts), dtype=torch.int32).pin_memory().to(feat.device, non_blocking=True)
     if B < 1:
         raise RuntimeError("windgnn_amd.make_windows: no complete window of %d (+3 label) steps in %d rows" % (seq_len, Ttot))
     X = torch.empty(B, seq_len, S, F, dtype=torch.float32, device=feat.device)

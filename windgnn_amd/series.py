@@ -74,6 +74,14 @@ def starts_coverage(starts, seq_len: int, rows: int) -> np.ndarray:
     return np.stack([np.searchsorted(st, tau - seq_len, side="right"), np.searchsorted(st, tau, side="right")], axis=1)
 
 
+def _upload(t: torch.Tensor, device) -> torch.Tensor:
+    """A host tensor on `device`, stream-ordered: from pinned memory, so the host does not wait for the work already queued on the
+    current stream (a pageable upload would, and the calls that take a table promise not to synchronise)."""
+    if torch.device(device).type == "cpu":
+        return t
+    return t.pin_memory().to(device, non_blocking=True)
+
+
 def _starts_table(starts, rows: int, seq_len: int, device, who: str, ordered: bool):
     """`starts` as the int32 device table the _at entry points take.  A list / numpy array / CPU tensor is checked here, before
     the upload (integer dtype, one dimension, every entry in [0, rows - seq_len], and non-decreasing where `ordered`):
@@ -101,7 +109,7 @@ def _starts_table(starts, rows: int, seq_len: int, device, who: str, ordered: bo
         w = int(np.nonzero(np.diff(host) < 0)[0][0]) + 1
         raise ValueError("%s: starts must be non-decreasing here, but starts[%d] = %d < starts[%d] = %d (GCN_GRU.forward_series "
                          "and TrainStep.step_series take any order)" % (who, w, host[w], w - 1, host[w - 1]))
-    return torch.from_numpy(host.astype(np.int32)).to(device)
+    return _upload(torch.from_numpy(host.astype(np.int32)), device)
 
 
 def sorted_starts(starts, rows: int, seq_len: int, device, who: str):
@@ -117,10 +125,10 @@ def sorted_starts(starts, rows: int, seq_len: int, device, who: str):
     table = _starts_table(starts, rows, seq_len, "cpu", who, ordered=False)
     table, order = torch.sort(table, stable=True)
     if torch.equal(order, torch.arange(order.numel())):
-        return table.to(device), None
+        return _upload(table, device), None
     inverse = torch.empty_like(order)
     inverse[order] = torch.arange(order.numel())
-    return table.to(device), inverse.to(device)
+    return _upload(table, device), _upload(inverse, device)
 
 
 def _no_stride_with_starts(who: str, stride, starts, n_windows=None) -> None:
