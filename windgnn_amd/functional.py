@@ -253,6 +253,22 @@ def gcn_gru_forward_raw(A, X, params: Sequence[torch.Tensor], math=_lib.MATH_F32
     return Y, stash, d
 
 
+def gcn_gru_forward_last_raw(A, X, params: Sequence[torch.Tensor], math=_lib.MATH_F32, wind_min: float = 0.0,
+                             wind_max: float = 1.0, prepared=None):
+    """last [B, H] fp32 = wgnn_fwd_last(...): Y[:, T - 1] * (wind_max - wind_min) + wind_min of gcn_gru_forward_raw's stash-less
+    forward, where the register-resident recurrences never write the other T - 1 rows.  fp32 X only.  With (0, 1), the
+    defaults, the read-out y * 1 + 0 is exact: the rows are Y's own."""
+    lib = _lib.load()
+    _require_gpu(X)
+    A, d, ws, ws_bytes = _forward_setup(A, X, params, math)
+    last = torch.empty(d.B, d.H, dtype=torch.float32, device=X.device)
+    ps = _params_struct(_lib.Params, params, prepared)
+    rc = lib.wgnn_fwd_last(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), float(wind_min), float(wind_max), _ptr(last), _ptr(ws),
+                           ws_bytes, _stream())
+    _lib.check(rc, "wgnn_fwd_last")
+    return last
+
+
 def gcn_gru_state(A, X, params: Sequence[torch.Tensor], math=_lib.MATH_F32, h0=None, want_y=True, h_n=None):
     """(Y or None, h_n) = wgnn_fwd_state(...): the forward from the initial state h0 [B,H] (None = zeros, exactly wgnn_fwd's
     recurrence), returning the unrounded fp32 last state h_n [B,H] as nn.GRU does.  No autograd (inference only).  X is
@@ -508,6 +524,95 @@ def val_close(record: torch.Tensor, best: torch.Tensor = None) -> None:
     word, stale = 0 if it won, else stale + 1."""
     _lib.check(_lib.load().wgnn_val_close(_val_ptr(record), _record_ptr(best) if best is not None else C.c_void_p(0), _stream()),
                "wgnn_val_close")
+
+
+VALIDATION_KINDS = ("mse", "l1", "huber")
+VALIDATION_CHUNK_BYTES = 64 << 20       # the cap on ONE fp64 temporary of validation_terms (it keeps two alive at most)
+
+
+def validation_spec(loss, huber_delta, loss_from, T, who="windgnn_amd: validation_terms"):
+    """loss= / huber_delta= / loss_from= of a validation on materialised windows of T steps, refused by the argument's name:
+    (kind, delta, first counted step)."""
+    import math as _math
+    if loss not in VALIDATION_KINDS:
+        raise ValueError("%s: loss=%r: a validation pass forms 'mse', 'l1' or 'huber'; any other loss works on "
+                         "GCN_GRU.forward's output with torch" % (who, loss))
+    t_from = int(loss_from)
+    if t_from != loss_from or not 0 <= t_from < int(T):
+        raise ValueError("%s: loss_from=%r must be a step of the window, an integer in [0, T = %d): 0 counts every step, "
+                         "T - 1 the last alone" % (who, loss_from, int(T)))
+    delta = float(huber_delta)
+    if loss == "huber" and not (_math.isfinite(delta) and delta > 0.0):
+        raise ValueError("%s: huber_delta=%r must be finite and > 0 (nn.HuberLoss's delta); loss='l1' is the limit of a small "
+                         "one and loss='mse' twice that of a large one" % (who, huber_delta))
+    return loss, delta, t_from
+
+
+def validation_chunk_windows(B: int, T: int, H: int, cap_bytes: int = VALIDATION_CHUNK_BYTES) -> int:
+    """Windows per chunk of validation_terms' reduction: as many whole windows of T counted steps as keep one fp64 temporary
+    (T * H * 8 bytes per window) under the cap, one at least -- a function of the shape alone."""
+    return max(1, min(int(B), int(cap_bytes) // (int(T) * int(H) * 8)))
+
+
+def validation_terms(Y: torch.Tensor, L: torch.Tensor, loss: str = "mse", huber_delta: float = 1.0, loss_from: int = 0,
+                     missing_labels: bool = False):
+    """What a validation call adds to the record, from Y and L [B, T, H] (fp32, fp16 or bf16; CPU tensors work as well), in
+    plain torch and fp64 throughout: with r = Y.double() - L.double() and the counted set
+    M = {(b, t, c): t >= loss_from and (not missing_labels or L[b, t, c] is not NaN)},
+
+        s = sum over M of rho(r)     rho = r^2 ("mse"), |r| ("l1"), nn.HuberLoss(delta=huber_delta) ("huber")
+        m = |M|                      a 0-dim int64 tensor on Y's device (no host read)
+        a = max over M of |r|        0 for an empty M
+
+    returned as (s, m, a), 0-dim.  The steps before loss_from are sliced away and a missing label's residual is replaced by 0
+    with torch.where before anything is formed from it (rho(0) = 0 = |0| exactly): nothing outside M reaches s or a, NaN or
+    not.  With missing_labels=False a NaN label is counted and poisons s and a.
+    Two levels, both fixed by the shape alone: chunks of validation_chunk_windows whole windows, each summed by
+    torch.sum in fp64, and the chunks' sums added in ascending order; equal shapes therefore sum in the same order."""
+    kind, delta, t0 = validation_spec(loss, huber_delta, loss_from, Y.shape[1] if Y.dim() == 3 else 1)
+    if Y.dim() != 3 or tuple(Y.shape) != tuple(L.shape):
+        raise ValueError("windgnn_amd: validation_terms wants Y and L of one shape [B, T, H], got %s and %s"
+                         % (tuple(Y.shape), tuple(L.shape)))
+    B, T, H = Y.shape
+    s = a = None
+    m = None if missing_labels else B * (T - t0) * H
+    step = validation_chunk_windows(B, T - t0, H, VALIDATION_CHUNK_BYTES)
+    for b0 in range(0, B, step):
+        Lc = L[b0:b0 + step, t0:]
+        r = Y[b0:b0 + step, t0:].to(torch.float64)
+        r -= Lc                                            # (type promotion: L enters as its exact fp64 value)
+        if missing_labels:
+            on = ~torch.isnan(Lc)
+            r = torch.where(on, r, torch.zeros((), dtype=torch.float64, device=r.device))
+            mk = on.sum()
+            m = mk if m is None else m + mk
+        ak = torch.linalg.vector_norm(r, ord=float("inf"))      # max |r| (NaN if any)
+        if kind == "mse":
+            rho = r.square_()
+        elif kind == "l1":
+            rho = r.abs_()
+        else:
+            rho = torch.nn.functional.huber_loss(r, torch.zeros((), dtype=torch.float64, device=r.device).expand_as(r),
+                                                 reduction="none", delta=delta)
+        sk = rho.sum()
+        s, a = (sk, ak) if s is None else (s + sk, torch.maximum(a, ak))
+    if not torch.is_tensor(m):
+        m = torch.full((), m, dtype=torch.int64, device=Y.device)
+    return s, m, a
+
+
+def val_add(record: torch.Tensor, s: torch.Tensor, m, a: torch.Tensor) -> None:
+    """What one validation call does to the public words of a validation record (include/windgnn_series_val.h), in torch
+    operations on val_word's views, in stream order and without a host read (a CPU buffer works as well):
+    sum += s; count += m; max_abs = max(max_abs, float32(a)); mean = sum / count (NaN while count = 0); loss = float32(mean);
+    calls += 1.  No other byte of the record is written."""
+    w = {name: val_word(record, name) for name in ("sum", "count", "mean", "max_abs", "loss", "calls")}
+    w["sum"] += s
+    w["count"] += m
+    torch.maximum(w["max_abs"], a.to(torch.float32), out=w["max_abs"])
+    torch.div(w["sum"], w["count"], out=w["mean"])          # (0.0 / 0 = NaN; a NaN sum stays NaN)
+    w["loss"].copy_(w["mean"])
+    w["calls"] += 1
 
 
 def rows_align(d) -> int:

@@ -71,7 +71,10 @@ Validation (validate_series; include/windgnn_series_val.h): the loss of step_ser
 on, forward-only (wgnn_series_val: no Y, no stash, no backward) and accumulated over calls in a device record.  With
 TrainStep(keep_best=..., best_on="validation") no training step decides on the best model; a closed validation pass does --
 wgnn_keep_best on the record's loss word, then wgnn_val_close, which keeps the patience counter `val_stale`.  Nothing is
-exchanged under a process group: every rank validates the same tables and takes the same decision.  No host read anywhere."""
+exchanged under a process group: every rank validates the same tables and takes the same decision.  No host read anywhere.
+validate is the same pass on materialised windows, for what series mode refuses (the fp16-plane modes, 16-bit I/O, a CSR
+adjacency, the wide-GRU path, the reference's own test_loader): the stash-less forward, the loss terms in fp64 torch operations on
+the device (functional.validation_terms) and the record's public words updated by functional.val_add."""
 from __future__ import annotations
 
 import collections
@@ -82,9 +85,10 @@ from . import _lib
 from .distributed import HEADER, LOSS_SLOT, BucketExchange, grad_block_plan
 from .functional import (PARAM_ORDER, _forward_setup, _require_gpu, best_bytes, best_init, best_word, bwd_rows, check_range_status,
                          clip_buffer, clip_bytes, finish_clipped, finish_norm, finish_rows, finish_step,
-                         gcn_gru_backward_mse_raw, gcn_gru_forward_raw, gcn_gru_state_backward_raw, gcn_gru_state_forward_raw,
-                         keep_best_args, keep_best_launch, mse_loss_grad, prepared_weights, refresh_prepared, rows_align,
-                         val_begin, val_buffer, val_close, val_init, val_word)
+                         gcn_gru_backward_mse_raw, gcn_gru_forward_last_raw, gcn_gru_forward_raw, gcn_gru_state_backward_raw,
+                         gcn_gru_state_forward_raw, keep_best_args, keep_best_launch, mse_loss_grad, prepared_weights,
+                         refresh_prepared, rows_align, val_add, val_begin, val_buffer, val_close, val_init, val_word,
+                         validation_spec, validation_terms)
 from .modules import GCN_GRU
 from .series import (_no_stride_with_starts, _starts_table, loss_spec, n_series_windows, series_backward_mse_raw,
                      series_forward_loss_raw, series_val_raw, sorted_starts, val_spec)
@@ -160,7 +164,7 @@ class TrainStep:
         Every schedule takes it, the empty-shard step included.
 
         best_on (with keep_best): "train" = the rule above, launch for launch; "validation" = no step decides -- a CLOSED
-        validation pass does (validate_series): its held-out loss is compared, and the parameters at that moment are kept."""
+        validation pass does (validate_series or validate): its held-out loss is compared, and the parameters at that moment are kept."""
         if not getattr(model, "fused", True):
             raise RuntimeError("windgnn_amd: TrainStep drives the fused hot path, i.e. the reference model's own widths "
                                "(input_dim = hidden_dim = 13, src/main.py:41); a GCN_GRU of other widths trains through "
@@ -810,6 +814,74 @@ class TrainStep:
             self._close_validation()
         return val_word(self._val, "loss")
 
+    def validate(self, A, X, L, missing_labels=False, loss="mse", huber_delta=1.0, loss_from=0, more=False, evaluator=None):
+        """validate_series' pass on MATERIALISED windows, for everything GCN_GRU.forward accepts: X [B, T, S, 13] and L [B, T, H]
+        ([T, H] or [1, T, H] at B = 1, as the reference's test_loader yields them; fp32 or X's dtype), any math mode, fp32 / fp16 /
+        bf16 I/O (X's dtype), a dense adjacency or a CsrAdjacency, any H.  The forward is the stash-less one model(A, X) runs
+        under torch.no_grad() -- the same call on the current parameters (and the current W_ih images, when they are current),
+        hence the same Y bits -- from h = 0 also with carry_state=True; it changes nothing of the optimiser, the gradient bucket,
+        `steps`, the images or the carried state, and it does not read the range-status word (check() does).  The loss terms
+        are functional.validation_terms' (fp64, torch operations on the device) and functional.val_add puts them into the same
+        record wgnn_series_val writes: missing_labels, loss, huber_delta, loss_from, more, the closing (wgnn_keep_best under
+        best_on="validation", wgnn_val_close, `val_stale`) and the returned 0-dim VIEW `val_loss` are validate_series'; calls of
+        both kinds may share a pass.
+        loss_from = T - 1 with fp32 X: wgnn_fwd_last with (wind_min, wind_max) = (0, 1) -- y * 1 + 0 is exact -- so the
+        register-resident recurrences never write the other T - 1 rows; the terms are the full route's.
+        evaluator=ev: the last rows of the same forward, de-normalised by wgnn_predict_last with ev's wind_min / wind_max, go to
+        ev's accumulator through wgnn_eval_accum as ev.update(X, L) would put them there.  Not with missing_labels=True:
+        wgnn_eval_accum has no skip.
+        Nothing synchronises with the host.  Under a process group nothing is exchanged: every rank validates the SAME windows."""
+        from .data import predict_last
+        from .evaluate import eval_accum
+        who = "windgnn_amd: TrainStep.validate"
+        H = self.p_views[5].shape[1]
+        if X.dim() != 4 or X.shape[0] < 1 or X.shape[3] != 13 or X.shape[2] * 13 != self.p_views[4].shape[1]:
+            raise RuntimeError("%s: X must be [B >= 1, T, S = %d, 13], got %s" % (who, self.p_views[4].shape[1] // 13, tuple(X.shape)))
+        B, T = X.shape[0], X.shape[1]
+        kind, delta, t0 = validation_spec(loss, huber_delta, loss_from, T, who)
+        Lw = L.unsqueeze(0) if L.dim() == 2 else L
+        if tuple(Lw.shape) != (B, T, H):
+            raise ValueError("%s: L must be X's windows x H = [%d, %d, %d] ([T, H] is taken at B = 1), got %s"
+                             % (who, B, T, H, tuple(L.shape)))
+        if L.dtype not in (torch.float32, X.dtype):
+            raise ValueError("%s: L must be float32 or X's dtype %s, got %s" % (who, X.dtype, L.dtype))
+        if evaluator is not None:
+            if getattr(evaluator, "H", None) != H:
+                raise ValueError("%s: evaluator= must be an evaluate.Evaluator of this model's %d outputs, got %r" % (who, H, evaluator))
+            if missing_labels:
+                raise ValueError("%s: evaluator= with missing_labels=True: wgnn_eval_accum has no skip, so a NaN truth would poison "
+                                 "its column; feed the evaluator from the series (validate_series(..., missing_labels=True, "
+                                 "evaluator=ev) or ev.update_series(..., skip_missing=True)), or call ev.update on the windows "
+                                 "whose last label exists" % who)
+        _require_gpu(X, Lw, io_ok=True)      # before the record and any launch: nothing runs on host memory
+        _require_gpu(*self.p_views)
+        X = X.contiguous()
+        # the images as they are: used when current, never built or refreshed here (the library stages its own otherwise)
+        pre = self._prepared if self._prepared is not None and self._prepared_version == self._param_version() else None
+        if t0 == T - 1 and X.dtype == torch.float32:
+            Y = gcn_gru_forward_last_raw(A, X, self.p_views, self.model.math, prepared=pre).view(B, 1, H)
+            s, m, a = validation_terms(Y, Lw[:, T - 1:], kind, delta, 0, missing_labels)
+        else:
+            Y, _, _ = gcn_gru_forward_raw(A, X, self.p_views, self.model.math, want_stash=False, prepared=pre)
+            s, m, a = validation_terms(Y, Lw, kind, delta, t0, missing_labels)
+        if self._val is None:
+            self._val = val_buffer(self.device)
+        if not self._val_open:
+            val_begin(self._val)
+            self._val_open = True
+        val_add(self._val, s, m, a)
+        if evaluator is not None:
+            f32 = Y.dtype == torch.float32 and Lw.dtype == torch.float32
+            pred = predict_last(Y if f32 else Y[:, -1:].float(), evaluator.wind_min, evaluator.wind_max)
+            err = torch.empty_like(pred) if evaluator.keep_errors else None
+            eval_accum(pred, (Lw if f32 else Lw[:, -1:].float()).contiguous(), evaluator.wind_min, evaluator.wind_max,
+                       evaluator._acc(), err)
+            if err is not None:
+                evaluator._errors.append(err)
+        if not more:
+            self._close_validation()
+        return val_word(self._val, "loss")
+
     def _validate_refusals(self, A, series, seq_len, stride):
         """What validate_series refuses, each before any launch and with the alternative: step_series' scope without what
         belongs to the optimiser's schedule (a pass takes no step, so carry_state, grad_blocks and overlap_collectives do not
@@ -859,6 +931,7 @@ class TrainStep:
         self._val_open = False
 
     def _val_word(self, name, word):
+        """A public word of the validation record, which the first validate_series or validate call makes."""
         if self._val is None:
             raise RuntimeError("windgnn_amd: TrainStep.%s is kept by validate_series (include/windgnn_series_val.h); no "
                                "validation call has run on this TrainStep yet" % name)
