@@ -287,14 +287,16 @@ def gcn_gru_state(A, X, params: Sequence[torch.Tensor], math=_lib.MATH_F32, h0=N
     return Y, h_n
 
 
-def gcn_gru_backward_raw(d, A, X, params, Y, dY, stash, grads: Sequence[torch.Tensor], part: int = 7, stream=None):
-    """part bit mask (wgnn_bwd_part): 1 = BPTT recurrence, 4 = GRU weight-gradient GEMMs, 2 = dg + GCN backward."""
+def gcn_gru_backward_raw(d, A, X, params, Y, dY, stash, grads: Sequence[torch.Tensor], part: int = 7, stream=None,
+                         prepared=None):
+    """part bit mask (wgnn_bwd_part): 1 = BPTT recurrence, 4 = GRU weight-gradient GEMMs, 2 = dg + GCN backward.
+    prepared: the caller-kept images of W_ih (wgnn_params.prepared), which part 2 then reads instead of staging its own."""
     lib = _lib.load()
     _require_contiguous(X=X, Y=Y, dY=dY, grads=grads, params=params)
     A = getattr(A, "blob", A)              # CsrAdjacency -> its device buffer (d.adj_format says which it is)
     _require_contiguous(adj_matrix=A)
     ws, ws_bytes = _workspace(d, X.device)
-    ps = _params_struct(_lib.Params, params)
+    ps = _params_struct(_lib.Params, params, prepared)
     gs = _params_struct(_lib.Grads, grads)
     rc = lib.wgnn_bwd_part(C.byref(d), _ptr(A), _ptr(X), C.byref(ps), _ptr(Y), _ptr(dY), _stash_ptr(stash), C.byref(gs),
                            _ptr(ws), ws_bytes, _stream() if stream is None else C.c_void_p(stream.cuda_stream), part)
@@ -531,11 +533,12 @@ VALIDATION_CHUNK_BYTES = 64 << 20       # the cap on ONE fp64 temporary of valid
 
 
 def validation_spec(loss, huber_delta, loss_from, T, who="windgnn_amd: validation_terms"):
-    """loss= / huber_delta= / loss_from= of a validation on materialised windows of T steps, refused by the argument's name:
+    """loss= / huber_delta= / loss_from= of a validation or a training step on materialised windows of T steps (the caller's
+    name goes into `who`), refused by the argument's name:
     (kind, delta, first counted step)."""
     import math as _math
     if loss not in VALIDATION_KINDS:
-        raise ValueError("%s: loss=%r: a validation pass forms 'mse', 'l1' or 'huber'; any other loss works on "
+        raise ValueError("%s: loss=%r: the losses formed here are 'mse', 'l1' or 'huber'; any other loss works on "
                          "GCN_GRU.forward's output with torch" % (who, loss))
     t_from = int(loss_from)
     if t_from != loss_from or not 0 <= t_from < int(T):
@@ -613,6 +616,76 @@ def val_add(record: torch.Tensor, s: torch.Tensor, m, a: torch.Tensor) -> None:
     torch.div(w["sum"], w["count"], out=w["mean"])          # (0.0 / 0 = NaN; a NaN sum stays NaN)
     w["loss"].copy_(w["mean"])
     w["calls"] += 1
+
+
+_SPEC_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def loss_spec_grad(Y: torch.Tensor, L: torch.Tensor, loss: str = "mse", huber_delta: float = 1.0, loss_from: int = 0,
+                   missing_labels: bool = False, grad_scale: float = 1.0, loss_out: torch.Tensor = None,
+                   who: str = "windgnn_amd: loss_spec_grad"):
+    """(loss, dY, count) of a loss spec on materialised windows: Y and L [B, T, H] (fp32, fp16 or bf16; L fp32 or Y's dtype; CPU
+    tensors work as well), in plain torch on the current stream, without a host read.  With r = Y - L over the counted set
+    M = {(b, t, c): t >= loss_from and (not missing_labels or L[b, t, c] is not NaN)} and m = |M| (the definitions of
+    include/windgnn_series_lossfn.h):
+
+        loss  = sum over M of rho(r) / m                 rho = r^2 ("mse"), |r| ("l1"), nn.HuberLoss(delta=huber_delta) ("huber")
+        dY    = grad_scale * rho'(r) / m on M, exactly 0 elsewhere        fp32 [B, T, H], contiguous
+        count = m                                        a 0-dim int64 tensor on Y's device
+
+    The counted steps are strided views (a 16-bit one is upcast to fp32 once); a missing label is replaced by Y's own value
+    with torch.where, so its residual is exactly 0 and rho(0) = rho'(0) = 0 for all three kinds: nothing is multiplied by a
+    mask.  The sum is torch's own loss with reduction="sum" (F.mse_loss / F.huber_loss: on the device two kernels, the elementwise
+    rho and its sum, not one fused reduction; "l1": the 1-norm of r, which is formed once, the abs inside the reduction) and dY on the counted steps ONE fused elementwise kernel (aten mse_loss_backward / huber_loss_backward with
+    the coefficient grad_scale / m as a 0-dim device tensor; "l1": sign(r) times it), written into dY's view; only
+    dY[:, :loss_from] is zero-filled.  m = 0 (possible
+    with missing_labels alone): the loss is NaN (0 / 0), dY all zero, count 0 -- the coefficient is selected with torch.where,
+    not a branch.  Without missing_labels a NaN label is counted and poisons the loss, as it does mse_loss_grad's.
+    loss_out: an optional 0-dim fp32 tensor (a view is fine) that receives the loss instead of a new one.
+    The keywords are refused by the argument's name (validation_spec, under `who`).
+    Limit: a non-finite Y at a missing label gives a NaN residual (NaN - NaN); the GRU's output is finite unless the
+    parameters are not."""
+    kind, delta, t0 = validation_spec(loss, huber_delta, loss_from, Y.shape[1] if Y.dim() == 3 else 1, who)
+    if Y.dim() != 3 or tuple(Y.shape) != tuple(L.shape):
+        raise ValueError("%s wants Y and L of one shape [B, T, H], got %s and %s" % (who, tuple(Y.shape), tuple(L.shape)))
+    if Y.dtype not in _SPEC_DTYPES or L.dtype not in (torch.float32, Y.dtype):
+        raise ValueError("%s: Y must be float32, float16 or bfloat16 and L float32 or Y's dtype, got %s and %s"
+                         % (who, Y.dtype, L.dtype))
+    if L.device != Y.device:
+        raise ValueError("%s: Y is on %s but L on %s" % (who, Y.device, L.device))
+    if loss_out is not None and (loss_out.dim() != 0 or loss_out.dtype != torch.float32 or loss_out.device != Y.device):
+        raise ValueError("%s: loss_out must be a 0-dim float32 tensor on %s, got %s %s on %s"
+                         % (who, Y.device, tuple(loss_out.shape), loss_out.dtype, loss_out.device))
+    B, T, H = Y.shape
+    Ys, Ls = Y[:, t0:].to(torch.float32), L[:, t0:].to(torch.float32)       # (fp32: the views themselves, no copy)
+    if missing_labels:
+        miss = torch.isnan(Ls)
+        Ls = torch.where(miss, Ys, Ls)
+        count = (~miss).sum()
+        coef = torch.where(count > 0, torch.full((), float(grad_scale), dtype=torch.float64, device=Y.device) / count,
+                           0.0).to(torch.float32)
+    else:
+        n = B * (T - t0) * H
+        count = torch.full((), n, dtype=torch.int64, device=Y.device)
+        coef = torch.full((), float(grad_scale) / n, dtype=torch.float32, device=Y.device)
+    dY = torch.empty(B, T, H, dtype=torch.float32, device=Y.device)
+    if t0:
+        dY[:, :t0].zero_()
+    dv = dY[:, t0:]
+    if kind == "mse":
+        s = torch.nn.functional.mse_loss(Ys, Ls, reduction="sum")
+        torch.ops.aten.mse_loss_backward.grad_input(coef, Ys, Ls, 2, grad_input=dv)             # 2 = Reduction::Sum
+    elif kind == "l1":
+        r = Ys - Ls                                            # formed once, for the sum and for the sign
+        s = torch.linalg.vector_norm(r, ord=1)                 # sum |r|: the abs is taken inside the reduction
+        torch.mul(torch.sign(r), coef, out=dv)
+    else:
+        s = torch.nn.functional.huber_loss(Ys, Ls, reduction="sum", delta=delta)
+        torch.ops.aten.huber_loss_backward.out(coef, Ys, Ls, 2, delta, grad_input=dv)
+    if loss_out is None:
+        loss_out = torch.empty((), dtype=torch.float32, device=Y.device)
+    torch.div(s, count, out=loss_out)                          # (0.0 / 0 = NaN; a NaN sum stays NaN)
+    return loss_out, dY, count
 
 
 def rows_align(d) -> int:

@@ -74,7 +74,18 @@ wgnn_keep_best on the record's loss word, then wgnn_val_close, which keeps the p
 exchanged under a process group: every rank validates the same tables and takes the same decision.  No host read anywhere.
 validate is the same pass on materialised windows, for what series mode refuses (the fp16-plane modes, 16-bit I/O, a CSR
 adjacency, the wide-GRU path, the reference's own test_loader): the stash-less forward, the loss terms in fp64 torch operations on
-the device (functional.validation_terms) and the record's public words updated by functional.val_add."""
+the device (functional.validation_terms) and the record's public words updated by functional.val_add.
+
+Loss specs on materialised windows (step / forward_backward with loss= / huber_delta= / loss_from= / missing_labels=): the loss
+validate scores, trained on, in every math mode, adjacency format, I/O type and width.  At the defaults the step is the fused MSE
+step above, call for call.  Any other spec: the forward runs without labels (wgnn_fwd), functional.loss_spec_grad forms the loss
+(into the bucket's header word) and dY from Y and L with torch's own fused loss kernels, and the backward takes that dY through
+wgnn_bwd_part (wgnn_bwd_state_part with carry_state) with its parts deferred -- the route the carried-state step has always
+taken with wgnn_mse_loss_grad's dY -- so every schedule, clipping, keep_best and the checkpoints see it unchanged.  No kernel
+and no entry point of the library is added; the price is one pass over Y and L that the fused step does not have.  With fp16 /
+bf16 windows such a step runs on fp32 copies of X and L (_spec_forward), so that the loss is formed from the unrounded Y.
+`loss_count` is the step's count of labels.  Under a process group missing_labels=True is refused (the ranks' label counts
+would have to be exchanged); the other specs count the same (T - loss_from) * H entries per window on every rank."""
 from __future__ import annotations
 
 import collections
@@ -85,8 +96,9 @@ from . import _lib
 from .distributed import HEADER, LOSS_SLOT, BucketExchange, grad_block_plan
 from .functional import (PARAM_ORDER, _forward_setup, _require_gpu, best_bytes, best_init, best_word, bwd_rows, check_range_status,
                          clip_buffer, clip_bytes, finish_clipped, finish_norm, finish_rows, finish_step,
-                         gcn_gru_backward_mse_raw, gcn_gru_forward_last_raw, gcn_gru_forward_raw, gcn_gru_state_backward_raw,
-                         gcn_gru_state_forward_raw, keep_best_args, keep_best_launch, mse_loss_grad, prepared_weights,
+                         gcn_gru_backward_mse_raw, gcn_gru_backward_raw, gcn_gru_forward_last_raw, gcn_gru_forward_raw,
+                         gcn_gru_state_backward_raw, gcn_gru_state_forward_raw, keep_best_args, keep_best_launch, loss_spec_grad,
+                         mse_loss_grad, prepared_weights,
                          refresh_prepared, rows_align, val_add, val_begin, val_buffer, val_close, val_init, val_word,
                          validation_spec, validation_terms)
 from .modules import GCN_GRU
@@ -262,6 +274,7 @@ class TrainStep:
         # carried state: two [B, H] buffers (h0 of this step, h_n into the other: they may not alias), swapped per step
         self.carry_state = carry_state
         self._hbuf, self._hcur, self._has_state = None, 0, False
+        self._count = None              # loss_count: made by the first step on a loss spec
 
     def _grad_block_plan(self, grad_blocks, sizes, carry_state, overlap_collectives, direct_rccl):
         """The blocked exchange's plan (distributed.grad_block_plan), or None for the one-bucket schedules."""
@@ -344,6 +357,15 @@ class TrainStep:
         """min(1, max_grad_norm / (grad_norm + 1e-6)) of the last step, the factor its gradient entered Adam with: a 0-dim
         VIEW, overwritten by the next step."""
         return self._clip_word(_lib.CLIP_COEF, "clip_coef")
+
+    @property
+    def loss_count(self):
+        """The labels the last step on a loss spec counted (windows x steps from loss_from on x outputs, less the missing
+        labels): a 0-dim int64 VIEW of the device value, overwritten by the next such step."""
+        if self._count is None:
+            raise RuntimeError("windgnn_amd: TrainStep.loss_count is written by a step on a loss spec (step / forward_backward "
+                               "with loss=, loss_from= or missing_labels= off their defaults); no such step has run yet")
+        return self._count
 
     def _reset_best(self, threshold, words=None):
         """wgnn_best_init for `threshold`; `words`: public words to set after that (a checkpoint's)."""
@@ -599,10 +621,67 @@ class TrainStep:
         self._end_step(check=False)             # no host read on this path: the next step with windows checks
         return self._loss, torch.empty(0, d.T, d.H, dtype=X.dtype, device=X.device)
 
-    def forward_backward(self, A, X, L):
+    def _step_spec(self, who, X, L, loss, huber_delta, loss_from, missing_labels):
+        """loss= / huber_delta= / loss_from= / missing_labels= of step / forward_backward, refused here by name before any
+        launch: None at the defaults, which are the calls the two methods have always made, else (kind, delta, first counted
+        step, missing_labels, L as [B, T, H])."""
+        if loss == "mse" and loss_from == 0 and not missing_labels:
+            return None
+        who = "windgnn_amd: TrainStep." + who
+        H = self.p_views[5].shape[1]
+        if X.dim() != 4 or X.shape[3] != 13 or X.shape[2] * 13 != self.p_views[4].shape[1]:
+            raise RuntimeError("%s: X must be [B, T, S = %d, 13], got %s" % (who, self.p_views[4].shape[1] // 13, tuple(X.shape)))
+        B, T = X.shape[0], X.shape[1]
+        kind, delta, t0 = validation_spec(loss, huber_delta, loss_from, T, who)
+        if missing_labels and self.collective:
+            raise RuntimeError("%s with missing_labels=True under a process group: the mean is over the labels that exist, so the "
+                               "ranks' label counts would have to be exchanged before the backward, which is out of scope; train "
+                               "on one device, or drop the windows that touch a gap and pass missing_labels=False" % who)
+        if B == 0:                      # an empty shard: the keywords are checked, and the step is the one it was
+            return kind, delta, t0, bool(missing_labels), L
+        Lw = L.unsqueeze(0) if L.dim() == 2 else L
+        if tuple(Lw.shape) != (B, T, H):
+            raise ValueError("%s: L must be X's windows x H = [%d, %d, %d] ([T, H] is taken at B = 1), got %s"
+                             % (who, B, T, H, tuple(L.shape)))
+        if L.dtype not in (torch.float32, X.dtype):
+            raise ValueError("%s: L must be float32 or X's dtype %s, got %s" % (who, X.dtype, L.dtype))
+        return kind, delta, t0, bool(missing_labels), Lw
+
+    def _spec_loss(self, who, Y, spec, gs):
+        """The loss of `spec` into the bucket's header word (the unweighted shard mean: the exchange weights it), the count
+        into loss_count, and dY weighted by gs."""
+        kind, delta, t0, missing, Lw = spec
+        _, dY, count = loss_spec_grad(Y, Lw, kind, delta, t0, missing, grad_scale=gs, loss_out=self._loss,
+                                      who="windgnn_amd: TrainStep." + who)
+        if self._count is None:
+            self._count = torch.zeros((), dtype=torch.int64, device=count.device)
+        self._count.copy_(count)
+        return dY
+
+    def _spec_forward(self, A, X, spec):
+        """The forward of a step on a loss spec, without labels: (X as the kernels read it, Y in fp32, stash, d, spec).  With
+        fp16 / bf16 X the Y that wgnn_fwd returns is rounded to that type, and a loss formed from it would carry the rounding
+        (2^-9 at |y| near 1 in bf16) into every residual, where the fused MSE step reads the unrounded state: such a step
+        therefore runs on an fp32 copy of X and of the labels (exact conversions), which gives the same hidden state
+        unrounded; the caller gets Y rounded once to X's type, as the 16-bit forward gives it."""
+        if X.dtype != torch.float32:
+            _forward_setup(A, X, self.p_views, self.model.math)      # what refuses 16-bit I/O (math "f32") still does, unconverted
+            kind, delta, t0, missing, Lw = spec
+            X, spec = X.to(torch.float32), (kind, delta, t0, missing, Lw.to(torch.float32))
+        Y, stash, d = self._forward(A, X, None)
+        return X, Y, stash, d, spec
+
+    def forward_backward(self, A, X, L, *, loss="mse", huber_delta=1.0, loss_from=0, missing_labels=False):
         """src/main.py:66,72,79: returns (loss, Y); gradients land in the flat bucket (no optimiser step).  `loss` is a
-        view of the bucket's header word (see the module docstring)."""
+        view of the bucket's header word (see the module docstring).  loss, huber_delta, loss_from, missing_labels: as in
+        step."""
         X, L = X.contiguous(), L.contiguous()
+        spec = self._step_spec("forward_backward", X, L, loss, huber_delta, loss_from, missing_labels)
+        if spec is not None:
+            Xf, Y, stash, d, spec = self._spec_forward(A, X, spec)
+            dY = self._spec_loss("forward_backward", Y, spec, 1.0)
+            gcn_gru_backward_raw(d, A, Xf, self.p_views, Y, dY, stash, self.g_views, part=7, prepared=self._prepared)
+            return self._loss, Y.to(X.dtype)
         Y, stash, d = self._forward(A, X, L)
         loss = self._loss
         gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, loss, 1.0, part=7 | 8,
@@ -991,11 +1070,15 @@ class TrainStep:
                                                    prepared=self._prepared)
         return Y, stash, d
 
-    def _state_step(self, A, X, L, gs):
-        """The carry_state=True step: the loss and dY from wgnn_mse_loss_grad (into the bucket's loss slot) and the backward
-        through wgnn_bwd_state_part (dh_n = 0, no dh0: the carried state is detached)."""
+    def _state_step(self, A, X, L, gs, spec=None):
+        """The carry_state=True step: the loss and dY from wgnn_mse_loss_grad (into the bucket's loss slot) -- on a loss spec
+        from functional.loss_spec_grad -- and the backward through wgnn_bwd_state_part (dh_n = 0, no dh0: the carried state is
+        detached)."""
         Y, stash, d = self._state_forward(A, X, L)
-        _, dY = mse_loss_grad(Y, L, gs, loss=self._loss)    # the unweighted shard mean: the exchange weights it
+        if spec is not None:
+            dY = self._spec_loss("step", Y, spec, gs)
+        else:
+            _, dY = mse_loss_grad(Y, L, gs, loss=self._loss)    # the unweighted shard mean: the exchange weights it
 
         def parts(mask):
             gcn_gru_state_backward_raw(d, A, X, self.p_views, Y, dY, None, stash, self.g_views, part=mask | _lib.BWD_DEFER,
@@ -1014,17 +1097,39 @@ class TrainStep:
         self._run_schedule(d, _Deferred(self, d, parts, Y, stash), gs)
         return Y
 
-    def step(self, A, X, L, n_global=None):
+    def _spec_step(self, A, X, L, gs, spec):
+        """The step from h = 0 on a loss spec: wgnn_fwd (no labels), the loss and dY from functional.loss_spec_grad, then
+        wgnn_bwd_part on that dY, its parts deferred as the carried-state step's are."""
+        Xf, Y, stash, d, spec = self._spec_forward(A, X, spec)
+        dY = self._spec_loss("step", Y, spec, gs)
+
+        def parts(mask):
+            gcn_gru_backward_raw(d, A, Xf, self.p_views, Y, dY, stash, self.g_views, part=mask | _lib.BWD_DEFER,
+                                 prepared=self._prepared)
+        self._run_schedule(d, _Deferred(self, d, parts, Y, stash), gs)
+        return Y.to(X.dtype)
+
+    def step(self, A, X, L, n_global=None, *, loss="mse", huber_delta=1.0, loss_from=0, missing_labels=False):
         """One optimiser step on this rank's windows (src/main.py:66-80).  `n_global`: windows of ALL ranks in this step,
         when the caller knows it (a fixed global batch); None = the exchange all-reduces the count on every step (a host
         sync).  Launch-sized tail: ONE wgnn_finish (reduce the deferred partial sums + Adam + next step's W_ih images);
         with a process group two of them around the one all-reduce.  The returned loss is a VIEW of the gradient bucket's
-        header word, overwritten by the next step (module docstring): float() or .clone() it to keep it."""
+        header word, overwritten by the next step (module docstring): float() or .clone() it to keep it.
+        loss="mse" | "l1" | "huber", huber_delta, loss_from=t, missing_labels: the loss validate scores (the definitions of
+        include/windgnn_series_lossfn.h, which step_series' docstring restates), in every math mode, on a dense or CSR
+        adjacency, any H, fp32 / fp16 / bf16 I/O, with or without carry_state, in every schedule.  At the defaults the step is
+        the one it was.  Otherwise the loss and dY come from functional.loss_spec_grad on the forward's Y (module docstring); L
+        is [B, T, H] ([T, H] at B = 1), fp32 or X's dtype; `loss_count` holds the labels counted; with no label at all the
+        loss is NaN and the gradients are zero.  missing_labels=True is refused under a process group."""
         X, L = X.contiguous(), L.contiguous()   # a strided batch slice is copied here, never read as if dense
+        spec = self._step_spec("step", X, L, loss, huber_delta, loss_from, missing_labels)
         if X.shape[0] == 0:
             return self._empty_shard_step(A, X, n_global)
         gs = self.exchange.shard_weight(X.shape[0], n_global) if self.collective else 1.0
-        Y = (self._state_step if self.carry_state else self._plain_step)(A, X, L, gs)
+        if spec is None:
+            Y = (self._state_step if self.carry_state else self._plain_step)(A, X, L, gs)
+        else:
+            Y = (self._state_step if self.carry_state else self._spec_step)(A, X, L, gs, spec)
         self._end_step()
         return self._loss, Y
 
