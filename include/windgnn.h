@@ -371,9 +371,15 @@ int wgnn_prepare_weights(const wgnn_dims* d, const wgnn_params* p, void* workspa
 
 /* One GraphConvLayer(F, F_out) (src/step5_gcn_layer_model.py:5-23: weight [F, F_out], bias [F_out]):
  * out[n,S,F_out] = relu(A X[n] W + b) for n = 0..ntiles-1 (ntiles = prod of the leading dims of attr_matrix), dense A with
- * S <= 64, 1 <= F, F_out <= 64.  Backward: dW [F, F_out], db [F_out] (overwritten) and, if dX != NULL, dX [n,S,F].
- * F == F_out == 13 -- the only widths the reference's own model builds (src/main.py:41) -- run the MFMA kernels; other widths
- * an exact-fp32 kernel of their own (csrc/gcn_any.hip).  Wider layers / more stations: WGNN_ERR_UNSUPPORTED. */
+ * S <= 64 and any widths F, F_out >= 1.  Backward: dW [F, F_out], db [F_out] (overwritten) and, if dX != NULL, dX [n,S,F]
+ * (dX == NULL skips that half of the work).  Exact fp32 at every width.
+ * F == F_out == 13 -- the only widths the reference's own model builds (src/main.py:41) -- run the MFMA kernels of csrc/gcn.hip;
+ * other widths up to 64 an FMA kernel of their own (csrc/gcn_any.hip); max(F, F_out) > 64 the tiled fp32-MFMA kernels of
+ * csrc/gcn_wide.hip, for ntiles * S * max(F, F_out) < 2^31 and F * F_out < 2^31 (beyond: WGNN_ERR_SHAPE).  More than 64
+ * stations: WGNN_ERR_UNSUPPORTED (a CSR adjacency serves 13 -> 13 alone, below).  Checks in this order: shape, unsupported, NULL,
+ * workspace.  wgnn_gcn_layer_workspace_bytes depends on its four arguments alone, is a multiple of 256 past 64 features (there
+ * it holds A^T dZ [n,S,F_out], the per-workgroup sums of db and the split-K partials of dW) and is 0 for a refused shape; the
+ * workspace may be dirty: every byte a call reads, that call has written.  Repeated calls give the same bits (no atomics). */
 size_t wgnn_gcn_layer_workspace_bytes(int32_t ntiles, int32_t S, int32_t F, int32_t F_out);
 int wgnn_gcn_layer_fwd(int32_t ntiles, int32_t S, int32_t F, int32_t F_out, const float* A, const float* X,
                        const float* W, const float* b, float* out, void* stream);

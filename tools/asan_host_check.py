@@ -54,11 +54,19 @@ for bad in (L.Dims(0, 1, 1, 13, 1, 0, 0, 0, 0), L.Dims(1, 1, 1, 12, 1, 0, 0, 0, 
     assert lib.wgnn_workspace_bytes(C.byref(bad)) == 0
 assert lib.wgnn_workspace_bytes(None) == 0 and lib.wgnn_stash_bytes(None) == 0
 assert lib.wgnn_gcn_layer_workspace_bytes(10, 34, 13, 13) > 0 and lib.wgnn_gcn_layer_workspace_bytes(10, 65, 13, 13) == 0
-assert lib.wgnn_gcn_layer_workspace_bytes(10, 34, 5, 64) > 0 and lib.wgnn_gcn_layer_workspace_bytes(10, 34, 65, 13) == 0
+assert lib.wgnn_gcn_layer_workspace_bytes(10, 34, 5, 64) > 0 and lib.wgnn_gcn_layer_workspace_bytes(10, 65, 65, 13) == 0
+for nt, S, Fi, Fo in ((10, 34, 65, 13), (2100, 34, 13, 128), (9, 5, 257, 129), (1, 1, 65536, 32767)):   # csrc/gcn_wide.hip
+    wb = lib.wgnn_gcn_layer_workspace_bytes(nt, S, Fi, Fo)
+    assert wb > 0 and wb %% 256 == 0
+    assert lib.wgnn_gcn_layer_bwd(nt, S, Fi, Fo, None, None, None, None, None, None, None, None, None, wb, None) == -1
+    assert lib.wgnn_gcn_layer_bwd(nt, S, Fi, Fo, 64, 64, 64, 64, 64, 64, 64, None, 64, wb - 1, None) == -4
+assert lib.wgnn_gcn_layer_workspace_bytes(1 << 20, 64, 128, 13) == 0 and lib.wgnn_gcn_layer_workspace_bytes(1, 1, 65536, 32768) == 0
 assert lib.wgnn_gcn_layer_csr_workspace_bytes(10, 4096, 13) > 0
 assert lib.wgnn_gcn_layer_fwd(4, 34, 13, 13, None, None, None, None, None, None) == -1
 assert lib.wgnn_gcn_layer_fwd(4, 34, 6, 9, None, None, None, None, None, None) == -1
-assert lib.wgnn_gcn_layer_fwd(4, 34, 6, 65, None, None, None, None, None, None) == -5
+assert lib.wgnn_gcn_layer_fwd(4, 34, 6, 65, None, None, None, None, None, None) == -1
+assert lib.wgnn_gcn_layer_fwd(4, 65, 6, 65, None, None, None, None, None, None) == -5
+assert lib.wgnn_gcn_layer_fwd(1 << 20, 64, 128, 13, None, None, None, None, None, None) == -2
 assert lib.wgnn_gcn_layer_bwd(4, 34, 13, 13, None, None, None, None, None, None, None, None, None, 0, None) == -1
 dg = L.Dims(4, 24, 34, 13, 102, 0, 0, 0, 0)
 assert lib.wgnn_gru_fwd(C.byref(dg), None, C.byref(L.Params()), None, None, None, 0, None) == -1

@@ -10,7 +10,7 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libwindgnn_hip.so")
-SOURCES = ["api.hip", "finish.hip", "gcn.hip", "gemm.hip", "gru.hip", "train_ops.hip", "prof.hip", "gcnx.hip", "grux.hip", "pgemm.hip", "data_ops.hip", "general.hip", "gru_small.hip", "gcn32.hip", "gemm32.hip", "gcngi.hip", "pgemm_big.hip", "gcn_any.hip", "gru_step.hip", "eval.hip", "best.hip", "series.hip"]
+SOURCES = ["api.hip", "finish.hip", "gcn.hip", "gemm.hip", "gru.hip", "train_ops.hip", "prof.hip", "gcnx.hip", "grux.hip", "pgemm.hip", "data_ops.hip", "general.hip", "gru_small.hip", "gcn32.hip", "gemm32.hip", "gcngi.hip", "pgemm_big.hip", "gcn_any.hip", "gru_step.hip", "eval.hip", "best.hip", "series.hip", "gcn_wide.hip"]
 HEADERS = ["common.h", "gcnx_dev.h", os.path.join("..", "..", "include", "windgnn.h"),
            os.path.join("..", "..", "include", "windgnn_optim.h"), os.path.join("..", "..", "include", "windgnn_sched.h"),
            os.path.join("..", "..", "include", "windgnn_eval.h"), os.path.join("..", "..", "include", "windgnn_best.h"),

@@ -1391,18 +1391,31 @@ int wgnn_finish_rows(const wgnn_dims* d, const wgnn_params* p, const wgnn_grads*
   return launch_adam_rows(r, (hipStream_t)stream);
 }
 
-// F == F_out == 13 (the reference's own layers, src/main.py:41): the MFMA kernels of gcn.hip; any other widths: gcn_any.hip
+// F == F_out == 13 (the reference's own layers, src/main.py:41): the MFMA kernels of gcn.hip; other widths up to 64: gcn_any.hip;
+// max(F, F_out) > 64: gcn_wide.hip.  0 = fits none of them; WGNN_ERR_SHAPE / WGNN_ERR_UNSUPPORTED otherwise.
+static int gcn_layer_route(int32_t ntiles, int32_t S, int32_t F, int32_t F_out, bool* wide) {
+  if (ntiles < 1 || S < 1 || F < 1 || F_out < 1) return WGNN_ERR_SHAPE;
+  *wide = F > 64 || F_out > 64;
+  if (*wide && !gcn_wide_countable(ntiles, S, F, F_out)) return WGNN_ERR_SHAPE;
+  if (!(*wide ? gcn_wide_supported(S, F, F_out) : gcn_any_supported(S, F, F_out))) return WGNN_ERR_UNSUPPORTED;
+  return WGNN_OK;
+}
+
 size_t wgnn_gcn_layer_workspace_bytes(int32_t ntiles, int32_t S, int32_t F, int32_t F_out) {
-  if (ntiles < 1 || !gcn_any_supported(S, F, F_out)) return 0;
+  bool wide = false;
+  if (gcn_layer_route(ntiles, S, F, F_out, &wide) != WGNN_OK) return 0;
+  if (wide) return sizeof(float) * gcn_wide_bwd_ws_floats(ntiles, S, F, F_out);
   if (F == 13 && F_out == 13) return sizeof(float) * gcn1_bwd_partial_floats(ntiles);
   return sizeof(float) * gcn_any_bwd_partial_floats(ntiles, F, F_out);
 }
 
 int wgnn_gcn_layer_fwd(int32_t ntiles, int32_t S, int32_t F, int32_t F_out, const float* A, const float* X, const float* W,
                        const float* b, float* out, void* stream) {
-  if (ntiles < 1 || S < 1 || F < 1 || F_out < 1) return WGNN_ERR_SHAPE;
-  if (!gcn_any_supported(S, F, F_out)) return WGNN_ERR_UNSUPPORTED;
+  bool wide = false;
+  const int rc = gcn_layer_route(ntiles, S, F, F_out, &wide);
+  if (rc != WGNN_OK) return rc;
   if (!A || !X || !W || !b || !out) return WGNN_ERR_NULL;
+  if (wide) return launch_gcn_wide_fwd(ntiles, S, F, F_out, A, X, W, b, out, (hipStream_t)stream);
   if (F == 13 && F_out == 13) return launch_gcn1_fwd(ntiles, S, A, X, W, b, out, (hipStream_t)stream);
   return launch_gcn_any_fwd(ntiles, S, F, F_out, A, X, W, b, out, (hipStream_t)stream);
 }
@@ -1410,10 +1423,13 @@ int wgnn_gcn_layer_fwd(int32_t ntiles, int32_t S, int32_t F, int32_t F_out, cons
 int wgnn_gcn_layer_bwd(int32_t ntiles, int32_t S, int32_t F, int32_t F_out, const float* A, const float* X, const float* W,
                        const float* out, const float* dout, float* dW, float* db, float* dX, void* workspace,
                        size_t workspace_bytes, void* stream) {
-  if (ntiles < 1 || S < 1 || F < 1 || F_out < 1) return WGNN_ERR_SHAPE;
-  if (!gcn_any_supported(S, F, F_out)) return WGNN_ERR_UNSUPPORTED;
+  bool wide = false;
+  const int rc = gcn_layer_route(ntiles, S, F, F_out, &wide);
+  if (rc != WGNN_OK) return rc;
   if (!A || !X || !W || !out || !dout || !dW || !db || !workspace) return WGNN_ERR_NULL;
   if (workspace_bytes < wgnn_gcn_layer_workspace_bytes(ntiles, S, F, F_out)) return WGNN_ERR_WORKSPACE;
+  if (wide)
+    return launch_gcn_wide_bwd(ntiles, S, F, F_out, A, X, W, out, dout, dW, db, dX, (float*)workspace, (hipStream_t)stream);
   if (F == 13 && F_out == 13)
     return launch_gcn1_bwd(ntiles, S, A, X, W, out, dout, dW, db, dX, (float*)workspace, (hipStream_t)stream);
   return launch_gcn_any_bwd(ntiles, S, F, F_out, A, X, W, out, dout, dW, db, dX, (float*)workspace, (hipStream_t)stream);

@@ -226,6 +226,14 @@ int launch_gcn_any_bwd(int ntiles, int S, int Fi, int Fo, const float* A, const 
                        const float* dout, float* dW, float* db, float* dX, float* partial, hipStream_t st);
 int launch_pack_g(const float* gin, size_t rows, int I, float* g, int ld, hipStream_t st);
 int launch_unpack_dg(const float* dg, size_t rows, int I, int ld, float* out, hipStream_t st);
+// GraphConvLayer wider than 64 features, S <= 64 dense (gcn_wide.hip): max(Fi, Fo) > 64; countable: every extent fits an int
+bool gcn_wide_supported(int S, int Fi, int Fo);
+bool gcn_wide_countable(int ntiles, int S, int Fi, int Fo);
+size_t gcn_wide_bwd_ws_floats(int ntiles, int S, int Fi, int Fo);   // a multiple of 64
+int launch_gcn_wide_fwd(int ntiles, int S, int Fi, int Fo, const float* A, const float* X, const float* W, const float* b,
+                        float* out, hipStream_t st);
+int launch_gcn_wide_bwd(int ntiles, int S, int Fi, int Fo, const float* A, const float* X, const float* W, const float* out,
+                        const float* dout, float* dW, float* db, float* dX, float* ws, hipStream_t st);
 // large-shape NT plane GEMM (pgemm_big.hip); opt_big_gemm(): WGNN_OPT_BIG_GEMM (api.hip), 1 unless switched off for an A/B
 bool pgemm_nt256_wanted(int M, int N, int Kp);
 int launch_pgemm_nt256(const void* Aimg_hi, const void* Aimg_lo, int M, int k0, int klen, const void* Bplanes, int Np,

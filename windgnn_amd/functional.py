@@ -828,8 +828,9 @@ def gcn_gru_with_state(A, X, params, math=_lib.MATH_F32, h0=None):
 
 
 class GraphConvFunction(torch.autograd.Function):
-    """out = relu(A X W + b) for X [..., S, F_in], W [F_in, F_out] (src/step5_gcn_layer_model.py:13-23).  Dense adjacency: any
-    widths up to 64 (13 -> 13, the reference model's own, on the MFMA kernels); CSR adjacency: 13 -> 13 only."""
+    """out = relu(A X W + b) for X [..., S, F_in], W [F_in, F_out] (src/step5_gcn_layer_model.py:13-23).  Dense adjacency (S <= 64):
+    any widths, exact fp32 -- 13 -> 13, the reference model's own, on the MFMA kernels of gcn.hip, other widths up to 64 on
+    gcn_any.hip, wider ones on the tiled fp32-MFMA kernels of gcn_wide.hip; CSR adjacency: 13 -> 13 only."""
 
     @staticmethod
     def forward(ctx, A, X, W, b):
@@ -852,7 +853,8 @@ class GraphConvFunction(torch.autograd.Function):
             rc = lib.wgnn_gcn_layer_csr_fwd(nt, S, F, nnz, _ptr(A), _ptr(X), _ptr(W), _ptr(b), _ptr(out), _stream())
         else:
             rc = lib.wgnn_gcn_layer_fwd(nt, S, F, Fo, _ptr(A), _ptr(X), _ptr(W), _ptr(b), _ptr(out), _stream())
-        _lib.check(rc, "wgnn_gcn_layer_fwd(S=%d, %d -> %d)" % (S, F, Fo))
+        _lib.check(rc, "wgnn_gcn_layer_fwd(S=%d, %d -> %d%s)"
+                   % (S, F, Fo, ": a dense adjacency holds at most 64 stations, every width" if fmt != _lib.ADJ_CSR and S > 64 else ""))
         ctx.save_for_backward(A, X, W, out)
         ctx.dims = (nt, S, F, Fo, fmt, nnz)
         return out

@@ -20,8 +20,9 @@ NUM_FEATURES = 13   # hard-coded in the reference: src/step6_gcn_gru_combined_mo
 
 class GraphConvLayer(nn.Module):
     """The reference's constructor domain (src/step5_gcn_layer_model.py:6-10): any input_dim -> output_dim.  13 -> 13, the only
-    widths its model builds (src/main.py:41), run the MFMA kernels; other widths (up to 64, dense adjacency of S <= 64) an
-    exact-fp32 kernel of their own; beyond that the forward raises."""
+    widths its model builds (src/main.py:41), run the MFMA kernels of gcn.hip; other widths, over a dense adjacency of S <= 64, exact-fp32
+    kernels of their own (up to 64 features gcn_any.hip, wider layers the tiled fp32-MFMA kernels of gcn_wide.hip); more than 64
+    stations over a dense adjacency, or other widths than 13 -> 13 over a CSR one, raise at the first forward."""
 
     def __init__(self, input_dim, output_dim):
         super().__init__()
