@@ -45,7 +45,7 @@ struct Layout {
   size_t st_h1;                                  // general GCN: layer-1 activations
   size_t st_stats;                               // wgnn_fwd_loss: MSE partial pairs (sum | max) of the forward recurrence
   size_t st_GI;                                  // split modes, register-resident recurrence: GI lives in the stash (BPTT recomputes n from its n third)
-  bool gi_stash;
+  bool gi_stash, ghn_rc;                         // ghn_rc: ... and those records are r | z, BPTT recomputes gh_n as well (ghn_recompute)
   size_t ws_gh, ws_h1, ws_yp, ws_hhp_f, ws_kp_f, ws_hc, ws_du, ws_dhz, ws_dhw, ws_hhp_b, ws_kp_b, ws_dc;   // general GRU / GCN scratch
   size_t ws_ntk_f, ws_ntk_b;                     // exact fp32, few rows: split-K partial sums of the GI / dg products
   size_t ws_aimg_f, ws_aimg_b;                   // large-shape NT plane GEMMs (configs[4]): the A operand (g / dGI) rewritten as an image
@@ -140,9 +140,9 @@ Layout make_layout(const wgnn_dims* d, bool state = false, int series = SER_NONE
     const size_t nb = L.small ? (size_t)gru_small_blocks(d->B) : (size_t)grux_blocks(d->B);
     L.st_stats = o; o += al(series ? 0 : 2 * nb + 4);   // (series mode keeps them in the caller's loss_buf: windgnn_series_train.h)
   }
-  // split fp16 modes with the register-resident recurrence: the gate records hold r | z | gh_n only and the BPTT kernel forms
-  // n = tanh(gi_n + r gh_n) from GI, so GI (which the projection GEMM writes anyway) goes into the stash, not the workspace
-  L.gi_stash = (x3 && !L.gen_gru && three_pass(d)) || L.rec32;   // (and gru.hip's)
+  // split fp16 modes with the register-resident recurrence: the gate records hold r | z | gh_n only (r | z under ghn_rc, in the
+  // same region) and the BPTT kernel forms n = tanh(gi_n + r gh_n) from GI, so GI goes into the stash, not the workspace
+  L.gi_stash = (x3 && !L.gen_gru && three_pass(d)) || L.rec32; L.ghn_rc = !series && !L.gen_gru && ghn_recompute(d, state);
   L.st_GI = o; o += al(ser_front(series, L.gi_stash ? L.BT * L.Gp : 0));
   L.hq = (int)rup(L.H + 1, 16);
   const bool hprev_rows = L.g32tn || (state && !x3);                // (the state stash: every exact-fp32 path)
@@ -535,7 +535,7 @@ int fwd_recurrence(const Fwd& f) {
     }
     rc = launch_grux_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, f.Y, f.gates,   // (no Y planes for a dW_hh from Y)
                          f.sf && !hh_from_y(d, L.tn_merge, c.sst) ? f.sf + L.st_yp : nullptr, f.full, f.status, labels, stats,
-                         d->io, 0, 1.f, 0.f, f.st, c.h0, c.hn, c.sst ? L.plane_rows : 0);
+                         d->io, 0, 1.f, 0.f, f.st, c.h0, c.hn, c.sst ? L.plane_rows : 0, L.ghn_rc);
   } else if (L.rec32) {       // exact fp32, W_hh in registers
     if (c.last)
       return launch_gru_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, c.last, nullptr, nullptr, nullptr, nullptr, 0,
@@ -708,7 +708,7 @@ int bwd_rec(const Bwd& b) {
     return launch_grux_bwd(d->B, d->T, d->H, p->w_hh, c.Y, b.fused_loss ? nullptr : dY, b.fused_loss ? c.labels : nullptr,
                            d->io, gates, L.gi_stash ? b.sf + L.st_GI : nullptr, (int)L.Gp, b.scales, b.dGI, b.dGH, (int)L.Gp,
                            b.full, stats, (int64_t)L.BT * L.H, c.grad_scale, c.loss, b.scales, b.status, L.dgi1 ? 0 : 1, b.st,
-                           sb);
+                           sb, p->b_hh, L.ghn_rc);
   }
   if (L.gen_gru)
     return launch_gru_gen_bwd(d->B, d->T, d->H, p->w_hh, b.Y, dY, gates, b.dGI, b.dGH, (int)L.Gp, b.ws + L.ws_dhz,
@@ -947,6 +947,20 @@ int opt_big_gemm() { return opt(WGNN_OPT_BIG_GEMM); }
 bool hh_from_y(const wgnn_dims* d, bool tn_merge, bool sst) {
   static const int from_env = env_int("WGNN_TN_YFP32", 1, 0, 1);
   return tn_merge && three_pass(d) && d->io == WGNN_IO_F32 && !sst && from_env && opt(WGNN_OPT_TN_MERGED);
+}
+
+// Whether the gate records of this step are r | z: the forward recurrence stores no gh_n and the BPTT kernel recomputes it as
+// b_hn + W_hn h_{t-1} from the h_{t-1} it loads anyway (grux.hip, the RC instances) -- 4 B x 16 ceil(H / 16) columns x B*T less
+// written and less read back.  make_layout asks once per call (Layout::ghn_rc), and the forward launch and bwd_rec take it from
+// their layout, so every forward and every backward entry point on the same dims agree on the record.  In scope, as hh_from_y:
+// the register-resident recurrence (H <= 127) of the split-fp16 modes with fp32 I/O -- only there is Y[b, t-1] the very fp32 h
+// the forward split into its MFMA operand, which makes the recomputed gh_n the forward's bit for bit -- and the stateless
+// step; 16-bit I/O, the carried-state entries, series mode, the one-pass fp16 records, gru.hip, gru_small.hip and the wide-GRU
+// path keep their records.  The record region and everything behind it stay where they are: the freed third is left alone.
+// The environment variable WGNN_GHN_RECOMPUTE = 0 keeps the three-component record; it is read at every call (not cached), so one
+// process can run both forms -- a forward and its backward must see the same value.
+bool ghn_recompute(const wgnn_dims* d, bool sst) {
+  return three_pass(d) && grux_shape_supported(d->H) && d->io == WGNN_IO_F32 && !sst && env_int("WGNN_GHN_RECOMPUTE", 1, 0, 1);
 }
 
 // ---- series mode (series.hip validates and sizes; the launches live here, next to the layouts and the parts they reuse) ----

@@ -161,7 +161,8 @@ int launch_grux_fwd(int B, int T, int H, const void* GI /*fp32 rows if x3, else 
                     int io /*wgnn_io of Y and labels*/, int last_only, float y_mul, float y_add, hipStream_t st,
                     const float* h0 = nullptr /*[B][H] initial state (wgnn_fwd_state)*/,
                     float* hn = nullptr /*[B][H] fp32 h_{T-1}; Y may then be NULL with 16-bit I/O*/,
-                    size_t plane_rows = 0 /*rows per y plane: 0 = B*T + 1 (wgnn_stash_bytes' layout)*/);
+                    size_t plane_rows = 0 /*rows per y plane: 0 = B*T + 1 (wgnn_stash_bytes' layout)*/,
+                    bool ghn_rc = false /*ghn_recompute(): the gate records are r | z (x3, fp32 I/O, no state)*/);
 int grux_blocks(int B);   // workgroups of launch_grux_fwd = MSE partial pairs it writes when given labels
 int mse_stats_blocks();
 // exactly one of dY / labels is non-null (labels: dY = (Y - labels) * scales[2], see launch_mse_stats)
@@ -175,7 +176,8 @@ int launch_grux_bwd(int B, int T, int H, const float* Whh, const void* Y, const 
                     const float* scales, void* dGI_planes, void* dGHn_planes, int ldd, bool x3, const float* stat_part,
                     int64_t n_loss, float grad_scale, float* loss, float* scales_out, unsigned* status,
                     int write_lo /*0: dGI / dGHn as one fp16 plane (x3 only)*/, hipStream_t st,
-                    const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given, no labels*/);
+                    const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given, no labels*/,
+                    const float* bhh = nullptr, bool ghn_rc = false /*ghn_recompute(): r | z records, gh_n from Y, W_hh and bhh*/);
 #define WGNN_STATS_TAG 20261004.0f   // float word behind the MSE partial pairs: "wgnn_fwd_loss wrote these"
 #define WGNN_STATS_TAG_MASKED 20261019.0f   // the same word from wgnn_series_fwd_loss_masked: sums over the labels that exist
 // a third value from wgnn_series_fwd_lossfn (fp32 spacing is 2 up here: 20261019 IS 20261020), which also fills the three spare
@@ -243,6 +245,8 @@ int launch_pgemm_repack_a(const void* Ahi, const void* Alo, int lda, int M, int 
 int opt_big_gemm();   // WGNN_OPT_BIG_GEMM: 0 off, 1 on (needs the caller's A-image scratch)
 // api.hip: the dW_hh product of this step reads h from the caller's fp32 Y, the forward recurrence writes no Y planes
 bool hh_from_y(const wgnn_dims* d, bool tn_merge, bool sst);
+// api.hip: the gate records of this step are r | z -- the forward recurrence stores no gh_n, BPTT recomputes it from Y
+bool ghn_recompute(const wgnn_dims* d, bool sst);
 // ---- The image of a B operand (weights: W_ih | b_ih, W_ih^T, W_hh | b_hh), written by split_weight2_kernel / finish.hip and
 // staged by the NT plane GEMMs and the fused front end: one fp16 plane of B[Np][Kp] is STAGE-major (a 32-deep K step of all
 // Np rows is contiguous) and, since round 5, FRAGMENT-major inside a stage: the 16 rows x 32 k of one MFMA B fragment are 1 KB

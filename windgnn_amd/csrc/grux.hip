@@ -87,13 +87,52 @@ __device__ __forceinline__ void put_split(_Float16* hi, _Float16* lo, int idx, f
   hi[idx] = h;
   if (X3) lo[idx] = (_Float16)(v - (float)h);
 }
+// One gate's slice of W_hh as the forward's B operand, [k = h index][n = gate unit j], k = 32 ks + 8 g + jj: zero from column H
+// on, so the ones column of the state tile meets zeros (b_hh enters through the accumulators).  The BPTT kernel that
+// recomputes gh_n builds its n-gate fragments here too: the same values in the same registers of the fragment.
+template <int KS>
+__device__ __forceinline__ bool whh_gate_frags(const float* __restrict__ Whh, int H, int gate, int j, bool jv, int g,
+                                               Frag (&W)[KS]) {
+  bool bad = false;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    float x[8];
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) {
+      const int k = 32 * ks + 8 * g + jj;
+      x[jj] = (jv && k < H) ? Whh[(size_t)(gate * H + j) * H + k] : 0.f;
+      bad |= out_of_fp16_range(x[jj]);
+    }
+    W[ks] = split_vals(x);
+  }
+  return bad;
+}
+// acc[q] += [h | 1 | 0..] W[q] for NG gates over the state tile (hi plane, lo plane; rows of HS = 32 KS + 8 halfs): K steps in
+// ascending order, per K step the three passes of mfma3, one accumulator per gate.  The forward runs it on all three gates,
+// the BPTT kernel that recomputes gh_n on the n gate alone: per accumulator the same instructions in the same order.
+template <int KS, bool X3, int NG>
+__device__ __forceinline__ void hh_product(const _Float16* hhi, const _Float16* hlo, int c, int g, const Frag (*W)[KS],
+                                           f32x4 (&acc)[NG]) {
+  constexpr int HS = 32 * KS + 8;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    Frag a;
+    a.hi = *(const h8*)(hhi + c * HS + 32 * ks + 8 * g);
+    if (X3) a.lo = *(const h8*)(hlo + c * HS + 32 * ks + 8 * g);
+    else a.lo = a.hi;
+#pragma unroll
+    for (int q = 0; q < NG; ++q) acc[q] = mfma3<X3>(a, W[q][ks], acc[q]);
+  }
+}
 
 // ------------------------------------------------------------------------------------------------
 // IO: Y and the labels are 16-bit on the wire (fp16 / bf16 by `io`) and move through LDS as whole rows; the fp32
 // instance keeps the direct per-lane accesses (the row path was 30 % slower there: measured 116 vs 84 us).
 // GI: the input projection [B*T][ldgi] in the 3H layout -- fp32 for the split (X3) instances, ONE fp16 plane for the one-pass
 // fp16 instances (WGNN_MATH_F16: pgemm_nt's OUT16 epilogue; half the bytes of the largest intermediate of that mode)
-template <int KS, bool X3, bool IO, bool ST = false>   // K steps of 32 over the hidden index (+ the ones column): KS = ceil((H+1)/32)
+// RC (the split modes' stateless fp32-I/O step, api.hip ghn_recompute): the record is r | z -- gh_n is not stored, the BPTT
+// kernel recomputes it from the h_{t-1} it loads anyway
+template <int KS, bool X3, bool IO, bool ST = false, bool RC = false>   // K steps of 32 over the hidden index (+ the ones column): KS = ceil((H+1)/32)
 __global__ void __launch_bounds__(NTHREADS) grux_fwd_kernel(int B, int T, int H, const void* __restrict__ GI, int ldgi,
                                                             const float* __restrict__ Whh,
                                                             const float* __restrict__ bhh, void* __restrict__ Y,
@@ -106,6 +145,7 @@ __global__ void __launch_bounds__(NTHREADS) grux_fwd_kernel(int B, int T, int H,
   // h0 (nullable, wgnn_fwd_state): [B][H] fp32 initial state instead of zeros, split into the planes like every h_t (a value
   // beyond fp16's range is reported as WGNN_STATUS_ACT_RANGE); hn (nullable): h_{T-1} [B][H] as fp32, never rounded to `io`.
   // ST: the wgnn_fwd_state instance; the plain forward's (ST = false) ignores h0 / hn and compiles exactly as before
+  static_assert(!RC || (X3 && !IO && !ST), "gh_n is recomputed in the stateless fp32-I/O split step only");
   if (!ST) { h0 = nullptr; hn = nullptr; }
   // last_only (wgnn_fwd_last, inference): Y is [B][H] fp32 and receives only h_{T-1} * y_mul + y_add -- the evaluation
   // read-out of src/main.py:103,116 without writing (and re-reading) the other T-1 rows
@@ -147,18 +187,7 @@ __global__ void __launch_bounds__(NTHREADS) grux_fwd_kernel(int B, int T, int H,
   bool wbad = false;
   Frag WB[3][KS];                                  // B operand: W_hh[(gate*H + j)][k], k = 32ks + 8g + jj
 #pragma unroll
-  for (int gate = 0; gate < 3; ++gate)
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      float x[8];
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) {
-        const int k = 32 * ks + 8 * g + jj;
-        x[jj] = (jv && k < H) ? Whh[(size_t)(gate * H + j) * H + k] : 0.f;
-        wbad |= out_of_fp16_range(x[jj]);
-      }
-      WB[gate][ks] = split_vals(x);
-    }
+  for (int gate = 0; gate < 3; ++gate) wbad |= whh_gate_frags<KS>(Whh, H, gate, j, jv, g, WB[gate]);
   if (blockIdx.x == 0) report_status(status, wbad, WGNN_STATUS_WEIGHT_RANGE);
   const float bh_r = bhh[jc], bh_z = bhh[H + jc], bh_n = bhh[2 * H + jc];
 
@@ -182,7 +211,9 @@ __global__ void __launch_bounds__(NTHREADS) grux_fwd_kernel(int B, int T, int H,
   // Split modes (round 4): THREE fp32 components, r | z | gh_n -- n is not stored: the BPTT kernel recomputes it as
   // tanh(gi_n + r gh_n) from the n third of GI, which the forward keeps in the stash (the projection GEMM writes GI there
   // instead of into the workspace: no extra traffic); 44 MB less stash per step at B = 4096 for 42 MB of GI read back.
-  constexpr int GREC = X3 ? (IO ? 4 : 3) : (IO ? 3 : 2);       // 16-byte components per lane and (t, wave)
+  // RC: TWO, r | z, packed at the start of the same region -- gh_n depends on nothing but h_{t-1}, which the BPTT kernel loads
+  // from Y anyway and multiplies by the n rows of W_hh itself (another 44 MB less written here and 44 MB less read there).
+  constexpr int GREC = X3 ? (IO ? 4 : (RC ? 2 : 3)) : (IO ? 3 : 2);       // 16-byte components per lane and (t, wave)
   f32x4* gatesw = gates ? (f32x4*)gates + ((size_t)blockIdx.x * T * NW + wave) * GREC * 64 + lane : nullptr;
   int rowt[4];            // (local window row) * T, clamped to the last valid window
   bool rowok[4];
@@ -283,23 +314,15 @@ __global__ void __launch_bounds__(NTHREADS) grux_fwd_kernel(int B, int T, int H,
     const float* lt = ltile + (t & 1) * MB * HY;
     float hnew[4] = {0.f, 0.f, 0.f, 0.f};
     if (active) {
-      f32x4 ar, az, an;
+      f32x4 acc[3];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        ar[r] = gi[0][r] + bh_r;
-        az[r] = gi[1][r] + bh_z;
-        an[r] = bh_n;
+        acc[0][r] = gi[0][r] + bh_r;
+        acc[1][r] = gi[1][r] + bh_z;
+        acc[2][r] = bh_n;
       }
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        Frag a;
-        a.hi = *(const h8*)(hhi + c * HS + 32 * ks + 8 * g);
-        if (X3) a.lo = *(const h8*)(hlo + c * HS + 32 * ks + 8 * g);
-        else a.lo = a.hi;
-        ar = mfma3<X3>(a, WB[0][ks], ar);
-        az = mfma3<X3>(a, WB[1][ks], az);
-        an = mfma3<X3>(a, WB[2][ks], an);
-      }
+      hh_product<KS, X3, 3>(hhi, hlo, c, g, WB, acc);
+      const f32x4 ar = acc[0], az = acc[1], an = acc[2];
       f32x4 rg4, zg4, ng4;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {                      // the four rows' gate chains in ONE basic block (they interleave);
@@ -330,7 +353,7 @@ __global__ void __launch_bounds__(NTHREADS) grux_fwd_kernel(int B, int T, int H,
         if (X3) {
           rec[0] = rg4;
           rec[64] = zg4;
-          rec[128] = an;
+          if (!RC) rec[128] = an;
         } else {
           h8 rz, ng;
 #pragma unroll
@@ -434,7 +457,12 @@ __global__ void __launch_bounds__(NTHREADS) grux_fwd_kernel(int B, int T, int H,
 // for the copy-out; the W_hh^T fragments' k index follows the same layout.
 // St (empty, or one BwdState: wgnn_bwd_state_part): h_{-1} = h0, the carry starts at s dh_n, and the step at t = 0 also
 // forms dh_{-1} = dh z + dgh W_hh, written (times scales[1]) to dh0.
-template <int KSB, bool X3, bool IO, typename... St>   // K steps of 32 over the padded dgh row: KSB = ceil((MS + H) / 32); IO: as grux_fwd_kernel
+// KSF > 0 (the forward's RC instances wrote r | z records; KSF is the forward's KS = ceil((H + 1) / 32)): gh_n of step t - 1 is
+// recomputed during step t, as b_hn + [h_{t-2} | 1 | 0..] W_hn by the forward's own hh_product on the forward's own
+// fragments, from a state tile split exactly as the forward's -- Y[b, t-2] IS the fp32 h the forward split, so the product is
+// the forward's bit for bit.  h_{t-2} is prefetched two steps ahead, its tile is written before the step's first barrier and
+// read behind it, beside the dgh W_hh product: nothing of it sits on the chain from dh_next to the next step.
+template <int KSB, bool X3, bool IO, int KSF, typename... St>   // K steps of 32 over the padded dgh row: KSB = ceil((MS + H) / 32); IO: as grux_fwd_kernel
 __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H, const float* __restrict__ Whh,
                                                             const void* __restrict__ Y, const float* __restrict__ dY,
                                                             const void* __restrict__ Lab, int io,
@@ -447,8 +475,10 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
                                                             const float* __restrict__ stat_part, int nstat, float inv_n,
                                                             float coef_in, float* __restrict__ loss_out,
                                                             float* __restrict__ scales_out, unsigned* status,
-                                                            int write_lo, St... state) {
+                                                            int write_lo, const float* __restrict__ bhh, St... state) {
   constexpr bool ST = sizeof...(St) > 0;
+  constexpr bool RC = KSF > 0;
+  static_assert(!RC || (X3 && !IO && !ST), "gh_n is recomputed in the stateless fp32-I/O split step only");
   const BwdState sb = bwd_state(state...);
   // write_lo == 0 (X3, large B*T): dGI / dGHn leave the chip as ONE fp16 plane (the lo halves stay in LDS, where the
   // recurrence's own product dgh W_hh uses them): the three GEMMs that consume them run two passes
@@ -502,6 +532,14 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
   // the second barrier below: dropping that barrier was slower)
   __shared__ __attribute__((aligned(16))) _Float16 dbuf2[2 * 4 * MB * DS];
   for (int i = threadIdx.x; i < 2 * 4 * MB * DS; i += NTHREADS) dbuf2[i] = (_Float16)0.f;
+  // RC: the forward's state tile [h | 1 | 0..], hi plane then lo plane, rows of HSF halfs; the tile of step s is htile2[s & 1]
+  constexpr int HPF = 32 * KSF, HSF = 32 * KSF + 8;
+  __shared__ __attribute__((aligned(16))) _Float16 htile2[RC ? 2 * 2 * MB * HSF : 8];
+  if (RC) {
+    for (int i = threadIdx.x; i < 2 * 2 * MB * HSF; i += NTHREADS)   // zeros, and the ones column of both hi planes
+      htile2[i] = (_Float16)((i % (2 * MB * HSF) < MB * HSF && i % HSF == H) ? 1.f : 0.f);
+    __syncthreads();                                                 // (the owner lanes write h_{T-2} below)
+  }
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int j = 16 * wave + c;
@@ -527,12 +565,18 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
     }
     WT[ks] = split_vals(x);
   }
+  Frag WN[1][RC ? KSF : 1];                        // RC: the forward's n-gate B operand (32 registers at H = 102) and b_hn
+  float bh_n = 0.f;
+  if constexpr (RC) {
+    whh_gate_frags<KSF>(Whh, H, 2, j, jv, g, WN[0]);
+    bh_n = bhh[2 * H + jc];
+  }
+  constexpr int GREC = X3 ? (IO ? 4 : (RC ? 2 : 3)) : (IO ? 3 : 2);       // as grux_fwd_kernel: r | z (| gh_n) (+ h), or fp16 records
   const int NW = (H + 15) / 16;                              // gate stash: grux_fwd_kernel's register layout
-  const f32x4* gatesw = (const f32x4*)gates + ((size_t)blockIdx.x * T * NW + (active ? wave : 0)) * (X3 ? (IO ? 4 : 3) : (IO ? 3 : 2)) * 64 + lane;
+  const f32x4* gatesw = (const f32x4*)gates + ((size_t)blockIdx.x * T * NW + (active ? wave : 0)) * GREC * 64 + lane;
   // 16-bit I/O: Y on the wire is rounded, so h_{t-1} (and the Y of the fused dY) is the 5th component of the stash
   // records; explicit dY is always fp32; labels are io-typed and come in through LDS as whole rows (see grux_fwd_kernel)
   constexpr int esz = IO ? 2 : 4;
-  constexpr int GREC = X3 ? (IO ? 4 : 3) : (IO ? 3 : 2);       // as grux_fwd_kernel: r | z | gh_n (+ h), or fp16 records
   const float* GIw = X3 ? GIn + (size_t)b0 * T * ldgi + 2 * H : nullptr;   // n third of this workgroup's GI rows (stash)
   const void* Labw = Lab ? (const char*)Lab + (size_t)b0 * T * H * esz : nullptr;
   const float* dYw = dY ? dY + (size_t)b0 * T * H : nullptr;
@@ -637,9 +681,10 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
   auto load_step = [&](int t, StepIn& s) {
     const int tc = t > 0 ? t : 0;
     const f32x4* rec = gatesw + (size_t)tc * NW * GREC * 64;
-    f32x4 r4, z4, n4, g4;
+    f32x4 r4, z4, n4, g4 = {0.f, 0.f, 0.f, 0.f};
     if (X3) {
-      r4 = rec[0]; z4 = rec[64]; g4 = rec[128];
+      r4 = rec[0]; z4 = rec[64];
+      if (!RC) g4 = rec[128];                            // (RC: gh_n comes out of the step before, see the loop)
 #pragma unroll
       for (int r = 0; r < 4; ++r) n4[r] = GIw[(rowt[r] + tc) * ldgi + jc];      // gi_n: n itself is formed in the step
     } else {
@@ -661,7 +706,7 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
       s.z[r] = z4[r];
       s.n[r] = n4[r];
       s.ghn[r] = g4[r];
-      const float hp = IO ? 0.f : Yw[(bt - (tc > 0 ? 1 : 0)) * H + jc];
+      const float hp = (IO || RC) ? 0.f : Yw[(bt - (tc > 0 ? 1 : 0)) * H + jc];   // (RC: load_hprev, a step earlier)
       s.hp[r] = tc > 0 ? hp : 0.f;
       if constexpr (ST) {   // (a discarded branch: the plain instance's lambda does not even capture sb)
         if (tc == 0) s.hp[r] = h0r[r];
@@ -673,8 +718,37 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
       for (int r = 0; r < 4; ++r) s.hp[r] = h4[r];
     }
   };
+  // RC: h_{s-1}, the hp of step s, on its own -- the loop asks for it two steps ahead, so that its tile can be written
+  // before the first barrier of the step that recomputes gh_n of step s, from a load issued a whole step earlier
+  auto load_hprev = [&](int s, float (&hp)[4]) {
+    const int sc = s > 0 ? s : 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float v = Yw[(rowt[r] + sc - (sc > 0 ? 1 : 0)) * H + jc];
+      hp[r] = sc > 0 ? v : 0.f;
+    }
+  };
+  // the owner lanes' part of the tile of step s: the forward's put_split, columns past H into the row's pad halfs
+  auto put_hprev = [&](int s, const float (&hp)[4]) {
+    _Float16* thi = htile2 + (s & 1) * 2 * MB * HSF;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) put_split<true>(thi, thi + MB * HSF, (4 * g + r) * HSF + (jv ? j : HPF + (c & 7)), hp[r]);
+  };
+  auto ghn_of = [&](int s, float (&ghn)[4]) {            // gh_n of step s from its tile: the forward's product, n gate alone
+    const _Float16* thi = htile2 + (s & 1) * 2 * MB * HSF;
+    f32x4 a[1] = {{bh_n, bh_n, bh_n, bh_n}};
+    hh_product<RC ? KSF : 1, true, 1>(thi, thi + MB * HSF, c, g, WN, a);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ghn[r] = a[0][r];
+  };
   StepIn cur, nxt;
   load_step(T - 1, cur);
+  float hq[4] = {0.f, 0.f, 0.f, 0.f};                    // RC: the hp of the step after next
+  if (RC) {
+    load_hprev(T - 1, cur.hp);
+    load_hprev(T - 2, hq);
+    if (active) put_hprev(T - 1, cur.hp);                // read behind the barrier in front of the loop
+  }
   float ycur[4] = {0.f, 0.f, 0.f, 0.f};
   if (Lab) {
     if (IO) {
@@ -699,6 +773,7 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
   const int o_pad = 32 * KSB + 8 + (c & 7);
   const int o_r = jv ? j : o_pad, o_z = jv ? H + j : o_pad, o_n = jv ? MS + j : o_pad, o_t = jv ? 2 * H + j : o_pad;
   __syncthreads();
+  if (RC && active) ghn_of(T - 1, cur.ghn);
 
   for (int t = T - 1; t >= 0; --t) {
     _Float16* dbuf = dbuf2 + (t & 1) * 4 * MB * DS;
@@ -707,6 +782,11 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
     _Float16* ihi = dbuf + 2 * MB * DS;
     _Float16* ilo = dbuf + 3 * MB * DS;
     load_step(t - 1, nxt);
+    if (RC) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) nxt.hp[r] = hq[r];     // loaded during step t + 1
+      load_hprev(t - 2, hq);
+    }
     if (IO && Lab) load_lab(t - 1);
     const float* lt = ltile + (t & 1) * MB * HY;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -746,8 +826,9 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
           ilo[m * DS + o_t] = (_Float16)(dnt - (float)nth);
         }
       }
+      if (RC && t > 0) put_hprev(t - 1, nxt.hp);         // the other parity than the tile this step's gh_n came from
     }
-    if (IO && Lab) stage_lab(t - 1);    // other parity than the labels read above; visible after the barrier
+    if (IO && Lab) stage_lab(t - 1);   // other parity than the labels read above; visible after the barrier
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {   // planes out: rows (b, t) of dGI and of dGHn
@@ -770,6 +851,7 @@ __global__ void __launch_bounds__(NTHREADS) grux_bwd_kernel(int B, int T, int H,
         for (int r = 0; r < 4; ++r)
           if (rowok[r]) sb.dh0[(size_t)(b0 + 4 * g + r) * H + j] = acc[r] * s_out;
       }
+      if (RC && t > 0) ghn_of(t - 1, nxt.ghn);           // behind the same barrier as dgh: complete for every wave
     }
     dhn = acc;
     __syncthreads();   // measured: without it the waves drift apart and the step gets 8 % slower (LDS contention)
@@ -790,15 +872,26 @@ size_t grux_gates_floats(int B, int T, int H, int io) {
 int grux_blocks(int B) { return cdiv_i(B, MB); }
 // bytes the recurrences really move for the stash: fp16 records in the one-pass mode (grux_gates_floats() sizes the buffer
 // for the split modes' fp32 records whatever the mode)
-static double gates_bytes(int B, int T, int H, int io, bool x3) {
-  return (double)cdiv_i(B, MB) * T * cdiv_i(H, 16) * (x3 ? (io ? 4 : 3) : (io ? 3 : 2)) * 64 * 16.0;
+static double gates_bytes(int B, int T, int H, int io, bool x3, bool rc = false /*r | z records: gh_n is recomputed*/) {
+  return (double)cdiv_i(B, MB) * T * cdiv_i(H, 16) * (x3 ? (io ? 4 : (rc ? 2 : 3)) : (io ? 3 : 2)) * 64 * 16.0;
+}
+// The forward K steps (KS of grux_fwd_kernel) among the hidden widths of one BPTT instance KSB: the lowest and the highest
+// (they differ where a bracket of KSB straddles H + 1 = 32 n); 0: no H <= 127 selects that KSB
+constexpr int ghn_ksb(int H) { return (8 * ((2 * H + 7) / 8) + H + 31) / 32; }
+constexpr int ghn_ksf(int K, bool hi) {
+  int v = 0;
+  for (int H = 1; H <= 127; ++H)
+    if (ghn_ksb(H) == K && (v == 0 || hi)) v = (H + 32) / 32;
+  return v;
 }
 
 int launch_grux_fwd(int B, int T, int H, const void* GI /*fp32 rows (x3) or fp16 rows (one-pass fp16)*/, int ldgi, const float* Whh, const float* bhh, void* Y,
                     float* gates, void* y_planes /*nullable: 2 x [B*T+1][grux_hp(H)] halfs*/, bool x3, unsigned* status,
                     const void* labels /*nullable*/, float* stat_part /*2 * grux_blocks(B) floats if labels*/, int io,
                     int last_only /*Y is [B][H]: only h_{T-1} * y_mul + y_add is written (fp32 I/O, no stash)*/,
-                    float y_mul, float y_add, hipStream_t st, const float* h0, float* hn, size_t plane_rows) {
+                    float y_mul, float y_add, hipStream_t st, const float* h0, float* hn, size_t plane_rows, bool ghn_rc) {
+  const bool rc = ghn_rc && gates;                 // r | z records (api.hip ghn_recompute): the stateless fp32-I/O split step only
+  if (rc && (!x3 || io || h0 || hn)) return WGNN_ERR_UNSUPPORTED;
   if (last_only && (io != 0 || gates || y_planes || labels)) return WGNN_ERR_UNSUPPORTED;
   if (!Y && (!io || !hn || last_only)) return WGNN_ERR_NULL;   // Y = NULL: 16-bit I/O with h_n only (fp32: last_only into h_n)
   _Float16* yh = (_Float16*)y_planes;
@@ -807,7 +900,7 @@ int launch_grux_fwd(int B, int T, int H, const void* GI /*fp32 rows (x3) or fp16
   const double bt = (double)B * T;
   const double fl = bt * 2.0 * 3 * H * H,
                by = bt * ((x3 ? 4.0 : 2.0) * 3 * H + (io ? 2.0 : 4.0) * ((last_only ? 0 : H) + (labels ? H : 0))) +
-                    (gates ? gates_bytes(B, T, H, io, x3) : 0.0);
+                    (gates ? gates_bytes(B, T, H, io, x3, rc) : 0.0);
   const dim3 grid(cdiv_i(B, MB));
 #define FLAUNCH(K, X3V, IOV, NAME)                                                                                 \
   PROF_LAUNCH(NAME, fl, by, st,                                                                                    \
@@ -818,7 +911,11 @@ int launch_grux_fwd(int B, int T, int H, const void* GI /*fp32 rows (x3) or fp16
                                       Whh, bhh, Y, gates, yh, yl, status, labels, stat_part, io, last_only, y_mul, y_add,      \
                                       nullptr, nullptr))
 #define FCASE(K)                                                                                                   \
-  if (x3 && !io) FLAUNCH(K, true, false, "grux_fwd_kernel<" #K ">");                                               \
+  if (rc) PROF_LAUNCH("grux_fwd_kernel<" #K ">", fl, by, st,                                                       \
+                      hipLaunchKernelGGL((grux_fwd_kernel<K, true, false, false, true>), grid, dim3(NTHREADS), 0, st, B, T, H, \
+                                         GI, ldgi, Whh, bhh, Y, gates, yh, yl, status, labels, stat_part, io, last_only, y_mul,  \
+                                         y_add, nullptr, nullptr));                                                             \
+  else if (x3 && !io) FLAUNCH(K, true, false, "grux_fwd_kernel<" #K ">");                                          \
   else if (x3) FLAUNCH(K, true, true, "grux_fwd_kernel<" #K ">");                                                  \
   else if (!io) FLAUNCH(K, false, false, "grux_fwd_kernel<" #K ",f16>");                                           \
   else FLAUNCH(K, false, true, "grux_fwd_kernel<" #K ",f16>")
@@ -842,8 +939,10 @@ int launch_grux_bwd(int B, int T, int H, const float* Whh, const void* Y, const 
                     const float* gates, const float* GI /*x3: the forward's GI rows [B*T][ldgi] fp32 (stash)*/, int ldgi,
                     const float* scales, void* dGI_planes, void* dGHn_planes, int ldd, bool x3, const float* stat_part,
                     int64_t n_loss, float grad_scale, float* loss, float* scales_out, unsigned* status, int write_lo,
-                    hipStream_t st, const BwdState* state) {
+                    hipStream_t st, const BwdState* state, const float* bhh, bool ghn_rc) {
   if (state && (!state->h0 || labels || stat_part)) return WGNN_ERR_UNSUPPORTED;   // (the state backward takes dY)
+  if (ghn_rc && (!x3 || io || state || !bhh)) return WGNN_ERR_UNSUPPORTED;         // (r | z records: api.hip ghn_recompute)
+  const int ksf = cdiv_i(H + 1, 32);               // the forward's K steps: the recomputed gh_n runs the forward's product
   // stat_part != null: loss and scales are finalised inside the kernel (once a separate one-block launch)
   const int nstat = grux_blocks(B);
   const float inv_n = stat_part ? 1.0f / (float)n_loss : 0.f, coef_in = stat_part ? 2.0f * grad_scale / (float)n_loss : 0.f;
@@ -857,17 +956,25 @@ int launch_grux_bwd(int B, int T, int H, const float* Whh, const void* Y, const 
   const double bt = (double)B * T;
   const double fl = bt * 2.0 * 3 * H * H,
                by = bt * ((io ? 2.0 + 4.0 : 4.0 + 4.0) * H + (x3 && write_lo ? 4.0 : 2.0) * (3 * H + H)) +
-                    gates_bytes(B, T, H, io, x3) + (x3 ? bt * 4.0 * H : 0.0);   // Y + labels in, planes out, stash (+ GI's n third) in
+                    gates_bytes(B, T, H, io, x3, ghn_rc) + (x3 ? bt * 4.0 * H : 0.0);   // Y + labels in, planes out, stash (+ GI's n third) in
   const dim3 grid(cdiv_i(B, MB));
 #define BLAUNCH(K, X3V, IOV, NAME, BYTES)                                                                         \
   PROF_LAUNCH(NAME, fl, BYTES, st,                                                                                \
-              if (state) hipLaunchKernelGGL((grux_bwd_kernel<K, X3V, IOV, BwdState>), grid, dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY, \
+              if (state) hipLaunchKernelGGL((grux_bwd_kernel<K, X3V, IOV, 0, BwdState>), grid, dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY, \
                                             labels, io, gates, GI, ldgi, scales, ih, il, ldd, nh, nl, stat_part, nstat, inv_n, coef_in, \
-                                            loss, scales_out, status, write_lo, *state);                                            \
-              else hipLaunchKernelGGL((grux_bwd_kernel<K, X3V, IOV>), grid, dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY, labels, io, \
-                                 gates, GI, ldgi, scales, ih, il, ldd, nh, nl, stat_part, nstat, inv_n, coef_in, loss, scales_out, status, write_lo))
+                                            loss, scales_out, status, write_lo, bhh, *state);                                       \
+              else hipLaunchKernelGGL((grux_bwd_kernel<K, X3V, IOV, 0>), grid, dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY, labels, io, \
+                                 gates, GI, ldgi, scales, ih, il, ldd, nh, nl, stat_part, nstat, inv_n, coef_in, loss, scales_out, status, write_lo, bhh))
+#define BLAUNCH_RC(K, KSFV)                                                                                       \
+  PROF_LAUNCH("grux_bwd_kernel<" #K ">", fl, by, st,                                                              \
+              hipLaunchKernelGGL((grux_bwd_kernel<K, true, false, KSFV>), grid, dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY, labels, \
+                                 io, gates, GI, ldgi, scales, ih, il, ldd, nh, nl, stat_part, nstat, inv_n, coef_in, loss, scales_out, \
+                                 status, write_lo, bhh))
 #define BCASE(K)                                                                                                  \
-  if (x3 && !io) BLAUNCH(K, true, false, "grux_bwd_kernel<" #K ">", by);                                          \
+  if (ghn_rc && ksf == ghn_ksf(K, false)) BLAUNCH_RC(K, ghn_ksf(K, false));                                       \
+  else if (ghn_rc && ksf == ghn_ksf(K, true)) BLAUNCH_RC(K, ghn_ksf(K, true));                                    \
+  else if (ghn_rc) return WGNN_ERR_UNSUPPORTED;                                                                   \
+  else if (x3 && !io) BLAUNCH(K, true, false, "grux_bwd_kernel<" #K ">", by);                                     \
   else if (x3) BLAUNCH(K, true, true, "grux_bwd_kernel<" #K ">", by);                                             \
   else if (!io) BLAUNCH(K, false, false, "grux_bwd_kernel<" #K ",f16>", by);                                      \
   else BLAUNCH(K, false, true, "grux_bwd_kernel<" #K ",f16>", by)
@@ -887,6 +994,7 @@ int launch_grux_bwd(int B, int T, int H, const float* Whh, const void* Y, const 
     default: return WGNN_ERR_UNSUPPORTED;
   }
 #undef BCASE
+#undef BLAUNCH_RC
 #undef BLAUNCH
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;
