@@ -704,9 +704,9 @@ _never(_keys("pgemm_nt_kernel<%d%s>|out16=0|narrow", [11, 12, 13, 14], ["", ",f1
        "the products with fp16 C or a single-plane A have N <= 13 S <= 832, which makes at most 9", 399, "d->S > 64")
 _never(_keys("pgemm_tn_kernel<%d%s>|a2=0|pw=1", [1, 2, 3], ["", ",x2", ",f16"]) + _keys("pgemm_tn_kernel<%d,x2>|a2=0|pw=0", [1, 2, 3]),
        "a per-window or single-plane product without the two-source A operand is dW_hh of the wide-GRU path: H + 1 >= 129 "
-       "columns, tiles of 4 to 7", 754, "hh.Ahi = dGHh")
+       "columns, tiles of 4 to 7", 773, "hh.Ahi = dGHh")
 _never(_keys("gemm32_tn_kernel<%d>|a2=1", [6, 7]),
-       "the two-source A operand is dW_hh's: H + 1 <= 129 columns, tiles of at most 5", 784, "launch_gemm32_tn(b.dGI")
+       "the two-source A operand is dW_hh's: H + 1 <= 129 columns, tiles of at most 5", 803, "launch_gemm32_tn(b.dGI")
 
 # Reachable, but only on the wide-GRU path at dims whose fp64 reference takes far longer than a test may: key -> dims
 # (S, T, B, H, math).  plan() confirms the dims; no GPU case.

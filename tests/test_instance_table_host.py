@@ -308,20 +308,29 @@ def test_series_plan_decides_where_the_sources_do():
     assert "L.small = !x3 && !L.gen_gru && !series && gru_small_supported(d->B, d->H);" in api
     assert "L.dghn = (x3 && !L.gen_gru) || (L.rec32 && L.g32tn);" in api
     assert "pl->front = wgnn_dims{1, sd->rows, sd->S," in series and "pl->rec = wgnn_dims{sd->n, sd->T, sd->S," in series
-    # the launch order of series_backward, and which layout each part runs on
-    bwd = _body(api, "int series_backward(")
-    order = ["launch_gru_bwd(dr->B, dr->T, dr->H", "bwd_weights(br, WGNN_ROWS_HH", "launch_series_fold(br.dGI",
+    # the launch order of series_bwd, and which layout each part runs on
+    bwd = _body(api, "int series_bwd(")
+    order = ["launch_gru_bwd(a, br.st)", "bwd_weights(br, WGNN_ROWS_HH", "launch_series_fold(br.dGI",
              "bwd_weights(bf, WGNN_ROWS_IH", "bwd_dg(bf)"]
     at = [bwd.find(x) for x in order]
     assert min(at) >= 0 and at == sorted(at), at
-    assert "Lr.dghn ? br.dGH : nullptr, Lr.dghn ? nullptr : br.dGH" in bwd
-    fwd = _body(api, "int series_forward(")
-    assert "fwd_front(f)" in fwd and "sr && Lr.g32tn ? sr + Lr.st_hprev : nullptr" in fwd
-    assert fwd.count("st, nullptr, nullptr, stride") == 2         # both launch_gru_fwd calls (last_only and Y) pass the stride
+    assert "a.B = dr->B; a.T = dr->T; a.H = dr->H;" in bwd[:at[0]]         # BPTT runs on the rec layout's dims
+    assert "a.dGHn = Lr.dghn ? br.dGH : nullptr; a.dGH = Lr.dghn ? nullptr : br.dGH;" in bwd
+    fwd = _body(api, "int series_fwd(")
+    assert "fwd_front(f)" in fwd and "a.hprev = sr && Lr.g32tn ? sr + Lr.st_hprev : nullptr;" in fwd
+    # both launch_gru_fwd calls (last_only and Y) pass the stride: the one request they share takes the caller's map first
+    go = [m.start() for m in re.finditer(re.escape("return launch_gru_fwd(a, f.st);"), fwd)]
+    assert fwd.count("launch_gru_fwd(") == 2 == len(go) and fwd.count("GruFwdArgs a") == 1
+    assert fwd.count("a.map = c.map;") == 1 and 0 <= fwd.find("a.map = c.map;") < go[0] and "a.map.stride" not in fwd
+    assert bwd.count("a.map = c.map;") == 1 and 0 <= bwd.find("a.map = c.map;") < at[0] and "a.map.stride" not in bwd
+    assert series.count("c.map.stride = sd->stride;") == 1 and "map.stride =" not in series.replace("c.map.stride = sd->stride;", "")
     # a non-zero stride selects the SeriesRows instances, under the window-major instances' names
-    assert gru.count("if (series_stride) hipLaunchKernelGGL((gru_fwd_kernel<K, false, SeriesRows>)") == 1
-    assert gru.count("if (series_stride) hipLaunchKernelGGL((gru_bwd_kernel<K, SeriesRows>)") == 1
+    assert gru.count("if (m.stride) gru_fwd_go<K, false>(a, st, SeriesRows{m.stride});") == 1
+    assert gru.count("if (m.stride) gru_bwd_go<K>(a, inv_n, coef, st, SeriesRows{m.stride});") == 1
+    assert gru.count("const SeriesMap& m = a.map;") == 2
     assert 'PROF_LAUNCH("gru_fwd_kernel<" #K ">"' in gru and 'PROF_LAUNCH("gru_bwd_kernel<" #K ">"' in gru
+    for d in ("fwd", "bwd"):                                       # ... and that name is the one the stride branch launches under
+        assert re.search(r'PROF_LAUNCH\("gru_%s_kernel<" #K ">", fl, by, st, +\\\n +if \(m\.stride\) gru_%s_go<K' % (d, d), gru), d
     assert 'PROF_LAUNCH("series_fold_kernel"' in series
     assert "if (sd->rows < 1 || sd->T < 1 || sd->stride < 1" in series         # no entry point passes a zero stride on
 

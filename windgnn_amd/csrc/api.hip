@@ -525,29 +525,38 @@ int fwd_recurrence(const Fwd& f) {
   float* hprev = (f.sf && (L.g32tn || c.sst)) ? f.sf + L.st_hprev : nullptr;   // [Hprev | 1 | 0..] rows for the dW_hh GEMM
   int rc;
   if (L.x3 && !L.gen_gru) {   // split fp16, W_hh in registers
-    if (c.last)
-      return launch_grux_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, c.last, nullptr, nullptr, f.full, f.status,
-                             nullptr, nullptr, 0, 1, y_mul, y_add, f.st);
+    GruxFwdArgs a = {};
+    a.B = d->B; a.T = d->T; a.H = d->H; a.GI = f.GI; a.ldgi = (int)L.Gp; a.Whh = p->w_hh; a.bhh = p->b_hh;
+    a.x3 = f.full; a.status = f.status;
+    if (c.last) {
+      a.Y = c.last; a.last_only = 1; a.y_mul = y_mul; a.y_add = y_add;
+      return launch_grux_fwd(a, f.st);
+    }
+    a.io = d->io; a.h0 = c.h0;
     if (c.state) {
       const int lo = hn_only && d->io == WGNN_IO_F32;
-      return launch_grux_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, lo ? (void*)c.hn : f.Y, nullptr, nullptr,
-                             f.full, f.status, nullptr, nullptr, d->io, lo, 1.f, 0.f, f.st, c.h0, lo ? nullptr : c.hn);
+      a.Y = lo ? (void*)c.hn : f.Y; a.last_only = lo; a.hn = lo ? nullptr : c.hn;
+      return launch_grux_fwd(a, f.st);
     }
-    rc = launch_grux_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, f.Y, f.gates,   // (no Y planes for a dW_hh from Y)
-                         f.sf && !hh_from_y(d, L.tn_merge, c.sst) ? f.sf + L.st_yp : nullptr, f.full, f.status, labels, stats,
-                         d->io, 0, 1.f, 0.f, f.st, c.h0, c.hn, c.sst ? L.plane_rows : 0, L.ghn_rc);
-  } else if (L.rec32) {       // exact fp32, W_hh in registers
-    if (c.last)
-      return launch_gru_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, c.last, nullptr, nullptr, nullptr, nullptr, 0,
-                            1, y_mul, y_add, f.st);
-    if (c.state)
-      return launch_gru_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, hn_only ? c.hn : Y, nullptr, nullptr, nullptr,
-                            nullptr, 0, hn_only ? 1 : 0, 1.f, 0.f, f.st, c.h0, hn_only ? nullptr : c.hn);
-    rc = launch_gru_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, Y, f.gates, (const float*)labels, stats, hprev,
-                        L.hq, 0, 1.f, 0.f, f.st, c.h0, c.hn);
-  } else if (L.small) {       // few windows: one per workgroup instead of sixteen
-    rc = launch_gru_small_fwd(d->B, d->T, d->H, f.GI, (int)L.Gp, p->w_hh, p->b_hh, Y, f.gates, hprev, L.hq,
-                              (const float*)labels, stats, f.st, c.h0, c.hn);
+    a.Y = f.Y; a.hn = c.hn; a.gates = f.gates; a.labels = labels; a.stat_part = stats;
+    a.y_planes = f.sf && !hh_from_y(d, L.tn_merge, c.sst) ? f.sf + L.st_yp : nullptr;   // (no Y planes for a dW_hh from Y)
+    a.plane_rows = c.sst ? L.plane_rows : 0; a.ghn_rc = L.ghn_rc;
+    rc = launch_grux_fwd(a, f.st);
+  } else if (L.rec32 || L.small) {   // exact fp32, W_hh in registers
+    GruFwdArgs a = {};
+    a.B = d->B; a.T = d->T; a.H = d->H; a.GI = f.GI; a.ldgi = (int)L.Gp; a.Whh = p->w_hh; a.bhh = p->b_hh;
+    if (L.rec32 && c.last) {
+      a.Y = c.last; a.last_only = 1; a.y_mul = y_mul; a.y_add = y_add;
+      return launch_gru_fwd(a, f.st);
+    }
+    a.h0 = c.h0;
+    if (L.rec32 && c.state) {
+      a.Y = hn_only ? c.hn : Y; a.last_only = hn_only ? 1 : 0; a.hn = hn_only ? nullptr : c.hn;
+      return launch_gru_fwd(a, f.st);
+    }
+    a.Y = Y; a.hn = c.hn; a.gates = f.gates; a.labels = (const float*)labels; a.stat_part = stats; a.hprev = hprev; a.hq = L.hq;
+    // few windows (L.small): one per workgroup instead of sixteen
+    rc = L.rec32 ? launch_gru_fwd(a, f.st) : launch_gru_small_fwd(a, f.st);
   } else if (L.x3) {          // any hidden width: one plane GEMM per step against split(W_hh | b_hh)
     rc = launch_split_weight2(p->w_hh, (int)L.G3, (int)L.H, 0, p->b_hh, (int)L.H, f.ws + L.ws_hhp_f, L.np_g3, (int)L.Hp,
                               f.status, f.st);
@@ -705,22 +714,32 @@ int bwd_rec(const Bwd& b) {
       return launch_gru_gen_bwd_x3(d->B, d->T, d->H, b.ws + L.ws_hhp_b, L.np_h, b.Y, dY, gates, b.scales, b.dGI, b.dGH,
                                    (int)L.Gp, b.ws + L.ws_dhz, b.ws + L.ws_dhw, b.ws + L.ws_kp_b, b.ws + L.ws_dc, b.full, b.st, sb);
     }
-    return launch_grux_bwd(d->B, d->T, d->H, p->w_hh, c.Y, b.fused_loss ? nullptr : dY, b.fused_loss ? c.labels : nullptr,
-                           d->io, gates, L.gi_stash ? b.sf + L.st_GI : nullptr, (int)L.Gp, b.scales, b.dGI, b.dGH, (int)L.Gp,
-                           b.full, stats, (int64_t)L.BT * L.H, c.grad_scale, c.loss, b.scales, b.status, L.dgi1 ? 0 : 1, b.st,
-                           sb, p->b_hh, L.ghn_rc);
+    GruxBwdArgs a = {};
+    a.B = d->B; a.T = d->T; a.H = d->H; a.Whh = p->w_hh; a.Y = c.Y; a.io = d->io; a.gates = gates;
+    a.dY = b.fused_loss ? nullptr : dY; a.labels = b.fused_loss ? c.labels : nullptr;
+    a.GI = L.gi_stash ? b.sf + L.st_GI : nullptr; a.ldgi = (int)L.Gp;
+    a.scales = b.scales; a.dGI_planes = b.dGI; a.dGHn_planes = b.dGH; a.ldd = (int)L.Gp; a.x3 = b.full;
+    a.stat_part = stats; a.n_loss = (int64_t)L.BT * L.H; a.grad_scale = c.grad_scale; a.loss = c.loss; a.scales_out = b.scales;
+    a.status = b.status; a.write_lo = L.dgi1 ? 0 : 1; a.state = sb; a.bhh = p->b_hh; a.ghn_rc = L.ghn_rc;
+    return launch_grux_bwd(a, b.st);
   }
   if (L.gen_gru)
     return launch_gru_gen_bwd(d->B, d->T, d->H, p->w_hh, b.Y, dY, gates, b.dGI, b.dGH, (int)L.Gp, b.ws + L.ws_dhz,
                               b.ws + L.ws_dhw, b.st, sb);
-  if (L.small)
-    return launch_gru_small_bwd(d->B, d->T, d->H, p->w_hh, b.Y, b.fused_loss ? nullptr : dY, b.fused_loss ? labels : nullptr,
-                                gates, b.dGI, b.dGH, (int)L.Gp, stats, (int64_t)L.BT * L.H, c.grad_scale, c.loss, b.status,
-                                b.st, sb);
+  GruBwdArgs a = {};
+  a.B = d->B; a.T = d->T; a.H = d->H; a.Whh = p->w_hh; a.Y = b.Y; a.gates = gates;
+  a.dY = b.fused_loss ? nullptr : dY; a.labels = b.fused_loss ? labels : nullptr;
+  a.dGI = b.dGI; a.ldd = (int)L.Gp;
+  a.stat_part = stats; a.n_loss = (int64_t)L.BT * L.H; a.grad_scale = c.grad_scale; a.loss = c.loss; a.status = b.status;
+  a.state = sb;
+  if (L.small) {
+    a.dGH = b.dGH;
+    return launch_gru_small_bwd(a, b.st);
+  }
   // register-resident recurrence: dGHn alone when the dW_hh GEMM has the two-source A operand; fused loss
-  return launch_gru_bwd(d->B, d->T, d->H, p->w_hh, b.Y, b.fused_loss ? nullptr : dY, b.fused_loss ? labels : nullptr, gates,
-                        b.sf + L.st_GI, (int)L.Gp, b.dGI, (int)L.Gp, L.dghn ? b.dGH : nullptr, L.dghn ? nullptr : b.dGH, stats,
-                        (int64_t)L.BT * L.H, c.grad_scale, c.loss, b.status, b.st, sb);
+  a.GI = b.sf + L.st_GI; a.ldgi = (int)L.Gp;
+  a.dGHn = L.dghn ? b.dGH : nullptr; a.dGH = L.dghn ? nullptr : b.dGH;
+  return launch_gru_bwd(a, b.st);
 }
 
 // Part 4: dW_hh | db_hh = dGH^T [Hprev | 1] and dW_ih | db_ih = dGI^T [g | 1] (prods: WGNN_ROWS_HH | WGNN_ROWS_IH, in that
@@ -982,59 +1001,65 @@ int series_plan(const wgnn_dims* df, const wgnn_dims* dr, SeriesPlan* sp) {
   return WGNN_OK;
 }
 
-namespace {
-
 // Ls / loss_buf (wgnn_series_fwd_loss, both or neither): the recurrence also reads the label series and leaves the MSE partial
-// pairs and the tag in loss_buf; Y and the stash are the same either way.  starts (with stride = 0; include/windgnn_series_at.h):
-// window w begins at row starts[w], clamped into [0, rows - T], instead of w * stride -- the recurrence is the only reader
-int series_forward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
-                   float* Y, float* last, float wind_min, float wind_max, void* stash, void* workspace, const SeriesPlan& sp,
-                   void* stream, const float* Ls, int64_t ls_rows, float* loss_buf, const int* starts, bool masked = false,
-                   const LossFn* lossfn = nullptr) {
-  const int last_start = df->T - dr->T;        // the largest legal start: rows - T
-  const Layout Lf = make_layout(df, false, SER_FRONT), Lr = make_layout(dr, false, SER_REC);
-  FwdCall cf(workspace, sizeof(float) * sp.ws_front, stream);
-  cf.A = A; cf.X = Xs; cf.p = p; cf.stash = stash;
+// pairs and the tag in loss_buf; Y and the stash are the same either way.  map.starts (with stride = 0; include/windgnn_series_at.h):
+// window w begins at row starts[w], clamped into [0, rows - T], instead of w * stride -- the recurrence is the only reader.
+// last with Ls (include/windgnn_series_val.h): a forward alone, nothing is kept
+int series_fwd(const SeriesCall& c) {
+  const wgnn_dims *df = c.front, *dr = c.rec;
+  const wgnn_params* p = c.p;
+  const Layout Lf = make_layout(df, false, SER_FRONT);
+  FwdCall cf(c.workspace, sizeof(float) * (c.last && c.Ls ? c.sp.ws_front_fwd : c.sp.ws_front), c.stream);
+  cf.A = c.A; cf.X = c.Xs; cf.p = p; cf.stash = c.stash;
   const Fwd f{df, cf, Lf};
-  int rc = fwd_front(f);                 // g_s and GI_s, once per hour (into the stash if there is one)
+  int rc = fwd_front(f);                 // g_s and GI_s, once per hour (into the stash if there is one, else the workspace)
   if (rc != WGNN_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const int ld = (int)Lf.Gp;
-  if (last)
-    return launch_gru_fwd(dr->B, dr->T, dr->H, f.GI, ld, p->w_hh, p->b_hh, last, nullptr, nullptr, nullptr, nullptr, 0, 1,
-                          wind_max - wind_min, wind_min, st, nullptr, nullptr, stride, 0, starts, last_start);
-  float* sr = stash ? (float*)stash + sp.st_front : nullptr;
-  return launch_gru_fwd(dr->B, dr->T, dr->H, f.GI, ld, p->w_hh, p->b_hh, Y, sr ? sr + Lr.st_gates : nullptr, Ls, loss_buf,
-                        sr && Lr.g32tn ? sr + Lr.st_hprev : nullptr, Lr.hq, 0, 1.f, 0.f, st, nullptr, nullptr, stride, ls_rows,
-                        starts, last_start, masked, lossfn);
+  GruFwdArgs a = {};
+  a.B = dr->B; a.T = dr->T; a.H = dr->H; a.GI = f.GI; a.ldgi = (int)Lf.Gp; a.Whh = p->w_hh; a.bhh = p->b_hh;
+  a.map = c.map;
+  a.map.starts_last = df->T - dr->T;     // the largest legal start: rows - T
+  a.labels = c.Ls; a.stat_part = c.loss_buf; a.masked = c.masked; a.lossfn = c.lossfn;
+  if (c.last) {
+    a.Y = c.last; a.last_only = 1; a.y_mul = c.wind_max - c.wind_min; a.y_add = c.wind_min;
+    return launch_gru_fwd(a, f.st);
+  }
+  const Layout Lr = make_layout(dr, false, SER_REC);
+  float* sr = c.stash ? (float*)c.stash + c.sp.st_front : nullptr;
+  a.Y = c.Y; a.gates = sr ? sr + Lr.st_gates : nullptr;
+  a.hprev = sr && Lr.g32tn ? sr + Lr.st_hprev : nullptr; a.hq = Lr.hq;
+  return launch_gru_fwd(a, f.st);
 }
 
 // dY, or Ls with the forward's loss_buf (wgnn_series_bwd_mse): BPTT forms dY = (Y - label) 2 grad_scale / (n T H) itself and its
 // workgroup 0 finalises loss[0]; a missing tag sets WGNN_STATUS_NO_LOSS_STATS in the rec half's status block
-int series_backward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
-                    const float* Y, const float* dY, const void* stash, const wgnn_grads* g, void* workspace, const SeriesPlan& sp,
-                    void* stream, const float* Ls, int64_t ls_rows, float grad_scale, const float* loss_buf, float* loss,
-                    const int* starts, bool masked = false, const LossFn* lossfn = nullptr) {
+int series_bwd(const SeriesCall& c) {
+  const wgnn_dims *df = c.front, *dr = c.rec;
   const Layout Lf = make_layout(df, false, SER_FRONT), Lr = make_layout(dr, false, SER_REC);
-  const float* sff = (const float*)stash;
-  BwdCall cr((float*)workspace + sp.ws_front, sizeof(float) * sp.ws_rec, stream);
-  cr.p = p; cr.Y = Y; cr.dY = dY; cr.stash = sff + sp.st_front; cr.g = g; cr.part = 7;
+  const float* sff = (const float*)c.stash;
+  BwdCall cr((float*)c.workspace + c.sp.ws_front, sizeof(float) * c.sp.ws_rec, c.stream);
+  cr.p = c.p; cr.Y = c.Y; cr.dY = c.dY; cr.stash = sff + c.sp.st_front; cr.g = c.grads; cr.part = 7;
   const Bwd br{dr, cr, Lr};
-  BwdCall cf(workspace, sizeof(float) * sp.ws_front, stream);
-  cf.A = A; cf.X = Xs; cf.p = p; cf.Y = Y; cf.dY = dY; cf.stash = stash; cf.g = g; cf.part = 7;
+  BwdCall cf(c.workspace, sizeof(float) * c.sp.ws_front, c.stream);
+  cf.A = c.A; cf.X = c.Xs; cf.p = c.p; cf.Y = c.Y; cf.dY = c.dY; cf.stash = c.stash; cf.g = c.grads; cf.part = 7;
   const Bwd bf{df, cf, Lf};
   // 1. BPTT per window: n is recomputed from GI_s rows w * stride + t; dGI / dGHn (or dGH) come out window-major
-  int rc = launch_gru_bwd(dr->B, dr->T, dr->H, p->w_hh, Y, dY, Ls, br.sf + Lr.st_gates, sff + Lf.st_GI, (int)Lf.Gp, br.dGI,
-                          (int)Lr.Gp, Lr.dghn ? br.dGH : nullptr, Lr.dghn ? nullptr : br.dGH, loss_buf, (int64_t)Lr.BT * Lr.H,
-                          grad_scale, loss, Ls ? br.status : nullptr, br.st, nullptr, stride, ls_rows, starts,
-                          df->T - dr->T, masked, lossfn);
+  GruBwdArgs a = {};
+  a.B = dr->B; a.T = dr->T; a.H = dr->H; a.Whh = c.p->w_hh; a.Y = c.Y; a.dY = c.dY; a.labels = c.Ls;
+  a.gates = br.sf + Lr.st_gates; a.GI = sff + Lf.st_GI; a.ldgi = (int)Lf.Gp; a.dGI = br.dGI; a.ldd = (int)Lr.Gp;
+  a.dGHn = Lr.dghn ? br.dGH : nullptr; a.dGH = Lr.dghn ? nullptr : br.dGH;
+  a.stat_part = c.loss_buf; a.n_loss = (int64_t)Lr.BT * Lr.H; a.grad_scale = c.grad_scale; a.loss = c.loss;
+  a.status = c.Ls ? br.status : nullptr;
+  a.map = c.map;
+  a.map.starts_last = df->T - dr->T;
+  a.masked = c.masked; a.lossfn = c.lossfn;
+  int rc = launch_gru_bwd(a, br.st);
   if (rc != WGNN_OK) return rc;
   // 2. dW_hh | db_hh over the n * T window-major rows
   rc = bwd_weights(br, WGNN_ROWS_HH, 0, (int)Lr.G3);
   if (rc != WGNN_OK) return rc;
   // 3. dGI_s[tau] = sum over the windows that cover tau
-  rc = starts ? launch_series_fold_at(br.dGI, starts, dr->B, dr->T, df->T, (int)Lf.G3, (int)Lf.Gp, bf.dGI, bf.st)
-              : launch_series_fold(br.dGI, dr->B, dr->T, stride, df->T, (int)Lf.G3, (int)Lf.Gp, bf.dGI, bf.st);
+  rc = c.map.starts ? launch_series_fold_at(br.dGI, c.map.starts, dr->B, dr->T, df->T, (int)Lf.G3, (int)Lf.Gp, bf.dGI, bf.st)
+                    : launch_series_fold(br.dGI, dr->B, dr->T, c.map.stride, df->T, (int)Lf.G3, (int)Lf.Gp, bf.dGI, bf.st);
   if (rc != WGNN_OK) return rc;
   // 4. + 5. dW_ih | db_ih, dg and the GCN backward over the `rows` hours, each with its reduction
   rc = bwd_weights(bf, WGNN_ROWS_IH, 0, (int)Lf.G3);
@@ -1042,53 +1067,8 @@ int series_backward(const wgnn_dims* df, const wgnn_dims* dr, int stride, const 
   return bwd_dg(bf);
 }
 
-}  // namespace
-
-int series_fwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
-               float* Y, float* last, float wind_min, float wind_max, void* stash, void* workspace, const SeriesPlan& sp,
-               void* stream, const int* starts) {
-  return series_forward(df, dr, stride, A, Xs, p, Y, last, wind_min, wind_max, stash, workspace, sp, stream, nullptr, 0, nullptr,
-                        starts);
-}
-
-int series_bwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
-               const float* Y, const float* dY, const void* stash, const wgnn_grads* g, void* workspace, const SeriesPlan& sp,
-               void* stream, const int* starts) {
-  return series_backward(df, dr, stride, A, Xs, p, Y, dY, stash, g, workspace, sp, stream, nullptr, 0, 1.f, nullptr, nullptr,
-                         starts);
-}
-
 size_t series_loss_floats(int n) { return 2 * (size_t)gru_blocks(n) + 4; }   // pairs, tag, 3 spare words (as Layout::st_stats)
 size_t series_masked_loss_floats(int n) { return series_loss_floats(n) + (size_t)gru_blocks(n); }   // + the label counts
-
-int series_fwd_loss(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
-                    const float* Ls, int64_t ls_rows, float* Y, void* stash, float* loss_buf, void* workspace,
-                    const SeriesPlan& sp, void* stream, const int* starts, bool masked, const LossFn* lossfn) {
-  return series_forward(df, dr, stride, A, Xs, p, Y, nullptr, 0.f, 1.f, stash, workspace, sp, stream, Ls, ls_rows, loss_buf,
-                        starts, masked, lossfn);
-}
-
-int series_bwd_mse(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
-                   const float* Y, const float* Ls, int64_t ls_rows, float grad_scale, const void* stash, const float* loss_buf,
-                   float* loss, const wgnn_grads* g, void* workspace, const SeriesPlan& sp, void* stream, const int* starts,
-                   bool masked, const LossFn* lossfn) {
-  return series_backward(df, dr, stride, A, Xs, p, Y, nullptr, stash, g, workspace, sp, stream, Ls, ls_rows, grad_scale, loss_buf,
-                         loss, starts, masked, lossfn);
-}
-
-int series_val_fwd(const wgnn_dims* df, const wgnn_dims* dr, int stride, const float* A, const float* Xs, const wgnn_params* p,
-                   const float* Ls, int64_t ls_rows, float* last, float wind_min, float wind_max, float* loss_buf,
-                   void* workspace, const SeriesPlan& sp, void* stream, const int* starts, const LossFn* lossfn) {
-  const Layout Lf = make_layout(df, false, SER_FRONT);
-  FwdCall cf(workspace, sizeof(float) * sp.ws_front_fwd, stream);
-  cf.A = A; cf.X = Xs; cf.p = p;
-  const Fwd f{df, cf, Lf};
-  int rc = fwd_front(f);                 // g_s and GI_s in the workspace: nothing is kept
-  if (rc != WGNN_OK) return rc;
-  return launch_gru_fwd(dr->B, dr->T, dr->H, f.GI, (int)Lf.Gp, p->w_hh, p->b_hh, last, nullptr, Ls, loss_buf, nullptr, 0, 1,
-                        wind_max - wind_min, wind_min, (hipStream_t)stream, nullptr, nullptr, stride, ls_rows, starts,
-                        df->T - dr->T, false, lossfn);
-}
 
 extern "C" {
 

@@ -156,28 +156,45 @@ int launch_amax_scale(const float* x, int64_t n, float* scales, float* part /*>=
 bool grux_shape_supported(int H);
 int grux_hp(int H);   // row width (halfs) of the Y planes: 32*ceil((H+1)/32)
 size_t grux_gates_floats(int B, int T, int H, int io);   // gate stash of the register-resident recurrences (their own layout)
-int launch_grux_fwd(int B, int T, int H, const void* GI /*fp32 rows if x3, else fp16 rows*/, int ldgi, const float* Whh, const float* bhh, void* Y,
-                    float* gates, void* y_planes, bool x3, unsigned* status, const void* labels, float* stat_part,
-                    int io /*wgnn_io of Y and labels*/, int last_only, float y_mul, float y_add, hipStream_t st,
-                    const float* h0 = nullptr /*[B][H] initial state (wgnn_fwd_state)*/,
-                    float* hn = nullptr /*[B][H] fp32 h_{T-1}; Y may then be NULL with 16-bit I/O*/,
-                    size_t plane_rows = 0 /*rows per y plane: 0 = B*T + 1 (wgnn_stash_bytes' layout)*/,
-                    bool ghn_rc = false /*ghn_recompute(): the gate records are r | z (x3, fp32 I/O, no state)*/);
+// Request of launch_grux_fwd; zero-initialise (GruxFwdArgs a = {};) and assign what the call needs
+struct GruxFwdArgs {
+  int B, T, H;
+  const void* GI; int ldgi;              // fp32 rows if x3, else fp16 rows
+  const float *Whh, *bhh;
+  void* Y; int io;                       // wgnn_io of Y and labels; Y may be NULL with 16-bit I/O and hn (h_n alone)
+  float* gates; void* y_planes;          // nullable: grux_gates_floats() of stash, 2 x [plane_rows][grux_hp(H)] halfs
+  size_t plane_rows;                     // rows per y plane: 0 = B*T + 1 (wgnn_stash_bytes' layout; the state stash: B*T + B)
+  bool x3; unsigned* status;
+  const void* labels; float* stat_part;  // nullable: 2 * grux_blocks(B) MSE partials of (Y - labels)
+  int last_only;                         // Y is [B][H]: only h_{T-1} * y_mul + y_add is written (fp32 I/O, no stash, no labels)
+  float y_mul = 1.f, y_add = 0.f;
+  const float* h0; float* hn;            // [B][H] initial state (wgnn_fwd_state), [B][H] fp32 h_{T-1}
+  bool ghn_rc;                           // ghn_recompute(): the gate records are r | z (x3, fp32 I/O, no state)
+};
+int launch_grux_fwd(const GruxFwdArgs& a, hipStream_t st);
 int grux_blocks(int B);   // workgroups of launch_grux_fwd = MSE partial pairs it writes when given labels
 int mse_stats_blocks();
-// exactly one of dY / labels is non-null (labels: dY = (Y - labels) * scales[2], see launch_mse_stats)
-// dGI planes [B*T][ldd] (3H layout) and the n third of dGH alone, dGHn planes [B*T][grux_hn(H)] (dGH's r and z thirds equal dGI's)
 int grux_hn(int H);       // row width (halfs) of the dGHn planes: 8*ceil(H/8)
 int grux_msplit(int H);   // 8*ceil(2H/8): first GEMM row of the dGHn block in the dW_hh product
-// stat_part != null (the partial pairs + tag wgnn_fwd_loss left in the stash): loss[0], scales_out[0..2] are finalised inside
-// the kernel (n_loss = B*T*H, grad_scale as in wgnn_bwd_mse_part); a missing tag gives loss = NaN + WGNN_STATUS_NO_LOSS_STATS
-int launch_grux_bwd(int B, int T, int H, const float* Whh, const void* Y, const float* dY, const void* labels, int io,
-                    const float* gates, const float* GI /*split modes: the forward's GI rows (stash), n recomputed*/, int ldgi,
-                    const float* scales, void* dGI_planes, void* dGHn_planes, int ldd, bool x3, const float* stat_part,
-                    int64_t n_loss, float grad_scale, float* loss, float* scales_out, unsigned* status,
-                    int write_lo /*0: dGI / dGHn as one fp16 plane (x3 only)*/, hipStream_t st,
-                    const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given, no labels*/,
-                    const float* bhh = nullptr, bool ghn_rc = false /*ghn_recompute(): r | z records, gh_n from Y, W_hh and bhh*/);
+// Request of launch_grux_bwd
+struct GruxBwdArgs {
+  int B, T, H;
+  const float* Whh; const void* Y; int io;
+  const float* dY; const void* labels;   // exactly one (labels: dY = (Y - labels) * scales[2], see launch_mse_stats)
+  const float* gates;
+  const float* GI; int ldgi;             // split modes: the forward's GI rows [B*T][ldgi] fp32 (stash), n recomputed
+  const float* scales;
+  void *dGI_planes, *dGHn_planes;        // [B*T][ldd] (3H layout), and the n third of dGH alone [B*T][grux_hn(H)] (its r and z
+  int ldd, write_lo;                     //   thirds equal dGI's); write_lo = 0: each as one fp16 plane (x3 only)
+  bool x3;
+  // stat_part != null (the partial pairs + tag wgnn_fwd_loss left in the stash): loss[0], scales_out[0..2] are finalised inside
+  // the kernel (n_loss = B*T*H, grad_scale as in wgnn_bwd_mse_part); a missing tag gives loss = NaN + WGNN_STATUS_NO_LOSS_STATS
+  const float* stat_part; int64_t n_loss; float grad_scale;
+  float *loss, *scales_out; unsigned* status;
+  const BwdState* state;                 // wgnn_bwd_state_part: dY given, no labels
+  const float* bhh; bool ghn_rc;         // ghn_recompute(): r | z records, gh_n from Y, W_hh and bhh
+};
+int launch_grux_bwd(const GruxBwdArgs& a, hipStream_t st);
 #define WGNN_STATS_TAG 20261004.0f   // float word behind the MSE partial pairs: "wgnn_fwd_loss wrote these"
 #define WGNN_STATS_TAG_MASKED 20261019.0f   // the same word from wgnn_series_fwd_loss_masked: sums over the labels that exist
 // a third value from wgnn_series_fwd_lossfn (fp32 spacing is 2 up here: 20261019 IS 20261020), which also fills the three spare
@@ -330,29 +347,46 @@ int launch_gcn1_bwd(int ntiles, int S, const float* A, const float* X, const flo
                     const float* out, const float* dout, float* dW, float* db, float* dX,
                     float* partial, hipStream_t st);
 
-// exact-fp32 recurrences with register-resident W_hh (gru.hip), H <= 128
-//   forward: gates (nullable) = gru_gates_floats() floats of stash in the kernels' own layout; labels + stat_part (nullable):
-//   2 * gru_blocks(B) MSE partials + a tag word; hprev (nullable): [B*T][hq] rows [h_{t-1} | 1 | 0..] for the dW_hh GEMM;
-//   last_only: Y is [B][H] and receives only h_{T-1} * y_mul + y_add (no gates, no hprev; labels with a lossfn alone)
-int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
-                   float* gates, const float* labels, float* stat_part, float* hprev, int hq, int last_only, float y_mul,
-                   float y_add, hipStream_t st, const float* h0 = nullptr, float* hn = nullptr,
-                   int series_stride = 0 /*> 0: GI is one series [rows][ldgi], window w at rows w * stride + t (no h0)*/,
-                   int64_t ls_rows = 0 /*series with labels: they are one series too, Ls [ls_rows][H], read at the same rows*/,
-                   const int* starts = nullptr /*instead of a stride: window w at rows clamp(starts[w], 0, starts_last) + t*/,
-                   int starts_last = 0, bool masked = false /*series with labels: NaN = no label, counts behind stat_part*/,
-                   const LossFn* lossfn = nullptr /*series with labels: the spec's statistics, counts, tag and spare words*/);
-//   backward: exactly one of dY / labels; dGI [B*T][ldd] and EITHER dGHn [B*T][gru_hn(H)] (dGH's r and z thirds equal
-//   dGI's) OR the full dGH [B*T][ldd]; stat_part (nullable, with labels): loss[0] is finalised from the forward's partials
-int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
-                   const float* gates, const float* GI /*forward's GI rows (stash): n is recomputed*/, int ldgi, float* dGI, int ldd, float* dGHn, float* dGH, const float* stat_part,
-                   int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st,
-                   const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given*/,
-                   int series_stride = 0 /*> 0: GI is one series, as in launch_gru_fwd (no state)*/,
-                   int64_t ls_rows = 0 /*series with labels: Ls [ls_rows][H], as in launch_gru_fwd*/,
-                   const int* starts = nullptr /*instead of a stride, as in launch_gru_fwd*/, int starts_last = 0,
-                   bool masked = false /*as in launch_gru_fwd: n_loss is then the forward's count, summed in the kernel*/,
-                   const LossFn* lossfn = nullptr /*as in launch_gru_fwd: n_loss is then B (T - t_from) H, or the count*/);
+// Row mapping of a series recurrence (include/windgnn_series.h); all zero: window-major GI and labels
+struct SeriesMap {
+  int stride;                            // > 0: GI is one series [rows][ldgi], window w at rows w * stride + t (no h0 / hn, no state)
+  const int* starts; int starts_last;    // instead of a stride: window w at rows clamp(starts[w], 0, starts_last) + t
+  int64_t ls_rows;                       // series with labels: they are one series too, Ls [ls_rows][H], read at the same rows
+};
+// exact-fp32 recurrences with register-resident W_hh (gru.hip), H <= 128, and gru_small.hip's (below)
+// Request of launch_gru_fwd / launch_gru_small_fwd; zero-initialise (GruFwdArgs a = {};) and assign what the call needs
+struct GruFwdArgs {
+  int B, T, H;
+  const float* GI; int ldgi;
+  const float *Whh, *bhh;
+  float* Y;
+  float* gates;                          // nullable: gru_gates_floats() floats of stash in the kernels' own layout
+  const float* labels; float* stat_part; // nullable: 2 * gru_blocks(B) (gru_small_blocks(B)) MSE partials + a tag word
+  float* hprev; int hq;                  // nullable: [B*T][hq] rows [h_{t-1} | 1 | 0..] for the dW_hh GEMM
+  int last_only;                         // Y is [B][H] and receives only h_{T-1} * y_mul + y_add (no gates, no hprev; labels with a lossfn alone)
+  float y_mul = 1.f, y_add = 0.f;
+  const float* h0; float* hn;            // [B][H] initial state (wgnn_fwd_state), [B][H] h_{T-1}
+  SeriesMap map;
+  bool masked;                           // series with labels: NaN = no label, counts behind stat_part
+  const LossFn* lossfn;                  // series with labels: the spec's statistics, counts, tag and spare words
+};
+int launch_gru_fwd(const GruFwdArgs& a, hipStream_t st);
+// Request of launch_gru_bwd / launch_gru_small_bwd
+struct GruBwdArgs {
+  int B, T, H;
+  const float *Whh, *Y;
+  const float *dY, *labels;              // exactly one (labels: dY is formed in the kernel)
+  const float* gates;
+  const float* GI; int ldgi;             // the forward's GI rows [B*T][ldgi] (stash): n is recomputed (gru_small: unread)
+  float* dGI; int ldd;                   // [B*T][ldd]
+  float *dGHn, *dGH;                     // EITHER dGHn [B*T][gru_hn(H)] (dGH's r and z thirds equal dGI's; not gru_small) OR the full dGH [B*T][ldd]
+  const float* stat_part;                // nullable, with labels: loss[0] is finalised from the forward's partials
+  int64_t n_loss;                        // masked: the forward's count, summed in the kernel; lossfn: B (T - t_from) H, or the count
+  float grad_scale; float* loss; unsigned* status;
+  const BwdState* state;                 // wgnn_bwd_state_part: dY given
+  SeriesMap map; bool masked; const LossFn* lossfn;   // as in GruFwdArgs (no state)
+};
+int launch_gru_bwd(const GruBwdArgs& a, hipStream_t st);
 bool gru_shape_supported(int H);
 size_t gru_gates_floats(int B, int T, int H);
 int gru_blocks(int B);
@@ -360,16 +394,10 @@ int gru_hn(int H);
 int gru_msplit(int H);
 // small batches (B <= 768, H <= 128), exact fp32, one window per workgroup with W_hh in registers (gru_small.hip)
 bool gru_small_supported(int B, int H);
-int launch_gru_small_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
-                         float* gates, float* hprev /*nullable: [B*T][hq] rows [h_{t-1} | 1 | 0..]*/, int hq,
-                         const float* labels /*nullable*/, float* stat_part /*2 * gru_small_blocks(B) + 1 floats*/,
-                         hipStream_t st, const float* h0 = nullptr, float* hn = nullptr);
+// no kernel for a series map, masked, lossfn or last_only (nor, backward, for dGHn): WGNN_ERR_UNSUPPORTED
+int launch_gru_small_fwd(const GruFwdArgs& a, hipStream_t st);
 int gru_small_blocks(int B);
-// exactly one of dY / labels (labels: dY formed in the kernel, loss finalised from stat_part as launch_gru_bwd)
-int launch_gru_small_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
-                         const float* gates, float* dGI, float* dGH, int ldd, const float* stat_part, int64_t n_loss,
-                         float grad_scale, float* loss, unsigned* status, hipStream_t st,
-                         const BwdState* state = nullptr /*wgnn_bwd_state_part: dY given*/);
+int launch_gru_small_bwd(const GruBwdArgs& a, hipStream_t st);
 
 // ---- series mode (include/windgnn_series.h): series.hip holds the entry points, their validation and the fold kernel;
 // api.hip runs the launches on two of its layouts -- front: dims {B = 1, T = rows}, rec: dims {B = n, T} (float counts below)
@@ -387,29 +415,29 @@ struct SeriesPlan {
   size_t st_g, st_GI, st_gates, st_hprev;   // what the stash holds, unpadded: g_s, GI_s | gate records, [Hprev | 1] rows
 };
 int series_plan(const wgnn_dims* front, const wgnn_dims* rec, SeriesPlan* sp);   // check_dims of both + the sizes
-int series_fwd(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs, const wgnn_params* p,
-               float* Y, float* last /*one of Y / last*/, float wind_min, float wind_max, void* stash /*nullable*/,
-               void* workspace, const SeriesPlan& sp, void* stream, const int* starts = nullptr /*stride = 0: the table*/);
-int series_bwd(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs, const wgnn_params* p,
-               const float* Y, const float* dY, const void* stash, const wgnn_grads* g, void* workspace, const SeriesPlan& sp,
-               void* stream, const int* starts = nullptr);
-// include/windgnn_series_train.h (series_train.hip validates): the same two sequences with the labels as a series Ls [ls_rows][H]
-// in the recurrences; loss_buf = 2 * gru_blocks(n) partials (sum | max) + the tag word, series_loss_floats(n) floats in all
+// loss_buf (include/windgnn_series_train.h): 2 * gru_blocks(n) partials (sum | max) + the tag word + 3 spare words
 size_t series_loss_floats(int n);
 size_t series_masked_loss_floats(int n);   // + gru_blocks(n) label counts (include/windgnn_series_masked.h)
-int series_fwd_loss(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs,
-                    const wgnn_params* p, const float* Ls, int64_t ls_rows, float* Y, void* stash /*nullable*/, float* loss_buf,
-                    void* workspace, const SeriesPlan& sp, void* stream, const int* starts = nullptr, bool masked = false,
-                    const LossFn* lossfn = nullptr /*include/windgnn_series_lossfn.h*/);
-int series_bwd_mse(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs,
-                   const wgnn_params* p, const float* Y, const float* Ls, int64_t ls_rows, float grad_scale, const void* stash,
-                   const float* loss_buf, float* loss, const wgnn_grads* g, void* workspace, const SeriesPlan& sp, void* stream,
-                   const int* starts = nullptr, bool masked = false, const LossFn* lossfn = nullptr);
-// include/windgnn_series_val.h: the front end without a stash, then the spec's recurrence with last_only = 1 and neither gate
-// records nor [Hprev | 1] rows: `last` [n][H] and the statistics in loss_buf are all it writes (workspace: ws_front_fwd floats)
-int series_val_fwd(const wgnn_dims* front, const wgnn_dims* rec, int stride, const float* A, const float* Xs,
-                   const wgnn_params* p, const float* Ls, int64_t ls_rows, float* last, float wind_min, float wind_max,
-                   float* loss_buf, void* workspace, const SeriesPlan& sp, void* stream, const int* starts, const LossFn* lossfn);
+// One request for every series entry point; zero-initialise and assign what the call has.  series_bwd only reads Y, the stash
+// and loss_buf.
+struct SeriesCall {
+  const wgnn_dims *front, *rec;
+  SeriesMap map;                         // stride, or the table with stride = 0 (include/windgnn_series_at.h); starts_last: set by api.hip
+  const float *A, *Xs; const wgnn_params* p;
+  float *Y, *last;                       // the forward writes one: Y [n][T][H], or last [n][H] = h_{T-1} * (wind_max - wind_min) + wind_min
+  float wind_min = 0.f, wind_max = 1.f;
+  // Ls [map.ls_rows][H] with loss_buf (both or neither): the labels as a series in the recurrences, which leave the statistics in
+  // loss_buf (forward) and form dY = (Y - label) 2 grad_scale / (n T H) and loss[0] from them (backward, instead of dY).
+  // With last (include/windgnn_series_val.h): the front end without a stash in ws_front_fwd floats of workspace, then the
+  // spec's recurrence with last_only = 1 and neither gate records nor [Hprev | 1] rows
+  const float* Ls; float* loss_buf;
+  bool masked; const LossFn* lossfn;     // include/windgnn_series_masked.h, include/windgnn_series_lossfn.h
+  const float* dY; float grad_scale = 1.f; float* loss; const wgnn_grads* grads;
+  void *stash, *workspace;               // stash: nullable in the forward
+  SeriesPlan sp; void* stream;
+};
+int series_fwd(const SeriesCall& c);
+int series_bwd(const SeriesCall& c);
 // dGIs [rows][ld] = the sum, in ascending w, of the window-major rows dGI [(w, tau - w * stride)][ld] that cover hour tau;
 // uncovered rows and the columns [G3, ld) are written as zeros (series.hip)
 int launch_series_fold(const float* dGI, int n, int T, int stride, int rows, int G3, int ld, float* dGIs, hipStream_t st);

@@ -613,154 +613,122 @@ int gru_blocks(int B) { return cdiv_i(B, MB); }
 int gru_hn(int H) { return 4 * cdiv_i(H, 4); }          // row width of the dGHn rows (16-byte aligned rows)
 int gru_msplit(int H) { return 4 * cdiv_i(2 * H, 4); }   // first GEMM row of the dGHn block in the dW_hh product
 
-int launch_gru_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
-                   float* gates, const float* labels, float* stat_part, float* hprev, int hq, int last_only, float y_mul,
-                   float y_add, hipStream_t st, const float* h0, float* hn, int series_stride, int64_t ls_rows,
-                   const int* starts, int starts_last, bool masked, const LossFn* lossfn) {
+// The one place each kernel's argument list is written.  Pack is the kernel's trailing pack: nothing, a row mapping
+// (SeriesRows / SeriesStarts), a MaskedLabels or LossFn behind one, or (backward) a BwdState.
+template <int K, bool ST, typename... Pack>
+static void gru_fwd_go(const GruFwdArgs& a, hipStream_t st, Pack... pack) {
+  hipLaunchKernelGGL((gru_fwd_kernel<K, ST, Pack...>), dim3(cdiv_i(a.B, MB)), dim3(NTHREADS), 0, st, a.B, a.T, a.H, a.GI, a.ldgi,
+                     a.Whh, a.bhh, a.Y, a.gates, a.labels, a.stat_part, a.hprev, a.hq, a.last_only, a.y_mul, a.y_add,
+                     ST ? a.h0 : nullptr, ST ? a.hn : nullptr, pack...);
+}
+template <int K, typename... Pack>
+static void gru_bwd_go(const GruBwdArgs& a, float inv_n, float coef, hipStream_t st, Pack... pack) {
+  hipLaunchKernelGGL((gru_bwd_kernel<K, Pack...>), dim3(cdiv_i(a.B, MB)), dim3(NTHREADS), 0, st, a.B, a.T, a.H, a.Whh, a.Y, a.dY,
+                     a.labels, a.gates, a.GI, a.ldgi, a.dGI, a.ldd, a.dGHn, gru_hn(a.H), a.dGH, a.stat_part, gru_blocks(a.B), inv_n,
+                     coef, a.loss, a.status, pack...);
+}
+
+int launch_gru_fwd(const GruFwdArgs& a, hipStream_t st) {
+  const int B = a.B, T = a.T, H = a.H;
+  const SeriesMap& m = a.map;
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
-  if (masked && (!(series_stride || starts) || !labels || !stat_part || last_only)) return WGNN_ERR_UNSUPPORTED;
-  if (lossfn && (!(series_stride || starts) || !labels || !stat_part || masked)) return WGNN_ERR_UNSUPPORTED;
-  if (lossfn && !lossfn_valid(*lossfn, T)) return WGNN_ERR_SHAPE;
+  if (a.masked && (!(m.stride || m.starts) || !a.labels || !a.stat_part || a.last_only)) return WGNN_ERR_UNSUPPORTED;
+  if (a.lossfn && (!(m.stride || m.starts) || !a.labels || !a.stat_part || a.masked)) return WGNN_ERR_UNSUPPORTED;
+  if (a.lossfn && !lossfn_valid(*a.lossfn, T)) return WGNN_ERR_SHAPE;
   // last_only with labels: a spec alone (include/windgnn_series_val.h: the statistics of a forward that keeps nothing else)
-  if (last_only && (gates || hprev || (labels && !lossfn))) return WGNN_ERR_UNSUPPORTED;
-  if (series_stride < 0 || (series_stride && (h0 || hn))) return WGNN_ERR_UNSUPPORTED;
-  if (starts && (series_stride || h0 || hn || starts_last < 0)) return WGNN_ERR_UNSUPPORTED;
-  if ((series_stride || starts) && labels && ls_rows * H >= (1ll << 31)) return WGNN_ERR_SHAPE;   // 32-bit offsets into Ls
-  if (starts && labels && ls_rows < (int64_t)starts_last + T) return WGNN_ERR_SHAPE;   // every clamped window has its label rows
-  if (hprev && (hq < H + 1 || hq % 4 != 0)) return WGNN_ERR_SHAPE;
+  if (a.last_only && (a.gates || a.hprev || (a.labels && !a.lossfn))) return WGNN_ERR_UNSUPPORTED;
+  if (m.stride < 0 || (m.stride && (a.h0 || a.hn))) return WGNN_ERR_UNSUPPORTED;
+  if (m.starts && (m.stride || a.h0 || a.hn || m.starts_last < 0)) return WGNN_ERR_UNSUPPORTED;
+  if ((m.stride || m.starts) && a.labels && m.ls_rows * H >= (1ll << 31)) return WGNN_ERR_SHAPE;   // 32-bit offsets into Ls
+  if (m.starts && a.labels && m.ls_rows < (int64_t)m.starts_last + T) return WGNN_ERR_SHAPE;   // every clamped window has its label rows
+  if (a.hprev && (a.hq < H + 1 || a.hq % 4 != 0)) return WGNN_ERR_SHAPE;
   const int ks = pick_ks(cdiv_i(H, 4), FWD_KS, (int)(sizeof(FWD_KS) / sizeof(int)));
   const double bt = (double)B * T;
   const double fl = bt * 2.0 * 3 * H * H;
-  const double by = bt * 4.0 * (3 * H + (last_only ? 0 : H) + (labels ? H : 0) + (hprev ? hq : 0)) +
-                    (gates ? 3.0 * gate_floats(B, T, H) : 0.0);     // three of the buffer's four components are used
-#define FMASKED(K, NAME, MAP, ...)                                                                                \
-  PROF_LAUNCH("gru_fwd_kernel<" #K NAME ">", fl, by, st,                                                          \
-              hipLaunchKernelGGL((gru_fwd_kernel<K, false, MAP, MaskedLabels>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, \
-                                 H, GI, ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq, last_only, y_mul, y_add, nullptr,  \
-                                 nullptr, MAP{__VA_ARGS__}, MaskedLabels{}))
-#define FLOSSFN(K, NAME, MAP, ...)                                                                                \
-  PROF_LAUNCH("gru_fwd_kernel<" #K NAME ">", fl, by, st,                                                          \
-              hipLaunchKernelGGL((gru_fwd_kernel<K, false, MAP, LossFn>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, GI, \
-                                 ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq, last_only, y_mul, y_add, nullptr,         \
-                                 nullptr, MAP{__VA_ARGS__}, *lossfn))
+  const double by = bt * 4.0 * (3 * H + (a.last_only ? 0 : H) + (a.labels ? H : 0) + (a.hprev ? a.hq : 0)) +
+                    (a.gates ? 3.0 * gate_floats(B, T, H) : 0.0);     // three of the buffer's four components are used
+  // FGO: a series instance under its own name, the pack spelled out; FMAP: either row mapping ahead of what else the pack holds
+#define FGO(K, NAME, ...) PROF_LAUNCH("gru_fwd_kernel<" #K NAME ">", fl, by, st, (gru_fwd_go<K, false>(a, st, __VA_ARGS__)))
+#define FMAP(K, NAME, TAIL)                                                                                       \
+  do {                                                                                                            \
+    if (m.starts) FGO(K, ",starts" NAME, SeriesStarts{m.starts, m.starts_last}, TAIL);                            \
+    else FGO(K, NAME, SeriesRows{m.stride}, TAIL);                                                                \
+  } while (0)
 #define FCASE(K)                                                                                                  \
   case K:                                                                                                         \
-    if (lossfn) {                                                                                                 \
-      if (starts) FLOSSFN(K, ",starts,lossfn", SeriesStarts, starts, starts_last);                                \
-      else FLOSSFN(K, ",lossfn", SeriesRows, series_stride);                                                      \
-      break;                                                                                                      \
-    }                                                                                                             \
-    if (masked) {                                                                                                 \
-      if (starts) FMASKED(K, ",starts,masked", SeriesStarts, starts, starts_last);                                \
-      else FMASKED(K, ",masked", SeriesRows, series_stride);                                                      \
-      break;                                                                                                      \
-    }                                                                                                             \
-    if (starts) {                                                                                                 \
-      PROF_LAUNCH("gru_fwd_kernel<" #K ",starts>", fl, by, st,                                                    \
-                  hipLaunchKernelGGL((gru_fwd_kernel<K, false, SeriesStarts>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, \
-                                     GI, ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq, last_only, y_mul, y_add,         \
-                                     nullptr, nullptr, SeriesStarts{starts, starts_last}));                                       \
-      break;                                                                                                      \
-    }                                                                                                             \
-    PROF_LAUNCH("gru_fwd_kernel<" #K ">", fl, by, st,                                                             \
-                if (series_stride) hipLaunchKernelGGL((gru_fwd_kernel<K, false, SeriesRows>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, \
-                                                      st, B, T, H, GI, ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq,       \
-                                                      last_only, y_mul, y_add, nullptr, nullptr, SeriesRows{series_stride});        \
-                else if (h0 || hn) hipLaunchKernelGGL((gru_fwd_kernel<K, true>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, \
-                                                 GI, ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq, last_only, y_mul,  \
-                                                 y_add, h0, hn);                                                                \
-                else hipLaunchKernelGGL((gru_fwd_kernel<K, false>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, GI,    \
-                                        ldgi, Whh, bhh, Y, gates, labels, stat_part, hprev, hq, last_only, y_mul, y_add,         \
-                                        nullptr, nullptr));                                                                     \
+    if (a.lossfn) FMAP(K, ",lossfn", *a.lossfn);                                                                  \
+    else if (a.masked) FMAP(K, ",masked", MaskedLabels{});                                                        \
+    else if (m.starts) FGO(K, ",starts", SeriesStarts{m.starts, m.starts_last});                                  \
+    else PROF_LAUNCH("gru_fwd_kernel<" #K ">", fl, by, st,                                                        \
+                     if (m.stride) gru_fwd_go<K, false>(a, st, SeriesRows{m.stride});                             \
+                     else if (a.h0 || a.hn) gru_fwd_go<K, true>(a, st);                                           \
+                     else gru_fwd_go<K, false>(a, st));                                                           \
     break
   switch (ks) {
     FCASE(4); FCASE(8); FCASE(12); FCASE(16); FCASE(20); FCASE(24); FCASE(26); FCASE(28); FCASE(32);
     default: return WGNN_ERR_UNSUPPORTED;
   }
 #undef FCASE
-#undef FLOSSFN
-#undef FMASKED
+#undef FMAP
+#undef FGO
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;
 }
 
-// exactly one of dY / labels is non-null.  labels: dY = (Y - labels) * 2 grad_scale / n_loss is formed in the kernel;
-// with stat_part (the forward's partial sums + tag) workgroup 0 also writes loss[0] = mean((Y - labels)^2).
-int launch_gru_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
-                   const float* gates, const float* GI /*the forward's GI rows [B*T][ldgi] (stash)*/, int ldgi, float* dGI, int ldd, float* dGHn, float* dGH, const float* stat_part,
-                   int64_t n_loss, float grad_scale, float* loss, unsigned* status, hipStream_t st, const BwdState* state,
-                   int series_stride, int64_t ls_rows, const int* starts, int starts_last, bool masked, const LossFn* lossfn) {
+// labels: dY = (Y - labels) * 2 grad_scale / n_loss is formed in the kernel; with stat_part (the forward's partial sums + tag)
+// workgroup 0 also writes loss[0] = mean((Y - labels)^2).
+int launch_gru_bwd(const GruBwdArgs& a, hipStream_t st) {
+  const int B = a.B, T = a.T, H = a.H;
+  const SeriesMap& m = a.map;
+  const LossFn* lossfn = a.lossfn;
   if (!gru_shape_supported(H)) return WGNN_ERR_UNSUPPORTED;
-  if (masked && (!(series_stride || starts) || !labels || !stat_part || state)) return WGNN_ERR_UNSUPPORTED;
-  if (lossfn && (!(series_stride || starts) || !labels || !stat_part || state || masked)) return WGNN_ERR_UNSUPPORTED;
+  if (a.masked && (!(m.stride || m.starts) || !a.labels || !a.stat_part || a.state)) return WGNN_ERR_UNSUPPORTED;
+  if (lossfn && (!(m.stride || m.starts) || !a.labels || !a.stat_part || a.state || a.masked)) return WGNN_ERR_UNSUPPORTED;
   if (lossfn && !lossfn_valid(*lossfn, T)) return WGNN_ERR_SHAPE;
-  if (state && (!state->h0 || labels)) return WGNN_ERR_UNSUPPORTED;
-  if (series_stride < 0 || (series_stride && state)) return WGNN_ERR_UNSUPPORTED;
-  if (starts && (series_stride || state || starts_last < 0)) return WGNN_ERR_UNSUPPORTED;
-  if ((series_stride || starts) && labels && ls_rows * H >= (1ll << 31)) return WGNN_ERR_SHAPE;   // 32-bit offsets into Ls
-  if (starts && labels && ls_rows < (int64_t)starts_last + T) return WGNN_ERR_SHAPE;
-  if ((dY == nullptr) == (labels == nullptr) || ldd < 3 * H || (dGHn == nullptr) == (dGH == nullptr)) return WGNN_ERR_SHAPE;
-  if (stat_part && (!labels || !loss)) return WGNN_ERR_NULL;
-  if (!GI || ldgi < 3 * H) return WGNN_ERR_NULL;
+  if (a.state && (!a.state->h0 || a.labels)) return WGNN_ERR_UNSUPPORTED;
+  if (m.stride < 0 || (m.stride && a.state)) return WGNN_ERR_UNSUPPORTED;
+  if (m.starts && (m.stride || a.state || m.starts_last < 0)) return WGNN_ERR_UNSUPPORTED;
+  if ((m.stride || m.starts) && a.labels && m.ls_rows * H >= (1ll << 31)) return WGNN_ERR_SHAPE;   // 32-bit offsets into Ls
+  if (m.starts && a.labels && m.ls_rows < (int64_t)m.starts_last + T) return WGNN_ERR_SHAPE;
+  if ((a.dY == nullptr) == (a.labels == nullptr) || a.ldd < 3 * H || (a.dGHn == nullptr) == (a.dGH == nullptr)) return WGNN_ERR_SHAPE;
+  if (a.stat_part && (!a.labels || !a.loss)) return WGNN_ERR_NULL;
+  if (!a.GI || a.ldgi < 3 * H) return WGNN_ERR_NULL;
   const int ks3 = pick_ks(cdiv_i(3 * H, 4), BWD_KS3, (int)(sizeof(BWD_KS3) / sizeof(int)));
-  const int hn = gru_hn(H);
-  const float inv_n = 1.0f / (float)n_loss, coef = 2.0f * grad_scale / (float)n_loss;
+  const float inv_n = 1.0f / (float)a.n_loss, coef = 2.0f * a.grad_scale / (float)a.n_loss;
   const double bt = (double)B * T;
-  const double fl = bt * 2.0 * 3 * H * H, by = bt * 4.0 * (H + H + 3 * H + (dGH ? 3 * H : H)) + 3.0 * gate_floats(B, T, H) +
+  const double fl = bt * 2.0 * 3 * H * H, by = bt * 4.0 * (H + H + 3 * H + (a.dGH ? 3 * H : H)) + 3.0 * gate_floats(B, T, H) +
                                           bt * 4.0 * H;   // + GI's n third
   // a loss spec without missing labels: m = B (T - t_from) H, and no factor 2 but for the mean square; with them, as masked
   const int64_t fn_m = lossfn ? (int64_t)B * (T - lossfn->t_from) * H : 1;
   const float fn_inv = lossfn && !lossfn->masked ? 1.0f / (float)fn_m : 0.f;
-  const float fn_coef = !lossfn || lossfn->masked ? grad_scale
-                        : (lossfn->kind == 0 ? 2.0f * grad_scale / (float)fn_m : grad_scale / (float)fn_m);
-#define BLOSSFN(K, NAME, MAP, ...)                                                                                \
-  PROF_LAUNCH("gru_bwd_kernel<" #K NAME ">", fl, by, st,                                                          \
-              hipLaunchKernelGGL((gru_bwd_kernel<K, MAP, LossFn>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY, \
-                                 labels, gates, GI, ldgi, dGI, ldd, dGHn, hn, dGH, stat_part, gru_blocks(B), fn_inv, fn_coef, loss, \
-                                 status, MAP{__VA_ARGS__}, *lossfn))
+  const float fn_coef = !lossfn || lossfn->masked ? a.grad_scale
+                        : (lossfn->kind == 0 ? 2.0f * a.grad_scale / (float)fn_m : a.grad_scale / (float)fn_m);
+  // BGO: a series instance under its own name with the two loss factors it takes; BMAP: either row mapping ahead of the tail.
   // masked: the kernel forms both factors from the forward's count; coef_lab carries grad_scale there
-#define BMASKED(K, NAME, MAP, ...)                                                                                \
-  PROF_LAUNCH("gru_bwd_kernel<" #K NAME ">", fl, by, st,                                                          \
-              hipLaunchKernelGGL((gru_bwd_kernel<K, MAP, MaskedLabels>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, Whh, \
-                                 Y, dY, labels, gates, GI, ldgi, dGI, ldd, dGHn, hn, dGH, stat_part, gru_blocks(B), 0.f,          \
-                                 grad_scale, loss, status, MAP{__VA_ARGS__}, MaskedLabels{}))
+#define BGO(K, NAME, INV, COEF, ...) \
+  PROF_LAUNCH("gru_bwd_kernel<" #K NAME ">", fl, by, st, (gru_bwd_go<K>(a, INV, COEF, st, __VA_ARGS__)))
+#define BMAP(K, NAME, INV, COEF, TAIL)                                                                            \
+  do {                                                                                                            \
+    if (m.starts) BGO(K, ",starts" NAME, INV, COEF, SeriesStarts{m.starts, m.starts_last}, TAIL);                 \
+    else BGO(K, NAME, INV, COEF, SeriesRows{m.stride}, TAIL);                                                     \
+  } while (0)
 #define BCASE(K)                                                                                                  \
   case K:                                                                                                         \
-    if (lossfn) {                                                                                                 \
-      if (starts) BLOSSFN(K, ",starts,lossfn", SeriesStarts, starts, starts_last);                                \
-      else BLOSSFN(K, ",lossfn", SeriesRows, series_stride);                                                      \
-      break;                                                                                                      \
-    }                                                                                                             \
-    if (masked) {                                                                                                 \
-      if (starts) BMASKED(K, ",starts,masked", SeriesStarts, starts, starts_last);                                \
-      else BMASKED(K, ",masked", SeriesRows, series_stride);                                                      \
-      break;                                                                                                      \
-    }                                                                                                             \
-    if (starts) {                                                                                                 \
-      PROF_LAUNCH("gru_bwd_kernel<" #K ",starts>", fl, by, st,                                                    \
-                  hipLaunchKernelGGL((gru_bwd_kernel<K, SeriesStarts>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, Whh, Y, \
-                                     dY, labels, gates, GI, ldgi, dGI, ldd, dGHn, hn, dGH, stat_part, gru_blocks(B), inv_n, coef,    \
-                                     loss, status, SeriesStarts{starts, starts_last}));                                              \
-      break;                                                                                                      \
-    }                                                                                                             \
-    PROF_LAUNCH("gru_bwd_kernel<" #K ">", fl, by, st,                                                             \
-                if (series_stride) hipLaunchKernelGGL((gru_bwd_kernel<K, SeriesRows>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, \
-                                                      T, H, Whh, Y, dY, labels, gates, GI, ldgi, dGI, ldd, dGHn, hn, dGH, stat_part,  \
-                                                      gru_blocks(B), inv_n, coef, loss, status, SeriesRows{series_stride});           \
-                else if (state) hipLaunchKernelGGL((gru_bwd_kernel<K, BwdState>), dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, \
-                                              Whh, Y, dY, labels, gates, GI, ldgi, dGI, ldd, dGHn, hn, dGH, stat_part,            \
-                                              gru_blocks(B), inv_n, coef, loss, status, *state);                                   \
-                else hipLaunchKernelGGL(gru_bwd_kernel<K>, dim3(cdiv_i(B, MB)), dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY,  \
-                                   labels, gates, GI, ldgi, dGI, ldd, dGHn, hn, dGH, stat_part, gru_blocks(B), inv_n, coef,  \
-                                   loss, status));                                                                      \
+    if (lossfn) BMAP(K, ",lossfn", fn_inv, fn_coef, *lossfn);                                                     \
+    else if (a.masked) BMAP(K, ",masked", 0.f, a.grad_scale, MaskedLabels{});                                     \
+    else if (m.starts) BGO(K, ",starts", inv_n, coef, SeriesStarts{m.starts, m.starts_last});                     \
+    else PROF_LAUNCH("gru_bwd_kernel<" #K ">", fl, by, st,                                                        \
+                     if (m.stride) gru_bwd_go<K>(a, inv_n, coef, st, SeriesRows{m.stride});                       \
+                     else if (a.state) gru_bwd_go<K>(a, inv_n, coef, st, *a.state);                               \
+                     else gru_bwd_go<K>(a, inv_n, coef, st));                                                     \
     break
   switch (ks3) {
     BCASE(12); BCASE(24); BCASE(36); BCASE(48); BCASE(60); BCASE(72); BCASE(78); BCASE(84); BCASE(96);
     default: return WGNN_ERR_UNSUPPORTED;
   }
 #undef BCASE
-#undef BLOSSFN
-#undef BMASKED
+#undef BMAP
+#undef BGO
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;
 }

@@ -409,43 +409,41 @@ bool gru_small_supported(int B, int H) { return H >= 1 && H <= 128 && B <= 768; 
     }                                                                                                            \
   } while (0)
 
+// the one place gru_small_fwd_kernel's argument list is written
 template <int HMAX, bool ST>
-static int launch_small_fwd_t(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
-                              float* gates, float* hprev, int hq, const float* labels, float* stat_part, const float* h0,
-                              float* hn, hipStream_t st) {
+static int launch_small_fwd_t(const GruFwdArgs& a, hipStream_t st) {
+  const int H = a.H;
   const size_t wbytes = (size_t)3 * H * H * sizeof(float);
   const int stage_w = wbytes <= 140 * 1024;
   const size_t smem = stage_w ? wbytes : 0;
   static std::atomic<unsigned long long> done{0};
   constexpr int KSP = small_ksp(HMAX);
   if (ensure_dyn_smem((const void*)gru_small_fwd_kernel<HMAX, 1, KSP, ST>, 140 * 1024, done) != WGNN_OK) return WGNN_ERR_HIP;
-  hipLaunchKernelGGL((gru_small_fwd_kernel<HMAX, 1, KSP, ST>), dim3(B), dim3(KSP * cdiv_i(3 * H, 64) * 64), smem, st, B, T, H, GI,
-                     ldgi, Whh, bhh, Y, gates, stage_w, hprev, hq, labels, stat_part, h0, hn);
+  hipLaunchKernelGGL((gru_small_fwd_kernel<HMAX, 1, KSP, ST>), dim3(a.B), dim3(KSP * cdiv_i(3 * H, 64) * 64), smem, st, a.B, a.T, H,
+                     a.GI, a.ldgi, a.Whh, a.bhh, a.Y, a.gates, stage_w, a.hprev, a.hq, a.labels, a.stat_part, a.h0, a.hn);
   return WGNN_OK;
 }
 
 template <bool ST>
-static int launch_small_fwd_s(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
-                              float* gates, float* hprev, int hq, const float* labels, float* stat_part, const float* h0,
-                              float* hn, hipStream_t st) {
-  return small_hmax(H) == 32   ? launch_small_fwd_t<32, ST>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st)
-         : small_hmax(H) == 64  ? launch_small_fwd_t<64, ST>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st)
-         : small_hmax(H) == 96  ? launch_small_fwd_t<96, ST>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st)
-         : small_hmax(H) == 108 ? launch_small_fwd_t<108, ST>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st)
-         : small_hmax(H) == 112 ? launch_small_fwd_t<112, ST>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st)
-         : launch_small_fwd_t<128, ST>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st);
+static int launch_small_fwd_s(const GruFwdArgs& a, hipStream_t st) {
+  const int hmax = small_hmax(a.H);
+  return hmax == 32    ? launch_small_fwd_t<32, ST>(a, st)
+         : hmax == 64  ? launch_small_fwd_t<64, ST>(a, st)
+         : hmax == 96  ? launch_small_fwd_t<96, ST>(a, st)
+         : hmax == 108 ? launch_small_fwd_t<108, ST>(a, st)
+         : hmax == 112 ? launch_small_fwd_t<112, ST>(a, st)
+                       : launch_small_fwd_t<128, ST>(a, st);
 }
 
-int launch_gru_small_fwd(int B, int T, int H, const float* GI, int ldgi, const float* Whh, const float* bhh, float* Y,
-                         float* gates, float* hprev, int hq, const float* labels, float* stat_part, hipStream_t st,
-                         const float* h0, float* hn) {
+int launch_gru_small_fwd(const GruFwdArgs& a, hipStream_t st) {
+  const int B = a.B, T = a.T, H = a.H;
   if (!gru_small_supported(B, H)) return WGNN_ERR_UNSUPPORTED;
-  if (hprev && (hq < H + 1 || hq % 4 != 0)) return WGNN_ERR_SHAPE;
+  if (a.hprev && (a.hq < H + 1 || a.hq % 4 != 0)) return WGNN_ERR_SHAPE;
+  if (a.map.stride || a.map.starts || a.masked || a.lossfn || a.last_only) return WGNN_ERR_UNSUPPORTED;   // no kernel for these
   const double bt = (double)B * T;
   int rc = WGNN_OK;
-  PROF_LAUNCH("gru_small_fwd_kernel", bt * 2.0 * 3 * H * H, bt * 4.0 * (3 * H + H + (gates ? 4 * H : 0) + (hprev ? hq : 0)), st,
-              rc = (h0 || hn) ? launch_small_fwd_s<true>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st)
-                              : launch_small_fwd_s<false>(B, T, H, GI, ldgi, Whh, bhh, Y, gates, hprev, hq, labels, stat_part, h0, hn, st));
+  PROF_LAUNCH("gru_small_fwd_kernel", bt * 2.0 * 3 * H * H, bt * 4.0 * (3 * H + H + (a.gates ? 4 * H : 0) + (a.hprev ? a.hq : 0)), st,
+              rc = (a.h0 || a.hn) ? launch_small_fwd_s<true>(a, st) : launch_small_fwd_s<false>(a, st));
   if (rc != WGNN_OK) return rc;
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;
@@ -453,23 +451,25 @@ int launch_gru_small_fwd(int B, int T, int H, const float* GI, int ldgi, const f
 
 int gru_small_blocks(int B) { return B; }        // workgroups of the forward = MSE partial pairs it writes with labels
 
-int launch_gru_small_bwd(int B, int T, int H, const float* Whh, const float* Y, const float* dY, const float* labels,
-                         const float* gates, float* dGI, float* dGH, int ldd, const float* stat_part, int64_t n_loss,
-                         float grad_scale, float* loss, unsigned* status, hipStream_t st, const BwdState* state) {
+int launch_gru_small_bwd(const GruBwdArgs& a, hipStream_t st) {
+  const int B = a.B, T = a.T, H = a.H;
   if (!gru_small_supported(B, H)) return WGNN_ERR_UNSUPPORTED;
-  if ((dY == nullptr) == (labels == nullptr)) return WGNN_ERR_SHAPE;
-  if (state && (!state->h0 || labels)) return WGNN_ERR_UNSUPPORTED;
-  if (stat_part && (!labels || !loss)) return WGNN_ERR_NULL;
+  if ((a.dY == nullptr) == (a.labels == nullptr)) return WGNN_ERR_SHAPE;
+  if (a.state && (!a.state->h0 || a.labels)) return WGNN_ERR_UNSUPPORTED;
+  if (a.stat_part && (!a.labels || !a.loss)) return WGNN_ERR_NULL;
+  if (a.map.stride || a.map.starts || a.masked || a.lossfn || a.dGHn) return WGNN_ERR_UNSUPPORTED;   // no kernel for these
   const double bt = (double)B * T;
-  const float inv_n = 1.0f / (float)n_loss, coef = 2.0f * grad_scale / (float)n_loss;
-  if (state)
+  const float inv_n = 1.0f / (float)a.n_loss, coef = 2.0f * a.grad_scale / (float)a.n_loss;
+  // the kernels' argument list, once: the state instances take the BwdState behind it
+#define SMALL_BWD_ARGS \
+  B, T, H, a.Whh, a.Y, a.dY, a.gates, a.dGI, a.dGH, a.ldd, a.labels, coef, a.stat_part, gru_small_blocks(B), inv_n, a.loss, a.status
+  if (a.state)
     PROF_LAUNCH("gru_small_bwd_kernel", bt * 2.0 * 3 * H * H, bt * 4.0 * (4 * H + 2 * H + 6 * H), st,
-                SMALL_DISPATCH(gru_small_bwd_state_kernel, B, T, H, Whh, Y, dY, gates, dGI, dGH, ldd, labels, coef, stat_part,
-                               gru_small_blocks(B), inv_n, loss, status, *state));
+                SMALL_DISPATCH(gru_small_bwd_state_kernel, SMALL_BWD_ARGS, *a.state));
   else
     PROF_LAUNCH("gru_small_bwd_kernel", bt * 2.0 * 3 * H * H, bt * 4.0 * (4 * H + 2 * H + 6 * H), st,
-                SMALL_DISPATCH(gru_small_bwd_kernel, B, T, H, Whh, Y, dY, gates, dGI, dGH, ldd, labels, coef, stat_part,
-                               gru_small_blocks(B), inv_n, loss, status));
+                SMALL_DISPATCH(gru_small_bwd_kernel, SMALL_BWD_ARGS));
+#undef SMALL_BWD_ARGS
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;
 }

@@ -885,36 +885,33 @@ constexpr int ghn_ksf(int K, bool hi) {
   return v;
 }
 
-int launch_grux_fwd(int B, int T, int H, const void* GI /*fp32 rows (x3) or fp16 rows (one-pass fp16)*/, int ldgi, const float* Whh, const float* bhh, void* Y,
-                    float* gates, void* y_planes /*nullable: 2 x [B*T+1][grux_hp(H)] halfs*/, bool x3, unsigned* status,
-                    const void* labels /*nullable*/, float* stat_part /*2 * grux_blocks(B) floats if labels*/, int io,
-                    int last_only /*Y is [B][H]: only h_{T-1} * y_mul + y_add is written (fp32 I/O, no stash)*/,
-                    float y_mul, float y_add, hipStream_t st, const float* h0, float* hn, size_t plane_rows, bool ghn_rc) {
-  const bool rc = ghn_rc && gates;                 // r | z records (api.hip ghn_recompute): the stateless fp32-I/O split step only
-  if (rc && (!x3 || io || h0 || hn)) return WGNN_ERR_UNSUPPORTED;
-  if (last_only && (io != 0 || gates || y_planes || labels)) return WGNN_ERR_UNSUPPORTED;
-  if (!Y && (!io || !hn || last_only)) return WGNN_ERR_NULL;   // Y = NULL: 16-bit I/O with h_n only (fp32: last_only into h_n)
-  _Float16* yh = (_Float16*)y_planes;
-  _Float16* yl = yh ? yh + (plane_rows ? plane_rows : (size_t)B * T + 1) * grux_hp(H) : nullptr;   // each plane has B*T + 1 rows
-                                                                                                    // (the state stash: B*T + B)
+// The one place each kernel's argument list is written (yh / yl: the two Y planes, formed by the launcher)
+template <int K, bool X3, bool IO, bool ST, bool RC = false>
+static void grux_fwd_go(const GruxFwdArgs& a, _Float16* yh, _Float16* yl, hipStream_t st) {
+  hipLaunchKernelGGL((grux_fwd_kernel<K, X3, IO, ST, RC>), dim3(cdiv_i(a.B, MB)), dim3(NTHREADS), 0, st, a.B, a.T, a.H, a.GI, a.ldgi,
+                     a.Whh, a.bhh, a.Y, a.gates, yh, yl, a.status, a.labels, a.stat_part, a.io, a.last_only, a.y_mul, a.y_add,
+                     ST ? a.h0 : nullptr, ST ? a.hn : nullptr);
+}
+
+int launch_grux_fwd(const GruxFwdArgs& a, hipStream_t st) {
+  const int B = a.B, T = a.T, H = a.H, io = a.io;
+  const bool x3 = a.x3;
+  const bool rc = a.ghn_rc && a.gates;             // r | z records (api.hip ghn_recompute): the stateless fp32-I/O split step only
+  if (rc && (!x3 || io || a.h0 || a.hn)) return WGNN_ERR_UNSUPPORTED;
+  if (a.last_only && (io != 0 || a.gates || a.y_planes || a.labels)) return WGNN_ERR_UNSUPPORTED;
+  if (!a.Y && (!io || !a.hn || a.last_only)) return WGNN_ERR_NULL;   // Y = NULL: 16-bit I/O with h_n only (fp32: last_only into h_n)
+  _Float16* yh = (_Float16*)a.y_planes;
+  _Float16* yl = yh ? yh + (a.plane_rows ? a.plane_rows : (size_t)B * T + 1) * grux_hp(H) : nullptr;
   const double bt = (double)B * T;
   const double fl = bt * 2.0 * 3 * H * H,
-               by = bt * ((x3 ? 4.0 : 2.0) * 3 * H + (io ? 2.0 : 4.0) * ((last_only ? 0 : H) + (labels ? H : 0))) +
-                    (gates ? gates_bytes(B, T, H, io, x3, rc) : 0.0);
-  const dim3 grid(cdiv_i(B, MB));
+               by = bt * ((x3 ? 4.0 : 2.0) * 3 * H + (io ? 2.0 : 4.0) * ((a.last_only ? 0 : H) + (a.labels ? H : 0))) +
+                    (a.gates ? gates_bytes(B, T, H, io, x3, rc) : 0.0);
 #define FLAUNCH(K, X3V, IOV, NAME)                                                                                 \
   PROF_LAUNCH(NAME, fl, by, st,                                                                                    \
-              if (h0 || hn) hipLaunchKernelGGL((grux_fwd_kernel<K, X3V, IOV, true>), grid, dim3(NTHREADS), 0, st, B, T, H, GI,  \
-                                               ldgi, Whh, bhh, Y, gates, yh, yl, status, labels, stat_part, io, last_only,     \
-                                               y_mul, y_add, h0, hn);                                                          \
-              else hipLaunchKernelGGL((grux_fwd_kernel<K, X3V, IOV, false>), grid, dim3(NTHREADS), 0, st, B, T, H, GI, ldgi,   \
-                                      Whh, bhh, Y, gates, yh, yl, status, labels, stat_part, io, last_only, y_mul, y_add,      \
-                                      nullptr, nullptr))
+              if (a.h0 || a.hn) grux_fwd_go<K, X3V, IOV, true>(a, yh, yl, st);                                     \
+              else grux_fwd_go<K, X3V, IOV, false>(a, yh, yl, st))
 #define FCASE(K)                                                                                                   \
-  if (rc) PROF_LAUNCH("grux_fwd_kernel<" #K ">", fl, by, st,                                                       \
-                      hipLaunchKernelGGL((grux_fwd_kernel<K, true, false, false, true>), grid, dim3(NTHREADS), 0, st, B, T, H, \
-                                         GI, ldgi, Whh, bhh, Y, gates, yh, yl, status, labels, stat_part, io, last_only, y_mul,  \
-                                         y_add, nullptr, nullptr));                                                             \
+  if (rc) PROF_LAUNCH("grux_fwd_kernel<" #K ">", fl, by, st, (grux_fwd_go<K, true, false, false, true>(a, yh, yl, st))); \
   else if (x3 && !io) FLAUNCH(K, true, false, "grux_fwd_kernel<" #K ">");                                          \
   else if (x3) FLAUNCH(K, true, true, "grux_fwd_kernel<" #K ">");                                                  \
   else if (!io) FLAUNCH(K, false, false, "grux_fwd_kernel<" #K ",f16>");                                           \
@@ -935,49 +932,54 @@ int launch_grux_fwd(int B, int T, int H, const void* GI /*fp32 rows (x3) or fp16
 int grux_hn(int H) { return 8 * cdiv_i(H, 8); }
 int grux_msplit(int H) { return 8 * cdiv_i(2 * H, 8); }
 
-int launch_grux_bwd(int B, int T, int H, const float* Whh, const void* Y, const float* dY, const void* labels, int io,
-                    const float* gates, const float* GI /*x3: the forward's GI rows [B*T][ldgi] fp32 (stash)*/, int ldgi,
-                    const float* scales, void* dGI_planes, void* dGHn_planes, int ldd, bool x3, const float* stat_part,
-                    int64_t n_loss, float grad_scale, float* loss, float* scales_out, unsigned* status, int write_lo,
-                    hipStream_t st, const BwdState* state, const float* bhh, bool ghn_rc) {
-  if (state && (!state->h0 || labels || stat_part)) return WGNN_ERR_UNSUPPORTED;   // (the state backward takes dY)
-  if (ghn_rc && (!x3 || io || state || !bhh)) return WGNN_ERR_UNSUPPORTED;         // (r | z records: api.hip ghn_recompute)
+// what launch_grux_bwd forms for the kernel: the hi / lo planes of dGI and dGHn, and the loss factors
+struct GruxBwdFormed {
+  _Float16 *ih, *il, *nh, *nl;
+  int nstat;
+  float inv_n, coef_in;
+};
+template <int K, bool X3, bool IO, int KSF, typename... Pack>   // Pack: nothing, or the BwdState
+static void grux_bwd_go(const GruxBwdArgs& a, const GruxBwdFormed& f, hipStream_t st, Pack... pack) {
+  hipLaunchKernelGGL((grux_bwd_kernel<K, X3, IO, KSF, Pack...>), dim3(cdiv_i(a.B, MB)), dim3(NTHREADS), 0, st, a.B, a.T, a.H, a.Whh,
+                     a.Y, a.dY, a.labels, a.io, a.gates, a.GI, a.ldgi, a.scales, f.ih, f.il, a.ldd, f.nh, f.nl, a.stat_part, f.nstat,
+                     f.inv_n, f.coef_in, a.loss, a.scales_out, a.status, a.write_lo, a.bhh, pack...);
+}
+
+int launch_grux_bwd(const GruxBwdArgs& a, hipStream_t st) {
+  const int B = a.B, T = a.T, H = a.H, io = a.io;
+  const bool x3 = a.x3, ghn_rc = a.ghn_rc;
+  if (a.state && (!a.state->h0 || a.labels || a.stat_part)) return WGNN_ERR_UNSUPPORTED;   // (the state backward takes dY)
+  if (ghn_rc && (!x3 || io || a.state || !a.bhh)) return WGNN_ERR_UNSUPPORTED;         // (r | z records: api.hip ghn_recompute)
   const int ksf = cdiv_i(H + 1, 32);               // the forward's K steps: the recomputed gh_n runs the forward's product
   // stat_part != null: loss and scales are finalised inside the kernel (once a separate one-block launch)
-  const int nstat = grux_blocks(B);
-  const float inv_n = stat_part ? 1.0f / (float)n_loss : 0.f, coef_in = stat_part ? 2.0f * grad_scale / (float)n_loss : 0.f;
-  _Float16* ih = (_Float16*)dGI_planes;
-  _Float16* il = ih + (size_t)B * T * ldd;
-  _Float16* nh = (_Float16*)dGHn_planes;
-  _Float16* nl = nh + (size_t)B * T * grux_hn(H);
+  GruxBwdFormed f;
+  f.nstat = grux_blocks(B);
+  f.inv_n = a.stat_part ? 1.0f / (float)a.n_loss : 0.f;
+  f.coef_in = a.stat_part ? 2.0f * a.grad_scale / (float)a.n_loss : 0.f;
+  f.ih = (_Float16*)a.dGI_planes;
+  f.il = f.ih + (size_t)B * T * a.ldd;
+  f.nh = (_Float16*)a.dGHn_planes;
+  f.nl = f.nh + (size_t)B * T * grux_hn(H);
   const int ksb = cdiv_i(grux_msplit(H) + H, 32);
-  if (ldd % 8 != 0 || ldd < 3 * H || ldd > 32 * ksb) return WGNN_ERR_SHAPE;
-  if (x3 && (!GI || ldgi < 3 * H)) return WGNN_ERR_NULL;
+  if (a.ldd % 8 != 0 || a.ldd < 3 * H || a.ldd > 32 * ksb) return WGNN_ERR_SHAPE;
+  if (x3 && (!a.GI || a.ldgi < 3 * H)) return WGNN_ERR_NULL;
   const double bt = (double)B * T;
   const double fl = bt * 2.0 * 3 * H * H,
-               by = bt * ((io ? 2.0 + 4.0 : 4.0 + 4.0) * H + (x3 && write_lo ? 4.0 : 2.0) * (3 * H + H)) +
+               by = bt * ((io ? 2.0 + 4.0 : 4.0 + 4.0) * H + (x3 && a.write_lo ? 4.0 : 2.0) * (3 * H + H)) +
                     gates_bytes(B, T, H, io, x3, ghn_rc) + (x3 ? bt * 4.0 * H : 0.0);   // Y + labels in, planes out, stash (+ GI's n third) in
-  const dim3 grid(cdiv_i(B, MB));
-#define BLAUNCH(K, X3V, IOV, NAME, BYTES)                                                                         \
-  PROF_LAUNCH(NAME, fl, BYTES, st,                                                                                \
-              if (state) hipLaunchKernelGGL((grux_bwd_kernel<K, X3V, IOV, 0, BwdState>), grid, dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY, \
-                                            labels, io, gates, GI, ldgi, scales, ih, il, ldd, nh, nl, stat_part, nstat, inv_n, coef_in, \
-                                            loss, scales_out, status, write_lo, bhh, *state);                                       \
-              else hipLaunchKernelGGL((grux_bwd_kernel<K, X3V, IOV, 0>), grid, dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY, labels, io, \
-                                 gates, GI, ldgi, scales, ih, il, ldd, nh, nl, stat_part, nstat, inv_n, coef_in, loss, scales_out, status, write_lo, bhh))
-#define BLAUNCH_RC(K, KSFV)                                                                                       \
-  PROF_LAUNCH("grux_bwd_kernel<" #K ">", fl, by, st,                                                              \
-              hipLaunchKernelGGL((grux_bwd_kernel<K, true, false, KSFV>), grid, dim3(NTHREADS), 0, st, B, T, H, Whh, Y, dY, labels, \
-                                 io, gates, GI, ldgi, scales, ih, il, ldd, nh, nl, stat_part, nstat, inv_n, coef_in, loss, scales_out, \
-                                 status, write_lo, bhh))
+#define BLAUNCH(K, X3V, IOV, NAME)                                                                                \
+  PROF_LAUNCH(NAME, fl, by, st,                                                                                   \
+              if (a.state) grux_bwd_go<K, X3V, IOV, 0>(a, f, st, *a.state);                                       \
+              else grux_bwd_go<K, X3V, IOV, 0>(a, f, st))
+#define BLAUNCH_RC(K, KSFV) PROF_LAUNCH("grux_bwd_kernel<" #K ">", fl, by, st, (grux_bwd_go<K, true, false, KSFV>(a, f, st)))
 #define BCASE(K)                                                                                                  \
   if (ghn_rc && ksf == ghn_ksf(K, false)) BLAUNCH_RC(K, ghn_ksf(K, false));                                       \
   else if (ghn_rc && ksf == ghn_ksf(K, true)) BLAUNCH_RC(K, ghn_ksf(K, true));                                    \
   else if (ghn_rc) return WGNN_ERR_UNSUPPORTED;                                                                   \
-  else if (x3 && !io) BLAUNCH(K, true, false, "grux_bwd_kernel<" #K ">", by);                                     \
-  else if (x3) BLAUNCH(K, true, true, "grux_bwd_kernel<" #K ">", by);                                             \
-  else if (!io) BLAUNCH(K, false, false, "grux_bwd_kernel<" #K ",f16>", by);                                      \
-  else BLAUNCH(K, false, true, "grux_bwd_kernel<" #K ",f16>", by)
+  else if (x3 && !io) BLAUNCH(K, true, false, "grux_bwd_kernel<" #K ">");                                         \
+  else if (x3) BLAUNCH(K, true, true, "grux_bwd_kernel<" #K ">");                                                 \
+  else if (!io) BLAUNCH(K, false, false, "grux_bwd_kernel<" #K ",f16>");                                          \
+  else BLAUNCH(K, false, true, "grux_bwd_kernel<" #K ",f16>")
   switch (ksb) {
     case 1: BCASE(1); break;
     case 2: BCASE(2); break;

@@ -252,6 +252,15 @@ int launch_starts_check(const wgnn_series_dims* sd, const int* starts, void* wor
   return WGNN_OK;
 }
 
+// what the request of every entry point shares
+SeriesCall request(const wgnn_series_dims* sd, const Plan& pl, const float* A, const float* Xs, const wgnn_params* p,
+                   const int* starts, void* workspace, void* stream) {
+  SeriesCall c = {};
+  c.front = &pl.front; c.rec = &pl.rec; c.map.stride = sd->stride; c.map.starts = starts;
+  c.A = A; c.Xs = Xs; c.p = p; c.workspace = workspace; c.sp = pl.sp; c.stream = stream;
+  return c;
+}
+
 // at: the table entry points (starts is then required, and checked on the device ahead of everything else)
 int forward(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, float* Y, float* last,
             float wind_min, float wind_max, void* stash, void* workspace, size_t workspace_bytes, void* stream,
@@ -262,8 +271,9 @@ int forward(const wgnn_series_dims* sd, const float* A, const float* Xs, const w
   if (!A || !Xs || !p || (!Y && !last) || !workspace || !complete(p) || (at && !starts)) return WGNN_ERR_NULL;
   if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
   if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
-  return series_fwd(&pl.front, &pl.rec, sd->stride, A, Xs, p, Y, last, wind_min, wind_max, stash, workspace, pl.sp, stream,
-                    starts);
+  SeriesCall c = request(sd, pl, A, Xs, p, starts, workspace, stream);
+  c.Y = Y; c.last = last; c.wind_min = wind_min; c.wind_max = wind_max; c.stash = stash;
+  return series_fwd(c);
 }
 
 int backward(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, const float* Y, const float* dY,
@@ -276,7 +286,9 @@ int backward(const wgnn_series_dims* sd, const float* A, const float* Xs, const 
     return WGNN_ERR_NULL;
   if (workspace_bytes < sizeof(float) * (pl.sp.ws_front + pl.sp.ws_rec)) return WGNN_ERR_WORKSPACE;
   if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
-  return series_bwd(&pl.front, &pl.rec, sd->stride, A, Xs, p, Y, dY, stash, grads, workspace, pl.sp, stream, starts);
+  SeriesCall c = request(sd, pl, A, Xs, p, starts, workspace, stream);
+  c.Y = (float*)Y; c.dY = dY; c.stash = (void*)stash; c.grads = grads;
+  return series_bwd(c);
 }
 
 // the label rows a call needs: up to the last row a window covers -- any row of the series, for a table
@@ -307,8 +319,10 @@ int forward_loss(const wgnn_series_dims* sd, const float* A, const float* Xs, co
   LossFn spec{};
   if (lossfn && (rc = loss_spec(sd, fn, &spec)) != WGNN_OK) return rc;      // last of the host checks, ahead of any launch
   if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
-  return series_fwd_loss(&pl.front, &pl.rec, sd->stride, A, Xs, p, Ls, ls_rows, Y, stash, (float*)loss_buf, workspace, pl.sp,
-                         stream, starts, masked, lossfn ? &spec : nullptr);
+  SeriesCall c = request(sd, pl, A, Xs, p, starts, workspace, stream);
+  c.Y = Y; c.stash = stash; c.Ls = Ls; c.map.ls_rows = ls_rows; c.loss_buf = (float*)loss_buf;
+  c.masked = masked; c.lossfn = lossfn ? &spec : nullptr;
+  return series_fwd(c);
 }
 
 int backward_mse(const wgnn_series_dims* sd, const float* A, const float* Xs, const wgnn_params* p, const float* Y,
@@ -327,8 +341,10 @@ int backward_mse(const wgnn_series_dims* sd, const float* A, const float* Xs, co
   LossFn spec{};
   if (lossfn && (rc = loss_spec(sd, fn, &spec)) != WGNN_OK) return rc;
   if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
-  return series_bwd_mse(&pl.front, &pl.rec, sd->stride, A, Xs, p, Y, Ls, ls_rows, grad_scale, stash, (const float*)loss_buf,
-                        loss, grads, workspace, pl.sp, stream, starts, masked, lossfn ? &spec : nullptr);
+  SeriesCall c = request(sd, pl, A, Xs, p, starts, workspace, stream);
+  c.Y = (float*)Y; c.stash = (void*)stash; c.grads = grads; c.Ls = Ls; c.map.ls_rows = ls_rows; c.loss_buf = (float*)loss_buf;
+  c.grad_scale = grad_scale; c.loss = loss; c.masked = masked; c.lossfn = lossfn ? &spec : nullptr;
+  return series_bwd(c);
 }
 
 // include/windgnn_series_val.h: floats of the workspace -- [front end, forward alone | loss_buf | last rows]
@@ -360,8 +376,10 @@ int validate(const wgnn_series_dims* sd, const float* A, const float* Xs, const 
   if (at && (rc = launch_starts_check(sd, starts, workspace, stream)) != WGNN_OK) return rc;
   float* ws = (float*)workspace;
   float* loss_buf = ws + vl.loss_buf;
-  rc = series_val_fwd(&pl.front, &pl.rec, sd->stride, A, Xs, p, Ls, ls_rows, last ? last : ws + vl.last, wind_min, wind_max,
-                      loss_buf, workspace, pl.sp, stream, starts, &spec);
+  SeriesCall c = request(sd, pl, A, Xs, p, starts, workspace, stream);   // last and Ls, no stash: a forward alone
+  c.last = last ? last : ws + vl.last; c.wind_min = wind_min; c.wind_max = wind_max;
+  c.Ls = Ls; c.map.ls_rows = ls_rows; c.loss_buf = loss_buf; c.lossfn = &spec;
+  rc = series_fwd(c);
   if (rc != WGNN_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int nb = gru_blocks(sd->n);
