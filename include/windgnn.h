@@ -375,7 +375,8 @@ int wgnn_prepare_weights(const wgnn_dims* d, const wgnn_params* p, void* workspa
  * (dX == NULL skips that half of the work).  Exact fp32 at every width.
  * F == F_out == 13 -- the only widths the reference's own model builds (src/main.py:41) -- run the MFMA kernels of csrc/gcn.hip;
  * other widths up to 64 an FMA kernel of their own (csrc/gcn_any.hip); max(F, F_out) > 64 the tiled fp32-MFMA kernels of
- * csrc/gcn_wide.hip, for ntiles * S * max(F, F_out) < 2^31 and F * F_out < 2^31 (beyond: WGNN_ERR_SHAPE).  More than 64
+ * csrc/gcn_wide.hip, for ntiles * S * max(F, F_out) < 2^31 and F * F_out < 2^31 (beyond: WGNN_ERR_SHAPE).  At every width
+ * ntiles <= 2^31 - 4097 (beyond: WGNN_ERR_SHAPE; the narrower kernels index in 64 bits and have no element limit).  More than 64
  * stations: WGNN_ERR_UNSUPPORTED (a CSR adjacency serves 13 -> 13 alone, below).  Checks in this order: shape, unsupported, NULL,
  * workspace.  wgnn_gcn_layer_workspace_bytes depends on its four arguments alone, is a multiple of 256 past 64 features (there
  * it holds A^T dZ [n,S,F_out], the per-workgroup sums of db and the split-K partials of dW) and is 0 for a refused shape; the
@@ -430,7 +431,8 @@ int wgnn_make_windows(const float* feat, int64_t Ttot, int32_t S, int32_t F, int
                       int32_t label_feat, const int32_t* starts_host, const int32_t* starts_dev,
                       int32_t B, float* X, float* L, void* stream);
 
-/* N4 (src/main.py:103,116,131,146): out[b][j] = Y[b][T-1][j] * (wind_max - wind_min) + wind_min. */
+/* N4 (src/main.py:103,116,131,146): out[b][j] = Y[b][T-1][j] * (wind_max - wind_min) + wind_min.  Y [B][T][H] may be of any
+ * size (its rows are addressed in 64 bits); out [B][H] must stay below 2^31 elements (beyond: WGNN_ERR_SHAPE). */
 int wgnn_predict_last(const float* Y, int32_t B, int32_t T, int32_t H, float wind_min, float wind_max,
                       float* out, void* stream);
 

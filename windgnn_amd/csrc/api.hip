@@ -1389,6 +1389,11 @@ int wgnn_finish_rows(const wgnn_dims* d, const wgnn_params* p, const wgnn_grads*
 // max(F, F_out) > 64: gcn_wide.hip.  0 = fits none of them; WGNN_ERR_SHAPE / WGNN_ERR_UNSUPPORTED otherwise.
 static int gcn_layer_route(int32_t ntiles, int32_t S, int32_t F, int32_t F_out, bool* wide) {
   if (ntiles < 1 || S < 1 || F < 1 || F_out < 1) return WGNN_ERR_SHAPE;
+  // the tile loops of gcn.hip (base += gridDim.x * WAVES) and gcn_any.hip (t += gridDim.x) advance a 32-bit tile counter by their
+  // grid past the last tile before they test it: it must not wrap (S = F = F_out = 1 reaches this with 8 GiB of X).  4096 = the
+  // largest such step: grid_for() / ga_grid() cap the grid at 1024 workgroups and gcn.hip runs WAVES = 4 tiles per workgroup; a
+  // larger grid cap or more waves per workgroup there raises this constant with it
+  if ((int64_t)ntiles + 4096 > INT32_MAX) return WGNN_ERR_SHAPE;
   *wide = F > 64 || F_out > 64;
   if (*wide && !gcn_wide_countable(ntiles, S, F, F_out)) return WGNN_ERR_SHAPE;
   if (!(*wide ? gcn_wide_supported(S, F, F_out) : gcn_any_supported(S, F, F_out))) return WGNN_ERR_UNSUPPORTED;

@@ -69,11 +69,13 @@ int wgnn_make_windows(const float* feat, int64_t Ttot, int32_t S, int32_t F, int
 
 int wgnn_predict_last(const float* Y, int32_t B, int32_t T, int32_t H, float wind_min, float wind_max, float* out,
                       void* stream) {
-  if (!Y || !out) return WGNN_ERR_NULL;
   if (B < 1 || T < 1 || H < 1) return WGNN_ERR_SHAPE;
+  if ((int64_t)B * H >= (1ll << 31)) return WGNN_ERR_SHAPE;   // one thread per element of out, counted in 32 bits
+  if (!Y || !out) return WGNN_ERR_NULL;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(predict_last_kernel, dim3(cdiv_i(B * H, 256)), dim3(256), 0, st, Y, B, T, H, wind_min, wind_max,
-                     out);
+  // (the block count in 64 bits: B * H + 255 does not fit an int from 2^31 - 255 elements on; the last thread's index does)
+  hipLaunchKernelGGL(predict_last_kernel, dim3((unsigned)(((int64_t)B * H + 255) / 256)), dim3(256), 0, st, Y, B, T, H, wind_min,
+                     wind_max, out);
   WGNN_CHECK_LAUNCH();
   return WGNN_OK;
 }
