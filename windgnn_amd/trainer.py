@@ -85,7 +85,17 @@ taken with wgnn_mse_loss_grad's dY -- so every schedule, clipping, keep_best and
 and no entry point of the library is added; the price is one pass over Y and L that the fused step does not have.  With fp16 /
 bf16 windows such a step runs on fp32 copies of X and L (_spec_forward), so that the loss is formed from the unrounded Y.
 `loss_count` is the step's count of labels.  Under a process group missing_labels=True is refused (the ranks' label counts
-would have to be exchanged); the other specs count the same (T - loss_from) * H entries per window on every rank."""
+would have to be exchanged); the other specs count the same (T - loss_from) * H entries per window on every rank.
+
+Accumulation (accumulate / accumulate_series / apply / discard): one optimiser step that sees several calls -- several series
+tensors, materialised and series windows mixed, or k calls per all-reduce under data parallel (DistributedDataParallel's no_sync).
+accumulate* is forward_backward* (a FINAL bucket at grad_scale 1) followed by one fused multiply-add of the bucket, header
+included, onto a second buffer of its size, weighted by the call's count of labels over the first call's (accumulate.py); apply
+scales the sum back into the bucket -- which is then the bucket of one call on the union of the windows, loss word included --
+and runs the tail every step runs on a final bucket (_run_schedule(d, _FINAL, gs), _end_step): one all-reduce under a process
+group, one wgnn_finish(0, adam) or the clipped pair, keep_best on the accumulated loss.  No kernel and no entry point of the
+library is added: the add and the scale are plain torch on the current stream, without a host read.  accumulate* issues no
+collective.  A TrainStep that never calls them is the object it was, launch for launch."""
 from __future__ import annotations
 
 import collections
@@ -93,6 +103,7 @@ import collections
 import torch
 
 from . import _lib
+from .accumulate import Accumulation
 from .distributed import HEADER, LOSS_SLOT, BucketExchange, grad_block_plan
 from .functional import (PARAM_ORDER, _forward_setup, _require_gpu, best_bytes, best_init, best_word, bwd_rows, check_range_status,
                          clip_buffer, clip_bytes, finish_clipped, finish_norm, finish_rows, finish_step,
@@ -275,6 +286,9 @@ class TrainStep:
         self.carry_state = carry_state
         self._hbuf, self._hcur, self._has_state = None, 0, False
         self._count = None              # loss_count: made by the first step on a loss spec
+        # accumulate / accumulate_series: the accumulator (one more buffer of the bucket's size, made by the first call and
+        # reused), what the open accumulation's calls must share, the tail's dims and this rank's windows so far
+        self._acc, self._acc_spec, self._acc_d, self._acc_windows = None, None, None, 0
 
     def _grad_block_plan(self, grad_blocks, sizes, carry_state, overlap_collectives, direct_rccl):
         """The blocked exchange's plan (distributed.grad_block_plan), or None for the one-bucket schedules."""
@@ -422,6 +436,7 @@ class TrainStep:
         "steps"; "best": None or the record's public words plus the snapshot under the reference's keys; "carry": the
         carried [B, H] state or None; and, only once validate_series has run, "val": the public words of the validation record
         (the last closed pass, `passes`, `stale`; an open pass raises).  The parameters are model.state_dict()'s."""
+        self._bucket_is_free("state_dict()")
         opt = torch.optim.Adam(self.params, lr=self.lr, betas=tuple(self.betas), eps=self.eps).state_dict()
         opt["state"] = {i: {"step": torch.tensor(float(self.steps)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
                         for i, (m, v) in enumerate(zip(self.m_views, self.v_views))}
@@ -442,6 +457,7 @@ class TrainStep:
         `state` is step 0).  Moments are written into the existing flat buffers, lr / betas / eps restored, and from the full
         form the best record + snapshot, the carried state and, when the checkpoint has one, the validation record ("val":
         val_passes, val_stale and the last closed pass).  Load the parameters with model.load_state_dict."""
+        self._bucket_is_free("load_state_dict()")
         full = "param_groups" not in sd
         opt = sd["optimizer"] if full else sd
         groups = opt["param_groups"]
@@ -675,18 +691,28 @@ class TrainStep:
         """src/main.py:66,72,79: returns (loss, Y); gradients land in the flat bucket (no optimiser step).  `loss` is a
         view of the bucket's header word (see the module docstring).  loss, huber_delta, loss_from, missing_labels: as in
         step."""
+        self._bucket_is_free("forward_backward")
+        return self._forward_backward(A, X, L, loss, huber_delta, loss_from, missing_labels)[:2]
+
+    def _forward_backward(self, A, X, L, loss, huber_delta, loss_from, missing_labels, admit=None):
+        """forward_backward's calls: (loss, Y, the call's dims, its counted labels -- a host integer, with missing_labels the
+        device scalar loss_count).  admit(windows, T, loss_from): accumulate's own refusals, after those of the keywords and
+        before any launch."""
         X, L = X.contiguous(), L.contiguous()
         spec = self._step_spec("forward_backward", X, L, loss, huber_delta, loss_from, missing_labels)
+        if admit is not None:
+            admit(X.shape[0], X.shape[1] if X.dim() == 4 else None, spec[2] if spec is not None else 0)
         if spec is not None:
             Xf, Y, stash, d, spec = self._spec_forward(A, X, spec)
             dY = self._spec_loss("forward_backward", Y, spec, 1.0)
             gcn_gru_backward_raw(d, A, Xf, self.p_views, Y, dY, stash, self.g_views, part=7, prepared=self._prepared)
-            return self._loss, Y.to(X.dtype)
+            count = self._count if spec[3] else Y.shape[0] * (Y.shape[1] - spec[2]) * Y.shape[2]
+            return self._loss, Y.to(X.dtype), d, count
         Y, stash, d = self._forward(A, X, L)
         loss = self._loss
         gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, loss, 1.0, part=7 | 8,
                                  prepared=self._prepared)
-        return loss, Y
+        return loss, Y, d, Y.numel()
 
     def _series_refusals(self, A, series, seq_len, stride, missing_labels=False):
         """What step_series / forward_backward_series refuse, each before any launch and with the alternative."""
@@ -776,6 +802,15 @@ class TrainStep:
         [>= (n - 1) * stride + seq_len, H]: returns (loss, Y [n, seq_len, H]); the gradients land in the flat bucket, final (no
         optimiser step).  `loss` is a view of the bucket's header word.  starts, missing_labels, loss, huber_delta, loss_from:
         as in step_series."""
+        self._bucket_is_free("forward_backward_series")
+        return self._forward_backward_series(A, series, Ls, seq_len, stride, n_windows, starts, missing_labels, loss,
+                                             huber_delta, loss_from)[:2]
+
+    def _forward_backward_series(self, A, series, Ls, seq_len, stride, n_windows, starts, missing_labels, loss, huber_delta,
+                                 loss_from, admit=None):
+        """forward_backward_series' calls: (loss, Y, the tail's dims, the call's counted labels -- a host integer, with
+        missing_labels the sum of the integer counts the masked forward leaves in loss_buf, a device scalar).  admit: as in
+        _forward_backward."""
         seq_len, table, inverse = int(seq_len), None, None
         self._series_refusals(A, series, seq_len, 1 if stride is None else int(stride), missing_labels)
         fn_f, fn_b = self._series_loss("forward_backward_series", seq_len, missing_labels, loss, huber_delta, loss_from)
@@ -788,12 +823,21 @@ class TrainStep:
         if n == 0:
             raise RuntimeError("windgnn_amd: TrainStep.forward_backward_series needs at least one window (a series of %d rows, "
                                "seq_len %d, n_windows %r)" % (series.shape[0], seq_len, n_windows))
+        if admit is not None:
+            admit(n, seq_len, int(loss_from))
         at = {} if table is None else {"starts": table}     # (the strided call is the call it has always been)
         masked = {"missing_labels": True} if missing_labels else {}     # (and so is the call without the flag)
-        Y, stash, loss_buf, sd, _ = self._series_forward(A, series, Ls, seq_len, stride, n, table, **masked, **fn_f)
+        Y, stash, loss_buf, sd, d = self._series_forward(A, series, Ls, seq_len, stride, n, table, **masked, **fn_f)
         series_backward_mse_raw(sd, A, series, self.p_views, Y, Ls, stash, loss_buf, self.g_views, self._loss, 1.0,
                                 prepared=self._prepared, **at, **masked, **fn_b)
-        return self._loss, (Y if inverse is None else Y.index_select(0, inverse))
+        if admit is None:               # (forward_backward_series: the call it has always been, launch for launch)
+            count = None
+        elif missing_labels:            # include/windgnn_series_masked.h: sums | maxima | tag + 3 words | uint32 counts
+            nb = -(-n // 16)
+            count = loss_buf[2 * nb + 4:3 * nb + 4].view(torch.int32).sum()
+        else:
+            count = n * (seq_len - int(loss_from)) * Y.shape[2]
+        return self._loss, (Y if inverse is None else Y.index_select(0, inverse)), d, count
 
     def step_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, n_global=None, starts=None,
                     missing_labels=False, loss="mse", huber_delta=1.0, loss_from=0):
@@ -817,6 +861,7 @@ class TrainStep:
         step, what the reference evaluates), while the gradient still flows back through the warm-up steps.  Both work with
         missing_labels, and under a process group without it (every window counts the same number of entries on every rank).
         The returned loss, keep_best, max_grad_norm and checkpoints see that loss; with the defaults the step is the one it was."""
+        self._bucket_is_free("step_series")
         seq_len, table, inverse = int(seq_len), None, None
         self._series_refusals(A, series, seq_len, 1 if stride is None else int(stride), missing_labels)
         fn_f, fn_b = self._series_loss("step_series", seq_len, missing_labels, loss, huber_delta, loss_from)
@@ -1121,6 +1166,7 @@ class TrainStep:
         the one it was.  Otherwise the loss and dY come from functional.loss_spec_grad on the forward's Y (module docstring); L
         is [B, T, H] ([T, H] at B = 1), fp32 or X's dtype; `loss_count` holds the labels counted; with no label at all the
         loss is NaN and the gradients are zero.  missing_labels=True is refused under a process group."""
+        self._bucket_is_free("step")
         X, L = X.contiguous(), L.contiguous()   # a strided batch slice is copied here, never read as if dense
         spec = self._step_spec("step", X, L, loss, huber_delta, loss_from, missing_labels)
         if X.shape[0] == 0:
@@ -1132,6 +1178,147 @@ class TrainStep:
             Y = (self._state_step if self.carry_state else self._spec_step)(A, X, L, gs, spec)
         self._end_step()
         return self._loss, Y
+
+    # ---- gradients accumulated over several calls, one optimiser step (accumulate.py has the arithmetic) ----------------------
+
+    @property
+    def accumulated(self):
+        """The calls in the open accumulation (a host int; 0: none is open)."""
+        return self._acc.calls if self._acc is not None else 0
+
+    @property
+    def accumulated_count(self):
+        """The labels the open accumulation has counted so far: a 0-dim int64 VIEW of the device value."""
+        if self._acc is None:
+            raise RuntimeError("windgnn_amd: TrainStep.accumulated_count is kept by accumulate / accumulate_series; no such call "
+                               "has run on this TrainStep yet")
+        return self._acc.count
+
+    def _bucket_is_free(self, who):
+        """step / step_series / forward_backward* / state_dict() / load_state_dict() while an accumulation is open."""
+        if self.accumulated:
+            raise RuntimeError("windgnn_amd: TrainStep.%s while an accumulation is open (%d call%s since the last apply() / "
+                               "discard()): it writes or reads the gradient bucket and the step count that the accumulation owns "
+                               "until its optimiser step; finish it with apply(), or drop it with discard(), first"
+                               % (who, self.accumulated, "" if self.accumulated == 1 else "s"))
+
+    def _accumulate_refusals(self, who, loss, huber_delta):
+        """What accumulate / accumulate_series refuse on top of forward_backward*'s own refusals; returns the admit callback
+        of _forward_backward*, which holds those that need the call's shape."""
+        who = "windgnn_amd: TrainStep." + who
+        one_bucket = ("an accumulation is final only at apply(), whose exchange and optimiser run on the one-bucket schedule; build "
+                      "the TrainStep without it, or take one step() per batch")
+        if self.plan is not None:
+            raise RuntimeError("%s with grad_blocks: the blocked exchange steps row blocks of the GRU weights before the whole "
+                               "bucket exists; %s" % (who, one_bucket))
+        if self.overlap_collectives:
+            raise RuntimeError("%s with overlap_collectives=True: that schedule steps the GRU tensors before the whole bucket "
+                               "exists; %s" % (who, one_bucket))
+        if self.carry_state:
+            raise RuntimeError("%s with carry_state=True: that would be truncated BPTT with one optimiser step per k chunks, a "
+                               "follow-up that is not built; take one step() per chunk, or build the TrainStep with "
+                               "carry_state=False (every window starts from h = 0)" % who)
+
+        def admit(windows, T, t_from):
+            kind = self._loss_kind(loss, huber_delta)
+            if windows == 0:
+                raise RuntimeError("%s needs at least one window; a rank without windows skips the call and still calls apply() "
+                                   "(the empty-shard form of the step)" % who)
+            if self._acc_spec is None:
+                return
+            if kind != self._acc_spec[0]:
+                was = "loss=%r" % self._acc_spec[0][0] + ("" if self._acc_spec[0][1] is None
+                                                          else ", huber_delta=%r" % self._acc_spec[0][1])
+                raise RuntimeError("%s: loss=%r, huber_delta=%r, but the open accumulation holds calls on %s: their sum would no "
+                                   "longer be one loss; apply() or discard() first, or pass the same loss (huber_delta counts "
+                                   "with loss='huber' only)" % (who, loss, huber_delta, was))
+            if self.collective and (T, t_from) != self._acc_spec[1]:
+                raise RuntimeError("%s under a process group: this call has (T, loss_from) = (%r, %r), the open accumulation's "
+                                   "calls (%r, %r); a rank's weight in the exchange is its share of the WINDOWS, which is its share "
+                                   "of the labels only while every window counts the same number of steps; apply() first, or "
+                                   "accumulate calls of one (T, loss_from)" % ((who, T, t_from) + self._acc_spec[1]))
+        return admit
+
+    @staticmethod
+    def _loss_kind(loss, huber_delta):
+        """What the calls of one accumulation share of the loss (huber_delta counts with loss="huber" only)."""
+        return loss, float(huber_delta) if loss == "huber" else None
+
+    def _accumulate(self, kind, out, windows, T, t_from):
+        """The add onto the accumulator after a forward_backward*: the last thing a call does, so a call that raises anywhere
+        before leaves the accumulation as it was."""
+        loss, Y, d, count = out
+        if self._acc is None:
+            self._acc = Accumulation(self._gbuf)
+        self._acc.add(self._gbuf, count)
+        if self._acc_spec is None:
+            self._acc_spec, self._acc_windows = (kind, (T, t_from)), 0
+        self._acc_d, self._acc_windows = d, self._acc_windows + windows
+        return loss.clone(), Y          # (a clone: the header word is the next call's)
+
+    def accumulate(self, A, X, L, *, loss="mse", huber_delta=1.0, loss_from=0, missing_labels=False):
+        """forward_backward(A, X, L, ...) followed by an add onto the accumulator: no optimiser step, no collective.  apply()
+        then takes ONE optimiser step on everything accumulated since the last apply() / discard(), exactly the step of one
+        call on the union of the windows: the gradient of the mean loss over all counted labels of all calls (a call's weight is
+        its count of labels -- with missing_labels the labels that exist, a device scalar -- not its windows).  Calls of this
+        kind and accumulate_series may alternate; they must share loss / huber_delta.  Returns (this call's own loss as a
+        0-dim clone, Y).  Refused: grad_blocks, overlap_collectives and carry_state (by name), and what forward_backward
+        refuses; while an accumulation is open, step / step_series / forward_backward* / state_dict() / load_state_dict()."""
+        admit = self._accumulate_refusals("accumulate", loss, huber_delta)
+        out = self._forward_backward(A, X, L, loss, huber_delta, loss_from, missing_labels, admit)
+        return self._accumulate(self._loss_kind(loss, huber_delta), out, X.shape[0], X.shape[1], int(loss_from))
+
+    def accumulate_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, starts=None, missing_labels=False,
+                          loss="mse", huber_delta=1.0, loss_from=0):
+        """accumulate on the sliding windows of one series: forward_backward_series(...) followed by the same add (several
+        series tensors -- sites, years, folds -- in one optimiser step; two seq_len on one rank).  Returns (this call's own loss
+        as a 0-dim clone, Y)."""
+        admit = self._accumulate_refusals("accumulate_series", loss, huber_delta)
+        out = self._forward_backward_series(A, series, Ls, seq_len, stride, n_windows, starts, missing_labels, loss,
+                                            huber_delta, loss_from, admit)
+        return self._accumulate(self._loss_kind(loss, huber_delta), out, out[1].shape[0], int(seq_len), int(loss_from))
+
+    def _tail_dims(self):
+        """Dims for the optimiser's launch of a rank that has never run a forward: S, H and the math mode size it, as they
+        size wgnn_keep_best's (B, T and the adjacency do not enter)."""
+        return _lib.Dims(1, 1, self.params[4].shape[1] // 13, 13, self.params[5].shape[1], self.model.math, _lib.ADJ_CSR, 1,
+                         _lib.IO_F32)
+
+    def apply(self, n_global=None):
+        """ONE optimiser step on everything accumulated since the last apply() / discard(): the bucket and the loss word become
+        those of one call on the union (accumulate.py), then the tail of every step -- under a process group one all-reduce
+        of the whole bucket, then wgnn_finish(0, adam) (wgnn_finish_norm + wgnn_finish_clipped with max_grad_norm), keep_best on
+        the accumulated loss, `steps` + 1, the periodic check().  Returns the loss, the same 0-dim VIEW step() returns.
+        n_global (process group): the windows of ALL ranks and ALL calls of this accumulation; None = the count collective, as
+        in step().  A rank that accumulated nothing still calls apply(): zero bucket, weight 0, the same collectives.  On one
+        rank apply() with nothing accumulated is refused.  An apply() that raises counts nothing and leaves the accumulation
+        open; as after a step that raised, rebuild from a checkpoint rather than retry (discard() first: state_dict() is
+        refused while it is open)."""
+        n = self.accumulated
+        if n == 0:
+            if not self.collective:
+                raise RuntimeError("windgnn_amd: TrainStep.apply(): nothing was accumulated since the last apply() / discard(); "
+                                   "call accumulate() or accumulate_series() first (only under a process group does a rank "
+                                   "without windows call apply() alone: it joins the collectives with a zero bucket)")
+            d = self._acc_d if self._acc_d is not None else self._tail_dims()
+            self._ensure_images(lambda: d)
+            gs = self.exchange.shard_weight(0, n_global)               # 0.0; the count collective, if any, is issued
+            self._gbuf.zero_()
+        else:
+            d = self._acc_d
+            gs = self.exchange.shard_weight(self._acc_windows, n_global) if self.collective else 1.0
+            self._acc.write(self._gbuf, LOSS_SLOT, gs)
+        self._run_schedule(d, _FINAL, gs)       # the bucket is final: (the all-reduce,) Adam and the W_ih images
+        self._end_step(check=n > 0)             # (an empty rank reads nothing from the device, as in _empty_shard_step)
+        self.discard()
+        return self._loss
+
+    def discard(self):
+        """Drop the open accumulation: parameters, moments, `steps` and the best record are untouched, nothing is launched
+        (the next accumulation's first call overwrites the accumulator)."""
+        if self._acc is not None:
+            self._acc.reset()
+        self._acc_spec, self._acc_windows = None, 0
 
     def close(self):
         """Release the step's own RCCL communicator, if it has one (before torch.distributed.destroy_process_group).
