@@ -3,5 +3,6 @@ the reference's own nn.Module API.  See DESIGN.md / INTEGRATION.md."""
 from .evaluate import Evaluator  # noqa: F401
 from .modules import GCN_GRU, GraphConvLayer  # noqa: F401
 from .streaming import StreamingForecaster  # noqa: F401
+from .ensemble import Ensemble, EnsembleForecast, PerMember  # noqa: F401
 
-__all__ = ["Evaluator", "GCN_GRU", "GraphConvLayer", "StreamingForecaster"]
+__all__ = ["Ensemble", "EnsembleForecast", "Evaluator", "GCN_GRU", "GraphConvLayer", "PerMember", "StreamingForecaster"]

@@ -74,6 +74,36 @@ def starts_coverage(starts, seq_len: int, rows: int) -> np.ndarray:
     return np.stack([np.searchsorted(st, tau - seq_len, side="right"), np.searchsorted(st, tau, side="right")], axis=1)
 
 
+def kfold_starts(starts, k: int, seq_len: int, horizon: int = 3):
+    """k folds of a table of window starts, blocked in time and purged: [(train, val)] * k, int64 numpy arrays.  The sorted
+    table is cut into k blocks of consecutive entries (the first len % k one longer); block j is fold j's validation table.
+    A window at row s reads rows [s, s + seq_len) and its labels reach `horizon` rows further, so its footprint is
+    [s, s + seq_len + horizon).  Fold j's training table is every start of the other blocks whose footprint does not intersect
+    the footprint of any window of block j: what a training window or its labels would share with a validation window or its
+    labels is dropped (the windows next to a block's ends; a duplicate of a validation start).  Together with
+    ens.step_series(..., starts=PerMember(trains)) and ens.validate_series(..., starts=PerMember(vals)) this is a blocked
+    cross-validation with one Ensemble member per fold.  numpy, no device."""
+    st = np.asarray(starts)
+    if st.ndim != 1 or (st.size and st.dtype.kind not in "iu"):
+        raise ValueError("kfold_starts: starts must be a 1-D sequence of integers, got dtype %s, shape %s" % (st.dtype, st.shape))
+    if int(seq_len) < 1 or int(horizon) < 0:
+        raise ValueError("kfold_starts: seq_len must be >= 1 and horizon >= 0, got %r and %r" % (seq_len, horizon))
+    if int(k) != k or int(k) < 2:
+        raise ValueError("kfold_starts: k=%r: at least two folds (one fold would validate on everything and train on nothing)" % (k,))
+    if int(k) > st.size:
+        raise ValueError("kfold_starts: k=%d folds of a table of %d starts: every fold needs a window to validate on" % (k, st.size))
+    st = np.sort(st.astype(np.int64), kind="stable")
+    span = int(seq_len) + int(horizon)
+    out = []
+    for val in np.array_split(st, int(k)):
+        # footprints of one length intersect iff the starts are closer than it: the nearest validation start above s - span
+        i = np.searchsorted(val, st - span, side="right")
+        near = val[np.minimum(i, val.size - 1)]
+        touches = (i < val.size) & (near < st + span)
+        out.append((st[~touches], val.copy()))
+    return out
+
+
 def _upload(t: torch.Tensor, device) -> torch.Tensor:
     """A host tensor on `device`, stream-ordered: from pinned memory, so the host does not wait for the work already queued on the
     current stream (a pageable upload would, and the calls that take a table promise not to synchronise)."""
