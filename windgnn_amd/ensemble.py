@@ -241,7 +241,9 @@ class Ensemble:
         return self._fan("step", ("A", "X", "L"), (A, X, L), kw)
 
     def step_series(self, A, series, Ls, seq_len, **kw):
-        """TrainStep.step_series of every member (stride / n_windows / starts, missing_labels and the loss spec by keyword);
+        """TrainStep.step_series of every member (stride / n_windows / starts, missing_labels, the loss spec and compact by
+        keyword -- compact= goes through **kw to every member here and in forward_backward_series / validate_series, and each
+        member compacts its own table: members on different folds of one series each run the front end on their fold's hours);
         the list of the members' (loss, Y)."""
         return self._fan("step_series", ("A", "series", "Ls", "seq_len"), (A, series, Ls, seq_len), kw)
 
@@ -335,16 +337,17 @@ class Ensemble:
         return EnsembleForecast(mean, std, members)
 
     def forward_last_series(self, adj, series, seq_len, wind_min, wind_max, stride=None, n_windows=None, starts=None,
-                            use_best=False):
+                            use_best=False, compact=False):
         """The rolling backtest of every member (series.forward_last_series) as EnsembleForecast(mean, std, members):
         members [K, n, 3S] holds each member's de-normalised last rows, exactly what the member returns alone; mean and std
         [n, 3S] are mean_std's.  use_best=True: from each member's best snapshot (TrainStep(keep_best=...)) instead of its
         current parameters; a member that has kept nothing yet (best_step = -1) forecasts from a snapshot of zeros.  starts may
-        be a PerMember of tables of one length."""
+        be a PerMember of tables of one length.  compact: series.forward_last_series', passed to every member."""
         from .series import forward_last_series as one
         who = "forward_last_series"
         models = self._forecast_models(who, use_best)
-        per = self._resolve(who, ("adj", "series"), (adj, series), dict(stride=stride, n_windows=n_windows, starts=starts))
+        per = self._resolve(who, ("adj", "series"), (adj, series), dict(stride=stride, n_windows=n_windows, starts=starts,
+                                                                      **({"compact": compact} if compact is not False else {})))
         counts = []
         for (a, kw) in per:
             if kw["starts"] is not None:

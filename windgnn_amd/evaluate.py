@@ -172,18 +172,21 @@ class Evaluator:
         return pred
 
     def update_series(self, series: torch.Tensor, Ls: torch.Tensor, seq_len: int, stride: Optional[int] = None, n_windows=None,
-                      starts=None, skip_missing: bool = False) -> torch.Tensor:
+                      starts=None, skip_missing: bool = False, compact=False) -> torch.Tensor:
         """The rolling backtest on ONE series: series.forward_last_series(model, adj, series, seq_len, ...) followed by
         wgnn_eval_accum_series against the label series Ls [ls_rows, 3S] (series.series_labels' first result: the truth of a
         window that starts at row s is row s + seq_len - 1).  Returns the [n, 3S] forecasts in the caller's order (starts= in any
         order, duplicates allowed; otherwise stride, default 1, and n_windows).  No [n, T, 3S] label tensor is built and nothing
         synchronises with the host.  skip_missing=True: a NaN in Ls is "no truth here" -- that station and horizon is left out of
         this window's sums and of its column's count, so the counts differ per column (compute().header[0]; compute().count is
-        column 0's); a column that never saw a truth has count 0 and NaN figures."""
+        column 0's); a column that never saw a truth has count 0 and NaN figures.  compact (with starts= only): the forecasts'
+        front end on the covered hours alone, as in TrainStep.step_series; the truths are still looked up in Ls at the
+        caller's starts."""
         from .series import _no_stride_with_starts, _starts_table, forward_last_series
         _no_stride_with_starts("Evaluator.update_series", stride, starts, n_windows)
         seq_len = int(seq_len)
-        pred = forward_last_series(self.model, self.adj, series, seq_len, self.wind_min, self.wind_max, stride, n_windows, starts)
+        pred = forward_last_series(self.model, self.adj, series, seq_len, self.wind_min, self.wind_max, stride, n_windows, starts,
+                                   **({} if compact is False else {"compact": compact}))
         table = None
         if starts is not None:      # in the caller's order, as the rows of pred are (the kernel only looks the table up)
             table = _starts_table(starts, series.shape[0], seq_len, series.device, "Evaluator.update_series", ordered=False)

@@ -101,7 +101,7 @@ class GCN_GRU(nn.Module):
             check_range_status(out.device)
         return out.squeeze(0)            # step6:26
 
-    def forward_series(self, adj_matrix, series, seq_len, stride=None, n_windows=None, starts=None):
+    def forward_series(self, adj_matrix, series, seq_len, stride=None, n_windows=None, starts=None, compact=False):
         """[n, seq_len, gru_hidden_dim]: forward() on every window of `series` [rows, S, 13] -- window w covers rows
         w*stride .. w*stride + seq_len - 1, n = n_windows or (rows - seq_len) // stride + 1, h0 = 0 each -- without building them:
         the graph convolutions and the input projection run once per hour (windgnn_amd/series.py).  Differentiable in the
@@ -110,17 +110,20 @@ class GCN_GRU(nn.Module):
         duplicates allowed (series.segment_starts: the windows inside clean segments; a hold-out; a shuffled mini-batch); row i
         of the result is the window at starts[i].  The table is sorted on the device without a synchronisation, and the
         parameter gradients do not depend on its order.  A host table is checked before the upload (ValueError); a device
-        table by the kernel (check_range_status)."""
-        from .series import _no_stride_with_starts, _require_fused, gcn_gru_series, sorted_starts
+        table by the kernel (check_range_status).  compact (with starts= only; False | True | "auto" | an int bound on the covered
+        hours, as in TrainStep.step_series): the graph convolutions and the input projection run on the hours some window
+        covers alone -- the gather of those rows sits outside the autograd function, and the series takes no gradient."""
+        from .series import _compact_arg, _no_stride_with_starts, _require_fused, compacted_starts, gcn_gru_series
         _require_fused(self, "GCN_GRU.forward_series")
         if series.dim() != 3 or series.shape[2] != NUM_FEATURES or series.shape[1] * NUM_FEATURES != self.gru.input_size:
             raise RuntimeError("GCN_GRU.forward_series: series must be [rows, %d, 13], got %s"
                                % (self.gru.input_size // NUM_FEATURES, tuple(series.shape)))
         _no_stride_with_starts("GCN_GRU.forward_series", stride, starts, n_windows)
+        _compact_arg("GCN_GRU.forward_series", compact, starts, stride)
         if starts is None:
             return gcn_gru_series(adj_matrix, series, seq_len, 1 if stride is None else stride, self.hot_path_parameters(),
                                   self.math, n_windows)
-        table, inverse = sorted_starts(starts, series.shape[0], int(seq_len), series.device, "GCN_GRU.forward_series")
+        series, _, table, inverse = compacted_starts(starts, series, None, int(seq_len), "GCN_GRU.forward_series", compact)
         Y = gcn_gru_series(adj_matrix, series, seq_len, None, self.hot_path_parameters(), self.math, starts=table)
         return Y if inverse is None else Y.index_select(0, inverse)
 

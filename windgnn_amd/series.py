@@ -6,13 +6,14 @@ those of GCN_GRU.forward on the materialised windows (make_windows(starts=...)).
 convolutions and the GRU's input projection -- runs once per hour instead of once per window and hour.
 
 With `starts` (include/windgnn_series_at.h) the windows begin at a table of rows instead of w*stride: a series with outages
-(segment_starts), a hold-out at window level, a shuffled mini-batch.  The front end still runs on every row of the series passed.
+(segment_starts), a hold-out at window level, a shuffled mini-batch.  The front end then runs on every row of the series passed,
+or with compact= (compact_table) on the rows some window covers alone.
 
 Exact fp32 with a dense adjacency (S <= 64) and H <= 128 only; everything else raises and names the materialised path."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Sequence, Tuple
+from typing import List, NamedTuple, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -159,6 +160,145 @@ def sorted_starts(starts, rows: int, seq_len: int, device, who: str):
     inverse = torch.empty_like(order)
     inverse[order] = torch.arange(order.numel())
     return _upload(table, device), _upload(inverse, device)
+
+
+# ---- covered hours only ------------------------------------------------------------------------------------------------------
+# compact="auto" compacts when the compacted series has at most this share of the rows, as measured on step_series at the
+# reference's widths (profiles/r22_series_compact_cost.txt, DESIGN.md section 5, "Covered hours only"): a host table up to 0.37; a
+# device table never (the dozen small launches of the device-side compaction cost a step more than the shorter front end
+# saves), and neither do the forward-only calls (validate_series, forward_last_series)
+COMPACT_AUTO_THETA = 0.37
+COMPACT_AUTO_THETA_DEVICE = 0.0
+
+
+class CompactTable(NamedTuple):
+    """compact_table's record.  hours [rows_c] int64: the series row behind every row of the compacted series; table [n] int32:
+    the windows' starts in the compacted series; rows_c: its row count (a host int); covered: m, the number of hours any window
+    covers (a host int for a host table, a 0-dim device tensor for a device table)."""
+    hours: torch.Tensor
+    table: torch.Tensor
+    rows_c: int
+    covered: object
+
+    def apply(self, series: torch.Tensor, Ls: torch.Tensor):
+        """(series_c, Ls_c): the rows `hours` of the series and of the label series (NaN labels travel unchanged)."""
+        return series.index_select(0, self.hours), Ls.index_select(0, self.hours)
+
+
+def _is_device_table(starts) -> bool:
+    return isinstance(starts, torch.Tensor) and starts.device.type != "cpu"
+
+
+def compact_table(starts, rows: int, seq_len: int, cover_bound=None, device=None) -> CompactTable:
+    """The windows of a NON-DECREASING table as windows of the series' COVERED hours alone.  C = the ascending hours
+    U_w [starts[w], starts[w] + seq_len), m = |C|: hours[c] = C[c], table[w] = the rank of starts[w] in C, so that
+    hours[table[w] + t] == starts[w] + t -- a window covers seq_len consecutive hours, hence seq_len consecutive ranks -- and
+    a series call on (series[hours], Ls[hours], table) is the call on (series, Ls, starts) with a front end of rows_c rows.
+    starts: what sorted_starts returns, checked as _starts_table checks it.
+    A host table (list, numpy, CPU tensor): numpy on the host, rows_c = m exactly; the results are uploaded to `device` (None:
+    they stay on the host) from pinned memory, as sorted_starts uploads.
+    A device table: torch operations on the current stream with no host read and no data-dependent shape, so rows_c is the
+    bound min(rows, n * seq_len) -- or min(rows, cover_bound), the caller's promise that the table covers at most that many
+    hours -- and the rows m .. rows_c - 1, which no window covers, repeat hour C[0] (real, finite data).  A start outside
+    [0, rows - seq_len] is clamped before it indexes anything and its window gets the entry -1, as does a window whose ranks
+    do not fit under cover_bound: the table entry points then report WGNN_STATUS_WINDOW_START, as for any bad device table.
+    device="cpu" with a host table runs that same arithmetic on CPU tensors."""
+    rows, T = int(rows), int(seq_len)
+    if T < 1 or rows < T:
+        raise ValueError("compact_table: no window of %d rows fits into a series of %d rows" % (T, rows))
+    if cover_bound is not None and (isinstance(cover_bound, bool) or int(cover_bound) != cover_bound or int(cover_bound) < T):
+        raise ValueError("compact_table: cover_bound=%r must be an integer >= seq_len = %d, the hours one window covers"
+                         % (cover_bound, T))
+    on_device = _is_device_table(starts)
+    if on_device and device is not None and torch.device(device) != starts.device:
+        raise ValueError("compact_table: starts is on %s, device= says %s" % (starts.device, device))
+    if not on_device and (device is None or torch.device(device).type != "cpu"):
+        st = _starts_table(starts, rows, T, "cpu", "compact_table", ordered=True).numpy().astype(np.int64)
+        if st.size < 1:
+            raise ValueError("compact_table: the table of starts is empty")
+        diff = np.zeros(rows + 1, dtype=np.int64)
+        np.add.at(diff, st, 1)
+        np.add.at(diff, st + T, -1)
+        cov = np.cumsum(diff[:rows]) > 0
+        hours = np.flatnonzero(cov)
+        m = int(hours.size)
+        if cover_bound is not None and m > int(cover_bound):
+            raise ValueError("compact_table: the table covers %d hours, more than cover_bound=%d" % (m, int(cover_bound)))
+        table = (np.cumsum(cov) - cov)[st].astype(np.int32)
+        to = "cpu" if device is None else device
+        return CompactTable(_upload(torch.from_numpy(hours), to), _upload(torch.from_numpy(table), to), m, m)
+    if not isinstance(starts, torch.Tensor):
+        starts = _starts_table(starts, rows, T, "cpu", "compact_table", ordered=True)
+    if starts.dtype not in (torch.int32, torch.int64) or starts.dim() != 1 or starts.numel() < 1:
+        raise ValueError("compact_table: starts must be a 1-D int32 / int64 tensor of at least one entry, got %s %s"
+                         % (starts.dtype, tuple(starts.shape)))
+    dev, n = starts.device, starts.numel()
+    rows_c = min(rows, n * T if cover_bound is None else int(cover_bound))
+    s = starts.to(torch.int64)
+    ok = (s >= 0) & (s <= rows - T)
+    s = s.clamp(0, rows - T)                            # from here on every index is in range, whatever the table held
+    one = ok.to(torch.int64)
+    diff = torch.zeros(rows + 1, dtype=torch.int64, device=dev)
+    diff.index_add_(0, s, one)                          # (integer adds: any order gives the same sums)
+    diff.index_add_(0, s + T, -one)
+    cov = (diff[:rows].cumsum(0) > 0).to(torch.int64)
+    incl = cov.cumsum(0)
+    rank, m = incl - cov, incl[rows - 1]
+    tau = torch.arange(rows, dtype=torch.int64, device=dev)
+    slot = torch.where((cov > 0) & (rank < rows_c), rank, torch.full_like(rank, rows_c))      # rows_c: the dump slot
+    hours = torch.zeros(rows_c + 1, dtype=torch.int64, device=dev).scatter_(0, slot, tau)[:rows_c]
+    c = torch.arange(rows_c, dtype=torch.int64, device=dev)
+    hours = torch.where(c < m, hours, hours[0])         # (m = 0: every window was bad, and hour 0 is as real as any)
+    t = rank.index_select(0, s)
+    table = torch.where(ok & (t + T <= rows_c), t, torch.full_like(t, -1)).to(torch.int32)
+    return CompactTable(hours, table, rows_c, m)
+
+
+def _compact_arg(who: str, compact, starts, stride=None):
+    """compact= of a series call as (wanted, auto, cover_bound); refused by name before any launch where it makes no sense."""
+    if compact is False or compact is None:
+        return False, False, None
+    if not (compact is True or compact == "auto" or (isinstance(compact, int) and not isinstance(compact, bool))):
+        raise ValueError("%s: compact=%r: False, True, 'auto', or an int, the number of hours the table covers at most"
+                         % (who, compact))
+    if starts is None or stride not in (None, 0):
+        raise ValueError("%s: compact=%r belongs to starts=: the strided windows cover the series densely, so there is no hour to "
+                         "drop (got %s)" % (who, compact, "stride=%r" % (stride,) if stride not in (None, 0) else "no table of starts"))
+    if isinstance(compact, int) and not isinstance(compact, bool):
+        return True, False, int(compact)
+    return True, compact == "auto", None
+
+
+def compacted_starts(starts, series, Ls, seq_len: int, who: str, compact, forward_only=False):
+    """sorted_starts for a call that takes compact=: (series, Ls, table, inverse) -- the series and the label series the raw
+    calls get (Ls may be None), the sorted int32 device table into them, and sorted_starts' inverse permutation.  With
+    compact=False, with a table that leaves no row to drop (rows_c == rows) and with "auto" above COMPACT_AUTO_THETA (a host
+    table; COMPACT_AUTO_THETA_DEVICE for a device table; never for a forward_only call) these are the series as it is and
+    sorted_starts' own results; otherwise compact_table's, the host table compacted on the host and uploaded once.  Ls must
+    have been checked to hold a row per series row."""
+    want, auto, bound = _compact_arg(who, compact, starts)
+    rows, T, device = series.shape[0], int(seq_len), series.device
+    if not want:
+        return (series, Ls, *sorted_starts(starts, rows, T, device, who))
+    if bound is not None and bound < T:
+        raise ValueError("%s: compact=%d: a table covers at least the seq_len = %d hours of one window" % (who, bound, T))
+    on_device = _is_device_table(starts)
+    table, inverse = sorted_starts(starts, rows, T, device if on_device else "cpu", who)
+    theta = 0.0 if forward_only else (COMPACT_AUTO_THETA_DEVICE if on_device else COMPACT_AUTO_THETA)
+    pays = lambda rows_c: rows_c < rows and not (auto and rows_c > theta * rows)   # noqa: E731
+    ct = None
+    if table.numel() >= 1 and on_device:
+        if pays(min(rows, table.numel() * T if bound is None else bound)):
+            ct = compact_table(table, rows, T, bound)
+    elif table.numel() >= 1:
+        ct = compact_table(table, rows, T, bound)
+        ct = ct if pays(ct.rows_c) else None
+    if not on_device:       # one upload each, after the decision: the sorted table or the compacted one, never both
+        table, inverse = (_upload(table, device) if ct is None else None), (None if inverse is None else _upload(inverse, device))
+        ct = ct and CompactTable(_upload(ct.hours, device), _upload(ct.table, device), ct.rows_c, ct.covered)
+    if ct is None:
+        return series, Ls, table, inverse
+    return series.index_select(0, ct.hours), (None if Ls is None else Ls.index_select(0, ct.hours)), ct.table, inverse
 
 
 def _no_stride_with_starts(who: str, stride, starts, n_windows=None) -> None:
@@ -479,21 +619,24 @@ def _require_fused(model, who: str) -> None:
 
 
 def forward_last_series(model, adj_matrix, series: torch.Tensor, seq_len: int, wind_min: float, wind_max: float,
-                        stride: int = None, n_windows=None, starts=None) -> torch.Tensor:
+                        stride: int = None, n_windows=None, starts=None, compact=False) -> torch.Tensor:
     """The rolling backtest: [n, 3S] de-normalised forecasts, one per window, each from its own zero-state seq_len-hour
     window (wgnn_series_fwd_last; no Y is written).  The rows are what forward_last gives on the materialised windows and feed
     evaluate.eval_accum as they are.  stride defaults to 1.  starts (instead of stride / n_windows): the windows at that table
-    of rows, in any order; row i of the result belongs to starts[i]."""
+    of rows, in any order; row i of the result belongs to starts[i].  compact (with starts= only): the front end on the covered
+    hours alone, as in TrainStep.step_series."""
     lib = _lib.load()
     _require_fused(model, "forward_last_series")
     _no_stride_with_starts("forward_last_series", stride, starts, n_windows)
+    _compact_arg("forward_last_series", compact, starts, stride)
     params = [p.detach().contiguous() for p in model.hot_path_parameters()]
     series = series.contiguous()
     inverse = None
     if starts is not None:
         if series.dim() != 3:
             raise RuntimeError("windgnn_amd: series must be [rows, S, 13], got %s" % (tuple(series.shape),))
-        starts, inverse = sorted_starts(starts, series.shape[0], int(seq_len), series.device, "forward_last_series")
+        series, _, starts, inverse = compacted_starts(starts, series, None, int(seq_len), "forward_last_series", compact,
+                                                      forward_only=True)
     A, sd, ws, ws_bytes, *table = _series_setup(adj_matrix, series, int(seq_len), None if starts is not None else
                                                 int(1 if stride is None else stride), params, model.math, n_windows, starts)
     out = torch.empty(sd.n, sd.H, dtype=torch.float32, device=series.device)

@@ -113,8 +113,8 @@ from .functional import (PARAM_ORDER, _forward_setup, _require_gpu, best_bytes, 
                          refresh_prepared, rows_align, val_add, val_begin, val_buffer, val_close, val_init, val_word,
                          validation_spec, validation_terms)
 from .modules import GCN_GRU
-from .series import (_no_stride_with_starts, _starts_table, loss_spec, n_series_windows, series_backward_mse_raw,
-                     series_forward_loss_raw, series_val_raw, sorted_starts, val_spec)
+from .series import (_compact_arg, _no_stride_with_starts, _starts_table, compacted_starts, loss_spec, n_series_windows,
+                     series_backward_mse_raw, series_forward_loss_raw, series_val_raw, val_spec)
 
 AUTO_GRAD_BLOCKS = 8                # grad_blocks="auto": row blocks per GRU weight ...
 AUTO_BLOCK_BYTES = 64 << 20         # ... from a gradient bucket of this size (smaller ones are latency-bound: one bucket)
@@ -760,17 +760,26 @@ class TrainStep:
                                                          n_windows=n, prepared=self._prepared, **masked)
         return Y, stash, loss_buf, sd, d
 
-    def _series_table(self, series, Ls, seq_len, stride, n_windows, starts, who="step_series"):
-        """starts= of step_series / forward_backward_series: (sorted device table, inverse or None, n) with the label series
-        checked -- a window may start at any row, so Ls needs a row for every row of the series."""
+    def _series_table(self, series, Ls, seq_len, stride, n_windows, starts, who="step_series", compact=False):
+        """starts= of step_series / forward_backward_series: (series, Ls, sorted device table, inverse or None, n) with the label
+        series checked -- a window may start at any row, so Ls needs a row for every row of the series.  compact=
+        (series.compacted_starts): the series and the label series come back as their covered rows and the table points into
+        them; Ls is then checked first, since its rows are gathered."""
         _no_stride_with_starts("windgnn_amd: TrainStep." + who, stride, starts, n_windows)
-        table, inverse = sorted_starts(starts, series.shape[0], seq_len, series.device, "windgnn_amd: TrainStep." + who)
         H = self.p_views[5].shape[1]
-        if table.numel() > 0 and (Ls.dim() != 2 or Ls.shape[1] != H or Ls.shape[0] < series.shape[0]):
-            raise RuntimeError("windgnn_amd: TrainStep." + who + ": with starts= the label series Ls must be [rows >= the "
-                               "series' %d, H = %d] (series_labels(feat, ...)[0] of a feat 3 rows longer than the series), got %s"
-                               % (series.shape[0], H, tuple(Ls.shape)))
-        return table, inverse, table.numel()
+
+        def labels_fit():
+            if Ls.dim() != 2 or Ls.shape[1] != H or Ls.shape[0] < series.shape[0]:
+                raise RuntimeError("windgnn_amd: TrainStep." + who + ": with starts= the label series Ls must be [rows >= the "
+                                   "series' %d, H = %d] (series_labels(feat, ...)[0] of a feat 3 rows longer than the series), "
+                                   "got %s" % (series.shape[0], H, tuple(Ls.shape)))
+        if compact is not False:
+            labels_fit()
+        series_c, Ls_c, table, inverse = compacted_starts(starts, series, Ls, seq_len, "windgnn_amd: TrainStep." + who, compact,
+                                                          forward_only=who == "validate_series")
+        if table.numel() > 0:
+            labels_fit()
+        return series_c, Ls_c, table, inverse, table.numel()
 
     def _series_count(self, series, Ls, seq_len, stride, n_windows, who="step_series"):
         """The window count of this call, with n_windows and Ls checked against it."""
@@ -797,26 +806,27 @@ class TrainStep:
         return dict(rest, loss=loss), dict(rest, loss_kind=loss)
 
     def forward_backward_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, starts=None, missing_labels=False,
-                                loss="mse", huber_delta=1.0, loss_from=0):
+                                loss="mse", huber_delta=1.0, loss_from=0, compact=False):
         """forward_backward on the first n_windows sliding windows of `series` [rows, S, 13] with the label series Ls
         [>= (n - 1) * stride + seq_len, H]: returns (loss, Y [n, seq_len, H]); the gradients land in the flat bucket, final (no
-        optimiser step).  `loss` is a view of the bucket's header word.  starts, missing_labels, loss, huber_delta, loss_from:
-        as in step_series."""
+        optimiser step).  `loss` is a view of the bucket's header word.  starts, missing_labels, loss, huber_delta, loss_from,
+        compact: as in step_series."""
         self._bucket_is_free("forward_backward_series")
         return self._forward_backward_series(A, series, Ls, seq_len, stride, n_windows, starts, missing_labels, loss,
-                                             huber_delta, loss_from)[:2]
+                                             huber_delta, loss_from, compact=compact)[:2]
 
     def _forward_backward_series(self, A, series, Ls, seq_len, stride, n_windows, starts, missing_labels, loss, huber_delta,
-                                 loss_from, admit=None):
+                                 loss_from, admit=None, compact=False, who="forward_backward_series"):
         """forward_backward_series' calls: (loss, Y, the tail's dims, the call's counted labels -- a host integer, with
         missing_labels the sum of the integer counts the masked forward leaves in loss_buf, a device scalar).  admit: as in
         _forward_backward."""
         seq_len, table, inverse = int(seq_len), None, None
         self._series_refusals(A, series, seq_len, 1 if stride is None else int(stride), missing_labels)
         fn_f, fn_b = self._series_loss("forward_backward_series", seq_len, missing_labels, loss, huber_delta, loss_from)
+        _compact_arg("windgnn_amd: TrainStep." + who, compact, starts, stride)
         series, Ls = series.contiguous(), Ls.contiguous()
         if starts is not None:
-            table, inverse, n = self._series_table(series, Ls, seq_len, stride, n_windows, starts)
+            series, Ls, table, inverse, n = self._series_table(series, Ls, seq_len, stride, n_windows, starts, compact=compact)
         else:
             stride = 1 if stride is None else int(stride)
             n = self._series_count(series, Ls, seq_len, stride, n_windows)
@@ -840,7 +850,7 @@ class TrainStep:
         return self._loss, (Y if inverse is None else Y.index_select(0, inverse)), d, count
 
     def step_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, n_global=None, starts=None,
-                    missing_labels=False, loss="mse", huber_delta=1.0, loss_from=0):
+                    missing_labels=False, loss="mse", huber_delta=1.0, loss_from=0, compact=False):
         """One optimiser step on the first `n_windows` (default: all that fit) sliding windows of this rank's `series`
         [rows, S, 13]: window w covers rows w * stride .. w * stride + seq_len - 1 and starts from h = 0, as step() on the
         materialised windows would.  Ls [>= (n - 1) * stride + seq_len, H]: the label SERIES (series_labels(feat, seq_len,
@@ -852,7 +862,17 @@ class TrainStep:
         or tensor in any order, duplicates allowed (series.segment_starts for a series with outages, a hold-out, one block of a
         shuffled epoch).  The loss and the gradients are over the listed windows, the window count is the table's length (an
         empty table: the empty-shard step), Y comes back in the table's order, and Ls needs a row for every row of `series`.
-        The graph convolutions and the input projection still run on every row of `series`.
+        With compact=False the graph convolutions and the input projection run on every row of `series`, whatever the table
+        lists.  compact=True: they run on the hours some window covers alone -- series.compact_table maps every covered hour to
+        its rank among them, the rows are gathered (series, Ls) and the same calls run on the shorter series with the table of
+        ranks; the window count, the counted labels and the shard weight are those of compact=False, Y, the loss and the
+        gradients agree with it to rounding (the weight-gradient sums are grouped over another row count, and a front layout
+        on the other side of 4096 rows takes the other GEMM instance).  A host table is compacted on the host to exactly the covered hours; a
+        device table on the device, without a host read, to min(rows, n * seq_len) rows -- compact=<int> promises that the
+        table covers at most that many hours and sizes the compacted series by it (a table that covers more is reported like a
+        bad device table).  compact="auto": compact where it is measured to pay -- a host table that covers at most
+        series.COMPACT_AUTO_THETA of the rows; not a device table, and not validate_series ("Covered hours
+        only", has the numbers).  Only with starts=.
         missing_labels=True (include/windgnn_series_masked.h): a NaN in Ls means "no label" -- it adds nothing to the loss or to
         any gradient, and the mean is over the labels that exist (build `series` from the filled table, Ls from the unfilled
         one).  With no label at all the loss is NaN and the gradients are zero.  Refused under a process group.
@@ -865,9 +885,10 @@ class TrainStep:
         seq_len, table, inverse = int(seq_len), None, None
         self._series_refusals(A, series, seq_len, 1 if stride is None else int(stride), missing_labels)
         fn_f, fn_b = self._series_loss("step_series", seq_len, missing_labels, loss, huber_delta, loss_from)
+        _compact_arg("windgnn_amd: TrainStep.step_series", compact, starts, stride)
         series, Ls = series.contiguous(), Ls.contiguous()
         if starts is not None:
-            table, inverse, n = self._series_table(series, Ls, seq_len, stride, n_windows, starts)
+            series, Ls, table, inverse, n = self._series_table(series, Ls, seq_len, stride, n_windows, starts, compact=compact)
         else:
             stride = 1 if stride is None else int(stride)
             n = self._series_count(series, Ls, seq_len, stride, n_windows)
@@ -884,11 +905,11 @@ class TrainStep:
         return self._loss, (Y if inverse is None else Y.index_select(0, inverse))
 
     def validate_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, starts=None, missing_labels=False,
-                        loss="mse", huber_delta=1.0, loss_from=0, more=False, evaluator=None):
+                        loss="mse", huber_delta=1.0, loss_from=0, more=False, evaluator=None, compact=False):
         """The loss of step_series' spec on windows the model is NOT training on (include/windgnn_series_val.h): the model's
         current parameters, forward-only -- no Y, no stash, no backward -- and no change to the optimiser, the gradient bucket or
         `steps`.  A, series, Ls, seq_len, stride / n_windows or starts (any order, duplicates allowed; series.segment_starts gives
-        a hold-out at window level), missing_labels, loss, huber_delta, loss_from: as in step_series.  A pass accumulates over
+        a hold-out at window level), missing_labels, loss, huber_delta, loss_from, compact: as in step_series.  A pass accumulates over
         calls: more=True leaves it open for the next table or segment of the hold-out, more=False (the default) closes it.  The
         return value is the pass's mean loss so far, a 0-dim fp32 VIEW of the device record (`val_loss`), overwritten by the
         next call.  Closing: with TrainStep(keep_best=..., best_on="validation") wgnn_keep_best runs on that loss word with the
@@ -908,9 +929,12 @@ class TrainStep:
         if evaluator is not None and (getattr(evaluator, "H", None) != self.p_views[5].shape[1]):
             raise ValueError("windgnn_amd: TrainStep.validate_series: evaluator= must be an evaluate.Evaluator of this model's %d "
                              "outputs, got %r" % (self.p_views[5].shape[1], evaluator))
+        _compact_arg("windgnn_amd: TrainStep.validate_series", compact, starts, stride)
         series, Ls = series.contiguous(), Ls.contiguous()
+        full, Ls_full = series, Ls           # (the evaluator looks its truths up at the caller's starts)
         if starts is not None:
-            table, inverse, n = self._series_table(series, Ls, seq_len, stride, n_windows, starts, "validate_series")
+            series, Ls, table, inverse, n = self._series_table(series, Ls, seq_len, stride, n_windows, starts, "validate_series",
+                                                               compact)
         else:
             stride = 1 if stride is None else int(stride)
             n = self._series_count(series, Ls, seq_len, stride, n_windows, "validate_series")
@@ -933,7 +957,7 @@ class TrainStep:
                        loss_from=loss_from, missing_labels=missing_labels, starts=table, last=last, val=self._val,
                        wind_min=wmin, wind_max=wmax)
         if evaluator is not None:
-            self._feed_evaluator(evaluator, last, inverse, series, Ls, seq_len, stride, starts, missing_labels)
+            self._feed_evaluator(evaluator, last, inverse, full, Ls_full, seq_len, stride, starts, missing_labels)
         if not more:
             self._close_validation()
         return val_word(self._val, "loss")
@@ -1269,13 +1293,13 @@ class TrainStep:
         return self._accumulate(self._loss_kind(loss, huber_delta), out, X.shape[0], X.shape[1], int(loss_from))
 
     def accumulate_series(self, A, series, Ls, seq_len, stride=None, n_windows=None, starts=None, missing_labels=False,
-                          loss="mse", huber_delta=1.0, loss_from=0):
+                          loss="mse", huber_delta=1.0, loss_from=0, compact=False):
         """accumulate on the sliding windows of one series: forward_backward_series(...) followed by the same add (several
-        series tensors -- sites, years, folds -- in one optimiser step; two seq_len on one rank).  Returns (this call's own loss
-        as a 0-dim clone, Y)."""
+        series tensors -- sites, years, folds -- in one optimiser step; two seq_len on one rank).  compact: as in step_series,
+        per call.  Returns (this call's own loss as a 0-dim clone, Y)."""
         admit = self._accumulate_refusals("accumulate_series", loss, huber_delta)
         out = self._forward_backward_series(A, series, Ls, seq_len, stride, n_windows, starts, missing_labels, loss,
-                                            huber_delta, loss_from, admit)
+                                            huber_delta, loss_from, admit, compact, "accumulate_series")
         return self._accumulate(self._loss_kind(loss, huber_delta), out, out[1].shape[0], int(seq_len), int(loss_from))
 
     def _tail_dims(self):
