@@ -4,5 +4,6 @@ from .evaluate import Evaluator  # noqa: F401
 from .modules import GCN_GRU, GraphConvLayer  # noqa: F401
 from .streaming import StreamingForecaster  # noqa: F401
 from .ensemble import Ensemble, EnsembleForecast, PerMember  # noqa: F401
+from .transfer import adopt_convs  # noqa: F401
 
-__all__ = ["Ensemble", "EnsembleForecast", "Evaluator", "GCN_GRU", "GraphConvLayer", "PerMember", "StreamingForecaster"]
+__all__ = ["Ensemble", "EnsembleForecast", "Evaluator", "GCN_GRU", "GraphConvLayer", "PerMember", "StreamingForecaster", "adopt_convs"]

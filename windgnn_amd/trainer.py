@@ -95,7 +95,19 @@ scales the sum back into the bucket -- which is then the bucket of one call on t
 and runs the tail every step runs on a final bucket (_run_schedule(d, _FINAL, gs), _end_step): one all-reduce under a process
 group, one wgnn_finish(0, adam) or the clipped pair, keep_best on the accumulated loss.  No kernel and no entry point of the
 library is added: the add and the scale are plain torch on the current stream, without a host read.  accumulate* issues no
-collective.  A TrainStep that never calls them is the object it was, launch for launch."""
+collective.  A TrainStep that never calls them is the object it was, launch for launch.
+
+Frozen parameter groups (trainable= / set_trainable): "gru" trains the four GRU tensors under frozen convolutions (a trained model
+moved to another station network: transfer.adopt_convs), "conv" the four conv tensors under a frozen GRU, "all" -- the default -- is
+every schedule above, launch for launch.  wgnn_bwd*_part already splits the backward (include/windgnn.h: part 1 BPTT, part 4 the
+weight-gradient GEMMs = the GRU gradients, part 2 the dg GEMM + GCN backward = the conv gradients; 4 and 2 read only what 1 wrote) and
+wgnn_finish(WGNN_FINISH_ADAM_GRU | _CONV) steps one group alone, so a step with a frozen group enqueues part 1 and the trained
+group's part only, the reduce-only wgnn_finish of that part, (the one all-reduce of the whole bucket,) and the optimiser's launch
+of that group: the frozen group's part is never launched and its slots of the bucket keep the zeros set_trainable wrote.  Series
+mode has no parts: its backward runs whole and the frozen slots are zeroed after it.  Adam keeps torch.optim.Adam's rule that a
+tensor without a gradient does not advance its step: `steps` counts optimiser steps, _sat_out how many of them each group was
+frozen for, and a group's bias-correction step is the difference + 1; "all" with unequal counts issues one optimiser launch per
+group.  No kernel and no entry point of the library is added."""
 from __future__ import annotations
 
 import collections
@@ -121,6 +133,11 @@ AUTO_BLOCK_BYTES = 64 << 20         # ... from a gradient bucket of this size (s
 
 
 _ROWS = {"ih": _lib.ROWS_IH, "hh": _lib.ROWS_HH}          # GradBlock.tensor -> `which` of wgnn_bwd_rows / wgnn_finish_rows
+
+# trainable=: the group that trains -> (the part of the backward whose products are its gradients, which is also the reduce bit
+# of wgnn_finish for them; the `which` of its optimiser step; the group that is frozen meanwhile)
+TRAINABLE = ("all", "gru", "conv")
+_GROUP = {"gru": (4, _lib.FINISH_ADAM_GRU, "conv"), "conv": (2, _lib.FINISH_ADAM_CONV, "gru")}
 
 
 class _Deferred:
@@ -159,10 +176,15 @@ _FINAL = _Final()
 
 
 class TrainStep:
+    # A step with a frozen group leaves the split-K partial sums of its one part deferred (WGNN_BWD_DEFER) and reduces them
+    # with a reduce-only wgnn_finish, as the one-bucket schedule does; False: the part reduces its own.  Both are legal
+    # (include/windgnn.h) and give the same bits; profiles/r23_finetune_cost.txt has the two timings behind the choice.
+    FROZEN_DEFER = True
+
     def __init__(self, model: GCN_GRU, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  process_group=None, check_every: int = 100, overlap_collectives: bool = False, direct_rccl=None,
                  rccl_loader=None, carry_state: bool = False, grad_blocks=None, max_grad_norm=None, keep_best=None,
-                 best_on: str = "train"):
+                 best_on: str = "train", trainable: str = "all"):
         """carry_state: truncated BPTT over consecutive chunks -- each step starts the recurrence from the h_n of the previous
         step (detached; zeros on the first step and after reset_state()), so a model trained on chunks of a long series
         learns the carried-state regime StreamingForecaster(window=None) serves.  The batch size must stay the same
@@ -187,7 +209,11 @@ class TrainStep:
         Every schedule takes it, the empty-shard step included.
 
         best_on (with keep_best): "train" = the rule above, launch for launch; "validation" = no step decides -- a CLOSED
-        validation pass does (validate_series or validate): its held-out loss is compared, and the parameters at that moment are kept."""
+        validation pass does (validate_series or validate): its held-out loss is compared, and the parameters at that moment are kept.
+
+        trainable: "all" = every schedule above, launch for launch; "gru" = the four GRU tensors train and the four conv tensors
+        are frozen; "conv" = the mirror image (set_trainable has the contract).  Under a process group every rank must hold
+        the same value: nothing checks it, and no collective is added for it."""
         if not getattr(model, "fused", True):
             raise RuntimeError("windgnn_amd: TrainStep drives the fused hot path, i.e. the reference model's own widths "
                                "(input_dim = hidden_dim = 13, src/main.py:41); a GCN_GRU of other widths trains through "
@@ -217,6 +243,11 @@ class TrainStep:
                                       else "grad_blocks=%r" % (grad_blocks,),
                                       "the GRU tensors" if overlap_collectives else "row blocks"))
         self.max_grad_norm = max_grad_norm
+        self.overlap_collectives = overlap_collectives
+        # completed optimiser steps that each group sat out frozen: a group's own count, which is Adam's bias-correction
+        # step number for it less one, is `steps` minus this (torch.optim.Adam: no gradient, no step)
+        self._sat_out = {"gru": 0, "conv": 0}
+        self.trainable = self._trainable_arg("TrainStep(trainable=%r)" % (trainable,), trainable)
         if keep_best is False:                          # off, as a user means it (not the threshold 0.0)
             keep_best = None
         if keep_best is not None:
@@ -272,7 +303,6 @@ class TrainStep:
             self._reset_best(keep_best)
             # the call's arguments but the step number: the views never move, so they are checked and marshalled once
             self._best_call = keep_best_args(self._best_dims, self._loss, self.p_views, self._best_views, self._best)
-        self.overlap_collectives = overlap_collectives
         # direct_rccl: None = only if WGNN_RCCL_DIRECT=1 (opt-in: distributed.DirectRccl); the two-collective form overlaps
         # through torch.distributed's own stream by design and never takes it
         self.exchange = None
@@ -320,6 +350,76 @@ class TrainStep:
                                "H = %d, math = %d" % (grad_blocks, H, math))
         return grad_block_plan(S, H, grad_blocks, align)
 
+    def _trainable_arg(self, who, group):
+        """trainable= of the constructor and set_trainable: the group, or the refusal by name, before any launch."""
+        if group not in TRAINABLE:
+            raise ValueError("windgnn_amd: %s: trainable is 'all', 'gru' (the four GRU tensors train, the convolutions are frozen) "
+                             "or 'conv' (the four conv tensors train, the GRU is frozen), got %r" % (who, group))
+        why = None
+        if group == "all":
+            pass
+        elif self.max_grad_norm is not None:
+            why = ("max_grad_norm=%r: wgnn_finish_clipped steps all eight tensors, and the norm over one group is not built"
+                   % (self.max_grad_norm,))
+        elif self.overlap_collectives:
+            why = ("overlap_collectives=True: that schedule interleaves the backward parts and the optimiser steps of both "
+                   "groups; a frozen group runs on the one-bucket schedule")
+        elif self.plan is not None:
+            why = ("grad_blocks: the blocked exchange interleaves the GRU tensors' row blocks with the conv tensors' part of the "
+                   "backward; a frozen group runs on the one-bucket schedule")
+        if why is not None:
+            raise RuntimeError("windgnn_amd: %s with %s" % (who, why))
+        return group
+
+    def set_trainable(self, group):
+        """Which tensors the following steps train: "all", "gru" (gru.weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0; the
+        four conv tensors are frozen) or "conv" (conv1 / conv2 weight and bias; the four GRU tensors are frozen).  Between
+        steps, e.g. a "gru" phase on a new station network followed by a few steps on "all".
+
+        A frozen tensor keeps the bits of its parameter and of both Adam moments under every call that takes a step, its slice
+        of the keep_best snapshot is a copy of those same bits, and its gradient view reads +0: this call zeroes the newly
+        frozen slots of the bucket once (one torch op on the current stream), and the steps that follow never write there.
+        On materialised windows (step, forward_backward, loss specs, carry_state) the part of the backward whose only
+        products are the frozen group's gradients is not launched: "gru" runs parts 1 and 4 of wgnn_bwd*_part (never the dg
+        GEMM and the GCN backward), "conv" parts 1 and 2 (never the weight-gradient GEMMs); the optimiser's launch is
+        wgnn_finish(WGNN_FINISH_ADAM_GRU) or (.._CONV) alone.  Series mode (step_series, forward_backward_series) has no parts:
+        its backward runs whole, the frozen slots are zeroed after it and only the trained group is stepped -- it saves no
+        backward time.  Under a process group the one all-reduce still covers the whole bucket (zeros in the frozen slots);
+        every rank must hold the same group, which is the caller's contract -- no collective checks it.
+
+        torch.optim.Adam's rule holds: a tensor without a gradient does not advance its `step`.  Each group keeps its own count
+        of steps taken, and its bias correction uses that count: after two steps on "gru", a step on "all" steps the conv tensors
+        at 1 and the GRU tensors at 3 (two launches, one per group, while the counts differ; the one launch when they agree).
+        `steps` stays the number of optimiser steps taken.
+
+        Refused, naming the reason: an unknown group (ValueError); while an accumulation or a validation pass is open; and,
+        for a group other than "all", max_grad_norm, overlap_collectives, grad_blocks (as the constructor refuses them) --
+        accumulate / accumulate_series / apply are refused while a group is frozen."""
+        who = "TrainStep.set_trainable(%r)" % (group,)
+        group = self._trainable_arg(who, group)
+        self._bucket_is_free("set_trainable")
+        if self._val_open:
+            raise RuntimeError("windgnn_amd: %s while a validation pass is open (validate*(..., more=True)): the pass scores one "
+                               "model, and a best_on='validation' decision belongs to the group that trained it; close it with a "
+                               "call with more=False first" % who)
+        newly = group != "all" and group != self.trainable
+        self.trainable = group
+        if newly:
+            self._frozen_grads().zero_()
+
+    def _defer(self):
+        """WGNN_BWD_DEFER for the parts a schedule enqueues: always, but for a frozen group under FROZEN_DEFER = False."""
+        return _lib.BWD_DEFER if self.trainable == "all" or self.FROZEN_DEFER else 0
+
+    def _parts(self):
+        """The `part` of a backward that is enqueued whole (forward_backward): 7, or without the frozen group's part."""
+        return 7 if self.trainable == "all" else 1 | _GROUP[self.trainable][0]
+
+    def _frozen_grads(self):
+        """The frozen group's slots of the gradient bucket (one-bucket layout: [header | conv | GRU])."""
+        conv = self._gbuf[HEADER:HEADER + self.n_conv]
+        return conv if self.trainable == "gru" else self._gbuf[HEADER + self.n_conv:]
+
     def _param_version(self):
         """torch's in-place version counters of the parameters: load_state_dict / optimiser-free edits through the
         nn.Parameters or the flat buffer bump them; the library's own kernels do not."""
@@ -337,21 +437,41 @@ class TrainStep:
             refresh_prepared(d, self.p_views, self._prepared)
         self._prepared_version = self._param_version()
 
-    def _adam(self):
-        # the step being taken: self.steps counts COMPLETED steps (a step that raises does not advance Adam's bias correction)
-        return dict(exp_avg=self.m_views, exp_avg_sq=self.v_views, step=self.steps + 1, lr=self.lr, beta1=self.betas[0],
+    def _group_count(self, group):
+        """Completed optimiser steps of one group ("gru" / "conv")."""
+        return self.steps - self._sat_out[group]
+
+    def _adam(self, group=None):
+        # the step being taken: self.steps counts COMPLETED steps (a step that raises does not advance Adam's bias correction);
+        # group: "gru" / "conv" = that group's own count, None = both groups', which are then equal
+        done = self._group_count(group or "gru")
+        return dict(exp_avg=self.m_views, exp_avg_sq=self.v_views, step=done + 1, lr=self.lr, beta1=self.betas[0],
                     beta2=self.betas[1], eps=self.eps)
 
     def _tail(self, d, which, pre):
         """The optimiser's end of a step: reduce the deferred partial sums `which` (0: the bucket is final) and step Adam --
-        ONE wgnn_finish, or with max_grad_norm wgnn_finish_norm (the same reduction + the norm) and wgnn_finish_clipped."""
-        if self.max_grad_norm is None:
-            finish_step(d, self.p_views, self.g_views, which, self._adam(), pre, self.device)
+        ONE wgnn_finish, or with max_grad_norm wgnn_finish_norm (the same reduction + the norm) and wgnn_finish_clipped.
+        Where the two groups do not step together -- one is frozen, or both train at different counts -- the reduce-only
+        wgnn_finish comes first (WGNN_FINISH_ADAM_GRU / _CONV take no reduce bit), then one wgnn_finish per stepped group,
+        each with its own step number."""
+        if self.trainable == "all" and self._sat_out["gru"] == self._sat_out["conv"]:
+            if self.max_grad_norm is None:
+                finish_step(d, self.p_views, self.g_views, which, self._adam(), pre, self.device)
+                return
+            if self._clip is None or self._clip.numel() * 4 < clip_bytes(d):
+                self._clip = clip_buffer(d, self.device)
+            finish_norm(d, self.g_views, which, self.max_grad_norm, self._clip, self.device)
+            finish_clipped(d, self.p_views, self.g_views, self._adam(), self._clip, pre, self.device)
             return
-        if self._clip is None or self._clip.numel() * 4 < clip_bytes(d):
-            self._clip = clip_buffer(d, self.device)
-        finish_norm(d, self.g_views, which, self.max_grad_norm, self._clip, self.device)
-        finish_clipped(d, self.p_views, self.g_views, self._adam(), self._clip, pre, self.device)
+        if self.max_grad_norm is not None:      # (a checkpoint's counts: set_trainable itself refuses max_grad_norm)
+            raise RuntimeError("windgnn_amd: TrainStep(max_grad_norm=%r) with the GRU tensors at optimiser step %d and the conv "
+                               "tensors at %d: wgnn_finish_clipped steps all eight tensors with one step number; clipping over "
+                               "groups at different counts is not built"
+                               % (self.max_grad_norm, self._group_count("gru"), self._group_count("conv")))
+        if which:
+            finish_step(d, self.p_views, self.g_views, which, device=self.device)
+        for group in ("gru", "conv") if self.trainable == "all" else (self.trainable,):
+            finish_step(d, self.p_views, self.g_views, _GROUP[group][1], self._adam(group), pre, self.device)
 
     def _clip_word(self, slot, name):
         if self._clip is None:
@@ -433,18 +553,25 @@ class TrainStep:
         """What this step owns besides the parameters, as clones on its device:
         "optimizer": torch.optim.Adam(model.parameters(), lr, betas, eps).state_dict()'s layout (state[i] = {step, exp_avg,
         exp_avg_sq} for i in 0..7, one param group; hot_path_parameters() is in model.parameters() order);
-        "steps"; "best": None or the record's public words plus the snapshot under the reference's keys; "carry": the
+        "steps"; "trainable", only once a group has been frozen -- now, or for some earlier step (state[i]["step"] is each tensor's
+        own group's count, and `steps`, which counts every optimiser step, may then exceed both); "best": None or the record's public words plus the snapshot under the reference's keys; "carry": the
         carried [B, H] state or None; and, only once validate_series has run, "val": the public words of the validation record
         (the last closed pass, `passes`, `stale`; an open pass raises).  The parameters are model.state_dict()'s."""
         self._bucket_is_free("state_dict()")
         opt = torch.optim.Adam(self.params, lr=self.lr, betas=tuple(self.betas), eps=self.eps).state_dict()
-        opt["state"] = {i: {"step": torch.tensor(float(self.steps)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+        # (each tensor at its own group's count -- torch.optim.Adam's own layout after a run with a frozen group)
+        opt["state"] = {i: {"step": torch.tensor(float(self._group_count("conv" if i < 4 else "gru"))), "exp_avg": m.clone(),
+                            "exp_avg_sq": v.clone()}
                         for i, (m, v) in enumerate(zip(self.m_views, self.v_views))}
         best = None
         if self._best is not None:
             best = {name: best_word(self._best, name).clone() for name in _lib.BEST_WORDS}
             best.update((k, v.clone()) for k, v in zip(PARAM_ORDER, self._best_views))
         out = {"optimizer": opt, "steps": self.steps, "best": best, "carry": self.state}
+        if self.trainable != "all" or any(self._sat_out.values()):
+            # only once a group has been frozen: else the keys it has always had.  With the key, `steps` may exceed the Adam
+            # counts (one step on "gru", one on "conv", one on "all": steps = 3, every tensor at 2)
+            out["trainable"] = self.trainable
         if self._val is not None:       # "val": only once validate_series has made a record (else the four keys above)
             if self._val_open:
                 raise RuntimeError("windgnn_amd: TrainStep.state_dict(): a validation pass is open (validate_series(..., more=True)); "
@@ -453,8 +580,10 @@ class TrainStep:
         return out
 
     def load_state_dict(self, sd):
-        """Takes state_dict()'s output or a bare torch.optim.Adam state dict (all eight `step` values must agree; an empty
-        `state` is step 0).  Moments are written into the existing flat buffers, lr / betas / eps restored, and from the full
+        """Takes state_dict()'s output or a bare torch.optim.Adam state dict (the `step` values must agree within the four conv
+        tensors and within the four GRU tensors; the two groups may differ, as after a phase with a frozen group; an empty
+        `state` is step 0; from a bare dict `steps` becomes the larger count).  "trainable" is restored, "all" where the key is
+        absent.  Moments are written into the existing flat buffers, lr / betas / eps restored, and from the full
         form the best record + snapshot, the carried state and, when the checkpoint has one, the validation record ("val":
         val_passes, val_stale and the last closed pass).  Load the parameters with model.load_state_dict."""
         self._bucket_is_free("load_state_dict()")
@@ -470,22 +599,38 @@ class TrainStep:
                              "weight_decay=%r amsgrad=%r maximize=%r"
                              % (grp.get("weight_decay"), grp.get("amsgrad"), grp.get("maximize")))
         state = opt["state"]
-        steps = 0
+        steps, have, done = 0, [], {"conv": 0, "gru": 0}
         if len(state):
-            if sorted(state) != list(range(8)):
-                raise ValueError("windgnn_amd: TrainStep.load_state_dict: Adam state for parameters %s, expected 0..7"
-                                 % sorted(state))
-            counts = [int(round(float(state[i]["step"]))) for i in range(8)]
-            if len(set(counts)) != 1:
-                raise ValueError("windgnn_amd: TrainStep.load_state_dict: the Adam `step` values disagree (%s): TrainStep "
-                                 "steps all 8 tensors together" % dict(zip(PARAM_ORDER, counts)))
-            steps = counts[0]
-            for i, key in enumerate(PARAM_ORDER):
+            # torch.optim.Adam makes a tensor's state at its first gradient: a run on one group alone has the state of that group only
+            have = sorted(state)
+            if have not in (list(range(8)), list(range(4)), list(range(4, 8))):
+                raise ValueError("windgnn_amd: TrainStep.load_state_dict: Adam state for parameters %s, expected 0..7 (or the "
+                                 "conv tensors 0..3 / the GRU tensors 4..7 alone)" % have)
+            counts = {i: int(round(float(state[i]["step"]))) for i in have}
+            for name, idx in (("conv", range(4)), ("gru", range(4, 8))):
+                mine = [counts[i] for i in idx if i in counts]
+                if len(set(mine)) > 1:
+                    raise ValueError("windgnn_amd: TrainStep.load_state_dict: the Adam `step` values disagree inside a group "
+                                     "(%s): TrainStep steps the four conv tensors together and the four GRU tensors together"
+                                     % {PARAM_ORDER[i]: c for i, c in counts.items()})
+                done[name] = mine[0] if mine else 0
+            steps = max(done.values())
+            for i in have:
                 for name, views in (("exp_avg", self.m_views), ("exp_avg_sq", self.v_views)):
                     if tuple(state[i][name].shape) != tuple(views[i].shape):
                         raise ValueError("windgnn_amd: TrainStep.load_state_dict: %s of %s is %s, expected %s"
-                                         % (name, key, tuple(state[i][name].shape), tuple(views[i].shape)))
-        if full and len(state) and int(sd["steps"]) != steps:
+                                         % (name, PARAM_ORDER[i], tuple(state[i][name].shape), tuple(views[i].shape)))
+        group = sd.get("trainable", "all") if full else "all"
+        self._trainable_arg("TrainStep.load_state_dict: trainable=%r" % (group,), group)
+        apart = group != "all" or done["gru"] != done["conv"]
+        if apart and self.max_grad_norm is not None:
+            raise RuntimeError("windgnn_amd: TrainStep.load_state_dict: the GRU tensors are at optimiser step %d and the conv "
+                               "tensors at %d, and this TrainStep has max_grad_norm=%r: wgnn_finish_clipped steps all eight "
+                               "tensors with one step number" % (done["gru"], done["conv"], self.max_grad_norm))
+        # (`steps` counts every optimiser step: the groups' own counts are no larger, and equal to it in a checkpoint without
+        # "trainable", which is written only while no group has ever sat a step out)
+        exact = not apart and "trainable" not in sd
+        if full and len(state) and (int(sd["steps"]) != steps if exact else int(sd["steps"]) < steps):
             raise ValueError("windgnn_amd: TrainStep.load_state_dict: steps = %r but the Adam state is at step %d"
                              % (sd["steps"], steps))
         best, carry = (sd.get("best"), sd.get("carry")) if full else (None, None)
@@ -515,14 +660,18 @@ class TrainStep:
             if carry.dim() != 2 or carry.shape[1] != H:
                 raise ValueError("windgnn_amd: TrainStep.load_state_dict: carry is %s, expected [B, %d]" % (tuple(carry.shape), H))
         # everything checked: write
-        if len(state):
-            for i in range(8):
-                self.m_views[i].copy_(state[i]["exp_avg"])
-                self.v_views[i].copy_(state[i]["exp_avg_sq"])
-        else:
+        if len(have) < 8:
             self.exp_avg.zero_()
             self.exp_avg_sq.zero_()
-        self.steps = int(sd["steps"]) if full and not len(state) else steps
+        for i in have:
+            self.m_views[i].copy_(state[i]["exp_avg"])
+            self.v_views[i].copy_(state[i]["exp_avg_sq"])
+        self.steps = int(sd["steps"]) if full else steps
+        self._sat_out = {g: self.steps - done[g] if len(state) else 0 for g in ("gru", "conv")}
+        if group != self.trainable:
+            self.trainable = group
+            if group != "all":
+                self._frozen_grads().zero_()
         self.lr, self.betas, self.eps = grp["lr"], tuple(grp["betas"]), grp["eps"]
         if self._best is not None and full:
             if best is None:
@@ -559,7 +708,22 @@ class TrainStep:
         docstring) -- the ONE place that orders them.  bwd: what the step kind enqueues (_Deferred), or _FINAL for a bucket
         that is final already; gs: this shard's weight, which the exchange scales the loss word with."""
         pre, ex = self._prepared, self.exchange
-        if self.plan is not None:
+        if self.trainable != "all":
+            # A frozen group (set_trainable): BPTT and the one part whose products are the trained group's gradients -- 4 for
+            # "gru", 2 for "conv"; the other part is never enqueued, so the frozen slots of the bucket keep their zeros -- then
+            # the one-rank or the one-bucket tail on that group alone.
+            part = _GROUP[self.trainable][0]
+            pending = bwd.pending & part if self.FROZEN_DEFER else 0       # (not deferred: the part reduces its own sums)
+            bwd.parts(1)
+            bwd.parts(part)
+            if self.collective:
+                if pending:
+                    bwd.reduce(part)
+                ex.all_reduce_all(gs)       # the whole bucket, as ever: zeros in the frozen slots, the loss word in the header
+                self._tail(d, 0, pre)
+            else:
+                self._tail(d, pending, pre)
+        elif self.plan is not None:
             # Blocked: part 1, then per row block its weight-gradient GEMM + reduction and the start of its all-reduce, then
             # part 2 under the last blocks' collectives, the tail's all-reduce and the blocked Adam.
             bwd.parts(1)
@@ -600,25 +764,26 @@ class TrainStep:
             # the conv gradients' (tiny, latency-bound) all-reduce runs under the GRU tensors' optimiser step
             wconv = ex.start_conv(gs)       # loss: sum of the weighted shard means = the big-batch mean
             work.wait()
-            adam = self._adam()
-            finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_GRU, adam, pre, self.device)   # src/main.py:80
+            finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_GRU, self._adam("gru"), pre, self.device)   # src/main.py:80
             wconv.wait()
-            finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_CONV, adam, pre, self.device)
+            finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_CONV, self._adam("conv"), pre, self.device)
 
     def _blocked_adam(self, d, works, wtail, pre):
         """The optimiser half of the blocked step: Adam per row block once its all-reduce (and the tail's) has arrived, then
         the conv tensors.  Every wgnn_finish_rows rewrites W_ih and its images in place, so this runs after part 2 of the
         backward (the HAZARD in _run_schedule)."""
         wtail.wait()                    # b_ih / b_hh ride in the tail, and every block's Adam steps its rows' biases
-        adam = self._adam()
+        adam = self._adam("gru")        # (each group at its own count: they differ only after a phase with a frozen group)
         for b, work in zip(self.plan.blocks, works):
             work.wait()
             finish_rows(d, self.p_views, self.g_views, _ROWS[b.tensor], b.row0, b.rows, adam, pre, self.device)
-        finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_CONV, adam, pre, self.device)
+        finish_step(d, self.p_views, self.g_views, _lib.FINISH_ADAM_CONV, self._adam("conv"), pre, self.device)
 
     def _end_step(self, check=True):
         """What follows the optimiser's launches of every schedule: the count, keep_best, the periodic check()."""
         self.steps += 1                         # only a step whose launches were all accepted counts
+        if self.trainable != "all":
+            self._sat_out[_GROUP[self.trainable][2]] += 1      # (the frozen group took no step: its own count stays)
         self._keep_best()                       # src/main.py:83-86
         if check and self.check_every and self.steps % self.check_every == 0 and (
                 self.model.math != _lib.MATH_F32 or (self.exchange is not None and self.exchange.direct is not None)):
@@ -705,12 +870,12 @@ class TrainStep:
         if spec is not None:
             Xf, Y, stash, d, spec = self._spec_forward(A, X, spec)
             dY = self._spec_loss("forward_backward", Y, spec, 1.0)
-            gcn_gru_backward_raw(d, A, Xf, self.p_views, Y, dY, stash, self.g_views, part=7, prepared=self._prepared)
+            gcn_gru_backward_raw(d, A, Xf, self.p_views, Y, dY, stash, self.g_views, part=self._parts(), prepared=self._prepared)
             count = self._count if spec[3] else Y.shape[0] * (Y.shape[1] - spec[2]) * Y.shape[2]
             return self._loss, Y.to(X.dtype), d, count
         Y, stash, d = self._forward(A, X, L)
         loss = self._loss
-        gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, loss, 1.0, part=7 | 8,
+        gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, loss, 1.0, part=self._parts() | 8,
                                  prepared=self._prepared)
         return loss, Y, d, Y.numel()
 
@@ -840,6 +1005,8 @@ class TrainStep:
         Y, stash, loss_buf, sd, d = self._series_forward(A, series, Ls, seq_len, stride, n, table, **masked, **fn_f)
         series_backward_mse_raw(sd, A, series, self.p_views, Y, Ls, stash, loss_buf, self.g_views, self._loss, 1.0,
                                 prepared=self._prepared, **at, **masked, **fn_b)
+        if self.trainable != "all":     # (wgnn_series_bwd* has no parts: the backward ran whole)
+            self._frozen_grads().zero_()
         if admit is None:               # (forward_backward_series: the call it has always been, launch for launch)
             count = None
         elif missing_labels:            # include/windgnn_series_masked.h: sums | maxima | tag + 3 words | uint32 counts
@@ -900,6 +1067,8 @@ class TrainStep:
         Y, stash, loss_buf, sd, d = self._series_forward(A, series, Ls, seq_len, stride, n, table, **masked, **fn_f)
         series_backward_mse_raw(sd, A, series, self.p_views, Y, Ls, stash, loss_buf, self.g_views, self._loss, gs,
                                 prepared=self._prepared, **at, **masked, **fn_b)
+        if self.trainable != "all":     # (wgnn_series_bwd* has no parts: the backward ran whole; series mode saves no time)
+            self._frozen_grads().zero_()
         self._run_schedule(d, _FINAL, gs)       # the bucket is final: (the all-reduce,) Adam and the W_ih images
         self._end_step()
         return self._loss, (Y if inverse is None else Y.index_select(0, inverse))
@@ -1150,7 +1319,7 @@ class TrainStep:
             _, dY = mse_loss_grad(Y, L, gs, loss=self._loss)    # the unweighted shard mean: the exchange weights it
 
         def parts(mask):
-            gcn_gru_state_backward_raw(d, A, X, self.p_views, Y, dY, None, stash, self.g_views, part=mask | _lib.BWD_DEFER,
+            gcn_gru_state_backward_raw(d, A, X, self.p_views, Y, dY, None, stash, self.g_views, part=mask | self._defer(),
                                        prepared=self._prepared)
         self._run_schedule(d, _Deferred(self, d, parts, Y, stash), gs)
         self._hcur, self._has_state = 1 - self._hcur, True     # h_n of this step is the next step's h0
@@ -1162,7 +1331,7 @@ class TrainStep:
 
         def parts(mask):
             gcn_gru_backward_mse_raw(d, A, X, self.p_views, Y, L, stash, self.g_views, self._loss, gs,
-                                     part=mask | (mask & 1) << 3 | _lib.BWD_DEFER, prepared=self._prepared)
+                                     part=mask | (mask & 1) << 3 | self._defer(), prepared=self._prepared)
         self._run_schedule(d, _Deferred(self, d, parts, Y, stash), gs)
         return Y
 
@@ -1173,7 +1342,7 @@ class TrainStep:
         dY = self._spec_loss("step", Y, spec, gs)
 
         def parts(mask):
-            gcn_gru_backward_raw(d, A, Xf, self.p_views, Y, dY, stash, self.g_views, part=mask | _lib.BWD_DEFER,
+            gcn_gru_backward_raw(d, A, Xf, self.p_views, Y, dY, stash, self.g_views, part=mask | self._defer(),
                                  prepared=self._prepared)
         self._run_schedule(d, _Deferred(self, d, parts, Y, stash), gs)
         return Y.to(X.dtype)
@@ -1226,10 +1395,17 @@ class TrainStep:
                                "until its optimiser step; finish it with apply(), or drop it with discard(), first"
                                % (who, self.accumulated, "" if self.accumulated == 1 else "s"))
 
+    def _no_frozen_group(self, who):
+        if self.trainable != "all":
+            raise RuntimeError("%s with trainable=%r: accumulation under a frozen group is not built (the accumulator adds whole "
+                               "buckets, and its calls would have to share the group); take one step() per batch, or "
+                               "set_trainable('all') first" % (who, self.trainable))
+
     def _accumulate_refusals(self, who, loss, huber_delta):
         """What accumulate / accumulate_series refuse on top of forward_backward*'s own refusals; returns the admit callback
         of _forward_backward*, which holds those that need the call's shape."""
         who = "windgnn_amd: TrainStep." + who
+        self._no_frozen_group(who)
         one_bucket = ("an accumulation is final only at apply(), whose exchange and optimiser run on the one-bucket schedule; build "
                       "the TrainStep without it, or take one step() per batch")
         if self.plan is not None:
@@ -1318,6 +1494,7 @@ class TrainStep:
         rank apply() with nothing accumulated is refused.  An apply() that raises counts nothing and leaves the accumulation
         open; as after a step that raised, rebuild from a checkpoint rather than retry (discard() first: state_dict() is
         refused while it is open)."""
+        self._no_frozen_group("windgnn_amd: TrainStep.apply()")
         n = self.accumulated
         if n == 0:
             if not self.collective:
